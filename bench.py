@@ -3,6 +3,7 @@
 gradient all-reduce + Adam) on N GPUs of one node, one process per GPU (BASELINE.json `metric`).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|eval] [--batch B_per_gpu]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,9 +11,13 @@ Workload: BASELINE.json configs[2] at N=1 (train.py L1-loss step, batch 64 on on
 N=8 (64 tiles per GPU = global batch 512, RCCL gradient all-reduce): weak scaling.  `--mode eval --batch 16`
 is configs[1] (eval forward).  Inputs are synthetic tiles (svs_fill_tiles) already resident in HBM.
 
-One JSON line on rank 0 with `roofline` (the dominant kernel timed live with HIP events on the stream it is
-launched on, against the fp32 MFMA peak) and `cpu_baseline` (the CPU oracle -- the plain-torch restatement of
-the reference -- timed on this box's host cores on a bounded sample).  The oracle is used ONLY there.
+A plain run sets up, runs W warm-up and K timed steps and prints one JSON line on rank 0 (`value`, `ms_per_step`, ...).
+`--dump-outputs DIR` then writes what the last timed step computed, as float32 .npy files (see dump_outputs).
+`--full` adds the side records after the timed steps: `roofline` (the dominant kernel timed live with HIP events on the
+stream it is launched on, against the fp32 MFMA peak), the strong-scaling, eval B=16, split-bf16, full-objective and
+signal-kernel records, and `cpu_baseline` (the CPU oracle -- the plain-torch restatement of the reference -- timed on the
+host cores on a bounded sample).  The oracle is used ONLY there.  `--no-layers` / `--no-extras` / `--no-cpu-baseline`
+leave parts of `--full` out.
 """
 from __future__ import annotations
 
@@ -34,6 +39,38 @@ from svs_unet_pytorch_amd.model import ALPHA_L1, DEC_IO, ENC_CHANNELS, UNet  # n
 FP32_MFMA_PEAK_TFLOPS = 157.3      # /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters
 FWD_GFLOP_PER_TILE = 1.507328
 TRAIN_GFLOP_PER_TILE = 4.5088768
+DUMP_LIMIT_BYTES = 64 << 20        # --dump-outputs: everything written, in all
+GRAD_SAMPLE = 1 << 20              # gradient elements kept (the parameters themselves take 39 MB)
+MASK_LIMIT = 1 << 23               # eval masks larger than this many elements are sampled down to it
+
+
+def _sample(a, n, seed):
+    """A fixed, seeded sample of n elements of `a` (the same indices on every run, in ascending order)."""
+    a = a.reshape(-1)
+    if a.size <= n:
+        return a
+    return a[np.sort(np.random.default_rng(seed).choice(a.size, size=n, replace=False))]
+
+
+def dump_outputs(out_dir, mode, model, result):
+    """What the timed path computed in its last step, as a caller of that path receives it, written as DIR/<name>.npy (float32).
+    train: `loss` (the value train_step returned), `params` (every parameter after Adam, in the flat order of
+    svs_unet_param_offset), `bn_running_stats` (BatchNorm running mean / var), `grads_sample` (a seeded sample of the flat
+    gradient).  eval: `mask` (B, 1, H, W), or `mask_sample` when the batch is large."""
+    if mode == "train":
+        arrays = {"loss": result.detach().reshape(1).float().cpu().numpy(),
+                  "params": model._flat.detach().cpu().numpy(),
+                  "bn_running_stats": model._bn_flat.detach().cpu().numpy(),
+                  "grads_sample": _sample(model._gflat.detach().cpu().numpy(), GRAD_SAMPLE, seed=1)}
+    else:
+        mask = result.detach().float().cpu().numpy()
+        arrays = {"mask": mask} if mask.size <= MASK_LIMIT else {"mask_sample": _sample(mask, MASK_LIMIT, seed=2)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"outputs take {total} bytes, more than {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(arrays)
 
 
 def gemm_calls(B, mode, H=512, W=128):
@@ -457,11 +494,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mode", choices=("train", "eval"), default="train")
     ap.add_argument("--batch", type=int, default=0, help="tiles per GPU (default 64 train / 16 eval)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-layers", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the eval-B16 / strong-scaling / signal-kernel sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the roofline / per-layer, strong-scaling, "
+                                                        "eval-B16, split-bf16, full-objective, signal-kernel and CPU-baseline records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-layers", action="store_true", help="with --full: skip the roofline / per-layer record")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the eval-B16 / strong-scaling / signal-kernel sub-records")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even with one rank")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"bench.py: --steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -518,18 +560,20 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     fence()
     elapsed = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:           # before any record of --full touches the model again
+        dump_outputs(args.dump_outputs, args.mode, model, last)
 
     # strong-scaling point of north_star (outside the timed region above): global batch 512 split over the ranks, every rank
     # takes part, MAX over ranks
     strong = None
-    if args.mode == "train" and not args.no_extras:
+    if args.full and args.mode == "train" and not args.no_extras:
         fence()
         strong = strong_record(model, dev, world, rank, grad_sync)
         if dist is not None:
@@ -553,7 +597,7 @@ def main():
         }
         if strong is not None:
             res["strong_b512"] = strong
-        if not args.no_layers:         # rank 0's GPU, any world size: the dominant kernel's roofline record
+        if args.full and not args.no_layers:         # rank 0's GPU, any world size: the dominant kernel's roofline record
             calls = time_gemm_calls(B, args.mode)
             fam = {}
             for name, kernel, ks, ms, gf, _ in calls:
@@ -582,7 +626,7 @@ def main():
             res["kernels"] = {k: {"calls": v[2], "ms": round(v[0], 4), "tflops": round(v[1] / v[0], 2)} for k, v in fam.items()}
             res["layers"] = {name: {"kernel": kernel, "ksplit": ks, "ms": round(ms, 4), "tflops": round(gf / ms, 2),
                                     "in_image": round(fr, 3)} for name, kernel, ks, ms, gf, fr in calls}
-        if world == 1:
+        if world == 1 and args.full:
             if not args.no_extras:
                 if args.mode == "train":
                     res["optional_mfma_split"] = split_mode_record(model, dev, B)

@@ -194,14 +194,14 @@ def test_resident_set_matches_reference_dataset_items(tmp_path, golden, report):
 
 
 def test_bench_contract_line():
-    """bench.py as the driver runs it (one rank, child process, few steps): exactly one JSON line on stdout with the contract's
-    keys, BASELINE's metric / config, and the `roofline` and `cpu_baseline` objects."""
+    """bench.py --full (one rank, child process, few steps): exactly one JSON line on stdout with the contract's keys,
+    BASELINE's metric / config, and the `roofline` and `cpu_baseline` objects."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-extras"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-extras"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -218,3 +218,37 @@ def test_bench_contract_line():
     assert rf["bound"] == "mfma" and rf["unit"] == "TFLOP/s" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
     assert 0.05 < rf["frac"] < 1.0 and rf["kernel"].startswith(("conv_gemm_kernel", "wgrad_", "parity_window"))
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["unit"] == "tiles/s" and cb["sample"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run (no --full) times the headline steps only and prints the contract line without the side records;
+    --dump-outputs writes the last timed step's loss, parameters, BatchNorm statistics and gradient sample as float32 .npy
+    files, within 64 MB, and two runs with the same arguments write the same numbers."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "tiles/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert abs(d["value"] - 64 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+        for k in ("roofline", "cpu_baseline", "strong_b512", "eval_b16", "optional_mfma_split", "full_objective", "signal", "layers"):
+            assert k not in d, k
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["bn_running_stats.npy", "grads_sample.npy", "loss.npy", "params.npy"], files
+        arrays = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert sum((out / f).stat().st_size for f in files) <= 64 << 20
+        assert arrays["params"].size == 9823313 and np.isfinite(arrays["params"]).all()
+        assert arrays["loss"].shape == (1,) and np.isfinite(arrays["loss"]).all() and arrays["loss"][0] > 0
+        runs.append(arrays)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k

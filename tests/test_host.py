@@ -301,3 +301,36 @@ def test_bench_gpus_n_launches_child_ranks(tmp_path):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], env=env,
                            capture_output=True, text=True, timeout=300)
         assert r.returncode != 0 and not r.stdout.strip() and "sees no GPU" in r.stderr, (r.returncode, r.stderr[-500:])
+
+
+def test_bench_dump_outputs_format(tmp_path):
+    """bench.dump_outputs on CPU stand-ins of the model's flat buffers at their real sizes: float32 .npy files, 64 MB at most
+    in all, the gradient sample drawn at the same indices every time; an eval mask too large for the limit is sampled.
+    --steps below 1 is refused."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+    model = types.SimpleNamespace(_flat=torch.randn(9823313, generator=g), _gflat=torch.randn(9823313, generator=g),
+                                  _bn_flat=torch.randn(2016, generator=g))
+    names = bench.dump_outputs(str(tmp_path / "a"), "train", model, torch.tensor(0.25))
+    bench.dump_outputs(str(tmp_path / "b"), "train", model, torch.tensor(0.25))
+    assert names == ["bn_running_stats", "grads_sample", "loss", "params"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+        total += (tmp_path / "a" / f"{n}.npy").stat().st_size
+    assert total <= 64 << 20
+    assert np.array_equal(np.load(tmp_path / "a" / "params.npy"), model._flat.numpy())
+    gs = np.load(tmp_path / "a" / "grads_sample.npy")
+    assert gs.size == bench.GRAD_SAMPLE and np.isin(gs, model._gflat.numpy()).all()
+    mask = torch.rand((216, 1, 512, 128), generator=g)
+    assert bench.dump_outputs(str(tmp_path / "e"), "eval", None, mask) == ["mask_sample"]
+    assert np.load(tmp_path / "e" / "mask_sample.npy").size == bench.MASK_LIMIT
+    assert bench.dump_outputs(str(tmp_path / "f"), "eval", None, mask[:16]) == ["mask"]
+    assert np.array_equal(np.load(tmp_path / "f" / "mask.npy"), mask[:16].numpy())
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
