@@ -26,10 +26,8 @@ static RedPlan red_plan(long P, int C) {
   r.sw = C < 32 ? C : 32;
   r.nslab = C / r.sw;
   r.lp = r.sw / 4;
-  long cap = svs_tune(SVS_TUNE_BN_BLOCKS) > 0 ? svs_tune(SVS_TUNE_BN_BLOCKS) : 512;
-  if (cap > 1024) cap = 1024;                       // (red_blocks: the workspaces' bound)
   long nb = (P * C) / 4096;
-  if (nb > cap) nb = cap;
+  if (nb > 512) nb = 512;
   long rows = nb / r.nslab;
   if (rows < 1) rows = 1;
   r.ppr = (P + rows - 1) / rows;

@@ -875,13 +875,38 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict_
 }
 
 // ---- host side -----------------------------------------------------------------------------------
-struct Bf16Plan { int BM, BN, cfg, ksplit, grid_y; long mtiles; };
-static Bf16Plan plan_bf16(int mode, long Mmax, int N, int nkt) {
+// One layer's launch, decided once for conv_bf16_run and the workspace layout: an LDS-window kernel for the shallow decoder layers
+// (whenever its tiles fill the chip), else the GEMM.  The GEMM tile and its K-split are planned for every layer: SVS_CONV_WINDOW=0
+// selects that form at any launch, so the workspace is sized for it.
+enum { BF16_GEMM, BF16_WINDOW };
+struct Bf16Plan {
+  int kind;
+  int wC, wTN, wTW;               // parity_window_bf16_kernel<C, TN, TW>
+  size_t lds;                     // its dynamic LDS
+  int BM, BN, cfg, ksplit, grid_y; long mtiles;
+  dim3 grid;
+  size_t slab_bytes;              // the GEMM form's split-K slabs
+};
+// LDS of parity_window_bf16_kernel<C, N / 16, TW>: window + weight buffers (all 25 taps when they fit 60 KB unpadded, else two)
+static size_t pw_lds(int C, int N, int TW) {
+  const size_t win = (size_t)(128 / TW + 2) * (TW + 2) * (C * 2 + 16);
+  const bool wall = 25L * N * (C * 2 + 16) <= 60 * 1024;
+  return win + (wall ? (size_t)25 * N * C * 2 : (size_t)2 * N * (C * 2 + 16));
+}
+static Bf16Plan plan_bf16(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, long ldx) {
   Bf16Plan pl{};
+  const long Mmax = mode == BF_GATHER ? (long)B * Ho * Wo : (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2);
+  const int nkt = (mode == BF_GATHER ? 25 : 4) * (C / 32);
   if (N % 128 == 0) { pl.cfg = Mmax >= 4096 ? 0 : 4; pl.BM = Mmax >= 4096 ? 128 : 64; pl.BN = 128; }
   else if (N == 64) { pl.cfg = 1; pl.BM = 128; pl.BN = 64; }
   else if (N == 32) { pl.cfg = 2; pl.BM = 256; pl.BN = 32; }
   else { pl.cfg = 3; pl.BM = 256; pl.BN = 16; }
+  if (svs_tune_on(SVS_TUNE_BF16_CFG)) {                       // sweeps: 0 128x128, 1 128x64, 4 64x128 (where N allows)
+    const int c = (int)svs_tune(SVS_TUNE_BF16_CFG);
+    if (c == 0 && N % 128 == 0) { pl.cfg = 0; pl.BM = 128; pl.BN = 128; }
+    if (c == 1 && N % 64 == 0) { pl.cfg = 1; pl.BM = 128; pl.BN = 64; }
+    if (c == 4 && N % 128 == 0) { pl.cfg = 4; pl.BM = 64; pl.BN = 128; }
+  }
   pl.mtiles = (Mmax + pl.BM - 1) / pl.BM;
   pl.grid_y = mode == BF_PARITY ? 4 : 1;
   const long blocks = pl.mtiles * (N / pl.BN) * pl.grid_y;
@@ -892,103 +917,70 @@ static Bf16Plan plan_bf16(int mode, long Mmax, int N, int nkt) {
     if (ks > cap) ks = cap;
     if (ks > 32) ks = 32;
   }
-  if (svs_tune_on(SVS_TUNE_BF16_CFG)) {                       // sweeps: 0 128x128, 1 128x64, 4 64x128 (where N allows)
-    const int c = (int)svs_tune(SVS_TUNE_BF16_CFG);
-    if (c == 0 && N % 128 == 0) { pl.cfg = 0; pl.BM = 128; pl.BN = 128; }
-    if (c == 1 && N % 64 == 0) { pl.cfg = 1; pl.BM = 128; pl.BN = 64; }
-    if (c == 4 && N % 128 == 0) { pl.cfg = 4; pl.BM = 64; pl.BN = 128; }
-    pl.mtiles = (Mmax + pl.BM - 1) / pl.BM;
-    const long blocks2 = pl.mtiles * (N / pl.BN) * pl.grid_y;
-    ks = 1;
-    if (blocks2 < 512) { ks = (int)((768 + blocks2 - 1) / blocks2); const int cap = nkt / 8 > 1 ? nkt / 8 : 1; if (ks > cap) ks = cap; if (ks > 32) ks = 32; }
-  }
-  if (svs_tune_on(SVS_TUNE_BF16_KSPLIT)) { const int f = (int)svs_tune(SVS_TUNE_BF16_KSPLIT); if (f >= 1 && f <= 32 && f <= nkt) ks = f; }   // sweeps
-  if (svs_tune_on(SVS_TUNE_BF16_CFG)) {                       // sweeps: 0 128x128, 1 128x64, 4 64x128 (where N allows)
-    const int c = (int)svs_tune(SVS_TUNE_BF16_CFG);
-    if (c == 0 && N % 128 == 0) { pl.cfg = 0; pl.BM = 128; pl.BN = 128; }
-    if (c == 1 && N % 64 == 0) { pl.cfg = 1; pl.BM = 128; pl.BN = 64; }
-    if (c == 4 && N % 128 == 0) { pl.cfg = 4; pl.BM = 64; pl.BN = 128; }
-    pl.mtiles = (Mmax + pl.BM - 1) / pl.BM;
-    const long blocks2 = pl.mtiles * (N / pl.BN) * pl.grid_y;
-    ks = 1;
-    if (blocks2 < 512) { ks = (int)((768 + blocks2 - 1) / blocks2); const int cap = nkt / 8 > 1 ? nkt / 8 : 1; if (ks > cap) ks = cap; if (ks > 32) ks = 32; }
-  }
   if (svs_tune_on(SVS_TUNE_BF16_KSPLIT)) { const int f = (int)svs_tune(SVS_TUNE_BF16_KSPLIT); if (f >= 1 && f <= 32 && f <= nkt) ks = f; }   // sweeps
   pl.ksplit = ks;
+  pl.slab_bytes = ks > 1 ? (size_t)ks * B * Ho * Wo * N * sizeof(float) : 0;
+  pl.kind = BF16_GEMM;
+  pl.grid = dim3((unsigned)(pl.mtiles * (N / pl.BN)), (unsigned)pl.ksplit, (unsigned)pl.grid_y);
+  if (svs_tune(SVS_TUNE_CONV_WINDOW) == 0 || mode != BF_PARITY || (long)H * W * ldx * 2 >= (1L << 31)) return pl;
+  // deconv4 / deconv5 on 8 x 16 tiles, persistent: two blocks per CU
+  const long wtiles = (long)B * ((H + 7) / 8) * ((W + 15) / 16);
+  if (((C == 128 && N == 32) || (C == 64 && N == 16)) && H >= 8 && W >= 16 && wtiles >= 128) {
+    pl.kind = BF16_WINDOW; pl.wC = C; pl.wTN = N / 16; pl.wTW = 16;
+    pl.grid = dim3((unsigned)(wtiles < 512 ? wtiles : 512));
+  }
+  // deconv3 (256 -> 64 channels on 32 x 8 anchors): the same kernel on 16 x 8 tiles.  In the GEMM form 1 GB goes from L2 to LDS
+  // per launch at 216 tiles (every anchor's 512 bytes once per tap, the 128 x 64 tile re-reading them for 64 channels only):
+  // 106 us; here the window is staged once and only the weights (819 KB per tile) stream.
+  const long wtiles8 = (long)B * ((H + 15) / 16) * ((W + 7) / 8);
+  if (C == 256 && N == 64 && W <= 8 && wtiles8 >= 128) {
+    pl.kind = BF16_WINDOW; pl.wC = 256; pl.wTN = 4; pl.wTW = 8;
+    pl.grid = dim3((unsigned)(wtiles8 < 256 ? wtiles8 : 256));
+  }
+  if (pl.kind == BF16_WINDOW) pl.lds = pw_lds(pl.wC, N, pl.wTW);
   return pl;
 }
+// (ldx = C: the stride enters the plan only through a 2 GiB guard, which conv_bf16_run's own limit on the view implies)
 static size_t bf16_layer_ws(int mode, int B, int H, int W, int C, int Ho, int Wo, int N) {
-  const long Mmax = mode == BF_GATHER ? (long)B * Ho * Wo : (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2);
-  const int nkt = (mode == BF_GATHER ? 25 : 4) * (C / 32);
-  const Bf16Plan pl = plan_bf16(mode, Mmax, N, nkt);
-  return pl.ksplit > 1 ? (size_t)pl.ksplit * B * Ho * Wo * N * sizeof(float) : 0;
+  return plan_bf16(mode, B, H, W, C, Ho, Wo, N, C).slab_bytes;
+}
+template <int C, int TN, int TW>
+static int launch_window_bf16(const ConvBf16Args& a, const Bf16Plan& pl, hipStream_t stream) {
+  SVS_HIP(hipFuncSetAttribute((const void*)parity_window_bf16_kernel<C, TN, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+  hipLaunchKernelGGL((parity_window_bf16_kernel<C, TN, TW>), pl.grid, dim3(256), pl.lds, stream, a);
+  return SVS_OK;
+}
+template <int MODE>
+static void launch_gemm_bf16(const ConvBf16Args& a, const Bf16Plan& pl, hipStream_t stream) {
+  switch (pl.cfg) {        // two K-tiles per barrier where the tile is 64 or 128 columns wide
+    case 0: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE, 128, 128, 2, 2, 2>), pl.grid, dim3(256), 0, stream, a); break;
+    case 1: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE, 128, 64, 2, 2, 2>), pl.grid, dim3(256), 0, stream, a); break;
+    case 2: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE, 256, 32, 4, 1, 1>), pl.grid, dim3(256), 0, stream, a); break;
+    case 3: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE, 256, 16, 4, 1, 1>), pl.grid, dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE, 64, 128, 2, 2, 2>), pl.grid, dim3(256), 0, stream, a); break;
+  }
 }
 static int conv_bf16_run(int mode, const u16* x, long ldx, int B, int H, int W, int C, const u16* wp, const float* shift, float slope,
                          u16* y, long ldy, int Ho, int Wo, int N, void* ws, size_t ws_bytes, hipStream_t stream) {
   SVS_REQUIRE(C % 32 == 0 && (N == 16 || N == 32 || N == 64 || N % 128 == 0), "conv_bf16: unsupported channels C=%d N=%d", C, N);
   SVS_REQUIRE(((long)B * H * W * ldx + 4L * (W + 2) * ldx) * 2 < (1L << 31) && (long)N * C * 25 * 2 < (1L << 31), "conv_bf16: view too large; split the batch");
-  const long Mmax = mode == BF_GATHER ? (long)B * Ho * Wo : (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2);
-  const int nkt = (mode == BF_GATHER ? 25 : 4) * (C / 32);
-  const Bf16Plan pl = plan_bf16(mode, Mmax, N, nkt);
+  const Bf16Plan pl = plan_bf16(mode, B, H, W, C, Ho, Wo, N, ldx);
   ConvBf16Args a{x, ldx, B, H, W, C, wp, shift, slope, y, ldy, Ho, Wo, N, pl.ksplit, nullptr};
-  // shallow decoder layers: LDS-window kernel (whenever its tiles fill the chip)
-  const long wtiles = (long)B * ((H + 7) / 8) * ((W + 15) / 16);
-  // LDS of parity_window_bf16_kernel<C, N / 16, TW>: window + weight buffers (all 25 taps when they fit 60 KB unpadded, else two)
-  auto pw_lds = [](int C_, int N_, int TW_) -> size_t {
-    const size_t win = (size_t)(128 / TW_ + 2) * (TW_ + 2) * (C_ * 2 + 16);
-    const bool wall = 25L * N_ * (C_ * 2 + 16) <= 60 * 1024;
-    return win + (wall ? (size_t)25 * N_ * C_ * 2 : (size_t)2 * N_ * (C_ * 2 + 16));
-  };
-  if (mode == BF_PARITY && ((C == 128 && N == 32) || (C == 64 && N == 16)) && H >= 8 && W >= 16 && wtiles >= 128 &&
-      (long)H * W * ldx * 2 < (1L << 31) && svs_tune(SVS_TUNE_CONV_WINDOW) != 0) {
+  if (pl.kind == BF16_WINDOW) {
     a.ksplit = 1;
-    const unsigned wgrid = (unsigned)(wtiles < 512 ? wtiles : 512);      // persistent: two blocks per CU
-    const size_t lds = pw_lds(C, N, 16);
-    if (C == 128) {
-      SVS_HIP(hipFuncSetAttribute((const void*)parity_window_bf16_kernel<128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((parity_window_bf16_kernel<128, 2>), dim3(wgrid), dim3(256), lds, stream, a);
-    } else {
-      SVS_HIP(hipFuncSetAttribute((const void*)parity_window_bf16_kernel<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((parity_window_bf16_kernel<64, 1>), dim3(wgrid), dim3(256), lds, stream, a);
-    }
-    SVS_CHECK_LAUNCH("parity_window_bf16");
-    return SVS_OK;
-  }
-  // deconv3 (256 -> 64 channels on 32 x 8 anchors): the same kernel on 16 x 8 tiles.  In the GEMM form 1 GB goes from L2 to LDS
-  // per launch at 216 tiles (every anchor's 512 bytes once per tap, the 128 x 64 tile re-reading them for 64 channels only):
-  // 106 us; here the window is staged once and only the weights (819 KB per tile) stream.  SVS_BF16_DECONV3_WINDOW=0: GEMM form.
-  const long wtiles8 = (long)B * ((H + 15) / 16) * ((W + 7) / 8);
-  if (mode == BF_PARITY && C == 256 && N == 64 && W <= 8 && wtiles8 >= 128 && (long)H * W * ldx * 2 < (1L << 31) &&
-      svs_tune(SVS_TUNE_CONV_WINDOW) != 0 && svs_tune(SVS_TUNE_BF16_DECONV3_WINDOW) != 0) {
-    a.ksplit = 1;
-    const size_t lds = pw_lds(256, 64, 8);
-    SVS_HIP(hipFuncSetAttribute((const void*)parity_window_bf16_kernel<256, 4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((parity_window_bf16_kernel<256, 4, 8>), dim3((unsigned)(wtiles8 < 256 ? wtiles8 : 256)), dim3(256), lds, stream, a);
+    int rc = pl.wC == 128 ? launch_window_bf16<128, 2, 16>(a, pl, stream)
+           : pl.wC == 64  ? launch_window_bf16<64, 1, 16>(a, pl, stream)
+                          : launch_window_bf16<256, 4, 8>(a, pl, stream);
+    if (rc) return rc;
     SVS_CHECK_LAUNCH("parity_window_bf16");
     return SVS_OK;
   }
   if (pl.ksplit > 1) {
-    const size_t need = (size_t)pl.ksplit * B * Ho * Wo * N * sizeof(float);
-    if (!ws || ws_bytes < need) { svs_set_error("conv_bf16: workspace too small (%zu < %zu)", ws_bytes, need); return SVS_ERR_WORKSPACE; }
+    if (!ws || ws_bytes < pl.slab_bytes) { svs_set_error("conv_bf16: workspace too small (%zu < %zu)", ws_bytes, pl.slab_bytes); return SVS_ERR_WORKSPACE; }
     a.slab = (float*)ws;
   }
-  dim3 grid((unsigned)(pl.mtiles * (N / pl.BN)), (unsigned)pl.ksplit, (unsigned)pl.grid_y);
-#define SVS_BF16_LAUNCH_KB(MODE_) \
-  switch (pl.cfg) { \
-    case 0: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE_, 128, 128, 2, 2, KB_>), grid, dim3(256), 0, stream, a); break; \
-    case 1: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE_, 128, 64, 2, 2, KB_>), grid, dim3(256), 0, stream, a); break; \
-    case 2: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE_, 256, 32, 4, 1, 1>), grid, dim3(256), 0, stream, a); break; \
-    case 3: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE_, 256, 16, 4, 1, 1>), grid, dim3(256), 0, stream, a); break; \
-    default: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE_, 64, 128, 2, 2, KB_>), grid, dim3(256), 0, stream, a); break; \
-  }
-  // K-tiles per barrier: 2 by default; BF16_KB = 1 / 2 / 4 for sweeps
-  const int kb = svs_tune_on(SVS_TUNE_BF16_KB) ? (int)svs_tune(SVS_TUNE_BF16_KB) : 2;
-#define SVS_BF16_LAUNCH(MODE_) \
-  if (kb >= 4) { constexpr int KB_ = 4; SVS_BF16_LAUNCH_KB(MODE_) } else if (kb == 2) { constexpr int KB_ = 2; SVS_BF16_LAUNCH_KB(MODE_) } \
-  else { constexpr int KB_ = 1; SVS_BF16_LAUNCH_KB(MODE_) }
-  if (mode == BF_GATHER) { SVS_BF16_LAUNCH(BF_GATHER) } else { SVS_BF16_LAUNCH(BF_PARITY) }
-#undef SVS_BF16_LAUNCH_KB
-#undef SVS_BF16_LAUNCH
+  if (mode == BF_GATHER) launch_gemm_bf16<BF_GATHER>(a, pl, stream);
+  else launch_gemm_bf16<BF_PARITY>(a, pl, stream);
   SVS_CHECK_LAUNCH("conv_gemm_bf16");
   if (pl.ksplit > 1) {
     const long P = (long)B * Ho * Wo, total4 = P * N / 4;
@@ -1109,7 +1101,7 @@ extern "C" int svs_unet_forward_eval_bf16(const void* prepared_bf16, const float
     const long ldx = 2L * BCH[k - 1];
     u16* y = k == 6 ? e.c6 : e.cat[k] + BCH[k];
     const long ldy = k == 6 ? 512 : 2L * BCH[k];
-    if (k == 3 && svs_tune(SVS_TUNE_BF16_CONV3_WINDOW) != 0) {           // LDS-window form (SVS_BF16_CONV3_WINDOW=0: the GEMM form)
+    if (k == 3) {                                                       // LDS-window form
       Conv3WinArgs c{x, ldx, B, e.h[2], e.w[2], (const u16*)(blob + L.w[2]), SH(2), 0.2f, y, ldy, e.h[3], e.w[3]};
       const long tiles = (long)B * ((e.h[3] + 7) / 8) * ((e.w[3] + 15) / 16);
       SVS_HIP(hipFuncSetAttribute((const void*)conv3_window_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CONV3_WIN_LDS));

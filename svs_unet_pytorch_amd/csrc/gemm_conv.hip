@@ -1003,19 +1003,32 @@ __global__ __launch_bounds__(256) void gather_window_kernel(ConvGemmArgs p, int 
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-struct ConvPlan { int cfg; int BM, BN; int ksplit; long mtiles; int grid_y; int pf; };
+// One call's launch, decided once (plan_conv_call): svs_conv_gemm_run launches it, svs_conv_gemm_workspace sizes it and
+// svs_conv_gemm_describe names it, so the three cannot disagree.
+enum ConvKind { CONV_GEMM, CONV_GATHER_WINDOW, CONV_PARITY_WINDOW, CONV_DIRECT };
+struct ConvPlan {
+  int kind;
+  int cfg, BM, BN, WM, WN, pf;    // GEMM tile (cfg: the case of launch_conv_gemm_cfg), K-tiles requested ahead
+  bool skip, split;               // tap skipping (batch-innermost rows), split-bf16 products (mfma_split.h)
+  long mtiles; int grid_y;        // M-tiles per parity class, parity classes
+  int wC, wCW, wTN, wNT;          // parity_window_kernel<C, CW, TN, NT>
+  int tpb, gtiles;                // gather_window_kernel: tiles per block, tiles
+  dim3 grid;
+  int ksplit;                     // slabs of the split-K epilogue (1: the kernel writes y itself)
+  ConvBal bal;                    // balanced splits (bal.enabled); rowsplit is pointed into the workspace at launch
+  size_t slab_bytes, rowtab_bytes;
+  long stat_rows;                 // rows of BatchNorm partials the kernel writes when asked (0: it cannot)
+};
 
-// `inference`: the call has the folded-BatchNorm epilogue (eval forward).  Those calls run at the serving batch sizes (1..16
-// tiles, BASELINE configs[0..1]) and take the rules of the batch-16 sweep; the training calls keep the batch-64 table (same-device
-// A/B: the batch-16 rules cost the batch-64 train step 0.6 %, and gain the batch-16 forward 3.6 %).
-static ConvPlan plan_conv(int mode, long Mmax, int N, int nkt_min, bool narrow = false, bool inference = false) {
-  ConvPlan pl{};
-  const bool v2 = inference && svs_tune(SVS_TUNE_CONV_PLAN) != 0;
+// GEMM tile and uniform K-split.  `inference`: the call has the folded-BatchNorm epilogue (eval forward).  Those calls run at the
+// serving batch sizes (1..16 tiles, BASELINE configs[0..1]) and take the rules of the batch-16 sweep; the training calls keep the
+// batch-64 table (same-device A/B: the batch-16 rules cost the batch-64 train step 0.6 %, and gain the batch-16 forward 3.6 %).
+static void plan_gemm_tile(int mode, long Mmax, int N, int nkt_min, bool narrow, bool inference, ConvPlan& pl) {
   if (N % 128 == 0) {
     if (Mmax <= 96) { pl.cfg = 4; pl.BM = 32; pl.BN = 128; }
     else { pl.cfg = 0; pl.BM = 128; pl.BN = 128; }
   } else if (N == 64) {
-    if (Mmax <= 512 || nkt_min <= 25 || (v2 && Mmax <= 16384)) { pl.cfg = 5; pl.BM = 64; pl.BN = 64; }      // (16 input channels: deconv5 backward-data, -9 % in the sweep; batch 16: conv3 forward 33 -> 27 us)
+    if (Mmax <= 512 || nkt_min <= 25 || (inference && Mmax <= 16384)) { pl.cfg = 5; pl.BM = 64; pl.BN = 64; }      // (16 input channels: deconv5 backward-data, -9 % in the sweep; batch 16: conv3 forward 33 -> 27 us)
     else { pl.cfg = 1; pl.BM = 128; pl.BN = 64; }
   } else if (N == 32) { pl.cfg = 2; pl.BM = 256; pl.BN = 32; }
   else { pl.cfg = 3; pl.BM = 256; pl.BN = 16; }
@@ -1026,15 +1039,15 @@ static ConvPlan plan_conv(int mode, long Mmax, int N, int nkt_min, bool narrow =
   // skip is exact per position, and 4x the tiles need a quarter of the K-splits (same-device sweep at B=64: 64x64
   // beats 128x128 on every such layer, by 20 % on the 8x2 parity layers).
   if (narrow && N % 64 == 0) { pl.cfg = 5; pl.BM = 64; pl.BN = 64; }
-  if (narrow && N == 128 && !(v2 && Mmax < (mode == MODE_PARITY ? 2048 : 8192))) { pl.cfg = 6; pl.BM = 64; pl.BN = 128; }     // (batch 64: deconv2 forward -9 %, conv4 fwd / conv5 bwd-data -2 %; batch 16: 64x64 is 10-15 % ahead)
+  if (narrow && N == 128 && !(inference && Mmax < (mode == MODE_PARITY ? 2048 : 8192))) { pl.cfg = 6; pl.BM = 64; pl.BN = 128; }     // (batch 64: deconv2 forward -9 %, conv4 fwd / conv5 bwd-data -2 %; batch 16: 64x64 is 10-15 % ahead)
   // conv5 forward (16x4 anchors, 128 -> 256 channels) with balanced K-splits (ConvBal): the 64x128 tile at 3 blocks per CU is
   // 13 % ahead of 64x64 in either form (68 vs 78 us at batch 64)
-  if (narrow && mode == MODE_GATHER && N == 256 && nkt_min == 200 && Mmax >= 4096 && Mmax % 64 == 0 && !v2 && svs_tune(SVS_TUNE_CONV_BALANCE) != 0) { pl.cfg = 6; pl.BM = 64; pl.BN = 128; }
+  if (narrow && mode == MODE_GATHER && N == 256 && nkt_min == 200 && Mmax >= 4096 && Mmax % 64 == 0 && !inference) { pl.cfg = 6; pl.BM = 64; pl.BN = 128; }
   // Optional split-bf16 product mode (mfma_split.h): the MFMA part of a K-tile is 2.7x shorter, the per-fragment limb split is
   // paid once per (row tile + column tile) of a wave, so LARGER wave tiles win (batch-64 sweep in that mode: 128x128 / 64x128
   // ahead of 64x64 by 8-30 % on every N >= 128 layer, 128x64 on the N = 64 ones), at two blocks per CU
-  const bool split = svs_tune(SVS_TUNE_MFMA_SPLIT) > 0 && svs_tune(SVS_TUNE_CONV_PLAN) != 0;
-  if (split && Mmax > 96) {
+  pl.split = svs_tune(SVS_TUNE_MFMA_SPLIT) > 0;
+  if (pl.split && Mmax > 96) {
     if (N % 128 == 0) {
       if (mode == MODE_GATHER && Mmax >= 4096) { pl.cfg = 0; pl.BM = 128; pl.BN = 128; }
       else { pl.cfg = 6; pl.BM = 64; pl.BN = 128; }
@@ -1045,11 +1058,14 @@ static ConvPlan plan_conv(int mode, long Mmax, int N, int nkt_min, bool narrow =
     const int c = (int)svs_tune(SVS_TUNE_CONV_CFG);
     if (c >= 0 && c < 7 && N % bn[c] == 0) { pl.cfg = c; pl.BM = bm[c]; pl.BN = bn[c]; }
   }
+  static const int wm[7] = {2, 2, 4, 4, 1, 2, 2};
+  pl.WM = wm[pl.cfg];
+  pl.WN = 4 / pl.WM;
   pl.mtiles = (Mmax + pl.BM - 1) / pl.BM;
   pl.grid_y = (mode == MODE_PARITY) ? 4 : 1;
   const long blocks = pl.mtiles * (N / pl.BN) * pl.grid_y;
   int ks = 1;
-  const long target = (mode == MODE_PARITY) ? 1024 : ((v2 || split) ? 512 : 768);     // (batch-16 sweep: two gather blocks per CU beat three on every layer)
+  const long target = (mode == MODE_PARITY) ? 1024 : ((inference || pl.split) ? 512 : 768);     // (batch-16 sweep: two gather blocks per CU beat three on every layer)
   if (blocks < ((mode == MODE_PARITY) ? 768 : 384)) {
     ks = (int)((target + blocks - 1) / blocks);
     // keep >= 8 K-tiles per split (16 in gather mode: with K = 25 or 50 tiles -- conv2 / conv3 at batch 16 -- finer
@@ -1062,97 +1078,19 @@ static ConvPlan plan_conv(int mode, long Mmax, int N, int nkt_min, bool narrow =
   }
   if (svs_tune_on(SVS_TUNE_CONV_KSPLIT)) { int f = (int)svs_tune(SVS_TUNE_CONV_KSPLIT); if (f >= 1 && f <= nkt_min) ks = f; }
   pl.ksplit = ks;
-  // K-tiles requested ahead: two on the 64-row tiles (same-device A/B of tools/ab_tune.py CONV_PF 1 2: train step at batch 64
-  // 3.530 -> 3.454 ms, eval forward 0.388 -> 0.379 ms at batch 16 and 1.030 -> 0.994 ms at batch 64: with 60-100 registers these
-  // tiles keep their occupancy, and one tile time -- 512 MFMA cycles -- is less than an L2 / Infinity-Cache round trip under load)
-  // (the 128x64 / 256x32 / 256x16 tiles: another -6 us on the train step, CONV_PF 2 against 3; the 128x128 and 32x128 tiles keep
-  //  one tile ahead: at 164 registers a second set costs the 128x128 tile its third resident block)
-  pl.pf = (pl.cfg == 5 || pl.cfg == 6 || (pl.cfg >= 1 && pl.cfg <= 3)) ? 2 : 1;
-  // CONV_PF (A/B runs): 1 = one tile ahead everywhere; 2 = two ahead on the 64-row tiles only; 3 = on every tile that has the variant
-  if (svs_tune_on(SVS_TUNE_CONV_PF)) {
-    const long f = svs_tune(SVS_TUNE_CONV_PF);
-    pl.pf = (f >= 2 && (pl.cfg == 5 || pl.cfg == 6)) || (f == 3 && pl.cfg >= 1 && pl.cfg <= 3) ? 2 : 1;
-  }
-  return pl;
-}
-
-template <int MODE, bool SPLIT>
-static void launch_conv_gemm_cfg(const ConvGemmArgs& a, const ConvPlan& pl, dim3 grid, hipStream_t stream, bool skip, const ConvBal& bal) {
-  dim3 block(256);
-  if (skip) {                                // batch-innermost rows + padding-tap skipping (deep levels)
-    switch (pl.cfg) {
-      case 0: hipLaunchKernelGGL((conv_gemm_kernel<MODE, 128, 128, 2, 2, true, SPLIT>), grid, block, 0, stream, a, bal); break;
-      case 1: if (pl.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, 128, 64, 2, 2, true, SPLIT, 2>), grid, block, 0, stream, a, bal);
-              else hipLaunchKernelGGL((conv_gemm_kernel<MODE, 128, 64, 2, 2, true, SPLIT>), grid, block, 0, stream, a, bal);
-              break;
-      case 4: hipLaunchKernelGGL((conv_gemm_kernel<MODE, 32, 128, 1, 4, true, SPLIT>), grid, block, 0, stream, a, bal); break;
-      case 6: if (pl.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, 64, 128, 2, 2, true, SPLIT, 2>), grid, block, 0, stream, a, bal);
-              else hipLaunchKernelGGL((conv_gemm_kernel<MODE, 64, 128, 2, 2, true, SPLIT>), grid, block, 0, stream, a, bal);
-              break;
-      default: if (pl.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, 64, 64, 2, 2, true, SPLIT, 2>), grid, block, 0, stream, a, bal);
-               else hipLaunchKernelGGL((conv_gemm_kernel<MODE, 64, 64, 2, 2, true, SPLIT>), grid, block, 0, stream, a, bal);
-               break;
-    }
-    return;
-  }
-  const ConvNoBal nb{};
-  switch (pl.cfg) {
-    case 0: hipLaunchKernelGGL((conv_gemm_kernel<MODE, 128, 128, 2, 2, false, SPLIT>), grid, block, 0, stream, a, nb); break;
-    case 1: if (pl.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, 128, 64, 2, 2, false, SPLIT, 2>), grid, block, 0, stream, a, nb);
-            else hipLaunchKernelGGL((conv_gemm_kernel<MODE, 128, 64, 2, 2, false, SPLIT>), grid, block, 0, stream, a, nb);
-            break;
-    case 2: if (pl.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, 256, 32, 4, 1, false, SPLIT, 2>), grid, block, 0, stream, a, nb);
-            else hipLaunchKernelGGL((conv_gemm_kernel<MODE, 256, 32, 4, 1, false, SPLIT>), grid, block, 0, stream, a, nb);
-            break;
-    case 3: if (pl.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, 256, 16, 4, 1, false, SPLIT, 2>), grid, block, 0, stream, a, nb);
-            else hipLaunchKernelGGL((conv_gemm_kernel<MODE, 256, 16, 4, 1, false, SPLIT>), grid, block, 0, stream, a, nb);
-            break;
-    case 4: hipLaunchKernelGGL((conv_gemm_kernel<MODE, 32, 128, 1, 4, false, SPLIT>), grid, block, 0, stream, a, nb); break;
-    case 6: if (pl.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, 64, 128, 2, 2, false, SPLIT, 2>), grid, block, 0, stream, a, nb);
-            else hipLaunchKernelGGL((conv_gemm_kernel<MODE, 64, 128, 2, 2, false, SPLIT>), grid, block, 0, stream, a, nb);
-            break;
-    default: if (pl.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, 64, 64, 2, 2, false, SPLIT, 2>), grid, block, 0, stream, a, nb);
-             else hipLaunchKernelGGL((conv_gemm_kernel<MODE, 64, 64, 2, 2, false, SPLIT>), grid, block, 0, stream, a, nb);
-             break;
-  }
-}
-template <int MODE>
-static int launch_conv_gemm(const ConvGemmArgs& a, const ConvPlan& pl, hipStream_t stream, bool skip, const ConvBal& bal) {
-  dim3 grid((unsigned)(pl.mtiles * (a.N / pl.BN)), (unsigned)pl.ksplit, (unsigned)pl.grid_y);      // (tiles, K-splits, parity classes)
-  if (skip && bal.enabled) grid = dim3(bal.first[pl.grid_y - 1][bal.npos[pl.grid_y - 1]], 1, 1);     // (class, position, M-tile, split, N-tile)
-  if (svs_tune(SVS_TUNE_MFMA_SPLIT) > 0) launch_conv_gemm_cfg<MODE, true>(a, pl, grid, stream, skip, bal);     // optional mode: mfma_split.h
-  else launch_conv_gemm_cfg<MODE, false>(a, pl, grid, stream, skip, bal);
-  SVS_CHECK_LAUNCH("conv_gemm");
-  return SVS_OK;
+  // K-tiles requested ahead: two on every tile but 128x128 and 32x128 (same-device A/B at batch 64, train step: 3.530 -> 3.454 ms
+  // for the 64-row tiles, another -6 us for 128x64 / 256x32 / 256x16; eval forward 0.388 -> 0.379 ms at batch 16).  The 128x128
+  // and 32x128 tiles keep one ahead: at 164 registers a second set costs the 128x128 tile its third resident block.
+  pl.pf = (pl.cfg == 0 || pl.cfg == 4) ? 1 : 2;
 }
 
 // Host side of ConvBal (see the struct): per-position split counts for a tap-skipping launch.  Returns the number of slabs
 // (the largest split count), 0 = not applicable / not worth it -> uniform grid.  Purely a function of the shape, so the
 // workspace query and the launch agree.
-static int plan_balance_search(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, const ConvPlan& pl, ConvBal* out);
-// memoised: the search walks a few hundred candidate plans of ~1000 blocks each (0.2-0.7 ms of host time -- per LAUNCH it would
-// cost more than the kernel it plans); a handful of distinct shapes per process
-static int plan_balance(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, const ConvPlan& pl, ConvBal* out) {
-  struct Key { int v[12]; bool operator==(const Key& o) const { return !memcmp(v, o.v, sizeof(v)); } };
-  struct Entry { Key k; int slabs; ConvBal bal; };
-  static std::mutex mu;
-  static std::vector<Entry> cache;
-  const Key key{{mode, B, H, W, C, Ho, Wo, N, pl.BM, pl.BN, pl.ksplit, (int)svs_tune(SVS_TUNE_CONV_BALANCE)}};
-  std::lock_guard<std::mutex> lock(mu);
-  for (const Entry& e : cache)
-    if (e.k == key) { if (out) { unsigned char* rs = out->rowsplit; *out = e.bal; out->rowsplit = rs; } return e.slabs; }
-  Entry e{};
-  e.k = key;
-  e.slabs = plan_balance_search(mode, B, H, W, C, Ho, Wo, N, pl, &e.bal);
-  if (cache.size() > 256) cache.clear();
-  cache.push_back(e);
-  if (out) { unsigned char* rs = out->rowsplit; *out = e.bal; out->rowsplit = rs; }
-  return e.slabs;
-}
-static int plan_balance_search(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, const ConvPlan& pl, ConvBal* out) {
-  if (out) out->enabled = 0;
-  if (svs_tune(SVS_TUNE_CONV_BALANCE) == 0 || pl.ksplit <= 1 || B % pl.BM != 0 || (C & (C - 1)) != 0) return 0;
-  const int ncls = (mode == MODE_PARITY) ? 4 : 1, cpt = C / 16, r = B / pl.BM, ntn = N / pl.BN;
+static int plan_balance_search(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, int BM, int BN, int ksplit, ConvBal* out) {
+  out->enabled = 0;
+  if (ksplit <= 1 || B % BM != 0 || (C & (C - 1)) != 0) return 0;
+  const int ncls = (mode == MODE_PARITY) ? 4 : 1, cpt = C / 16, r = B / BM, ntn = N / BN;
   int npos[4] = {0, 0, 0, 0}, nvk[4][64];
   long total = 0;
   for (int c = 0; c < ncls; ++c) {
@@ -1170,102 +1108,86 @@ static int plan_balance_search(int mode, int B, int H, int W, int C, int Ho, int
       total += (long)nvk[c][pos] * r * ntn;
     }
   }
-  // candidates: target work per block T (in K-tiles) and a cap on the splits; cost = load of the most loaded CU when the
-  // blocks go to the 256 CUs round-robin in launch order (how the dispatcher is observed to place a grid that is resident at
-  // once; only speed depends on it), each block paying a fixed prologue / epilogue share, plus the epilogue's slab traffic
-  const int NCU = 256;
-  // (units: one K-tile of one block = 4 * TM * TN MFMAs per wave; a 64x64 tile's is 512 cycles.  Fixed cost per block ~ 3 such;
-  //  a slab tile's write + read in the epilogue ~ 0.03 of them chip-wide, whatever the tile: bytes and unit both scale with it)
-  const double OVH = 3.0 * 4096.0 / (pl.BM * pl.BN), SLAB = 0.03;
-  const int smax_hi = pl.ksplit * 2 < 16 ? pl.ksplit * 2 : 16;
-  double best = 1e30;
-  int best_cap = 0; double best_T = 0, best_load = 0;
-  static thread_local double load[256];
-  // Same-device sweep at batch 64 (tools/gemm_sweep.py --ab-env CONV_BALANCE, targets 512 .. 1536): multiples of 256 blocks win
-  // (the round-robin model), 3 per CU for the GATHER direction and 5 per CU for the PARITY one; the 8x2-anchor layers gain
-  // 10-15 % (conv6 / deconv1, both directions), conv5 forward 13 % with the 64x128 tile, the 16x4-anchor PARITY layers LOSE
-  // 5-10 % (their uniform grid is 256 blocks per parity class, which round-robin already spreads evenly): rule below.
+  // Same-device sweep at batch 64 (tools/gemm_sweep.py, targets 512 .. 1536): multiples of 256 blocks win, 3 per CU for the GATHER
+  // direction and 5 per CU for the PARITY one; the 8x2-anchor layers gain 10-15 % (conv6 / deconv1, both directions), conv5 forward
+  // 13 % with the 64x128 tile, the 16x4-anchor PARITY layers LOSE 5-10 % (their uniform grid is 256 blocks per parity class, which
+  // round-robin already spreads evenly): rule below.
   int max_pos = 0;
   for (int c = 0; c < ncls; ++c) max_pos = npos[c] > max_pos ? npos[c] : max_pos;
-  const bool tuned = max_pos <= 16 || (mode == MODE_GATHER && max_pos <= 64 && pl.BN == 128);
-  long force_nb = svs_tune(SVS_TUNE_CONV_BALANCE) >= 16 ? svs_tune(SVS_TUNE_CONV_BALANCE) : 0;     // sweeps: aim at this many blocks
-  if (!force_nb && svs_tune(SVS_TUNE_CONV_BALANCE) != 3) {      // (3: the cost-model search below, for comparison)
-    if (!tuned) return 0;
-    force_nb = mode == MODE_GATHER ? 768 : 1280;
-  }
-  const int caps[2] = {force_nb ? 16 : pl.ksplit, force_nb ? 16 : smax_hi};
-  for (int ci = 0; ci < 2; ++ci) {
-    const int cap = caps[ci];
-    if (ci == 1 && cap == caps[0]) break;
-    // (block counts around the uniform plan's: that count -- 3 to 4 resident blocks per CU -- came out of the tile / split sweeps,
-    //  and the model knows nothing about latency hiding)
-    const long nb_uniform = pl.mtiles * ntn * pl.grid_y * pl.ksplit;
-    // a target count: the largest plan that does NOT exceed it (one block too many puts a whole extra block on some CUs);
-    // no target: every size around the uniform plan's, by the cost model
-    const long nb_lo = force_nb ? force_nb / 2 : nb_uniform * 7 / 8, nb_hi = force_nb ? force_nb : nb_uniform * 11 / 8;
-    for (long nb = nb_hi; nb >= nb_lo; nb -= 4) {
-      const double T = (double)total / nb;
-      for (int i = 0; i < NCU; ++i) load[i] = 0.0;
-      long idx = 0, slabs = 0;
-      for (int c = 0; c < ncls; ++c)
-        for (int pos = 0; pos < npos[c]; ++pos) {
-          int sp = (int)(nvk[c][pos] / T + 0.5);
-          sp = sp < 1 ? 1 : sp > cap ? cap : sp;
-          if (sp > nvk[c][pos]) sp = nvk[c][pos];
-          slabs += (long)sp * r * ntn;
-          for (int i = 0; i < r; ++i)
-            for (int j = 0; j < sp; ++j) {
-              const double w = (double)((long)nvk[c][pos] * (j + 1) / sp - (long)nvk[c][pos] * j / sp) + OVH;
-              for (int n = 0; n < ntn; ++n) load[idx++ % NCU] += w;
-            }
-        }
-      double mx = 0.0;
-      for (int i = 0; i < NCU; ++i) mx = load[i] > mx ? load[i] : mx;
-      const double cost = mx + SLAB * (double)slabs;
-      if (force_nb) {
-        if (idx <= force_nb) { best = cost; best_cap = cap; best_T = T; best_load = mx; break; }
-        continue;
-      }
-      if (cost < best) { best = cost; best_cap = cap; best_T = T; best_load = mx; }
-    }
-  }
-  if (best_cap == 0) return 0;
-  // coarse cases (few splits per position, e.g. batch 128 with two M-tiles per position) do not come out even: keep the
-  // uniform grid unless the modelled load of the most loaded CU is within 12 % of the mean (sweeps with a forced target excepted)
-  {
-    long nblk = 0;
+  if (!(max_pos <= 16 || (mode == MODE_GATHER && max_pos <= 64 && BN == 128))) return 0;
+  const long target = mode == MODE_GATHER ? 768 : 1280;
+  // splits of a position: its share of the valid K-tiles at T K-tiles per block, at most 16 and at most one per K-tile
+  auto splits = [&](int c, int pos, double T) {
+    int sp = (int)(nvk[c][pos] / T + 0.5);
+    sp = sp < 1 ? 1 : sp > 16 ? 16 : sp;
+    return sp > nvk[c][pos] ? nvk[c][pos] : sp;
+  };
+  // the largest plan that does NOT exceed the target (one block too many puts a whole extra block on some CUs)
+  double T = 0;
+  long nblk = 0;
+  for (long nb = target; nb >= target / 2 && !nblk; nb -= 4) {
+    const double t = (double)total / nb;
+    long idx = 0;
     for (int c = 0; c < ncls; ++c)
-      for (int pos = 0; pos < npos[c]; ++pos) {
-        int sp = (int)(nvk[c][pos] / best_T + 0.5);
-        sp = sp < 1 ? 1 : sp > best_cap ? best_cap : sp;
-        if (sp > nvk[c][pos]) sp = nvk[c][pos];
-        nblk += (long)sp * r * ntn;
-      }
-    const double mean = ((double)total + OVH * (double)nblk) / NCU;
-    if (svs_tune(SVS_TUNE_CONV_BALANCE) < 16 && best_load > 1.12 * mean) return 0;
+      for (int pos = 0; pos < npos[c]; ++pos) idx += (long)splits(c, pos, t) * r * ntn;
+    if (idx <= target) { T = t; nblk = idx; }
   }
+  if (!nblk) return 0;
+  // Coarse cases (few splits per position, e.g. batch 128 with two M-tiles per position) do not come out even: keep the uniform
+  // grid unless the most loaded CU is within 12 % of the mean, when the blocks go to the 256 CUs round-robin in launch order (how
+  // the dispatcher is observed to place a grid that is resident at once) and each block pays a fixed prologue / epilogue share
+  // (units: one K-tile of one block; fixed cost per block ~ 3 K-tiles of a 64x64 tile).
+  const int NCU = 256;
+  const double OVH = 3.0 * 4096.0 / (BM * BN);
+  double load[NCU] = {};
+  long idx = 0;
+  for (int c = 0; c < ncls; ++c)
+    for (int pos = 0; pos < npos[c]; ++pos) {
+      const int sp = splits(c, pos, T);
+      for (int i = 0; i < r; ++i)
+        for (int j = 0; j < sp; ++j) {
+          const double w = (double)((long)nvk[c][pos] * (j + 1) / sp - (long)nvk[c][pos] * j / sp) + OVH;
+          for (int n = 0; n < ntn; ++n) load[idx++ % NCU] += w;
+        }
+    }
+  double most = 0.0;
+  for (int i = 0; i < NCU; ++i) most = load[i] > most ? load[i] : most;
+  if (most > 1.12 * (((double)total + OVH * (double)nblk) / NCU)) return 0;
   int S = 1;
   unsigned at = 0;
   for (int c = 0; c < 4; ++c) {
-    if (out) out->npos[c] = npos[c];
+    out->npos[c] = npos[c];
     for (int pos = 0; pos < npos[c]; ++pos) {
-      int sp = (int)(nvk[c][pos] / best_T + 0.5);
-      sp = sp < 1 ? 1 : sp > best_cap ? best_cap : sp;
-      if (sp > nvk[c][pos]) sp = nvk[c][pos];
+      const int sp = splits(c, pos, T);
       S = sp > S ? sp : S;
-      if (out) { out->first[c][pos] = at; out->nsplit[c][pos] = (unsigned char)sp; }
+      out->first[c][pos] = at; out->nsplit[c][pos] = (unsigned char)sp;
       at += (unsigned)(sp * r * ntn);
     }
-    if (out) out->first[c][npos[c]] = at;
-    if (out && c + 1 < 4 && c + 1 >= ncls) { out->first[c + 1][0] = at; }
+    out->first[c][npos[c]] = at;
+    if (c + 1 < 4 && c + 1 >= ncls) { out->first[c + 1][0] = at; }
   }
   if (S <= 1) return 0;                       // (a layer that needs no slabs stays on its direct epilogue)
-  if (out) out->enabled = 1;
-  if (out && svs_tune(SVS_TUNE_CONV_BALANCE) == 2)      // sweeps: show the plan
-    fprintf(stderr, "[svs] balanced splits mode %d B %d in %dx%dx%d N %d tile %dx%d: uniform ks %d -> slabs %d, %u blocks (%.2f per CU), "
-            "%.1f K-tiles per block, most loaded CU %.0f (+ slabs: %.0f) vs mean %.0f\n", mode, B, H, W, C, N, pl.BM, pl.BN, pl.ksplit, S, at,
-            at / 256.0, best_T, best_load, best, (double)total / NCU);
+  out->enabled = 1;
   return S;
+}
+// memoised: the search walks up to a hundred candidate plans of ~1000 blocks each -- per LAUNCH it would cost more host time than
+// the kernel it plans; a handful of distinct shapes per process
+static int plan_balance(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, int BM, int BN, int ksplit, ConvBal* out) {
+  struct Key { int v[11]; bool operator==(const Key& o) const { return !memcmp(v, o.v, sizeof(v)); } };
+  struct Entry { Key k; int slabs; ConvBal bal; };
+  static std::mutex mu;
+  static std::vector<Entry> cache;
+  const Key key{{mode, B, H, W, C, Ho, Wo, N, BM, BN, ksplit}};
+  std::lock_guard<std::mutex> lock(mu);
+  for (const Entry& e : cache)
+    if (e.k == key) { *out = e.bal; return e.slabs; }
+  Entry e{};
+  e.k = key;
+  e.slabs = plan_balance_search(mode, B, H, W, C, Ho, Wo, N, BM, BN, ksplit, &e.bal);
+  if (cache.size() > 256) cache.clear();
+  cache.push_back(e);
+  *out = e.bal;
+  return e.slabs;
 }
 
 static int check_gemm_args(const char* who, const float* x, long ldx, int B, int H, int W, int C, const float* wp,
@@ -1279,40 +1201,125 @@ static int check_gemm_args(const char* who, const float* x, long ldx, int B, int
   return SVS_OK;
 }
 
-// LDS-window kernel for the shallow parity layers (N = 16 / 32, C = 32 / 64 / 128, large images)
-static int use_parity_window(int mode, int B, int H, int W, int C, int N, long ldx) {
-  const bool eligible = mode == MODE_PARITY && (N == 16 || N == 32) && (C == 32 || C == 64 || C == 128) &&
-                        ((long)H * W * ldx) * 4 < (1L << 31);
-  const bool fills_gpu = H >= 8 && W >= 16 && (long)B * ((H + 7) / 8) * ((W + 15) / 16) >= 128;   // (B=16 sweep: still ahead of the direct kernel at 128 blocks)
-  int window = eligible && fills_gpu;
-  if (svs_tune_on(SVS_TUNE_CONV_WINDOW)) {     // sweeps and tests: 0 = never, 2 = whenever the shape is eligible, 3 = same and
-    const int f = (int)svs_tune(SVS_TUNE_CONV_WINDOW);          // never with the channel halves in separate blocks
-    window = (f == 0) ? 0 : (f == 2 || f == 3) ? eligible : window;
+// The launch of one call.  Call facts beside the shape: `inference` (folded-BatchNorm epilogue) and `accumulate`.  `gemm_only`:
+// the GEMM form of the call, which the window and direct kernels fall back to (and SVS_CONV_WINDOW / SVS_CONV_GWINDOW = 0 select).
+static ConvPlan plan_conv_call(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, long ldx, bool inference, bool accumulate,
+                               bool gemm_only = false) {
+  ConvPlan p{};
+  const long Mmax = (mode == MODE_GATHER) ? (long)B * Ho * Wo : (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2);
+  const int nkt_min = (mode == MODE_GATHER ? 25 : 4) * (C / 16);
+  const long P = (long)B * Ho * Wo;
+  const bool view_32bit = ((long)B * H * W * ldx + 4L * (W + 2) * ldx) * 4 < (1L << 31);
+  const bool image_32bit = ((long)H * W * ldx) * 4 < (1L << 31);
+  p.ksplit = 1;
+  // conv2 forward: LDS-window form of the GATHER mode (SVS_CONV_GWINDOW=0: the GEMM kernel)
+  const long gtiles = (long)B * ((Ho + 7) / 8) * ((Wo + 15) / 16);
+  const long gw = svs_tune(SVS_TUNE_CONV_GWINDOW);
+  if (!gemm_only && mode == MODE_GATHER && C == 16 && N == 32 && !accumulate && gw != 0 && image_32bit &&
+      (gw == 2 /* tests: whenever the layer is eligible */ || (Ho >= 8 && Wo >= 16 && gtiles >= 256)) && gtiles < (1L << 30)) {
+    const long tblocks = gw >= 16 ? gw : 512;     // (>= 16: sweeps)
+    int tpb = (int)(gtiles / tblocks);            // one round of two resident blocks per CU; >= 1 tile per block
+    if (tpb < 1) tpb = 1;
+    if (tpb > 8) tpb = 8;
+    p.kind = CONV_GATHER_WINDOW;
+    p.tpb = tpb; p.gtiles = (int)gtiles;
+    p.grid = dim3((unsigned)((gtiles + tpb - 1) / tpb));
+    p.stat_rows = p.grid.x;
+    return p;
   }
-  return window;
-}
-
-// 32 output channels and at most one tile per CU (batch <= 32): the two 16-channel halves go to different blocks, each
-// staging the window itself (same-device A/B of the eval forward: batch 16 -7 %, batch 32 -1 %, batch 64 +2 %)
-static bool parity_window_halves(long tiles) {
-  return tiles <= 256 && !(svs_tune_on(SVS_TUNE_CONV_WINDOW) && svs_tune(SVS_TUNE_CONV_WINDOW) == 3);
-}
-
-static bool narrow_level(int mode, int B, int C, int Wo, int N) {
-  if (svs_tune_on(SVS_TUNE_CONV_SKIP) || svs_tune_on(SVS_TUNE_CONV_KORDER)) return false;          // sweeps and tests keep the generic tiles
-  return N > 32 && (C & (C - 1)) == 0 && B >= 16 && ((mode == MODE_GATHER) ? Wo : (Wo + 1) / 2) <= 8;
-}
-
-// narrow levels: batch-innermost rows so that whole taps of an M-tile fall into the padding and are skipped
-static int use_tap_skip(int mode, int B, int C, int Wo, int N, int cfg) {
-  const bool can = N > 32 /* tap-outer K order */ && (C & (C - 1)) == 0 && (cfg == 0 || cfg == 1 || cfg == 4 || cfg == 5 || cfg == 6);
-  int skip = can && B >= 16 && ((mode == MODE_GATHER) ? Wo : (Wo + 1) / 2) <= 8;
-  if (svs_tune_on(SVS_TUNE_CONV_SKIP)) {     // sweeps and tests: 0 = never, 2 = whenever the kernel supports it
-    const int f = (int)svs_tune(SVS_TUNE_CONV_SKIP);
-    skip = (f == 0) ? 0 : (f == 2) ? can : skip;
+  // LDS-window kernel for the shallow parity layers (N = 16 / 32, C = 32 / 64 / 128, large images).  SVS_CONV_WINDOW (sweeps and
+  // tests): 0 = never, 2 = whenever the shape is eligible, 3 = same and never with the channel halves in separate blocks
+  const long cw = svs_tune(SVS_TUNE_CONV_WINDOW);
+  const bool pw_eligible = mode == MODE_PARITY && (N == 16 || N == 32) && (C == 32 || C == 64 || C == 128) && image_32bit;
+  const long wtiles = (long)B * ((H + 7) / 8) * ((W + 15) / 16);
+  const bool fills_gpu = H >= 8 && W >= 16 && wtiles >= 128;   // (B=16 sweep: still ahead of the direct kernel at 128 blocks)
+  if (!gemm_only && pw_eligible && cw != 0 && (fills_gpu || cw == 2 || cw == 3)) {
+    p.kind = CONV_PARITY_WINDOW;
+    p.wC = C; p.wCW = C == 32 ? 32 : 64;
+    p.grid = dim3((unsigned)wtiles);
+    // 32 output channels and at most one tile per CU (batch <= 32): the two 16-channel halves go to different blocks, each
+    // staging the window itself (same-device A/B of the eval forward: batch 16 -7 %, batch 32 -1 %, batch 64 +2 %)
+    if (N == 32 && wtiles <= 256 && cw != 3) { p.wTN = 1; p.wNT = 2; p.grid.y = 2; }
+    else { p.wTN = N / 16; p.wNT = N / 16; }
+    p.stat_rows = p.grid.x;
+    return p;
   }
-  if (svs_tune_on(SVS_TUNE_CONV_KORDER)) skip = 0;           // (the K-order sweep switch may select tap-inner order)
-  return skip;
+  // LDS-free kernel for the 16-channel outputs (same-device A/B: 1.2-1.3x there; N = 32 is mixed, so it stays on the LDS kernel
+  // except in parity mode with a deep reduction); 64 rows per wave (128 measured slower)
+  if (!gemm_only && Mmax >= 16384 && view_32bit && (N == 16 || (N == 32 && mode == MODE_PARITY && C >= 128))) {
+    p.kind = CONV_DIRECT;
+    p.grid = dim3((unsigned)((Mmax + 255) / 256), mode == MODE_PARITY ? 4 : 1);     // 4 independent waves per block, 64 rows each
+    return p;
+  }
+  p.kind = CONV_GEMM;
+  // narrow levels: batch-innermost rows so that whole taps of an M-tile fall into the padding and are skipped.  SVS_CONV_SKIP
+  // (sweeps and tests; it also keeps the generic tiles): 0 = never, 2 = whenever the kernel supports it
+  const long cs = svs_tune(SVS_TUNE_CONV_SKIP);
+  const bool narrow_shape = N > 32 && (C & (C - 1)) == 0 && B >= 16 && ((mode == MODE_GATHER) ? Wo : (Wo + 1) / 2) <= 8;
+  plan_gemm_tile(mode, Mmax, N, nkt_min, narrow_shape && cs < 0, inference, p);
+  const bool can_skip = N > 32 /* tap-outer K order */ && (C & (C - 1)) == 0 && p.BN >= 64;
+  p.skip = cs == 0 ? false : cs == 2 ? can_skip : can_skip && narrow_shape;
+  p.grid = dim3((unsigned)(p.mtiles * (N / p.BN)), (unsigned)p.ksplit, (unsigned)p.grid_y);      // (tiles, K-splits, parity classes)
+  const int slabs = p.skip ? plan_balance(mode, B, H, W, C, Ho, Wo, N, p.BM, p.BN, p.ksplit, &p.bal) : 0;
+  if (slabs) {                                 // the largest split count of any position; 1-D grid (class, position, M-tile, split, N-tile)
+    p.ksplit = slabs;
+    p.grid = dim3(p.bal.first[p.grid_y - 1][p.bal.npos[p.grid_y - 1]], 1, 1);
+    p.rowtab_bytes = svs_align_up((size_t)P, 16);
+  }
+  if (p.ksplit > 1) p.slab_bytes = (size_t)p.ksplit * P * N * sizeof(float);
+  else p.stat_rows = p.mtiles * p.grid_y;      // one row of partials per (parity class, M-tile)
+  return p;
+}
+
+// one tile shape; the tap-skipping form exists for the tiles at least 64 wide, the two-ahead form for all but 128x128 and 32x128
+template <int MODE, bool SPLIT, int BM, int BN, int WM, int WN>
+static void launch_conv_gemm_tile(const ConvGemmArgs& a, const ConvPlan& p, hipStream_t stream) {
+  constexpr int PF2 = (BM == 128 && BN == 128) || BM == 32 ? 1 : 2;
+  if constexpr (BN >= 64) {
+    if (p.skip) {
+      if (p.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, true, SPLIT, PF2>), p.grid, dim3(256), 0, stream, a, p.bal);
+      else hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, true, SPLIT, 1>), p.grid, dim3(256), 0, stream, a, p.bal);
+      return;
+    }
+  }
+  if (p.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, SPLIT, PF2>), p.grid, dim3(256), 0, stream, a, ConvNoBal{});
+  else hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, SPLIT, 1>), p.grid, dim3(256), 0, stream, a, ConvNoBal{});
+}
+template <int MODE, bool SPLIT>
+static void launch_conv_gemm_cfg(const ConvGemmArgs& a, const ConvPlan& p, hipStream_t stream) {
+  switch (p.cfg) {
+    case 0: launch_conv_gemm_tile<MODE, SPLIT, 128, 128, 2, 2>(a, p, stream); break;
+    case 1: launch_conv_gemm_tile<MODE, SPLIT, 128, 64, 2, 2>(a, p, stream); break;
+    case 2: launch_conv_gemm_tile<MODE, SPLIT, 256, 32, 4, 1>(a, p, stream); break;
+    case 3: launch_conv_gemm_tile<MODE, SPLIT, 256, 16, 4, 1>(a, p, stream); break;
+    case 4: launch_conv_gemm_tile<MODE, SPLIT, 32, 128, 1, 4>(a, p, stream); break;
+    case 6: launch_conv_gemm_tile<MODE, SPLIT, 64, 128, 2, 2>(a, p, stream); break;
+    default: launch_conv_gemm_tile<MODE, SPLIT, 64, 64, 2, 2>(a, p, stream); break;
+  }
+}
+template <int MODE>
+static void launch_conv_plan(const ConvGemmArgs& a, const ConvPlan& p, hipStream_t stream) {
+  switch (p.kind) {
+    case CONV_GATHER_WINDOW: hipLaunchKernelGGL(gather_window_kernel, p.grid, dim3(256), 0, stream, a, p.gtiles, p.tpb); break;
+    case CONV_PARITY_WINDOW:
+#define SVS_LAUNCH_WINDOW(C_, CW_, TN_, NT_) hipLaunchKernelGGL((parity_window_kernel<C_, CW_, TN_, NT_>), p.grid, dim3(256), 0, stream, a)
+      if (p.wNT == 1) {
+        if (p.wC == 32) SVS_LAUNCH_WINDOW(32, 32, 1, 1); else if (p.wC == 64) SVS_LAUNCH_WINDOW(64, 64, 1, 1); else SVS_LAUNCH_WINDOW(128, 64, 1, 1);
+      } else if (p.wTN == 1) {
+        if (p.wC == 32) SVS_LAUNCH_WINDOW(32, 32, 1, 2); else if (p.wC == 64) SVS_LAUNCH_WINDOW(64, 64, 1, 2); else SVS_LAUNCH_WINDOW(128, 64, 1, 2);
+      } else {
+        if (p.wC == 32) SVS_LAUNCH_WINDOW(32, 32, 2, 2); else if (p.wC == 64) SVS_LAUNCH_WINDOW(64, 64, 2, 2); else SVS_LAUNCH_WINDOW(128, 64, 2, 2);
+      }
+#undef SVS_LAUNCH_WINDOW
+      break;
+    case CONV_DIRECT:
+      if (a.N == 16) hipLaunchKernelGGL((conv_direct_kernel<MODE, 4, 1>), p.grid, dim3(256), 0, stream, a);
+      else hipLaunchKernelGGL((conv_direct_kernel<MODE, 4, 2>), p.grid, dim3(256), 0, stream, a);
+      break;
+    default:
+      if (p.split) launch_conv_gemm_cfg<MODE, true>(a, p, stream);
+      else launch_conv_gemm_cfg<MODE, false>(a, p, stream);
+  }
 }
 
 // Shared by enc fwd / dec bwd_data (GATHER) and dec fwd / enc bwd_data (PARITY).
@@ -1323,203 +1330,95 @@ int svs_conv_gemm_run(int mode, const float* x, long ldx, int B, int H, int W, i
   if (stats_nblk) *stats_nblk = 0;
   int rc = check_gemm_args(who, x, ldx, B, H, W, C, wp, y, ldy, Ho, Wo, N);
   if (rc) return rc;
-  long Mmax;
-  int nkt_min;
-  if (mode == MODE_GATHER) {
+  if (mode == MODE_GATHER)
     SVS_REQUIRE(Ho == svs_conv_out(H) && Wo == svs_conv_out(W), "%s: output %dx%d does not match input %dx%d", who, Ho, Wo, H, W);
-    Mmax = (long)B * Ho * Wo;
-    nkt_min = 25 * (C / 16);
-  } else {
+  else
     SVS_REQUIRE((Ho == 2 * H || Ho == 2 * H - 1) && (Wo == 2 * W || Wo == 2 * W - 1),
                 "%s: output %dx%d unreachable from input %dx%d", who, Ho, Wo, H, W);
-    Mmax = (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2);
-    nkt_min = 4 * (C / 16);
-  }
   // operands are addressed with 32-bit byte offsets (buffer loads): each view must stay below 2 GiB
   SVS_REQUIRE(((long)B * H * W * ldx + 4L * (W + 2) * ldx) * 4 < (1L << 31) && (long)N * C * 25 * 4 < (1L << 31),
               "%s: input view of %ld bytes needs 64-bit offsets; split the batch", who, (long)B * H * W * ldx * 4);
-  ConvPlan pl = plan_conv(mode, Mmax, N, nkt_min, narrow_level(mode, B, C, Wo, N), scale != nullptr);
+  ConvPlan p = plan_conv_call(mode, B, H, W, C, Ho, Wo, N, ldx, scale != nullptr, accumulate != 0);
+  const size_t need = p.slab_bytes + p.rowtab_bytes;
+  if (need && (!ws || ws_bytes < need || !svs_aligned16(ws))) {
+    svs_set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    return SVS_ERR_WORKSPACE;
+  }
   ConvGemmArgs a{};
   a.x = x; a.ldx = ldx; a.B = B; a.H = H; a.W = W; a.C = C; a.wp = wp;
   a.bias = bias; a.scale = scale; a.shift = shift; a.slope = slope;
   a.y = y; a.ldy = ldy; a.Ho = Ho; a.Wo = Wo; a.N = N; a.accumulate = accumulate;
-  a.slab = nullptr;
-  // With few output channels the im2col operand dominates the traffic; consuming all taps of a 16-channel
-  // chunk before the next chunk keeps a block's re-read window in cache (same-device A/B: 5% faster for the
-  // N<=32 layers, 1-2% slower for the deep ones, hence the switch).
+  a.ksplit = p.ksplit;
+  a.slab = p.ksplit > 1 ? (float*)ws : nullptr;
+  if (p.bal.enabled) p.bal.rowsplit = (unsigned char*)ws + p.slab_bytes;
+  // With few output channels the im2col operand dominates the traffic; consuming all taps of a 16-channel chunk before the next
+  // chunk keeps a block's re-read window in cache (same-device A/B: 5% faster for the N<=32 layers, 1-2% slower for the deep ones).
   a.cpt_shift = -1;
   if ((C & (C - 1)) == 0) { a.cpt_shift = 0; while ((16 << a.cpt_shift) < C) ++a.cpt_shift; }
   a.tap_inner = N <= 32;
-  if (svs_tune_on(SVS_TUNE_CONV_KORDER)) a.tap_inner = svs_tune(SVS_TUNE_CONV_KORDER) != 0;     // sweeps only
-  const long P = (long)B * Ho * Wo;
-  const int window = use_parity_window(mode, B, H, W, C, N, ldx);
-  if (window) pl.ksplit = 1;
-  ConvBal bal{};
-  const int nslab_bal = (!window && use_tap_skip(mode, B, C, Wo, N, pl.cfg)) ? plan_balance(mode, B, H, W, C, Ho, Wo, N, pl, &bal) : 0;
-  if (nslab_bal) pl.ksplit = nslab_bal;          // slabs = the largest split count of any position
-  a.ksplit = pl.ksplit;
-  if (pl.ksplit > 1) {
-    const size_t need = (size_t)pl.ksplit * P * N * sizeof(float) + (nslab_bal ? svs_align_up((size_t)P, 16) : 0);
-    if (!ws || ws_bytes < need || !svs_aligned16(ws)) {
-      svs_set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-      return SVS_ERR_WORKSPACE;
-    }
-    a.slab = (float*)ws;
-    if (nslab_bal) bal.rowsplit = (unsigned char*)ws + (size_t)pl.ksplit * P * N * sizeof(float);
-  }
-  // LDS-free kernel for the 16-channel outputs (same-device A/B: 1.2-1.3x there; N = 32 is mixed, so it stays on
-  // the LDS kernel except in parity mode with a deep reduction)
-  int direct = 0;
-  if (Mmax >= 16384 && ((long)B * H * W * ldx + 4L * (W + 2) * ldx) * 4 < (1L << 31)) {
-    if (N == 16) direct = 1;                                    // 64 rows per wave (128 measured slower)
-    else if (N == 32 && mode == MODE_PARITY && C >= 128) direct = 1;
-  }
-  if (svs_tune_on(SVS_TUNE_CONV_DIRECT)) { const int f = (int)svs_tune(SVS_TUNE_CONV_DIRECT); if (f == 0 || (N <= 32 && Mmax >= 16384)) direct = f; }  // sweeps
   const bool want_stats = stats && stats_nblk && !scale && !accumulate;
-  // conv2 forward: LDS-window form of the GATHER mode (SVS_CONV_GWINDOW=0: the GEMM kernel)
-  if (mode == MODE_GATHER && C == 16 && N == 32 && !accumulate && ldy % 4 == 0 && svs_aligned16(y) && svs_tune(SVS_TUNE_CONV_GWINDOW) != 0 &&
-      ((long)H * W * ldx) * 4 < (1L << 31)) {
-    const long gtiles = (long)B * ((Ho + 7) / 8) * ((Wo + 15) / 16);
-    const bool forced = svs_tune(SVS_TUNE_CONV_GWINDOW) == 2;          // tests: whenever the layer is eligible
-    if ((forced || (Ho >= 8 && Wo >= 16 && gtiles >= 256)) && gtiles < (1L << 30)) {
-      const long tblocks = svs_tune(SVS_TUNE_CONV_GWINDOW) >= 16 ? svs_tune(SVS_TUNE_CONV_GWINDOW) : 512;     // (>= 16: sweeps)
-      int tpb = (int)(gtiles / tblocks);         // one round of two resident blocks per CU; >= 1 tile per block
-      if (tpb < 1) tpb = 1;
-      if (tpb > 8) tpb = 8;
-      const long gblocks = (gtiles + tpb - 1) / tpb;
-      a.ksplit = 1; a.slab = nullptr;
-      if (want_stats && gblocks * 2 * N <= stats_cap) { a.stats = stats; *stats_nblk = (int)gblocks; }
-      hipLaunchKernelGGL(gather_window_kernel, dim3((unsigned)gblocks), dim3(256), 0, stream, a, (int)gtiles, tpb);
-      SVS_CHECK_LAUNCH("gather_window");
-      return SVS_OK;
-    }
-  }
-  if (window) {
-    a.ksplit = 1; a.slab = nullptr;
-    dim3 grid((unsigned)((long)B * ((H + 7) / 8) * ((W + 15) / 16)));
-    if (want_stats && (long)grid.x * 2 * N <= stats_cap) { a.stats = stats; *stats_nblk = (int)grid.x; }
-#define SVS_LAUNCH_WINDOW(C_, CW_, TN_) hipLaunchKernelGGL((parity_window_kernel<C_, CW_, TN_>), grid, dim3(256), 0, stream, a)
-    if (N == 16) {
-      if (C == 32) SVS_LAUNCH_WINDOW(32, 32, 1); else if (C == 64) SVS_LAUNCH_WINDOW(64, 64, 1); else SVS_LAUNCH_WINDOW(128, 64, 1);
-    } else if (parity_window_halves(grid.x)) {
-      grid.y = 2;
-#define SVS_LAUNCH_WINDOW_HALF(C_, CW_) hipLaunchKernelGGL((parity_window_kernel<C_, CW_, 1, 2>), grid, dim3(256), 0, stream, a)
-      if (C == 32) SVS_LAUNCH_WINDOW_HALF(32, 32); else if (C == 64) SVS_LAUNCH_WINDOW_HALF(64, 64); else SVS_LAUNCH_WINDOW_HALF(128, 64);
-#undef SVS_LAUNCH_WINDOW_HALF
-    } else {
-      if (C == 32) SVS_LAUNCH_WINDOW(32, 32, 2); else if (C == 64) SVS_LAUNCH_WINDOW(64, 64, 2); else SVS_LAUNCH_WINDOW(128, 64, 2);
-    }
-#undef SVS_LAUNCH_WINDOW
-    SVS_CHECK_LAUNCH("parity_window");
+  if (want_stats && p.stat_rows && p.stat_rows * 2 * N <= stats_cap) { a.stats = stats; *stats_nblk = (int)p.stat_rows; }
+  if (mode == MODE_GATHER) launch_conv_plan<MODE_GATHER>(a, p, stream);
+  else launch_conv_plan<MODE_PARITY>(a, p, stream);
+  static const char* const kernel[4] = {"conv_gemm", "gather_window", "parity_window", "conv_direct"};
+  SVS_CHECK_LAUNCH(kernel[p.kind]);
+  if (p.ksplit == 1 || svs_tune_flag(SVS_TUNE_SKIP_REDUCE)) return SVS_OK;      // (the switch lets bench.py time the GEMM kernel alone)
+  const long P = (long)B * Ho * Wo, total4 = P * N / 4;
+  int grid = (int)((total4 + 255) / 256);
+  if (grid > 2048) grid = 2048;
+  // fused BatchNorm statistics: stats[grid][2][N] must fit the caller's buffer (stats_cap rows)
+  const bool fuse = stats && stats_nblk && stats_cap >= 2 * N && N % 4 == 0 && N <= 1024 && 256 % (N / 4) == 0 && !scale && !accumulate;
+  if (fuse && grid > 512) grid = 512;
+  if (fuse && (long)grid * 2 * N > stats_cap) grid = stats_cap / (2 * N);
+  int n_shift = -1;
+  if ((N & (N - 1)) == 0) { n_shift = 0; while ((1 << n_shift) < N) ++n_shift; }
+  if (fuse && N % 32 == 0 && svs_tune(SVS_TUNE_BN_INLINE) != 0) {
+    // slab form: blocks = slabs x pixel ranges, at most 512 (two per CU), a range no shorter than one pass of 32 pixels
+    const int nslab = N / 32;
+    long rows = 512 / nslab;
+    if (rows > (P + 31) / 32) rows = (P + 31) / 32;
+    if (rows * 2 * N > stats_cap) rows = stats_cap / (2 * N);
+    if (rows < 1) rows = 1;
+    const long ppr = (P + rows - 1) / rows;
+    rows = (P + ppr - 1) / ppr;
+    hipLaunchKernelGGL(splitk_epilogue_stats_kernel, dim3((unsigned)(rows * nslab)), dim3(256), 0, stream, a.slab, p.ksplit, P, N, bias,
+                       y, ldy, stats, ppr, p.bal.enabled ? p.bal.rowsplit : nullptr);
+    SVS_CHECK_LAUNCH("splitk_epilogue_stats");
+    *stats_nblk = (int)rows;
     return SVS_OK;
   }
-  if (direct && (N == 16 || N == 32)) {
-    a.ksplit = 1; a.slab = nullptr;
-    const int rows = (direct == 2 ? 8 : 4) * 64;      // 4 independent waves per block, TM*16 output rows each
-    dim3 grid((unsigned)((Mmax + rows - 1) / rows), (unsigned)pl.grid_y, 1);
-#define SVS_LAUNCH_DIRECT(MODE_, TM_, TN_) hipLaunchKernelGGL((conv_direct_kernel<MODE_, TM_, TN_>), grid, dim3(256), 0, stream, a)
-    if (mode == MODE_GATHER) {
-      if (N == 16) { if (direct == 2) SVS_LAUNCH_DIRECT(MODE_GATHER, 8, 1); else SVS_LAUNCH_DIRECT(MODE_GATHER, 4, 1); }
-      else { if (direct == 2) SVS_LAUNCH_DIRECT(MODE_GATHER, 8, 2); else SVS_LAUNCH_DIRECT(MODE_GATHER, 4, 2); }
-    } else {
-      if (N == 16) { if (direct == 2) SVS_LAUNCH_DIRECT(MODE_PARITY, 8, 1); else SVS_LAUNCH_DIRECT(MODE_PARITY, 4, 1); }
-      else { if (direct == 2) SVS_LAUNCH_DIRECT(MODE_PARITY, 8, 2); else SVS_LAUNCH_DIRECT(MODE_PARITY, 4, 2); }
-    }
-#undef SVS_LAUNCH_DIRECT
-    SVS_CHECK_LAUNCH("conv_direct");
-    return SVS_OK;
-  }
-  const int skip = use_tap_skip(mode, B, C, Wo, N, pl.cfg);
-  if (want_stats && pl.ksplit == 1 && pl.mtiles * pl.grid_y * 2 * N <= stats_cap) {
-    a.stats = stats;                         // one row of partials per (parity class, M-tile)
-    *stats_nblk = (int)(pl.mtiles * pl.grid_y);
-  }
-  rc = (mode == MODE_GATHER) ? launch_conv_gemm<MODE_GATHER>(a, pl, stream, skip, bal) : launch_conv_gemm<MODE_PARITY>(a, pl, stream, skip, bal);
-  if (rc) return rc;
-  if (pl.ksplit > 1 && !svs_tune_flag(SVS_TUNE_SKIP_REDUCE)) {      // (the switch lets bench.py time the GEMM kernel alone)
-    const long total4 = P * N / 4;
-    int grid = (int)((total4 + 255) / 256);
-    if (grid > 2048) grid = 2048;
-    // fused BatchNorm statistics: stats[grid][2][N] must fit the caller's buffer (stats_cap rows)
-    const bool fuse = stats && stats_nblk && stats_cap >= 2 * N && N % 4 == 0 && N <= 1024 && 256 % (N / 4) == 0 && !scale && !accumulate;
-    if (fuse && grid > 512) grid = 512;
-    if (fuse && (long)grid * 2 * N > stats_cap) grid = stats_cap / (2 * N);
-    int n_shift = -1;
-    if ((N & (N - 1)) == 0) { n_shift = 0; while ((1 << n_shift) < N) ++n_shift; }
-    if (fuse && N % 32 == 0 && svs_tune(SVS_TUNE_BN_INLINE) != 0) {
-      // slab form: blocks = slabs x pixel ranges, at most 512 (two per CU), a range no shorter than one pass of 32 pixels
-      const int nslab = N / 32;
-      long rows = 512 / nslab;
-      if (rows > (P + 31) / 32) rows = (P + 31) / 32;
-      if (rows * 2 * N > stats_cap) rows = stats_cap / (2 * N);
-      if (rows < 1) rows = 1;
-      const long ppr = (P + rows - 1) / rows;
-      rows = (P + ppr - 1) / ppr;
-      hipLaunchKernelGGL(splitk_epilogue_stats_kernel, dim3((unsigned)(rows * nslab)), dim3(256), 0, stream, a.slab, pl.ksplit, P, N, bias,
-                         y, ldy, stats, ppr, bal.enabled ? bal.rowsplit : nullptr);
-      SVS_CHECK_LAUNCH("splitk_epilogue_stats");
-      *stats_nblk = (int)rows;
-      return SVS_OK;
-    }
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(grid), dim3(256), 0, stream, a.slab, pl.ksplit, P, N, bias, scale,
-                       shift, slope, y, ldy, accumulate, fuse ? stats : nullptr, n_shift, bal.enabled ? bal.rowsplit : nullptr);
-    SVS_CHECK_LAUNCH("splitk_epilogue");
-    if (fuse) *stats_nblk = grid;
-  }
+  hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(grid), dim3(256), 0, stream, a.slab, p.ksplit, P, N, bias, scale,
+                     shift, slope, y, ldy, accumulate, fuse ? stats : nullptr, n_shift, p.bal.enabled ? p.bal.rowsplit : nullptr);
+  SVS_CHECK_LAUNCH("splitk_epilogue");
+  if (fuse) *stats_nblk = grid;
   return SVS_OK;
 }
 
+// One workspace serves every call of the shape, with either kind of epilogue and whatever the window switches are set to when it
+// runs: the GEMM form of the call (the window and direct kernels need none).  ldx = C: the input view's stride enters the plan only
+// through 2 GiB guards, which svs_conv_gemm_run's own limit on the view implies.
 size_t svs_conv_gemm_workspace(int mode, int B, int H, int W, int C, int Ho, int Wo, int N) {
   if (C < 16 || N < 16) return 0;
-  long Mmax;
-  int nkt_min;
-  if (mode == MODE_GATHER) { Mmax = (long)B * Ho * Wo; nkt_min = 25 * (C / 16); }
-  else { Mmax = (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2); nkt_min = 4 * (C / 16); }
-  const int ks_train = plan_conv(mode, Mmax, N, nkt_min, narrow_level(mode, B, C, Wo, N), false).ksplit;
-  const int ks_eval = plan_conv(mode, Mmax, N, nkt_min, narrow_level(mode, B, C, Wo, N), true).ksplit;
-  int ks = ks_train > ks_eval ? ks_train : ks_eval;               // (one workspace serves either kind of call, balanced or not)
-  size_t extra = 0;
-  for (int inference = 0; inference < 2; ++inference) {            // balanced splits (ConvBal) may need more slabs, and the row table
-    const ConvPlan pl = plan_conv(mode, Mmax, N, nkt_min, narrow_level(mode, B, C, Wo, N), inference != 0);
-    const bool window = use_parity_window(mode, B, H, W, C, N, C) != 0;
-    const int sb = (!window && use_tap_skip(mode, B, C, Wo, N, pl.cfg)) ? plan_balance(mode, B, H, W, C, Ho, Wo, N, pl, nullptr) : 0;
-    if (sb) { ks = sb > ks ? sb : ks; extra = svs_align_up((size_t)B * Ho * Wo, 16); }
+  size_t need = 0;
+  for (int inference = 0; inference < 2; ++inference) {
+    const ConvPlan p = plan_conv_call(mode, B, H, W, C, Ho, Wo, N, C, inference != 0, false, true);
+    need = p.slab_bytes + p.rowtab_bytes > need ? p.slab_bytes + p.rowtab_bytes : need;
   }
-  if (ks <= 1) return 0;
-  return (size_t)ks * B * Ho * Wo * N * sizeof(float) + extra;
+  return need;
 }
 
-// Name (as rocprofv3 prints it) and K-split of the kernel the planner picks for a conv GEMM -- bench.py groups its
-// live per-layer timings by this name so that they can be matched against the rocprofv3 kernel statistics.
+// Name (as rocprofv3 prints it) and K-split of the kernel a training-kind call (no folded BatchNorm, y written, not accumulated)
+// of this shape launches -- bench.py groups its live per-layer timings by this name so that they can be matched against the
+// rocprofv3 kernel statistics.
 int svs_conv_gemm_describe(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, long ldx, char* buf, size_t n) {
-  long Mmax;
-  int nkt_min;
-  if (mode == MODE_GATHER) { Mmax = (long)B * Ho * Wo; nkt_min = 25 * (C / 16); }
-  else { Mmax = (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2); nkt_min = 4 * (C / 16); }
-  int direct = 0;
-  if (Mmax >= 16384 && ((long)B * H * W * ldx + 4L * (W + 2) * ldx) * 4 < (1L << 31)) {
-    if (N == 16) direct = 1;
-    else if (N == 32 && mode == MODE_PARITY && C >= 128) direct = 1;
+  const ConvPlan p = plan_conv_call(mode, B, H, W, C, Ho, Wo, N, ldx, false, false);
+  switch (p.kind) {
+    case CONV_GATHER_WINDOW: snprintf(buf, n, "gather_window_kernel"); break;
+    case CONV_PARITY_WINDOW: snprintf(buf, n, "parity_window_kernel<%d, %d, %d, %d>", p.wC, p.wCW, p.wTN, p.wNT); break;
+    case CONV_DIRECT: snprintf(buf, n, "conv_direct_kernel<%d, 4, %d>", mode, N / 16); break;
+    default:
+      snprintf(buf, n, "conv_gemm_kernel<%d, %d, %d, %d, %d, %s, %s, %d>", mode, p.BM, p.BN, p.WM, p.WN, p.skip ? "true" : "false",
+               p.split ? "true" : "false", p.pf);
   }
-  if (mode == MODE_GATHER && C == 16 && N == 32 && svs_tune(SVS_TUNE_CONV_GWINDOW) != 0 && Ho >= 8 && Wo >= 16 &&
-      (long)B * ((Ho + 7) / 8) * ((Wo + 15) / 16) >= 256) {
-    snprintf(buf, n, "gather_window_kernel");
-    return 1;
-  }
-  if (use_parity_window(mode, B, H, W, C, N, ldx)) {
-    const bool halves = N == 32 && parity_window_halves((long)B * ((H + 7) / 8) * ((W + 15) / 16));
-    snprintf(buf, n, "parity_window_kernel<%d, %d, %d, %d>", C, C == 32 ? 32 : 64, halves ? 1 : N / 16, N / 16);
-    return 1;
-  }
-  if (direct) { snprintf(buf, n, "conv_direct_kernel<%d, 4, %d>", mode, N / 16); return 1; }
-  static const int wm[10] = {2, 2, 4, 4, 1, 2, 2, 4, 4, 4}, wn[10] = {2, 2, 1, 1, 4, 2, 2, 1, 1, 1};     // (6 = 64x128, 2x2 waves)
-  const ConvPlan pl = plan_conv(mode, Mmax, N, nkt_min, narrow_level(mode, B, C, Wo, N));
-  const bool skip = use_tap_skip(mode, B, C, Wo, N, pl.cfg) != 0;
-  // (the last template argument, K-tiles requested ahead, exists as 2 only for the tile shapes launch_conv_gemm_cfg has it for)
-  const int pf = (pl.pf == 2 && (pl.cfg == 5 || pl.cfg == 6 || pl.cfg == 1 || (!skip && (pl.cfg == 2 || pl.cfg == 3)))) ? 2 : 1;
-  snprintf(buf, n, "conv_gemm_kernel<%d, %d, %d, %d, %d, %s, %s, %d>", mode, pl.BM, pl.BN, wm[pl.cfg], wn[pl.cfg],
-           skip ? "true" : "false", svs_tune(SVS_TUNE_MFMA_SPLIT) > 0 ? "true" : "false", pf);
-  ConvBal show{};
-  const int sb = skip ? plan_balance(mode, B, H, W, C, Ho, Wo, N, pl, svs_tune(SVS_TUNE_CONV_BALANCE) == 2 ? &show : nullptr) : 0;      // balanced: the largest split count
-  return sb ? sb : pl.ksplit;
+  return p.ksplit;
 }

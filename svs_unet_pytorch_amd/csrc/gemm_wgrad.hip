@@ -452,10 +452,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
 }
 
-struct WgradPlan { int cfg, BM, BN, ksplit; long pps; };
-
-static WgradPlan plan_wgrad(int B, int Hs, int Ws, int Cs, int Cl) {
-  WgradPlan pl{};
+// GEMM tile and K-split
+struct WgradTile { int cfg, BM, BN, ksplit; long pps; };
+static WgradTile plan_wgrad(int B, int Hs, int Ws, int Cs, int Cl) {
+  WgradTile pl{};
   if (Cs % 128 == 0) { pl.cfg = 0; pl.BM = 128; }
   else if (Cs % 64 == 0) { pl.cfg = 1; pl.BM = 64; }
   else { pl.cfg = 2; pl.BM = 32; }
@@ -485,26 +485,17 @@ static WgradPlan plan_wgrad(int B, int Hs, int Ws, int Cs, int Cl) {
   return pl;
 }
 
-// deep levels: batch-innermost pixels, K-tiles whose taps are all in the padding are skipped (wgrad_gemm_kernel)
-static int use_wgrad_skip(int B, int Hs, int Ws, int Cl, long lds, int cfg) {
-  const bool can_skip = B >= 16 && (B & (B - 1)) == 0 && (Ws & (Ws - 1)) == 0 &&
-                        (long)B * Hs * Ws * lds * 4 < (1L << 31);
-  int skip = can_skip && Ws <= 8;
-  if (svs_tune_on(SVS_TUNE_WGRAD_SKIP)) { const int f = (int)svs_tune(SVS_TUNE_WGRAD_SKIP); skip = (f == 0) ? 0 : (f == 2) ? can_skip : skip; }   // sweeps, tests
-  return skip;
-}
-
 #define WG_GROUPS 8      // slabs are pre-summed in WG_GROUPS parallel groups when there are many of them
 
-// window kernel: which layers, and how many blocks / slabs
-struct WgWinPlan { int use, MT, gy, gx, tpb, ntiles, nslab; };
+// window kernel: which layers, and how many blocks / slabs (the geometry of every eligible layer, used or not)
+struct WgWinPlan { int eligible, use, MT, gy, gx, tpb, ntiles, nslab; };
 static WgWinPlan plan_wgrad_window(int B, int Hs, int Ws, int Cs, int Cl) {
   WgWinPlan w{};
-  const bool eligible = (Cl == 16 || Cl == 32) && (Cs == 32 || Cs == 64 || Cs == 128);
+  w.eligible = (Cl == 16 || Cl == 32) && (Cs == 32 || Cs == 64 || Cs == 128);
   w.ntiles = B * ((Hs + 3) / 4) * ((Ws + 15) / 16);
-  w.use = eligible && w.ntiles >= 1024;
-  if (svs_tune_on(SVS_TUNE_WGRAD_WINDOW)) { const int f = (int)svs_tune(SVS_TUNE_WGRAD_WINDOW); w.use = (f == 0) ? 0 : (f == 2) ? eligible : w.use; }   // sweeps, tests
-  if (!w.use) return w;
+  w.use = w.eligible && w.ntiles >= 1024;
+  if (svs_tune_on(SVS_TUNE_WGRAD_WINDOW)) { const int f = (int)svs_tune(SVS_TUNE_WGRAD_WINDOW); w.use = (f == 0) ? 0 : (f == 2) ? w.eligible : w.use; }   // sweeps, tests
+  if (!w.eligible) return w;
   w.MT = (Cs % 64 == 0) ? 4 : 2;
   w.gy = (Cs / (16 * w.MT)) * (Cl / 16);
   int gx = 512 / w.gy;                       // two resident blocks per CU
@@ -515,17 +506,48 @@ static WgWinPlan plan_wgrad_window(int B, int Hs, int Ws, int Cs, int Cl) {
   return w;
 }
 
-size_t svs_wgrad_gemm_workspace(int B, int Hs, int Ws, int Cs, int Cl) {
-  WgradPlan pl = plan_wgrad(B, Hs, Ws, Cs, Cl);
-  size_t nslab = (size_t)pl.ksplit;
-  // the window kernel's slab count does not depend on the sweep / test switches' current value: take the larger
-  const int tiles = B * ((Hs + 3) / 4) * ((Ws + 15) / 16);
-  if ((Cl == 16 || Cl == 32) && (Cs == 32 || Cs == 64 || Cs == 128)) {
-    const int MT = (Cs % 64 == 0) ? 4 : 2, gy = (Cs / (16 * MT)) * (Cl / 16);
-    size_t gx = (size_t)(512 / gy < tiles ? 512 / gy : tiles);
-    if (gx * (4 / MT) > nslab) nslab = gx * (4 / MT);
+// One call's launch, decided once for svs_wgrad_gemm_run and svs_wgrad_gemm_describe: the window kernel, or the GEMM where the
+// window is not planned or its per-image views need 64-bit offsets
+struct WgradPlan {
+  WgWinPlan win;                  // win.use: wgrad_window_kernel<win.MT>
+  WgradTile tile;                 // else wgrad_gemm_kernel<BM, BN, WM, WN, skip, split, pf>
+  int WM, WN, pf;
+  bool skip, split;
+  dim3 grid;
+  int nslab;                      // slabs the reduction sums
+};
+static WgradPlan plan_wgrad_call(int B, int Hs, int Ws, int Cs, int Cl, long lds, int Hl, int Wl, long ldl) {
+  WgradPlan p{};
+  p.win = plan_wgrad_window(B, Hs, Ws, Cs, Cl);
+  p.win.use = p.win.use && (long)Hs * Ws * lds * 4 < (1L << 31) && (long)Hl * Wl * ldl * 4 < (1L << 31);
+  if (p.win.use) {
+    p.grid = dim3(p.win.gx, p.win.gy);
+    p.nslab = p.win.nslab;
+    return p;
   }
-  return (nslab + WG_GROUPS) * Cs * 25 * Cl * sizeof(float);
+  p.tile = plan_wgrad(B, Hs, Ws, Cs, Cl);
+  p.WM = p.tile.cfg == 0 ? 2 : 1;
+  p.WN = 4 / p.WM;
+  // deep levels: batch-innermost pixels, K-tiles whose taps are all in the padding are skipped (wgrad_gemm_kernel).  SVS_WGRAD_SKIP
+  // (sweeps, tests): 0 = never, 2 = whenever the shape allows it
+  const bool can_skip = B >= 16 && (B & (B - 1)) == 0 && (Ws & (Ws - 1)) == 0 && (long)B * Hs * Ws * lds * 4 < (1L << 31);
+  const long f = svs_tune(SVS_TUNE_WGRAD_SKIP);
+  p.skip = f == 0 ? false : f == 2 ? can_skip : can_skip && Ws <= 8;
+  // K-tiles requested ahead by the tap-skipping 128x128 and 64x128 tiles: two (same-device A/B at batch 64: train step 3.465 ->
+  // 3.447 ms)
+  p.pf = p.skip && p.tile.cfg <= 1 ? 2 : 1;
+  p.split = svs_tune(SVS_TUNE_MFMA_SPLIT) > 0;      // optional mode: mfma_split.h
+  p.grid = dim3((unsigned)(Cs / p.tile.BM), (unsigned)((25 * Cl + p.tile.BN - 1) / p.tile.BN), (unsigned)p.tile.ksplit);
+  p.nslab = p.tile.ksplit;
+  return p;
+}
+
+// the window kernel's slab count does not depend on the sweep / test switches' current value: take the larger
+size_t svs_wgrad_gemm_workspace(int B, int Hs, int Ws, int Cs, int Cl) {
+  const WgWinPlan w = plan_wgrad_window(B, Hs, Ws, Cs, Cl);
+  int nslab = plan_wgrad(B, Hs, Ws, Cs, Cl).ksplit;
+  if (w.eligible && w.nslab > nslab) nslab = w.nslab;
+  return ((size_t)nslab + WG_GROUPS) * Cs * 25 * Cl * sizeof(float);
 }
 
 // fixed-order sum of nslab slabs [Cs][25*Cl] into torch's (cs, cl, kh, kw) layout; tmp: WG_GROUPS more slabs
@@ -544,6 +566,22 @@ static int wgrad_reduce_run(const float* slabs, int nslab, int Cs, int Cl, float
   return SVS_OK;
 }
 
+template <bool SPLIT, int BM, int WM, int WN>
+static void launch_wgrad_tile(const WgradArgs& a, const WgradPlan& p, hipStream_t stream) {
+  constexpr int PF2 = BM == 32 ? 1 : 2;      // (the two-ahead variant exists for the 128x128 and 64x128 tiles)
+  if (!p.skip) hipLaunchKernelGGL((wgrad_gemm_kernel<BM, 128, WM, WN, false, SPLIT>), p.grid, dim3(256), 0, stream, a);
+  else if (p.pf == 2) hipLaunchKernelGGL((wgrad_gemm_kernel<BM, 128, WM, WN, true, SPLIT, PF2>), p.grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((wgrad_gemm_kernel<BM, 128, WM, WN, true, SPLIT>), p.grid, dim3(256), 0, stream, a);
+}
+template <bool SPLIT>
+static void launch_wgrad_gemm(const WgradArgs& a, const WgradPlan& p, hipStream_t stream) {
+  switch (p.tile.cfg) {
+    case 0: launch_wgrad_tile<SPLIT, 128, 2, 2>(a, p, stream); break;
+    case 1: launch_wgrad_tile<SPLIT, 64, 1, 4>(a, p, stream); break;
+    default: launch_wgrad_tile<SPLIT, 32, 1, 4>(a, p, stream); break;
+  }
+}
+
 int svs_wgrad_gemm_run(const float* s, long lds, int B, int Hs, int Ws, int Cs, const float* l, long ldl, int Hl,
                        int Wl, int Cl, float* dw, void* ws, size_t ws_bytes, hipStream_t stream, const char* who) {
   SVS_REQUIRE(s && l && dw, "%s: null pointer", who);
@@ -551,66 +589,41 @@ int svs_wgrad_gemm_run(const float* s, long lds, int B, int Hs, int Ws, int Cs, 
   SVS_REQUIRE(Hs == svs_conv_out(Hl) && Ws == svs_conv_out(Wl), "%s: small grid %dx%d does not match %dx%d", who, Hs, Ws, Hl, Wl);
   SVS_REQUIRE(lds >= Cs && lds % 4 == 0 && ldl >= Cl && ldl % 4 == 0, "%s: bad ld", who);
   SVS_REQUIRE(svs_aligned16(s) && svs_aligned16(l) && svs_aligned16(ws), "%s: pointers must be 16-byte aligned", who);
-  WgradPlan pl = plan_wgrad(B, Hs, Ws, Cs, Cl);
   const size_t need = svs_wgrad_gemm_workspace(B, Hs, Ws, Cs, Cl);
   if (!ws || ws_bytes < need) {
     svs_set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
     return SVS_ERR_WORKSPACE;
   }
-  const WgWinPlan wp = plan_wgrad_window(B, Hs, Ws, Cs, Cl);
-  if (wp.use && (long)Hs * Ws * lds * 4 < (1L << 31) && (long)Hl * Wl * ldl * 4 < (1L << 31)) {
-    WgWinArgs wa{s, lds, l, ldl, B, Hs, Ws, Cs, Hl, Wl, Cl, (float*)ws, wp.ntiles, wp.tpb};
-    if (wp.MT == 4) hipLaunchKernelGGL((wgrad_window_kernel<4>), dim3(wp.gx, wp.gy), dim3(256), 0, stream, wa);
-    else hipLaunchKernelGGL((wgrad_window_kernel<2>), dim3(wp.gx, wp.gy), dim3(256), 0, stream, wa);
+  const WgradPlan p = plan_wgrad_call(B, Hs, Ws, Cs, Cl, lds, Hl, Wl, ldl);
+  if (p.win.use) {
+    WgWinArgs wa{s, lds, l, ldl, B, Hs, Ws, Cs, Hl, Wl, Cl, (float*)ws, p.win.ntiles, p.win.tpb};
+    if (p.win.MT == 4) hipLaunchKernelGGL((wgrad_window_kernel<4>), p.grid, dim3(256), 0, stream, wa);
+    else hipLaunchKernelGGL((wgrad_window_kernel<2>), p.grid, dim3(256), 0, stream, wa);
     SVS_CHECK_LAUNCH("wgrad_window");
-    pl.ksplit = wp.nslab;
-    if (svs_tune_flag(SVS_TUNE_SKIP_REDUCE)) return SVS_OK;
-    return wgrad_reduce_run((const float*)ws, pl.ksplit, Cs, Cl, dw, (float*)ws + (size_t)pl.ksplit * Cs * 25 * Cl, stream);
+  } else {
+    WgradArgs a{};
+    a.s = s; a.lds = lds; a.Hs = Hs; a.Ws = Ws; a.Cs = Cs;
+    a.l = l; a.ldl = ldl; a.Hl = Hl; a.Wl = Wl; a.Cl = Cl;
+    a.B = B; a.slab = (float*)ws; a.pix_per_split = p.tile.pps;
+    auto log2_or_neg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
+    a.ws_shift = log2_or_neg(Ws); a.hs_shift = log2_or_neg(Hs);
+    SVS_REQUIRE((long)B * Hs * Ws < (1L << 31), "%s: pixel count exceeds 2^31", who);
+    SVS_REQUIRE((long)B * Hl * Wl * ldl * 4 < (1L << 31) && (long)(p.tile.pps + 16) * lds * 4 < (1L << 31),
+                "%s: operand views need 64-bit offsets; split the batch", who);
+    if (p.skip) a.b_shift = log2_or_neg(B);
+    if (p.split) launch_wgrad_gemm<true>(a, p, stream);
+    else launch_wgrad_gemm<false>(a, p, stream);
+    SVS_CHECK_LAUNCH("wgrad_gemm");
   }
-  WgradArgs a{};
-  a.s = s; a.lds = lds; a.Hs = Hs; a.Ws = Ws; a.Cs = Cs;
-  a.l = l; a.ldl = ldl; a.Hl = Hl; a.Wl = Wl; a.Cl = Cl;
-  a.B = B; a.slab = (float*)ws; a.pix_per_split = pl.pps;
-  auto log2_or_neg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
-  a.ws_shift = log2_or_neg(Ws); a.hs_shift = log2_or_neg(Hs);
-  SVS_REQUIRE((long)B * Hs * Ws < (1L << 31), "%s: pixel count exceeds 2^31", who);
-  SVS_REQUIRE((long)B * Hl * Wl * ldl * 4 < (1L << 31) && (long)(pl.pps + 16) * lds * 4 < (1L << 31),
-              "%s: operand views need 64-bit offsets; split the batch", who);
-  dim3 grid((unsigned)(Cs / pl.BM), (unsigned)((25 * Cl + pl.BN - 1) / pl.BN), (unsigned)pl.ksplit);
-  const int skip = use_wgrad_skip(B, Hs, Ws, Cl, lds, pl.cfg);
-  if (skip) a.b_shift = log2_or_neg(B);
-  // K-tiles requested ahead by the tap-skipping tiles: two (same-device A/B of tools/ab_tune.py WGRAD_PF 1 2 at batch 64: train step
-  // 3.465 -> 3.447 ms); WGRAD_PF = 1 / 2 for A/B runs
-  int pf = 2;
-  if (svs_tune_on(SVS_TUNE_WGRAD_PF)) { const long f = svs_tune(SVS_TUNE_WGRAD_PF); pf = (f == 2 || (f == 3 && pl.cfg == 0) || (f == 4 && pl.cfg == 1)) ? 2 : 1; }   // 3 / 4: one tile shape only
-#define SVS_WGRAD_LAUNCH(SPLIT_) \
-  if (skip && pf == 2 && pl.cfg == 0) hipLaunchKernelGGL((wgrad_gemm_kernel<128, 128, 2, 2, true, SPLIT_, 2>), grid, dim3(256), 0, stream, a); \
-  else if (skip && pf == 2 && pl.cfg == 1) hipLaunchKernelGGL((wgrad_gemm_kernel<64, 128, 1, 4, true, SPLIT_, 2>), grid, dim3(256), 0, stream, a); \
-  else if (skip) { \
-    if (pl.cfg == 0) hipLaunchKernelGGL((wgrad_gemm_kernel<128, 128, 2, 2, true, SPLIT_>), grid, dim3(256), 0, stream, a); \
-    else if (pl.cfg == 1) hipLaunchKernelGGL((wgrad_gemm_kernel<64, 128, 1, 4, true, SPLIT_>), grid, dim3(256), 0, stream, a); \
-    else hipLaunchKernelGGL((wgrad_gemm_kernel<32, 128, 1, 4, true, SPLIT_>), grid, dim3(256), 0, stream, a); \
-  } else switch (pl.cfg) { \
-    case 0: hipLaunchKernelGGL((wgrad_gemm_kernel<128, 128, 2, 2, false, SPLIT_>), grid, dim3(256), 0, stream, a); break; \
-    case 1: hipLaunchKernelGGL((wgrad_gemm_kernel<64, 128, 1, 4, false, SPLIT_>), grid, dim3(256), 0, stream, a); break; \
-    default: hipLaunchKernelGGL((wgrad_gemm_kernel<32, 128, 1, 4, false, SPLIT_>), grid, dim3(256), 0, stream, a); break; \
-  }
-  if (svs_tune(SVS_TUNE_MFMA_SPLIT) > 0) { SVS_WGRAD_LAUNCH(true) } else { SVS_WGRAD_LAUNCH(false) }      // optional mode: mfma_split.h
-#undef SVS_WGRAD_LAUNCH
-  SVS_CHECK_LAUNCH("wgrad_gemm");
   if (svs_tune_flag(SVS_TUNE_SKIP_REDUCE)) return SVS_OK;             // lets bench.py time the GEMM kernel alone
-  return wgrad_reduce_run((const float*)ws, pl.ksplit, Cs, Cl, dw, (float*)ws + (size_t)pl.ksplit * Cs * 25 * Cl, stream);
+  return wgrad_reduce_run((const float*)ws, p.nslab, Cs, Cl, dw, (float*)ws + (size_t)p.nslab * Cs * 25 * Cl, stream);
 }
 
+// (the public query knows only the shape: the views are taken dense, the large image at its largest, 2Hs x 2Ws)
 int svs_wgrad_gemm_describe(int B, int Hs, int Ws, int Cs, int Cl, char* buf, size_t n) {
-  const WgWinPlan wp = plan_wgrad_window(B, Hs, Ws, Cs, Cl);
-  if (wp.use) { snprintf(buf, n, "wgrad_window_kernel<%d>", wp.MT); return wp.nslab; }
-  const WgradPlan pl = plan_wgrad(B, Hs, Ws, Cs, Cl);
-  const bool skip = use_wgrad_skip(B, Hs, Ws, Cl, Cs, pl.cfg) != 0;
-  int pf = 2;
-  if (svs_tune_on(SVS_TUNE_WGRAD_PF)) { const long f = svs_tune(SVS_TUNE_WGRAD_PF); pf = (f == 2 || (f == 3 && pl.cfg == 0) || (f == 4 && pl.cfg == 1)) ? 2 : 1; }
-  if (!skip || pl.cfg > 1) pf = 1;           // (the two-ahead variant exists for the tap-skipping 128x128 and 64x128 tiles)
-  snprintf(buf, n, "wgrad_gemm_kernel<%d, %d, %d, %d, %s, %s, %d>", pl.BM, pl.BN, pl.cfg == 0 ? 2 : 1, pl.cfg == 0 ? 2 : 4,
-           skip ? "true" : "false", svs_tune(SVS_TUNE_MFMA_SPLIT) > 0 ? "true" : "false", pf);
-  return pl.ksplit;
+  const WgradPlan p = plan_wgrad_call(B, Hs, Ws, Cs, Cl, Cs, 2 * Hs, 2 * Ws, Cl);
+  if (p.win.use) snprintf(buf, n, "wgrad_window_kernel<%d>", p.win.MT);
+  else snprintf(buf, n, "wgrad_gemm_kernel<%d, %d, %d, %d, %s, %s, %d>", p.tile.BM, p.tile.BN, p.WM, p.WN, p.skip ? "true" : "false",
+                p.split ? "true" : "false", p.pf);
+  return p.nslab;
 }

@@ -36,8 +36,9 @@ extern "C" const char* svs_last_error_string(void) { return g_err; }
 // tuning table (common.h: SvsTune)
 // ---------------------------------------------------------------------------------------------
 static const char* const TUNE_NAMES[SVS_TUNE_COUNT] = {
-    "CONV_CFG", "CONV_KSPLIT", "CONV_WINDOW", "CONV_SKIP", "CONV_KORDER", "CONV_DIRECT", "SKIP_REDUCE", "WGRAD_CFG",
-    "WGRAD_KSPLIT", "WGRAD_SKIP", "WGRAD_WINDOW", "WGRAD_C1_VALU", "SIDE_PRIORITY", "TRAIN_UNFUSED", "TRAIN_ONE_STREAM", "CONV_PLAN", "MFMA_SPLIT", "CONV_BALANCE", "CONV_C1_TILED", "BF16_KB", "BF16_CFG", "BF16_KSPLIT", "CONV_PF", "WGRAD_PF", "BN_INLINE", "BN_BLOCKS", "BF16_CONV3_WINDOW", "BF16_DECONV3_WINDOW", "CONV_GWINDOW"};
+    "CONV_CFG", "CONV_KSPLIT", "CONV_WINDOW", "CONV_SKIP", "SKIP_REDUCE", "WGRAD_CFG", "WGRAD_KSPLIT", "WGRAD_SKIP",
+    "WGRAD_WINDOW", "TRAIN_UNFUSED", "TRAIN_ONE_STREAM", "MFMA_SPLIT", "CONV_C1_TILED", "BF16_CFG", "BF16_KSPLIT", "BN_INLINE",
+    "CONV_GWINDOW"};
 static std::atomic<long> g_tune[SVS_TUNE_COUNT];      // written by svs_tuning_set while compute threads read: relaxed atomics
 static std::once_flag g_tune_once;
 static void tune_load_env() {
@@ -443,9 +444,7 @@ static SideStream* side_stream(hipStream_t of) {       // the side stream of the
     // GEMMs then start as soon as their d_raw exists and are out of the way when the main stream reaches its next GEMM
     int least = 0, greatest = 0;
     bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
-    int prio = greatest;
-    if (svs_tune_on(SVS_TUNE_SIDE_PRIORITY)) prio = (int)svs_tune(SVS_TUNE_SIDE_PRIORITY);   // sweeps only
-    ok = ok && hipStreamCreateWithPriority(&sd->s, hipStreamNonBlocking, prio) == hipSuccess;
+    ok = ok && hipStreamCreateWithPriority(&sd->s, hipStreamNonBlocking, greatest) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&sd->sync, hipEventDisableTiming) == hipSuccess;
     for (int i = 0; i < 4 && ok; ++i)
       ok = hipEventCreateWithFlags(&sd->fork[i], hipEventDisableTiming) == hipSuccess &&

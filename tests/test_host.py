@@ -251,7 +251,7 @@ def test_bss_eval_defining_properties(tmp_path):
 
 def test_library_has_no_packed_fp32_op_sel_forms():
     """gfx950: a packed-fp32 instruction whose op_sel takes the high half of a source for the low result returns garbage
-    while a bf16 MFMA of another wave executes on the CU (tools/attic/stress_victims.py on the GPU).  The
+    while a bf16 MFMA of another wave executes on the CU.  The
     built library must not contain that form anywhere (stft.hip / mrstft.hip are compiled without SLP vectorisation for
     this reason)."""
     import importlib.util
@@ -267,6 +267,46 @@ def test_library_has_no_packed_fp32_op_sel_forms():
     hits, n_inst, n_kernels = mod.scan(lib)
     assert n_kernels > 100 and n_inst > 100000                 # the scan really saw the device code
     assert not hits, hits[:5]
+
+
+@pytest.mark.parametrize("switch", [None, ("CONV_SKIP", 2), ("CONV_SKIP", 0), ("CONV_WINDOW", 0), ("CONV_WINDOW", 2),
+                                    ("CONV_WINDOW", 3), ("CONV_GWINDOW", 2), ("WGRAD_SKIP", 2), ("WGRAD_WINDOW", 2),
+                                    ("MFMA_SPLIT", 1)])
+def test_described_plans_name_built_kernels_and_fit_the_workspace(lib, tune, tmp_path, switch):
+    """Every GEMM call of a train step and an eval forward over batch sizes and tile shapes: the kernel svs_describe_plan names
+    (bench.py files its timings under that name) is a kernel of the built library, and the block's workspace query covers the
+    K-split slabs of that plan."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("check_isa", os.path.join(ROOT, "tools", "check_isa.py"))
+    isa = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(isa)
+    spec = importlib.util.spec_from_file_location("bench_calls", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    mangled = []
+    for co in isa.device_code_objects(_lib.LIB_PATH, str(tmp_path)):
+        syms = subprocess.run([f"{isa.LLVM}/llvm-objdump", "-t", co], capture_output=True, text=True, check=True).stdout
+        mangled += [ln.split()[-1] for ln in syms.splitlines() if " F .text" in ln]
+    demangled = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.splitlines()
+    kernels = {d.removeprefix("void ").split("(")[0] for d in demangled}
+    assert "gather_window_kernel" in kernels and len(kernels) > 100
+    if switch:
+        tune(*switch)
+    buf = ctypes.create_string_buffer(128)
+    for H, W in ((512, 128), (513, 100), (512, 512)):
+        for B in (1, 3, 16, 64, 128, 216, 512):
+            for name, kind, (h, w, c, ho, wo, n), _ in bench.gemm_calls(B, "train", H, W):
+                if kind == 2:
+                    ks = lib.svs_describe_plan(2, B, h, w, c, 0, 0, n, buf, 128)
+                    need, ws = ks * c * 25 * n * 4, lib.svs_block_bwd_weight_workspace_bytes(B, h, w, c, n)
+                else:
+                    ks = lib.svs_describe_plan(kind, B, h, w, c, ho, wo, n, buf, 128)
+                    need = ks * B * ho * wo * n * 4 if ks > 1 else 0
+                    ws = (lib.svs_enc_block_workspace_bytes(B, h, w, c, n) if kind == 0 else
+                          lib.svs_dec_block_workspace_bytes(B, h, w, c, ho, wo, n))
+                where = f"{name} B={B} {H}x{W} {switch}: {buf.value.decode()}"
+                assert ks >= 1 and buf.value.decode() in kernels, where
+                assert ws >= need, (where, ws, need)
 
 
 def test_bench_gpus_n_launches_child_ranks(tmp_path):

@@ -50,11 +50,13 @@ def main():
     ap.add_argument("--no-conv", action="store_true")
     ap.add_argument("--no-ks", action="store_true", help="skip the K-split sweep of the weight gradients")
     ap.add_argument("--ab", action="store_true", help="A/B an environment switch per call (see --ab-env)")
-    ap.add_argument("--ab-env", default="CONV_KORDER", help="switch toggled by --ab")
+    ap.add_argument("--ab-env", default="", help="switch toggled by --ab (a name svs_tuning_set knows)")
     ap.add_argument("--ab-vals", default="0,1", help="comma-separated values of the switch")
     ap.add_argument("--ks", default="1,2,4,8", help="K-splits to try for the conv GEMMs")
     ap.add_argument("--fwd-only", action="store_true", help="forward calls only (eval)")
     args = ap.parse_args()
+    if args.ab and not args.ab_env:
+        ap.error("--ab needs --ab-env")
     args.ks_list = tuple(int(t) for t in args.ks.split(","))
     B = args.batch
     L = _lib.lib()
