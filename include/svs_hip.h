@@ -330,6 +330,31 @@ int svs_absmax(const float* x, int64_t n, float* out /*device scalar*/, void* ws
 int svs_max(const float* x, int64_t n, float* out, hipStream_t stream);
 int svs_scale_by_inv(float* x, int64_t n, const float* denom /*device scalar; 0 -> 1*/, float numer, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * BSS-eval in fp64 (csrc/bss.hip): the Gram matrix and projection energies behind svs_unet_pytorch_amd/evaluate.py's
+ * _project and _criteria, without forming the projected signals (the formulation is written down in evaluate.py). */
+#define SVS_BSS_MAX_SIGNALS 6
+#define SVS_BSS_MAX_PAIRS 16
+#define SVS_BSS_MAX_LAG 512
+#define SVS_BSS_MAX_RHS 16
+/* Lagged correlations of signals x[s*ld + m], 0 <= s < nsig, 0 <= m < n (zero outside [0, n)).  pairs (HOST array of
+ * 3*npairs ints): pair q = (a, b, nlags), 1 <= nlags <= SVS_BSS_MAX_LAG, asks for
+ *   out[off_q + k] = sum_m x_a[m+k] x_b[m],   0 <= k < nlags,   off_q = sum of the nlags of the pairs before q.
+ * _project's toeplitz(...) block of G is R_ij[q-p] with R_ij[k] = pair (i, j) for k >= 0 and pair (j, i) at -k; its ssef
+ * vector D is pair (estimate, reference); a signal's energy is pair (s, s, 1).  Fixed-order sums: bitwise reproducible. */
+size_t svs_bss_corr_workspace_bytes(int64_t n, int npairs, const int* pairs);
+int svs_bss_corr(const double* x, int64_t ld, int nsig, int64_t n, const int* pairs, int npairs, double* out,
+                 void* ws, size_t ws_bytes, hipStream_t stream);
+/* Projection energies |P_S e|^2 = D^T G^-1 D = |y|^2 (G = L L^T, L y = D) of _project, K <= 2 references, filter length
+ * flen (order K*flen of G), from correlations `corr` laid out as svs_bss_corr writes them.  gram_off (HOST, K*K ints):
+ * gram_off[i*K + j] = offset in corr of R_ij[0 .. flen); rhs_off (HOST, K*nrhs ints): rhs_off[r*K + i] = offset of the
+ * D block of reference i for right-hand side r.  ynorm2[r] = |y_r|^2 (nrhs doubles).  *status (device int) = 0, or
+ * 1 + the index of the first pivot of the Cholesky factorisation that was not > 0 (a singular G, e.g. a silent
+ * reference: ynorm2 is then meaningless; _project solves by least squares instead). */
+size_t svs_bss_solve_workspace_bytes(int K, int flen, int nrhs);
+int svs_bss_solve(const double* corr, int K, int flen, const int* gram_off, const int* rhs_off, int nrhs, double* ynorm2,
+                  int* status, void* ws, size_t ws_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

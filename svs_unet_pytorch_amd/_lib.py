@@ -94,6 +94,10 @@ _SIGS = {
     "svs_absmax": (I, [P, L, P, P, Z, P]),
     "svs_max": (I, [P, L, P, P]),
     "svs_scale_by_inv": (I, [P, L, P, F, P]),
+    "svs_bss_corr_workspace_bytes": (Z, [L, I, P]),
+    "svs_bss_corr": (I, [P, L, I, L, P, I, P, P, Z, P]),
+    "svs_bss_solve_workspace_bytes": (Z, [I, I, I]),
+    "svs_bss_solve": (I, [P, I, I, P, P, I, P, P, P, Z, P]),
 }
 
 

@@ -1,0 +1,332 @@
+// BSS-eval on the GPU (svs_unet_pytorch_amd/evaluate.py: _project / _criteria), fp64 throughout, gfx950:
+//   bss_corr_kernel         lagged correlations C_xy[k] = sum_m x[m+k] y[m], 0 <= k < nlags, of requested signal pairs.
+//                           A block stages a chunk of T samples of every signal (plus a MAX_LAG halo) in LDS; a thread
+//                           owns a run of 8 consecutive lags of one pair and sweeps the chunk with the run's window in
+//                           registers (8 FMAs per two LDS reads).  Blocks stride over chunks and write one partial per
+//                           (block, lag) to a slab.
+//   bss_corr_reduce_kernel  sums the slab over blocks in a fixed order: no atomics, bitwise reproducible.
+//   bss_expand_kernel       block-Toeplitz Gram matrix G (order K*flen, padded to a multiple of 64 with an identity) and
+//                           the right-hand sides D, stored below G as extra rows: [G; D^T].
+//   bss_panel_kernel /      right-looking blocked Cholesky of G in 64-wide panels.  Because the right-hand sides are rows
+//   bss_update_kernel       under G, the same triangular solves and updates that form L turn them into y^T = (L^-1 D)^T.
+//   bss_norm_kernel         |y|^2 per right-hand side = D^T G^-1 D, the energy of the projection (fixed-order sums).
+// A pivot that is not > 0 (a silent reference: G singular) is reported through *status; the factorisation goes on with a
+// unit pivot so that nothing faults, and the caller discards the result.
+#include "common.h"
+
+namespace {
+
+constexpr int BSS_T = 1024;                          // samples per chunk
+constexpr int BSS_RUN = 8;                           // lags per thread
+constexpr int BSS_STAGE = BSS_T + SVS_BSS_MAX_LAG;   // staged samples per signal: chunk + halo (+1 for the last window load)
+constexpr int BSS_PADLEN = BSS_STAGE + BSS_STAGE / 8;
+constexpr int BSS_THREADS = 256;
+constexpr int BSS_MAX_BLOCKS = 1024;                 // blocks per launch (x * y); 2 blocks of 5 signals fit a CU's LDS
+constexpr int NB = 64;                               // Cholesky panel width
+
+// one padding double after every 8: the 8-lag runs of consecutive lanes start 9 doubles apart, so a wave's window loads
+// hit distinct banks
+__device__ __forceinline__ int pidx(int i) { return i + (i >> 3); }
+
+struct CorrArgs {
+  const double* x; long ld; long n; int nsig, npairs, runs, chunks;
+  int px[SVS_BSS_MAX_PAIRS], py[SVS_BSS_MAX_PAIRS], nl[SVS_BSS_MAX_PAIRS], run0[SVS_BSS_MAX_PAIRS + 1], off[SVS_BSS_MAX_PAIRS];
+  double* slab; double* out;
+};
+
+__device__ __forceinline__ int pair_of_run(const CorrArgs& a, int run) {
+  int p = 0;
+  while (p + 1 < a.npairs && run >= a.run0[p + 1]) ++p;
+  return p;
+}
+
+__global__ __launch_bounds__(BSS_THREADS) void bss_corr_kernel(CorrArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double sig[];      // [nsig][BSS_PADLEN]
+  const int tid = threadIdx.x;
+  const int run = blockIdx.y * BSS_THREADS + tid;
+  const bool active = run < a.runs;
+  int p = 0, k0 = 0;
+  if (active) {
+    p = pair_of_run(a, run);
+    k0 = (run - a.run0[p]) * BSS_RUN;
+  }
+  const double* X = sig + (active ? a.px[p] : 0) * BSS_PADLEN;
+  const double* Y = sig + (active ? a.py[p] : 0) * BSS_PADLEN;
+  double acc[BSS_RUN];
+#pragma unroll
+  for (int j = 0; j < BSS_RUN; ++j) acc[j] = 0.0;
+  for (int c = blockIdx.x; c < a.chunks; c += gridDim.x) {
+    const long m0 = (long)c * BSS_T;
+    __syncthreads();
+    for (int s = 0; s < a.nsig; ++s) {
+      const double* src = a.x + (long)s * a.ld;
+      for (int i = tid; i < BSS_STAGE; i += BSS_THREADS) {
+        const long g = m0 + i;
+        sig[s * BSS_PADLEN + pidx(i)] = g < a.n ? src[g] : 0.0;
+      }
+    }
+    __syncthreads();
+    if (active) {
+      double w[BSS_RUN];
+#pragma unroll
+      for (int j = 0; j < BSS_RUN; ++j) w[j] = X[pidx(k0 + j)];
+      for (int m = 0; m < BSS_T; m += BSS_RUN) {
+        // m, k0 multiples of 8: the next window and the 8 y samples are contiguous groups of the padded layout
+        const double* xn = X + (m + k0 + BSS_RUN) / 8 * 9;
+        const double* yn = Y + m / 8 * 9;
+        double nx[BSS_RUN], y[BSS_RUN];
+#pragma unroll
+        for (int j = 0; j < BSS_RUN; ++j) { nx[j] = xn[j]; y[j] = yn[j]; }
+#pragma unroll
+        for (int t = 0; t < BSS_RUN; ++t)
+#pragma unroll
+          for (int j = 0; j < BSS_RUN; ++j) acc[j] = fma(t + j < BSS_RUN ? w[t + j] : nx[t + j - BSS_RUN], y[t], acc[j]);
+#pragma unroll
+        for (int j = 0; j < BSS_RUN; ++j) w[j] = nx[j];
+      }
+    }
+  }
+  if (active) {
+    double* dst = a.slab + ((long)blockIdx.x * a.runs + run) * BSS_RUN;
+#pragma unroll
+    for (int j = 0; j < BSS_RUN; ++j) dst[j] = acc[j];
+  }
+}
+
+__global__ __launch_bounds__(BSS_THREADS) void bss_corr_reduce_kernel(CorrArgs a, int nblk) {
+  const int l = blockIdx.x * BSS_THREADS + threadIdx.x;
+  if (l >= a.runs * BSS_RUN) return;
+  const int run = l / BSS_RUN;
+  const int p = pair_of_run(a, run);
+  const int k = (run - a.run0[p]) * BSS_RUN + l % BSS_RUN;
+  if (k >= a.nl[p]) return;
+  const long stride = (long)a.runs * BSS_RUN;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += a.slab[b * stride + l];
+  a.out[a.off[p] + k] = s;
+}
+
+int corr_blocks(long n, int runs) {
+  const long chunks = (n + BSS_T - 1) / BSS_T;
+  const int ygroups = (runs + BSS_THREADS - 1) / BSS_THREADS;
+  return (int)std::min<long>(chunks, std::max(1, BSS_MAX_BLOCKS / ygroups));
+}
+
+int count_runs(int npairs, const int* pairs) {
+  int runs = 0;
+  for (int q = 0; q < npairs; ++q) runs += (pairs[3 * q + 2] + BSS_RUN - 1) / BSS_RUN;
+  return runs;
+}
+
+// ---- Gram matrix, Cholesky, forward solve ---------------------------------------------------
+
+struct SolveArgs {
+  const double* corr; int K, flen, nrhs, np, rows;      // np: order padded to NB; rows = np + rhs rows (padded to NB)
+  int goff[4], roff[2 * SVS_BSS_MAX_RHS];
+  double* M; int* status; double* ynorm2;               // M: rows x np, row-major
+};
+
+__global__ __launch_bounds__(BSS_THREADS) void bss_expand_kernel(SolveArgs a) {
+  const long e = (long)blockIdx.x * BSS_THREADS + threadIdx.x;
+  if (e == 0) *a.status = 0;
+  if (e >= (long)a.rows * a.np) return;
+  const int r = (int)(e / a.np), c = (int)(e % a.np), kf = a.K * a.flen;
+  double v = 0.0;
+  if (r < a.np) {
+    if (r < kf && c < kf) {                          // G[(i,p),(j,q)] = R_ij[q-p]; R_ij[-d] = R_ji[d]
+      const int i = r / a.flen, pp = r % a.flen, j = c / a.flen, q = c % a.flen;
+      v = q >= pp ? a.corr[a.goff[i * a.K + j] + (q - pp)] : a.corr[a.goff[j * a.K + i] + (pp - q)];
+    } else {
+      v = r == c ? 1.0 : 0.0;
+    }
+  } else if (r - a.np < a.nrhs && c < kf) {          // D[(i,p)] of right-hand side r
+    v = a.corr[a.roff[(r - a.np) * a.K + c / a.flen] + c % a.flen];
+  }
+  a.M[e] = v;
+}
+
+// Step k: block b factors the diagonal tile (k,k) in LDS (every block, the same bits) and either reports its first bad
+// pivot (b == 0) or solves tile (k+b, k) against it: X L_kk^T = A.  The factor is never written back: the blocks of one
+// launch may start at any time, and a late block must still read the unfactored tile.  Nothing later reads tile (k,k).
+__global__ __launch_bounds__(BSS_THREADS) void bss_panel_kernel(SolveArgs a, int k) {
+  __shared__ double L[NB][NB + 1];
+  __shared__ double A[NB][NB + 1];
+  const int tid = threadIdx.x, i = k + blockIdx.x;
+  const long ld = a.np;
+  const double* dk = a.M + (long)k * NB * ld + (long)k * NB;
+  const double* di = a.M + (long)i * NB * ld + (long)k * NB;
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) {
+    L[e / NB][e % NB] = dk[(e / NB) * ld + e % NB];
+    if (i != k) A[e / NB][e % NB] = di[(e / NB) * ld + e % NB];
+  }
+  int bad = -1;
+  for (int c = 0; c < NB; ++c) {
+    __syncthreads();
+    const double d = L[c][c];
+    const bool ok = d > 0.0;                         // false for 0, negative and NaN
+    if (!ok && bad < 0) bad = c;
+    const double piv = ok ? sqrt(d) : 1.0;
+    __syncthreads();
+    if (tid == c) L[c][c] = piv;
+    else if (tid > c && tid < NB) L[tid][c] /= piv;
+    __syncthreads();
+    for (int e = tid; e < NB * NB; e += BSS_THREADS) {
+      const int r = e / NB, q = e % NB;
+      if (q > c && r >= q) L[r][q] -= L[r][c] * L[q][c];
+    }
+  }
+  __syncthreads();
+  if (i == k) {
+    if (tid == 0 && bad >= 0 && *a.status == 0) *a.status = k * NB + bad + 1;
+    return;
+  }
+  for (int c = 0; c < NB; ++c) {
+    if (tid < NB) A[tid][c] /= L[c][c];
+    __syncthreads();
+    for (int e = tid; e < NB * NB; e += BSS_THREADS) {
+      const int r = e / NB, q = e % NB;
+      if (q > c) A[r][q] -= A[r][c] * L[q][c];
+    }
+    __syncthreads();
+  }
+  double* dst = a.M + (long)i * NB * ld + (long)k * NB;
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) dst[(e / NB) * ld + e % NB] = A[e / NB][e % NB];
+}
+
+// Step k: tile (i, j), k < j <= i, j a column tile of G: A_ij -= L_ik L_jk^T.  Thread (tr, tc) owns rows tr + 16 a and
+// columns tc + 16 b.
+__global__ __launch_bounds__(BSS_THREADS) void bss_update_kernel(SolveArgs a, int k) {
+  const int j = k + 1 + blockIdx.x, i = k + 1 + blockIdx.y;
+  if (i < j) return;
+  __shared__ double Li[NB][NB + 1];                  // [kk][r]
+  __shared__ double Lj[NB][NB + 1];
+  const int tid = threadIdx.x, tr = tid / 16, tc = tid % 16;
+  const long ld = a.np;
+  const double* si = a.M + (long)i * NB * ld + (long)k * NB;
+  const double* sj = a.M + (long)j * NB * ld + (long)k * NB;
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) {
+    const int r = e / NB, kk = e % NB;
+    Li[kk][r] = si[r * ld + kk];
+    Lj[kk][r] = sj[r * ld + kk];
+  }
+  __syncthreads();
+  double acc[4][4] = {};
+  for (int kk = 0; kk < NB; ++kk) {
+    double u[4], v[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { u[t] = Li[kk][tr + 16 * t]; v[t] = Lj[kk][tc + 16 * t]; }
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc[s][t] = fma(u[s], v[t], acc[s][t]);
+  }
+  double* dst = a.M + (long)i * NB * ld + (long)j * NB;
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) dst[(tr + 16 * s) * ld + tc + 16 * t] -= acc[s][t];
+}
+
+__global__ __launch_bounds__(BSS_THREADS) void bss_norm_kernel(SolveArgs a) {
+  __shared__ double red[BSS_THREADS];
+  const int tid = threadIdx.x;
+  const double* y = a.M + (long)(a.np + blockIdx.x) * a.np;
+  double s = 0.0;
+  for (int c = tid; c < a.np; c += BSS_THREADS) s = fma(y[c], y[c], s);
+  red[tid] = s;
+  for (int h = BSS_THREADS / 2; h > 0; h >>= 1) {
+    __syncthreads();
+    if (tid < h) red[tid] += red[tid + h];
+  }
+  if (tid == 0) a.ynorm2[blockIdx.x] = red[0];
+}
+
+int solve_dims(int K, int flen, int nrhs, int& np, int& rows) {
+  np = (K * flen + NB - 1) / NB * NB;
+  rows = np + (nrhs + NB - 1) / NB * NB;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" size_t svs_bss_corr_workspace_bytes(int64_t n, int npairs, const int* pairs) {
+  if (n < 1 || npairs < 1 || npairs > SVS_BSS_MAX_PAIRS || !pairs) return 0;
+  const int runs = count_runs(npairs, pairs);
+  return (size_t)corr_blocks(n, runs) * runs * BSS_RUN * sizeof(double);
+}
+
+extern "C" int svs_bss_corr(const double* x, int64_t ld, int nsig, int64_t n, const int* pairs, int npairs, double* out,
+                            void* ws, size_t ws_bytes, hipStream_t stream) {
+  SVS_REQUIRE(x && out && pairs && n >= 1 && ld >= n && nsig >= 1 && nsig <= SVS_BSS_MAX_SIGNALS && npairs >= 1 &&
+              npairs <= SVS_BSS_MAX_PAIRS, "svs_bss_corr: bad arguments");
+  CorrArgs a{};
+  a.x = x; a.ld = ld; a.n = n; a.nsig = nsig; a.npairs = npairs; a.out = out; a.slab = (double*)ws;
+  int off = 0, runs = 0;
+  for (int q = 0; q < npairs; ++q) {
+    const int px = pairs[3 * q], py = pairs[3 * q + 1], nl = pairs[3 * q + 2];
+    SVS_REQUIRE(px >= 0 && px < nsig && py >= 0 && py < nsig && nl >= 1 && nl <= SVS_BSS_MAX_LAG,
+                "svs_bss_corr: pair %d = (%d, %d, %d) out of range", q, px, py, nl);
+    a.px[q] = px; a.py[q] = py; a.nl[q] = nl; a.off[q] = off; a.run0[q] = runs;
+    off += nl;
+    runs += (nl + BSS_RUN - 1) / BSS_RUN;
+  }
+  a.run0[npairs] = runs;
+  a.runs = runs;
+  a.chunks = (int)((n + BSS_T - 1) / BSS_T);
+  SVS_REQUIRE((n + BSS_T - 1) / BSS_T < (1L << 31), "svs_bss_corr: n = %ld too large", (long)n);
+  if (!ws || ws_bytes < svs_bss_corr_workspace_bytes(n, npairs, pairs)) {
+    svs_set_error("svs_bss_corr: workspace too small");
+    return SVS_ERR_WORKSPACE;
+  }
+  const int gx = corr_blocks(n, runs), gy = (runs + BSS_THREADS - 1) / BSS_THREADS;
+  const int lds = nsig * BSS_PADLEN * (int)sizeof(double);
+  SVS_HIP(hipFuncSetAttribute((const void*)bss_corr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipLaunchKernelGGL(bss_corr_kernel, dim3(gx, gy), dim3(BSS_THREADS), lds, stream, a);
+  SVS_CHECK_LAUNCH("bss_corr");
+  hipLaunchKernelGGL(bss_corr_reduce_kernel, dim3(svs_cdiv((long)runs * BSS_RUN, BSS_THREADS)), dim3(BSS_THREADS), 0, stream,
+                     a, gx);
+  SVS_CHECK_LAUNCH("bss_corr_reduce");
+  return SVS_OK;
+}
+
+extern "C" size_t svs_bss_solve_workspace_bytes(int K, int flen, int nrhs) {
+  if (K < 1 || K > 2 || flen < 1 || flen > SVS_BSS_MAX_LAG || nrhs < 1 || nrhs > SVS_BSS_MAX_RHS) return 0;
+  int np, rows;
+  solve_dims(K, flen, nrhs, np, rows);
+  return (size_t)rows * np * sizeof(double);
+}
+
+extern "C" int svs_bss_solve(const double* corr, int K, int flen, const int* gram_off, const int* rhs_off, int nrhs,
+                             double* ynorm2, int* status, void* ws, size_t ws_bytes, hipStream_t stream) {
+  SVS_REQUIRE(corr && gram_off && rhs_off && ynorm2 && status && K >= 1 && K <= 2 && flen >= 1 &&
+              flen <= SVS_BSS_MAX_LAG && nrhs >= 1 && nrhs <= SVS_BSS_MAX_RHS, "svs_bss_solve: bad arguments");
+  SolveArgs a{};
+  a.corr = corr; a.K = K; a.flen = flen; a.nrhs = nrhs; a.M = (double*)ws; a.status = status; a.ynorm2 = ynorm2;
+  for (int q = 0; q < K * K; ++q) {
+    SVS_REQUIRE(gram_off[q] >= 0, "svs_bss_solve: negative offset");
+    a.goff[q] = gram_off[q];
+  }
+  for (int q = 0; q < K * nrhs; ++q) {
+    SVS_REQUIRE(rhs_off[q] >= 0, "svs_bss_solve: negative offset");
+    a.roff[q] = rhs_off[q];
+  }
+  solve_dims(K, flen, nrhs, a.np, a.rows);
+  if (!ws || ws_bytes < svs_bss_solve_workspace_bytes(K, flen, nrhs)) {
+    svs_set_error("svs_bss_solve: workspace too small");
+    return SVS_ERR_WORKSPACE;
+  }
+  const int tc = a.np / NB, tr = a.rows / NB;
+  hipLaunchKernelGGL(bss_expand_kernel, dim3(svs_cdiv((long)a.rows * a.np, BSS_THREADS)), dim3(BSS_THREADS), 0, stream, a);
+  SVS_CHECK_LAUNCH("bss_expand");
+  for (int k = 0; k < tc; ++k) {
+    hipLaunchKernelGGL(bss_panel_kernel, dim3(tr - k), dim3(BSS_THREADS), 0, stream, a, k);
+    SVS_CHECK_LAUNCH("bss_panel");
+    if (k + 1 < tc) {
+      hipLaunchKernelGGL(bss_update_kernel, dim3(tc - k - 1, tr - k - 1), dim3(BSS_THREADS), 0, stream, a, k);
+      SVS_CHECK_LAUNCH("bss_update");
+    }
+  }
+  hipLaunchKernelGGL(bss_norm_kernel, dim3(nrhs), dim3(BSS_THREADS), 0, stream, a);
+  SVS_CHECK_LAUNCH("bss_norm");
+  return SVS_OK;
+}
