@@ -354,6 +354,25 @@ int svs_bss_corr(const double* x, int64_t ld, int nsig, int64_t n, const int* pa
 size_t svs_bss_solve_workspace_bytes(int K, int flen, int nrhs);
 int svs_bss_solve(const double* corr, int K, int flen, const int* gram_off, const int* rhs_off, int nrhs, double* ynorm2,
                   int* status, void* ws, size_t ws_bytes, hipStream_t stream);
+/* Framewise form of svs_bss_corr (evaluate.py: bss_eval_sources_framewise): the same correlations for every window
+ * w < nwin of x[:, w*hop .. w*hop + window), each window zero past its end (the halo included) and past n, in one
+ * correlation launch and one reduce launch whatever nwin is:
+ *   out[w*out_stride + off_q + k],   out_stride >= the sum of the nlags.   window, hop, nwin >= 1.
+ * Fixed-order sums, no atomics: bitwise reproducible.  The query is 0 for invalid arguments and for a grid too wide for
+ * one launch. */
+size_t svs_bss_corr_windows_workspace_bytes(int64_t window, int64_t nwin, int npairs, const int* pairs);
+int svs_bss_corr_windows(const double* x, int64_t ld, int nsig, int64_t n, int64_t window, int64_t hop, int64_t nwin,
+                         const int* pairs, int npairs, double* out, int64_t out_stride, void* ws, size_t ws_bytes,
+                         hipStream_t stream);
+/* Batched form of svs_bss_solve: nbatch independent systems of one shape (K, flen, nrhs).  System s takes its offsets,
+ * absolute in corr, from gram_off[s*K*K ..] and rhs_off[s*K*nrhs ..] (HOST int64 arrays, read before the call returns),
+ * and writes ynorm2[s*nrhs + r] and status[s] (device).  The launches (expand, one panel and one update launch per
+ * 64-column step, norms) do not depend on nbatch; a bad pivot in one system changes no other system's result.  The
+ * query is 0 for invalid arguments and for a batch too wide for one launch. */
+size_t svs_bss_solve_batched_workspace_bytes(int64_t nbatch, int K, int flen, int nrhs);
+int svs_bss_solve_batched(const double* corr, int64_t nbatch, int K, int flen, const int64_t* gram_off,
+                          const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, void* ws, size_t ws_bytes,
+                          hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -98,6 +98,10 @@ _SIGS = {
     "svs_bss_corr": (I, [P, L, I, L, P, I, P, P, Z, P]),
     "svs_bss_solve_workspace_bytes": (Z, [I, I, I]),
     "svs_bss_solve": (I, [P, I, I, P, P, I, P, P, P, Z, P]),
+    "svs_bss_corr_windows_workspace_bytes": (Z, [L, L, I, P]),
+    "svs_bss_corr_windows": (I, [P, L, I, L, L, L, L, P, I, P, L, P, Z, P]),
+    "svs_bss_solve_batched_workspace_bytes": (Z, [L, I, I, I]),
+    "svs_bss_solve_batched": (I, [P, L, I, I, P, P, I, P, P, P, Z, P]),
 }
 
 

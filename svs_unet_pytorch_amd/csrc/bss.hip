@@ -3,15 +3,21 @@
 //                           A block stages a chunk of T samples of every signal (plus a MAX_LAG halo) in LDS; a thread
 //                           owns a run of 8 consecutive lags of one pair and sweeps the chunk with the run's window in
 //                           registers (8 FMAs per two LDS reads).  Blocks stride over chunks and write one partial per
-//                           (block, lag) to a slab.
+//                           (block, lag) to a slab.  The framewise form runs every window of a signal in the same launch:
+//                           each window has blocks and a slab of its own.
 //   bss_corr_reduce_kernel  sums the slab over blocks in a fixed order: no atomics, bitwise reproducible.
 //   bss_expand_kernel       block-Toeplitz Gram matrix G (order K*flen, padded to a multiple of 64 with an identity) and
 //                           the right-hand sides D, stored below G as extra rows: [G; D^T].
 //   bss_panel_kernel /      right-looking blocked Cholesky of G in 64-wide panels.  Because the right-hand sides are rows
 //   bss_update_kernel       under G, the same triangular solves and updates that form L turn them into y^T = (L^-1 D)^T.
 //   bss_norm_kernel         |y|^2 per right-hand side = D^T G^-1 D, the energy of the projection (fixed-order sums).
-// A pivot that is not > 0 (a silent reference: G singular) is reported through *status; the factorisation goes on with a
-// unit pivot so that nothing faults, and the caller discards the result.
+// The solve kernels take a batch of independent systems of one shape: the system is the leading part of the flattened
+// block index, so a batch costs the launches of one system.  A pivot that is not > 0 (a silent reference: G singular) is
+// reported through the system's status word; the factorisation goes on with a unit pivot so that nothing faults, and the
+// caller discards that system's result.
+#include <algorithm>
+#include <vector>
+
 #include "common.h"
 
 namespace {
@@ -22,16 +28,21 @@ constexpr int BSS_STAGE = BSS_T + SVS_BSS_MAX_LAG;   // staged samples per signa
 constexpr int BSS_PADLEN = BSS_STAGE + BSS_STAGE / 8;
 constexpr int BSS_THREADS = 256;
 constexpr int BSS_MAX_BLOCKS = 1024;                 // blocks per launch (x * y); 2 blocks of 5 signals fit a CU's LDS
+constexpr long BSS_MAX_GRID = 0xffffffffL / BSS_THREADS;   // blocks in one grid dimension (its work-items must fit 32 bits)
 constexpr int NB = 64;                               // Cholesky panel width
 
 // one padding double after every 8: the 8-lag runs of consecutive lanes start 9 doubles apart, so a wave's window loads
 // hit distinct banks
 __device__ __forceinline__ int pidx(int i) { return i + (i >> 3); }
 
+// Window w of a launch is x[:, w*hop .. w*hop + window), zero past its end and past n; the whole-signal call is one window
+// (hop 0, window n).  chunks: per window; gx: blocks per window (the grid is nwin * gx blocks wide); rblocks: reduce blocks
+// per window.  Slab [window][block][lag]; window w's correlations go to out + w * out_stride.
 struct CorrArgs {
   const double* x; long ld; long n; int nsig, npairs, runs, chunks;
   int px[SVS_BSS_MAX_PAIRS], py[SVS_BSS_MAX_PAIRS], nl[SVS_BSS_MAX_PAIRS], run0[SVS_BSS_MAX_PAIRS + 1], off[SVS_BSS_MAX_PAIRS];
   double* slab; double* out;
+  long hop, window, out_stride; int gx, rblocks;
 };
 
 __device__ __forceinline__ int pair_of_run(const CorrArgs& a, int run) {
@@ -52,24 +63,27 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_corr_kernel(CorrArgs a) {
   }
   const double* X = sig + (active ? a.px[p] : 0) * BSS_PADLEN;
   const double* Y = sig + (active ? a.py[p] : 0) * BSS_PADLEN;
+  const int w = blockIdx.x / a.gx, bx = blockIdx.x % a.gx;
+  const long base = (long)w * a.hop;
+  const long nw = a.n - base < a.window ? a.n - base : a.window;   // samples of window w that exist (<= 0: none)
   double acc[BSS_RUN];
 #pragma unroll
   for (int j = 0; j < BSS_RUN; ++j) acc[j] = 0.0;
-  for (int c = blockIdx.x; c < a.chunks; c += gridDim.x) {
+  for (int c = bx; c < a.chunks; c += a.gx) {
     const long m0 = (long)c * BSS_T;
     __syncthreads();
     for (int s = 0; s < a.nsig; ++s) {
-      const double* src = a.x + (long)s * a.ld;
+      const double* src = a.x + (long)s * a.ld + base;
       for (int i = tid; i < BSS_STAGE; i += BSS_THREADS) {
         const long g = m0 + i;
-        sig[s * BSS_PADLEN + pidx(i)] = g < a.n ? src[g] : 0.0;
+        sig[s * BSS_PADLEN + pidx(i)] = g < nw ? src[g] : 0.0;
       }
     }
     __syncthreads();
     if (active) {
-      double w[BSS_RUN];
+      double win[BSS_RUN];
 #pragma unroll
-      for (int j = 0; j < BSS_RUN; ++j) w[j] = X[pidx(k0 + j)];
+      for (int j = 0; j < BSS_RUN; ++j) win[j] = X[pidx(k0 + j)];
       for (int m = 0; m < BSS_T; m += BSS_RUN) {
         // m, k0 multiples of 8: the next window and the 8 y samples are contiguous groups of the padded layout
         const double* xn = X + (m + k0 + BSS_RUN) / 8 * 9;
@@ -80,36 +94,39 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_corr_kernel(CorrArgs a) {
 #pragma unroll
         for (int t = 0; t < BSS_RUN; ++t)
 #pragma unroll
-          for (int j = 0; j < BSS_RUN; ++j) acc[j] = fma(t + j < BSS_RUN ? w[t + j] : nx[t + j - BSS_RUN], y[t], acc[j]);
+          for (int j = 0; j < BSS_RUN; ++j) acc[j] = fma(t + j < BSS_RUN ? win[t + j] : nx[t + j - BSS_RUN], y[t], acc[j]);
 #pragma unroll
-        for (int j = 0; j < BSS_RUN; ++j) w[j] = nx[j];
+        for (int j = 0; j < BSS_RUN; ++j) win[j] = nx[j];
       }
     }
   }
   if (active) {
-    double* dst = a.slab + ((long)blockIdx.x * a.runs + run) * BSS_RUN;
+    double* dst = a.slab + (((long)w * a.gx + bx) * a.runs + run) * BSS_RUN;
 #pragma unroll
     for (int j = 0; j < BSS_RUN; ++j) dst[j] = acc[j];
   }
 }
 
-__global__ __launch_bounds__(BSS_THREADS) void bss_corr_reduce_kernel(CorrArgs a, int nblk) {
-  const int l = blockIdx.x * BSS_THREADS + threadIdx.x;
+__global__ __launch_bounds__(BSS_THREADS) void bss_corr_reduce_kernel(CorrArgs a) {
+  const int w = blockIdx.x / a.rblocks;
+  const int l = (blockIdx.x % a.rblocks) * BSS_THREADS + threadIdx.x;
   if (l >= a.runs * BSS_RUN) return;
   const int run = l / BSS_RUN;
   const int p = pair_of_run(a, run);
   const int k = (run - a.run0[p]) * BSS_RUN + l % BSS_RUN;
   if (k >= a.nl[p]) return;
   const long stride = (long)a.runs * BSS_RUN;
+  const double* slab = a.slab + (long)w * a.gx * stride;
   double s = 0.0;
-  for (int b = 0; b < nblk; ++b) s += a.slab[b * stride + l];
-  a.out[a.off[p] + k] = s;
+  for (int b = 0; b < a.gx; ++b) s += slab[b * stride + l];
+  a.out[(long)w * a.out_stride + a.off[p] + k] = s;
 }
 
-int corr_blocks(long n, int runs) {
-  const long chunks = (n + BSS_T - 1) / BSS_T;
-  const int ygroups = (runs + BSS_THREADS - 1) / BSS_THREADS;
-  return (int)std::min<long>(chunks, std::max(1, BSS_MAX_BLOCKS / ygroups));
+// blocks per window: one per chunk while the whole grid stays within BSS_MAX_BLOCKS (one window: the whole-signal grid)
+int corr_blocks(long window, int runs, long nwin = 1) {
+  const long chunks = (window + BSS_T - 1) / BSS_T;
+  const long ygroups = (runs + BSS_THREADS - 1) / BSS_THREADS;
+  return (int)std::min<long>(chunks, std::max<long>(1, BSS_MAX_BLOCKS / (ygroups * nwin)));
 }
 
 int count_runs(int npairs, const int* pairs) {
@@ -118,31 +135,83 @@ int count_runs(int npairs, const int* pairs) {
   return runs;
 }
 
+bool pairs_valid(int npairs, const int* pairs) {
+  if (npairs < 1 || npairs > SVS_BSS_MAX_PAIRS || !pairs) return false;
+  for (int q = 0; q < npairs; ++q)
+    if (pairs[3 * q] < 0 || pairs[3 * q + 1] < 0 || pairs[3 * q + 2] < 1 || pairs[3 * q + 2] > SVS_BSS_MAX_LAG) return false;
+  return true;
+}
+
+// the pair table of both correlation entry points; the launch geometry (window, hop, chunks, gx, rblocks) is the caller's
+int corr_setup(CorrArgs& a, const double* x, int64_t ld, int nsig, int64_t n, const int* pairs, int npairs, double* out,
+               void* ws, const char* who) {
+  SVS_REQUIRE(x && out && pairs && n >= 1 && ld >= n && nsig >= 1 && nsig <= SVS_BSS_MAX_SIGNALS && npairs >= 1 &&
+              npairs <= SVS_BSS_MAX_PAIRS, "%s: bad arguments", who);
+  a.x = x; a.ld = ld; a.n = n; a.nsig = nsig; a.npairs = npairs; a.out = out; a.slab = (double*)ws;
+  int off = 0, runs = 0;
+  for (int q = 0; q < npairs; ++q) {
+    const int px = pairs[3 * q], py = pairs[3 * q + 1], nl = pairs[3 * q + 2];
+    SVS_REQUIRE(px >= 0 && px < nsig && py >= 0 && py < nsig && nl >= 1 && nl <= SVS_BSS_MAX_LAG,
+                "%s: pair %d = (%d, %d, %d) out of range", who, q, px, py, nl);
+    a.px[q] = px; a.py[q] = py; a.nl[q] = nl; a.off[q] = off; a.run0[q] = runs;
+    off += nl;
+    runs += (nl + BSS_RUN - 1) / BSS_RUN;
+  }
+  a.run0[npairs] = runs;
+  a.runs = runs;
+  return SVS_OK;
+}
+
+int corr_launch(const CorrArgs& a, long nwin, hipStream_t stream) {
+  const int gy = (a.runs + BSS_THREADS - 1) / BSS_THREADS;
+  const int lds = a.nsig * BSS_PADLEN * (int)sizeof(double);
+  SVS_HIP(hipFuncSetAttribute((const void*)bss_corr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipLaunchKernelGGL(bss_corr_kernel, dim3((unsigned)(nwin * a.gx), gy), dim3(BSS_THREADS), lds, stream, a);
+  SVS_CHECK_LAUNCH("bss_corr");
+  hipLaunchKernelGGL(bss_corr_reduce_kernel, dim3((unsigned)(nwin * a.rblocks)), dim3(BSS_THREADS), 0, stream, a);
+  SVS_CHECK_LAUNCH("bss_corr_reduce");
+  return SVS_OK;
+}
+
 // ---- Gram matrix, Cholesky, forward solve ---------------------------------------------------
 
+// System s of a launch: its matrix at M + s * mstride, its status word status[s], its norms at ynorm2 + s * nrhs.  Its
+// offsets in corr come from goff / roff (one system) or from the device table tab (per system: K*K gram offsets, then
+// K*nrhs right-hand-side offsets).
 struct SolveArgs {
   const double* corr; int K, flen, nrhs, np, rows;      // np: order padded to NB; rows = np + rhs rows (padded to NB)
   int goff[4], roff[2 * SVS_BSS_MAX_RHS];
   double* M; int* status; double* ynorm2;               // M: rows x np, row-major
+  const int64_t* tab; long mstride;
 };
 
-__global__ __launch_bounds__(BSS_THREADS) void bss_expand_kernel(SolveArgs a) {
-  const long e = (long)blockIdx.x * BSS_THREADS + threadIdx.x;
-  if (e == 0) *a.status = 0;
+__device__ __forceinline__ long gram_at(const SolveArgs& a, int s, int q) {
+  return a.tab ? a.tab[(long)s * (a.K * a.K + a.K * a.nrhs) + q] : a.goff[q];
+}
+
+__device__ __forceinline__ long rhs_at(const SolveArgs& a, int s, int q) {
+  return a.tab ? a.tab[(long)s * (a.K * a.K + a.K * a.nrhs) + a.K * a.K + q] : a.roff[q];
+}
+
+__global__ __launch_bounds__(BSS_THREADS) void bss_expand_kernel(SolveArgs a, int per) {
+  const int s = blockIdx.x / per;
+  const long e = (long)(blockIdx.x % per) * BSS_THREADS + threadIdx.x;
+  double* M = a.M + s * a.mstride;
+  if (e == 0) a.status[s] = 0;
   if (e >= (long)a.rows * a.np) return;
   const int r = (int)(e / a.np), c = (int)(e % a.np), kf = a.K * a.flen;
   double v = 0.0;
   if (r < a.np) {
     if (r < kf && c < kf) {                          // G[(i,p),(j,q)] = R_ij[q-p]; R_ij[-d] = R_ji[d]
       const int i = r / a.flen, pp = r % a.flen, j = c / a.flen, q = c % a.flen;
-      v = q >= pp ? a.corr[a.goff[i * a.K + j] + (q - pp)] : a.corr[a.goff[j * a.K + i] + (pp - q)];
+      v = q >= pp ? a.corr[gram_at(a, s, i * a.K + j) + (q - pp)] : a.corr[gram_at(a, s, j * a.K + i) + (pp - q)];
     } else {
       v = r == c ? 1.0 : 0.0;
     }
   } else if (r - a.np < a.nrhs && c < kf) {          // D[(i,p)] of right-hand side r
-    v = a.corr[a.roff[(r - a.np) * a.K + c / a.flen] + c % a.flen];
+    v = a.corr[rhs_at(a, s, (r - a.np) * a.K + c / a.flen) + c % a.flen];
   }
-  a.M[e] = v;
+  M[e] = v;
 }
 
 // Step k: block b factors the diagonal tile (k,k) in LDS (every block, the same bits) and either reports its first bad
@@ -151,10 +220,13 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_expand_kernel(SolveArgs a) {
 __global__ __launch_bounds__(BSS_THREADS) void bss_panel_kernel(SolveArgs a, int k) {
   __shared__ double L[NB][NB + 1];
   __shared__ double A[NB][NB + 1];
-  const int tid = threadIdx.x, i = k + blockIdx.x;
+  const int nt = a.rows / NB - k;
+  const int s = blockIdx.x / nt;
+  const int tid = threadIdx.x, i = k + blockIdx.x % nt;
   const long ld = a.np;
-  const double* dk = a.M + (long)k * NB * ld + (long)k * NB;
-  const double* di = a.M + (long)i * NB * ld + (long)k * NB;
+  double* M = a.M + s * a.mstride;
+  const double* dk = M + (long)k * NB * ld + (long)k * NB;
+  const double* di = M + (long)i * NB * ld + (long)k * NB;
   for (int e = tid; e < NB * NB; e += BSS_THREADS) {
     L[e / NB][e % NB] = dk[(e / NB) * ld + e % NB];
     if (i != k) A[e / NB][e % NB] = di[(e / NB) * ld + e % NB];
@@ -177,7 +249,7 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_panel_kernel(SolveArgs a, int
   }
   __syncthreads();
   if (i == k) {
-    if (tid == 0 && bad >= 0 && *a.status == 0) *a.status = k * NB + bad + 1;
+    if (tid == 0 && bad >= 0 && a.status[s] == 0) a.status[s] = k * NB + bad + 1;
     return;
   }
   for (int c = 0; c < NB; ++c) {
@@ -189,21 +261,24 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_panel_kernel(SolveArgs a, int
     }
     __syncthreads();
   }
-  double* dst = a.M + (long)i * NB * ld + (long)k * NB;
+  double* dst = M + (long)i * NB * ld + (long)k * NB;
   for (int e = tid; e < NB * NB; e += BSS_THREADS) dst[(e / NB) * ld + e % NB] = A[e / NB][e % NB];
 }
 
 // Step k: tile (i, j), k < j <= i, j a column tile of G: A_ij -= L_ik L_jk^T.  Thread (tr, tc) owns rows tr + 16 a and
-// columns tc + 16 b.
+// columns tc + 16 b.  Block index: system, then tile row, then tile column.
 __global__ __launch_bounds__(BSS_THREADS) void bss_update_kernel(SolveArgs a, int k) {
-  const int j = k + 1 + blockIdx.x, i = k + 1 + blockIdx.y;
+  const int nj = a.np / NB - k - 1, ni = a.rows / NB - k - 1;
+  const int s = blockIdx.x / (ni * nj), t = blockIdx.x % (ni * nj);
+  const int j = k + 1 + t % nj, i = k + 1 + t / nj;
   if (i < j) return;
   __shared__ double Li[NB][NB + 1];                  // [kk][r]
   __shared__ double Lj[NB][NB + 1];
   const int tid = threadIdx.x, tr = tid / 16, tc = tid % 16;
   const long ld = a.np;
-  const double* si = a.M + (long)i * NB * ld + (long)k * NB;
-  const double* sj = a.M + (long)j * NB * ld + (long)k * NB;
+  double* M = a.M + s * a.mstride;
+  const double* si = M + (long)i * NB * ld + (long)k * NB;
+  const double* sj = M + (long)j * NB * ld + (long)k * NB;
   for (int e = tid; e < NB * NB; e += BSS_THREADS) {
     const int r = e / NB, kk = e % NB;
     Li[kk][r] = si[r * ld + kk];
@@ -214,37 +289,72 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_update_kernel(SolveArgs a, in
   for (int kk = 0; kk < NB; ++kk) {
     double u[4], v[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) { u[t] = Li[kk][tr + 16 * t]; v[t] = Lj[kk][tc + 16 * t]; }
+    for (int q = 0; q < 4; ++q) { u[q] = Li[kk][tr + 16 * q]; v[q] = Lj[kk][tc + 16 * q]; }
 #pragma unroll
-    for (int s = 0; s < 4; ++s)
+    for (int p = 0; p < 4; ++p)
 #pragma unroll
-      for (int t = 0; t < 4; ++t) acc[s][t] = fma(u[s], v[t], acc[s][t]);
+      for (int q = 0; q < 4; ++q) acc[p][q] = fma(u[p], v[q], acc[p][q]);
   }
-  double* dst = a.M + (long)i * NB * ld + (long)j * NB;
+  double* dst = M + (long)i * NB * ld + (long)j * NB;
 #pragma unroll
-  for (int s = 0; s < 4; ++s)
+  for (int p = 0; p < 4; ++p)
 #pragma unroll
-    for (int t = 0; t < 4; ++t) dst[(tr + 16 * s) * ld + tc + 16 * t] -= acc[s][t];
+    for (int q = 0; q < 4; ++q) dst[(tr + 16 * p) * ld + tc + 16 * q] -= acc[p][q];
 }
 
 __global__ __launch_bounds__(BSS_THREADS) void bss_norm_kernel(SolveArgs a) {
   __shared__ double red[BSS_THREADS];
   const int tid = threadIdx.x;
-  const double* y = a.M + (long)(a.np + blockIdx.x) * a.np;
-  double s = 0.0;
-  for (int c = tid; c < a.np; c += BSS_THREADS) s = fma(y[c], y[c], s);
-  red[tid] = s;
+  const int s = blockIdx.x / a.nrhs, r = blockIdx.x % a.nrhs;
+  const double* y = a.M + s * a.mstride + (long)(a.np + r) * a.np;
+  double acc = 0.0;
+  for (int c = tid; c < a.np; c += BSS_THREADS) acc = fma(y[c], y[c], acc);
+  red[tid] = acc;
   for (int h = BSS_THREADS / 2; h > 0; h >>= 1) {
     __syncthreads();
     if (tid < h) red[tid] += red[tid + h];
   }
-  if (tid == 0) a.ynorm2[blockIdx.x] = red[0];
+  if (tid == 0) a.ynorm2[(long)s * a.nrhs + r] = red[0];
 }
 
 int solve_dims(int K, int flen, int nrhs, int& np, int& rows) {
   np = (K * flen + NB - 1) / NB * NB;
   rows = np + (nrhs + NB - 1) / NB * NB;
   return 0;
+}
+
+// systems that fit one batch: the widest launch of one system (the expand launch, or the first update launch of a small
+// order) times the batch must stay within BSS_MAX_GRID blocks
+long solve_max_systems(int K, int flen, int nrhs) {
+  int np, rows;
+  solve_dims(K, flen, nrhs, np, rows);
+  const long tc = np / NB, tr = rows / NB;
+  const long widest = std::max<long>({(long)svs_cdiv((long)rows * np, BSS_THREADS), tr, (tc - 1) * (tr - 1), (long)nrhs});
+  return BSS_MAX_GRID / widest;
+}
+
+size_t solve_table_bytes(long nbatch, int K, int nrhs) {
+  return svs_align_up((size_t)nbatch * (K * K + K * nrhs) * sizeof(int64_t), 256);
+}
+
+// expand; per panel step one panel launch and one update launch; the norms -- each over all nsys systems at once
+int solve_launch(const SolveArgs& a, long nsys, hipStream_t stream) {
+  const int tc = a.np / NB, tr = a.rows / NB;
+  const int per = svs_cdiv((long)a.rows * a.np, BSS_THREADS);
+  hipLaunchKernelGGL(bss_expand_kernel, dim3((unsigned)(nsys * per)), dim3(BSS_THREADS), 0, stream, a, per);
+  SVS_CHECK_LAUNCH("bss_expand");
+  for (int k = 0; k < tc; ++k) {
+    hipLaunchKernelGGL(bss_panel_kernel, dim3((unsigned)(nsys * (tr - k))), dim3(BSS_THREADS), 0, stream, a, k);
+    SVS_CHECK_LAUNCH("bss_panel");
+    if (k + 1 < tc) {
+      hipLaunchKernelGGL(bss_update_kernel, dim3((unsigned)(nsys * (tc - k - 1) * (tr - k - 1))), dim3(BSS_THREADS), 0,
+                         stream, a, k);
+      SVS_CHECK_LAUNCH("bss_update");
+    }
+  }
+  hipLaunchKernelGGL(bss_norm_kernel, dim3((unsigned)(nsys * a.nrhs)), dim3(BSS_THREADS), 0, stream, a);
+  SVS_CHECK_LAUNCH("bss_norm");
+  return SVS_OK;
 }
 
 }  // namespace
@@ -257,36 +367,50 @@ extern "C" size_t svs_bss_corr_workspace_bytes(int64_t n, int npairs, const int*
 
 extern "C" int svs_bss_corr(const double* x, int64_t ld, int nsig, int64_t n, const int* pairs, int npairs, double* out,
                             void* ws, size_t ws_bytes, hipStream_t stream) {
-  SVS_REQUIRE(x && out && pairs && n >= 1 && ld >= n && nsig >= 1 && nsig <= SVS_BSS_MAX_SIGNALS && npairs >= 1 &&
-              npairs <= SVS_BSS_MAX_PAIRS, "svs_bss_corr: bad arguments");
   CorrArgs a{};
-  a.x = x; a.ld = ld; a.n = n; a.nsig = nsig; a.npairs = npairs; a.out = out; a.slab = (double*)ws;
-  int off = 0, runs = 0;
-  for (int q = 0; q < npairs; ++q) {
-    const int px = pairs[3 * q], py = pairs[3 * q + 1], nl = pairs[3 * q + 2];
-    SVS_REQUIRE(px >= 0 && px < nsig && py >= 0 && py < nsig && nl >= 1 && nl <= SVS_BSS_MAX_LAG,
-                "svs_bss_corr: pair %d = (%d, %d, %d) out of range", q, px, py, nl);
-    a.px[q] = px; a.py[q] = py; a.nl[q] = nl; a.off[q] = off; a.run0[q] = runs;
-    off += nl;
-    runs += (nl + BSS_RUN - 1) / BSS_RUN;
-  }
-  a.run0[npairs] = runs;
-  a.runs = runs;
-  a.chunks = (int)((n + BSS_T - 1) / BSS_T);
+  const int rc = corr_setup(a, x, ld, nsig, n, pairs, npairs, out, ws, "svs_bss_corr");
+  if (rc != SVS_OK) return rc;
   SVS_REQUIRE((n + BSS_T - 1) / BSS_T < (1L << 31), "svs_bss_corr: n = %ld too large", (long)n);
   if (!ws || ws_bytes < svs_bss_corr_workspace_bytes(n, npairs, pairs)) {
     svs_set_error("svs_bss_corr: workspace too small");
     return SVS_ERR_WORKSPACE;
   }
-  const int gx = corr_blocks(n, runs), gy = (runs + BSS_THREADS - 1) / BSS_THREADS;
-  const int lds = nsig * BSS_PADLEN * (int)sizeof(double);
-  SVS_HIP(hipFuncSetAttribute((const void*)bss_corr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  hipLaunchKernelGGL(bss_corr_kernel, dim3(gx, gy), dim3(BSS_THREADS), lds, stream, a);
-  SVS_CHECK_LAUNCH("bss_corr");
-  hipLaunchKernelGGL(bss_corr_reduce_kernel, dim3(svs_cdiv((long)runs * BSS_RUN, BSS_THREADS)), dim3(BSS_THREADS), 0, stream,
-                     a, gx);
-  SVS_CHECK_LAUNCH("bss_corr_reduce");
-  return SVS_OK;
+  a.hop = 0; a.window = n; a.out_stride = 0;
+  a.chunks = (int)((n + BSS_T - 1) / BSS_T);
+  a.gx = corr_blocks(n, a.runs);
+  a.rblocks = svs_cdiv((long)a.runs * BSS_RUN, BSS_THREADS);
+  return corr_launch(a, 1, stream);
+}
+
+extern "C" size_t svs_bss_corr_windows_workspace_bytes(int64_t window, int64_t nwin, int npairs, const int* pairs) {
+  if (window < 1 || nwin < 1 || !pairs_valid(npairs, pairs) || (window + BSS_T - 1) / BSS_T >= (1L << 31)) return 0;
+  const int runs = count_runs(npairs, pairs);
+  const long gx = corr_blocks(window, runs, nwin), rblocks = svs_cdiv((long)runs * BSS_RUN, BSS_THREADS);
+  if (nwin > BSS_MAX_GRID / gx || nwin > BSS_MAX_GRID / rblocks) return 0;
+  return (size_t)nwin * gx * runs * BSS_RUN * sizeof(double);
+}
+
+extern "C" int svs_bss_corr_windows(const double* x, int64_t ld, int nsig, int64_t n, int64_t window, int64_t hop,
+                                    int64_t nwin, const int* pairs, int npairs, double* out, int64_t out_stride, void* ws,
+                                    size_t ws_bytes, hipStream_t stream) {
+  CorrArgs a{};
+  const int rc = corr_setup(a, x, ld, nsig, n, pairs, npairs, out, ws, "svs_bss_corr_windows");
+  if (rc != SVS_OK) return rc;
+  const long lags = a.off[npairs - 1] + a.nl[npairs - 1];
+  SVS_REQUIRE(window >= 1 && hop >= 1 && nwin >= 1 && out_stride >= lags,
+              "svs_bss_corr_windows: window = %ld, hop = %ld, nwin = %ld, out_stride = %ld (>= %ld lags) out of range",
+              (long)window, (long)hop, (long)nwin, (long)out_stride, lags);
+  const size_t need = svs_bss_corr_windows_workspace_bytes(window, nwin, npairs, pairs);
+  SVS_REQUIRE(need > 0, "svs_bss_corr_windows: %ld windows of %ld samples do not fit one launch", (long)nwin, (long)window);
+  if (!ws || ws_bytes < need) {
+    svs_set_error("svs_bss_corr_windows: workspace too small");
+    return SVS_ERR_WORKSPACE;
+  }
+  a.hop = hop; a.window = window; a.out_stride = out_stride;
+  a.chunks = (int)((window + BSS_T - 1) / BSS_T);
+  a.gx = corr_blocks(window, a.runs, nwin);
+  a.rblocks = svs_cdiv((long)a.runs * BSS_RUN, BSS_THREADS);
+  return corr_launch(a, nwin, stream);
 }
 
 extern "C" size_t svs_bss_solve_workspace_bytes(int K, int flen, int nrhs) {
@@ -315,18 +439,45 @@ extern "C" int svs_bss_solve(const double* corr, int K, int flen, const int* gra
     svs_set_error("svs_bss_solve: workspace too small");
     return SVS_ERR_WORKSPACE;
   }
-  const int tc = a.np / NB, tr = a.rows / NB;
-  hipLaunchKernelGGL(bss_expand_kernel, dim3(svs_cdiv((long)a.rows * a.np, BSS_THREADS)), dim3(BSS_THREADS), 0, stream, a);
-  SVS_CHECK_LAUNCH("bss_expand");
-  for (int k = 0; k < tc; ++k) {
-    hipLaunchKernelGGL(bss_panel_kernel, dim3(tr - k), dim3(BSS_THREADS), 0, stream, a, k);
-    SVS_CHECK_LAUNCH("bss_panel");
-    if (k + 1 < tc) {
-      hipLaunchKernelGGL(bss_update_kernel, dim3(tc - k - 1, tr - k - 1), dim3(BSS_THREADS), 0, stream, a, k);
-      SVS_CHECK_LAUNCH("bss_update");
+  return solve_launch(a, 1, stream);
+}
+
+extern "C" size_t svs_bss_solve_batched_workspace_bytes(int64_t nbatch, int K, int flen, int nrhs) {
+  const size_t one = svs_bss_solve_workspace_bytes(K, flen, nrhs);
+  if (!one || nbatch < 1 || nbatch > solve_max_systems(K, flen, nrhs)) return 0;
+  return solve_table_bytes(nbatch, K, nrhs) + (size_t)nbatch * one;
+}
+
+extern "C" int svs_bss_solve_batched(const double* corr, int64_t nbatch, int K, int flen, const int64_t* gram_off,
+                                     const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, void* ws,
+                                     size_t ws_bytes, hipStream_t stream) {
+  SVS_REQUIRE(corr && gram_off && rhs_off && ynorm2 && status && nbatch >= 1 && K >= 1 && K <= 2 && flen >= 1 &&
+              flen <= SVS_BSS_MAX_LAG && nrhs >= 1 && nrhs <= SVS_BSS_MAX_RHS, "svs_bss_solve_batched: bad arguments");
+  SVS_REQUIRE(nbatch <= solve_max_systems(K, flen, nrhs), "svs_bss_solve_batched: nbatch = %ld too large for one launch",
+              (long)nbatch);
+  const int ng = K * K, nr = K * nrhs;
+  std::vector<int64_t> tab((size_t)nbatch * (ng + nr));
+  for (long s = 0; s < nbatch; ++s) {
+    for (int q = 0; q < ng; ++q) {
+      SVS_REQUIRE(gram_off[s * ng + q] >= 0, "svs_bss_solve_batched: negative offset (system %ld)", s);
+      tab[s * (ng + nr) + q] = gram_off[s * ng + q];
+    }
+    for (int q = 0; q < nr; ++q) {
+      SVS_REQUIRE(rhs_off[s * nr + q] >= 0, "svs_bss_solve_batched: negative offset (system %ld)", s);
+      tab[s * (ng + nr) + ng + q] = rhs_off[s * nr + q];
     }
   }
-  hipLaunchKernelGGL(bss_norm_kernel, dim3(nrhs), dim3(BSS_THREADS), 0, stream, a);
-  SVS_CHECK_LAUNCH("bss_norm");
-  return SVS_OK;
+  if (!ws || ws_bytes < svs_bss_solve_batched_workspace_bytes(nbatch, K, flen, nrhs)) {
+    svs_set_error("svs_bss_solve_batched: workspace too small");
+    return SVS_ERR_WORKSPACE;
+  }
+  SolveArgs a{};
+  a.corr = corr; a.K = K; a.flen = flen; a.nrhs = nrhs; a.status = status; a.ynorm2 = ynorm2;
+  solve_dims(K, flen, nrhs, a.np, a.rows);
+  a.tab = (const int64_t*)ws;
+  a.M = (double*)((char*)ws + solve_table_bytes(nbatch, K, nrhs));
+  a.mstride = (long)a.rows * a.np;
+  // from pageable memory: the runtime has staged `tab` by the time the copy call returns
+  SVS_HIP(hipMemcpyAsync((void*)a.tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+  return solve_launch(a, nbatch, stream);
 }

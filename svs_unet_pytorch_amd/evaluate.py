@@ -17,7 +17,9 @@ wav files are read with scipy.io.wavfile (mono downmix, native sample rate: eval
 
 `bss_eval_sources_gpu` and `metrics_from_waveforms(..., device="gpu")` (CLI `--device gpu`) compute the same metrics with
 fp64 gfx950 kernels (csrc/bss.hip) from the Gram-matrix form below; the numpy functions stay the reference they are
-tested against.
+tested against.  `bss_eval_sources_framewise` / `metrics_from_waveforms_framewise` (CLI `--frame_window`) score windows of
+a track the way mir_eval.separation.bss_eval_sources_framewise does; their GPU forms make one windowed correlation pass
+and factor the Gram matrices of all windows in batches.
 
 The Gram-matrix form of _project / _criteria.  References s_0 .. s_{K-1} and an estimate e of length n, zero outside
 [0, n); filter length F; x(.-p) is x delayed by p samples.  _project builds
@@ -46,6 +48,9 @@ import warnings
 import numpy as np
 
 FILTER_LEN = 512
+METRICS = ("SDR", "SIR", "SAR", "NSDR")
+WS_BUDGET = 1 << 30          # default workspace bytes of one batch of framewise factorisations
+MAX_BATCH = 1024             # systems per batched factorisation (the kernels' grid limit is far above this)
 
 
 def load_mono_audio(path):
@@ -255,16 +260,50 @@ def bss_eval_sources_gpu(reference_sources, estimated_sources, compute_permutati
     return _metrics_from_gram(energy, proj_one, y[nsrc] if nsrc == 2 else proj_one[:, 0], compute_permutation)
 
 
-def compute_metrics_for_track(mix_path, vocal_ref_path, vocal_est_path, device="cpu"):
-    """evaluate.py:26-84: vocal SDR / SIR / SAR on (vocal, mixture - vocal) and NSDR against the mixture."""
+def _load_track(mix_path, vocal_ref_path, vocal_est_path):
     mix, sr_mix = load_mono_audio(mix_path)
     vocal_ref, sr_ref = load_mono_audio(vocal_ref_path)
     vocal_est, sr_est = load_mono_audio(vocal_est_path)
     if not (sr_mix == sr_ref == sr_est):
         raise ValueError(f"Sample rate mismatch: mix={sr_mix}, ref={sr_ref}, est={sr_est}")
     n = min(len(mix), len(vocal_ref), len(vocal_est))
-    mix, vocal_ref, vocal_est = mix[:n], vocal_ref[:n], vocal_est[:n]
+    return mix[:n], vocal_ref[:n], vocal_est[:n], sr_mix
+
+
+def compute_metrics_for_track(mix_path, vocal_ref_path, vocal_est_path, device="cpu"):
+    """evaluate.py:26-84: vocal SDR / SIR / SAR on (vocal, mixture - vocal) and NSDR against the mixture."""
+    mix, vocal_ref, vocal_est, _ = _load_track(mix_path, vocal_ref_path, vocal_est_path)
     return metrics_from_waveforms(mix, vocal_ref, vocal_est, device)
+
+
+def frame_samples(seconds, sr):
+    """--frame_window / --frame_hop seconds -> samples: int(round(seconds * sr)), at least one."""
+    s = int(round(seconds * sr))
+    if s < 1:
+        raise ValueError(f"{seconds} s at {sr} Hz is less than one sample")
+    return s
+
+
+def compute_frame_metrics_for_track(mix_path, vocal_ref_path, vocal_est_path, window_s, hop_s=None, device="cpu"):
+    """metrics_from_waveforms_framewise of one track, windows given in seconds (hop: the window by default); adds
+    "start_s", the start of each frame in seconds."""
+    mix, vocal_ref, vocal_est, sr = _load_track(mix_path, vocal_ref_path, vocal_est_path)
+    window = frame_samples(window_s, sr)
+    hop = frame_samples(window_s if hop_s is None else hop_s, sr)
+    frames = metrics_from_waveforms_framewise(mix, vocal_ref, vocal_est, window, hop, device)
+    frames["start_s"] = frames["start"] / sr
+    return frames
+
+
+def frame_summary(frames):
+    """The NaN-ignoring median of each metric over a track's frames and the number of valid frames (SDR not NaN)."""
+    out = {}
+    for k in METRICS:
+        v = np.asarray(frames[k], dtype=np.float64)
+        v = v[~np.isnan(v)]
+        out[k] = float(np.median(v)) if v.size else float("nan")
+    out["frames"] = int(np.count_nonzero(~np.isnan(frames["SDR"])))
+    return out
 
 
 def metrics_from_waveforms(mix, vocal_ref, vocal_est, device="cpu"):
@@ -297,6 +336,229 @@ def _metrics_from_waveforms_gpu(mix, vocal_ref, vocal_est):
     return {"SDR": float(sdr[j]), "SIR": float(sir[j]), "SAR": float(sar[j]), "NSDR": float(sdr[j]) - float(sdr_mix[0])}
 
 
+# ---- framewise ------------------------------------------------------------------------------
+
+def frame_count(n, window, hop):
+    """Windows of mir_eval's bss_eval_sources_framewise: floor((n - window + hop) / hop) (< 2: score the whole signal)."""
+    return (n - window + hop) // hop
+
+
+def _frame_args(window, hop):
+    for name, v in (("window", window), ("hop", hop)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    return int(window), int(hop)
+
+
+def _sources_2d(x, what):
+    x = np.asarray(x, dtype=np.float64)
+    x = x[np.newaxis, :] if x.ndim == 1 else x
+    if x.ndim != 2:
+        raise ValueError(f"{what} must be 1-D or (nsrc, nsampl), got shape {x.shape}")
+    return x
+
+
+def _any_silent(sources):
+    return bool(np.any(np.all(sources == 0, axis=1)))
+
+
+def bss_eval_sources_framewise(reference_sources, estimated_sources, window=30 * 44100, hop=15 * 44100,
+                               compute_permutation=False, flen=FILTER_LEN):
+    """(sdr, sir, sar, perm), each (nsrc, nwin): bss_eval_sources of every window [k*hop, k*hop + window) of the signals,
+    as mir_eval.separation.bss_eval_sources_framewise (mir_eval 0.8.2) returns them.  PARITY UNPINNED: mir_eval is not
+    installed here, and these rules restate its source.  nwin = frame_count(n, window, hop); when it is < 2 the result is
+    bss_eval_sources of the whole signals with a trailing axis of length 1.  A window in which a reference or an estimate is
+    all zeros is NaN in all four outputs."""
+    ref, est = _sources_2d(reference_sources, "reference"), _sources_2d(estimated_sources, "estimate")
+    if ref.shape != est.shape:
+        raise ValueError(f"reference {ref.shape} and estimate {est.shape} must have the same shape")
+    window, hop = _frame_args(window, hop)
+    nsrc, n = ref.shape
+    nwin = frame_count(n, window, hop)
+    if nwin < 2:
+        return tuple(np.expand_dims(v, -1) for v in bss_eval_sources(ref, est, compute_permutation, flen))
+    sdr, sir, sar, perm = (np.full((nsrc, nwin), np.nan) for _ in range(4))
+    for k in range(nwin):
+        r, e = ref[:, k * hop:k * hop + window], est[:, k * hop:k * hop + window]
+        if not (_any_silent(r) or _any_silent(e)):
+            sdr[:, k], sir[:, k], sar[:, k], perm[:, k] = bss_eval_sources(r, e, compute_permutation, flen)
+    return sdr, sir, sar, perm
+
+
+def _frames(sdr, sir, sar, sdr_mix, hop):
+    return {"SDR": sdr, "SIR": sir, "SAR": sar, "NSDR": sdr - sdr_mix, "start": np.arange(sdr.size) * hop}
+
+
+def metrics_from_waveforms_framewise(mix, vocal_ref, vocal_est, window, hop, device="cpu", ws_budget=WS_BUDGET):
+    """Framewise metrics_from_waveforms: {"SDR", "SIR", "SAR", "NSDR", "start"}, 1-D arrays over the windows of
+    bss_eval_sources_framewise (start: first sample of each window).  The 2-source problem (vocal, mix - vocal) against
+    (estimate, mix - estimate) is scored without a permutation, so the vocal is row 0; NSDR = SDR - SDR(mixture taken as
+    the vocal estimate), NaN where the vocal or the mixture is silent.  device="gpu": one windowed correlation pass and
+    batched factorisations; ws_budget caps the workspace of one batch (the results do not depend on it)."""
+    if device == "gpu":
+        return _metrics_framewise_gpu(mix, vocal_ref, vocal_est, window, hop, ws_budget)
+    if device != "cpu":
+        raise ValueError(f"device must be 'cpu' or 'gpu', got {device!r}")
+    mix, vocal_ref, vocal_est = (np.asarray(x, dtype=np.float64) for x in (mix, vocal_ref, vocal_est))
+    sdr, sir, sar, _ = bss_eval_sources_framewise(np.stack([vocal_ref, mix - vocal_ref]),
+                                                  np.stack([vocal_est, mix - vocal_est]), window, hop)
+    sdr_mix = bss_eval_sources_framewise(vocal_ref, mix, window, hop)[0][0]
+    return _frames(sdr[0], sir[0], sar[0], sdr_mix, _frame_args(window, hop)[1])
+
+
+def _gpu_framewise_projections(sig, window, hop, nwin, solves, energies, flen, ws_budget):
+    """_gpu_projections for every window [w*hop, w*hop + window) of the rows of sig: ONE windowed correlation pass, then
+    per solve batched factorisations over all windows, in batches whose workspace stays within ws_budget bytes (at least
+    one system).  Returns numpy (energy (nwin, len(energies)), [|P e|^2 (nwin, nrhs) per solve], [status (nwin,) per
+    solve]); a status that is not 0 marks a window whose factorisation met a pivot that was not > 0."""
+    import torch
+    from . import _lib
+    L = _lib.lib()
+    pairs, off = [], {}
+
+    def need(a, b, nl):                              # offset of pair (a, b, nl) in one window's correlations
+        if (a, b, nl) not in off:
+            off[(a, b, nl)] = sum(p[2] for p in pairs)
+            pairs.append((a, b, nl))
+        return off[(a, b, nl)]
+
+    plans = []
+    for refs, ests in solves:
+        gram = [need(i, j, flen) for i in refs for j in refs]
+        rhs = [need(e, i, flen) for e in ests for i in refs]
+        plans.append((len(refs), np.asarray(gram, dtype=np.int64), np.asarray(rhs, dtype=np.int64), len(ests)))
+    eoff = [need(e, e, 1) for e in energies]
+    stride = sum(p[2] for p in pairs)
+    flat = np.asarray([v for p in pairs for v in p], dtype=np.int32)
+    dev = sig.device
+    n = sig.shape[1]
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr()
+        ws_bytes = L.svs_bss_corr_windows_workspace_bytes(window, nwin, len(pairs), flat.ctypes.data)
+        if ws_bytes == 0:
+            raise ValueError(f"{nwin} windows of {window} samples do not fit one correlation launch")
+        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+        corr = torch.empty(nwin, stride, dtype=torch.float64, device=dev)
+        _lib.check(L.svs_bss_corr_windows(sig.data_ptr(), sig.stride(0), sig.shape[0], n, window, hop, nwin,
+                                          flat.ctypes.data, len(pairs), corr.data_ptr(), stride, ws.data_ptr(),
+                                          ws.numel(), stream), "svs_bss_corr_windows")
+        del ws
+        ys, sts = [], []
+        for k, gram, rhs, nr in plans:
+            nb = int(max(1, min(nwin, MAX_BATCH, ws_budget // L.svs_bss_solve_workspace_bytes(k, flen, nr))))
+            ws = torch.empty(int(L.svs_bss_solve_batched_workspace_bytes(nb, k, flen, nr)), dtype=torch.uint8, device=dev)
+            y = torch.empty(nwin, nr, dtype=torch.float64, device=dev)
+            status = torch.empty(nwin, dtype=torch.int32, device=dev)
+            for w0 in range(0, nwin, nb):
+                b = min(nb, nwin - w0)
+                base = np.arange(w0, w0 + b, dtype=np.int64)[:, None] * stride
+                g, r = np.ascontiguousarray(base + gram), np.ascontiguousarray(base + rhs)
+                _lib.check(L.svs_bss_solve_batched(corr.data_ptr(), b, k, flen, g.ctypes.data, r.ctypes.data, nr,
+                                                   y[w0].data_ptr(), status[w0:].data_ptr(), ws.data_ptr(), ws.numel(),
+                                                   stream), "svs_bss_solve_batched")
+            ys.append(y)
+            sts.append(status)
+            del ws
+        energy = corr[:, eoff].cpu().numpy()
+        return energy, [y.cpu().numpy() for y in ys], [s.cpu().numpy() for s in sts]
+
+
+def _warn_framewise_fallback():
+    warnings.warn("BSS-eval: a Gram matrix has a pivot that is not > 0 in the GPU Cholesky (singular or numerically "
+                  "indefinite); the windows concerned fall back to the numpy path", RuntimeWarning, stacklevel=4)
+
+
+def bss_eval_sources_framewise_gpu(reference_sources, estimated_sources, window=30 * 44100, hop=15 * 44100,
+                                   compute_permutation=False, flen=FILTER_LEN, ws_budget=WS_BUDGET):
+    """bss_eval_sources_framewise on the GPU (numpy or torch inputs, K = 1 or 2 sources, flen <= 512): the same
+    (sdr, sir, sar, perm).  Silent windows are NaN from the per-window energies; a window whose Gram matrix is singular
+    although no row is silent is scored by the numpy bss_eval_sources, with a RuntimeWarning."""
+    import torch
+    ref, est = _device_f64(reference_sources), _device_f64(estimated_sources)
+    ref, est = ref.reshape(1, -1) if ref.dim() == 1 else ref, est.reshape(1, -1) if est.dim() == 1 else est
+    if ref.dim() != 2 or ref.shape != est.shape:
+        raise ValueError(f"reference {tuple(ref.shape)} and estimate {tuple(est.shape)} must have the same 2-D shape")
+    window, hop = _frame_args(window, hop)
+    nsrc, n = ref.shape
+    if nsrc not in (1, 2):
+        raise ValueError(f"bss_eval_sources_framewise_gpu handles 1 or 2 sources, got {nsrc}")
+    if not 1 <= flen <= 512:
+        raise ValueError(f"flen = {flen}: the GPU path supports filter lengths 1 .. 512")
+    nwin = frame_count(n, window, hop)
+    if nwin < 2:
+        return tuple(np.expand_dims(v, -1) for v in bss_eval_sources_gpu(ref, est, compute_permutation, flen))
+    est = est.to(ref.device)
+    refs, ests = list(range(nsrc)), [nsrc + a for a in range(nsrc)]
+    solves = [((i,), ests) for i in refs] + ([(tuple(refs), ests)] if nsrc == 2 else [])
+    energy, y, status = _gpu_framewise_projections(torch.cat([ref, est]).contiguous(), window, hop, nwin, solves,
+                                                   refs + ests, flen, ws_budget)
+    bad = np.any(np.stack(status) != 0, axis=0)
+    out = [np.full((nsrc, nwin), np.nan) for _ in range(4)]
+    host = None
+    for w in range(nwin):
+        if (energy[w] == 0).any():                     # a silent reference or estimate
+            continue
+        if bad[w]:
+            if host is None:
+                _warn_framewise_fallback()
+                host = ref.cpu().numpy(), est.cpu().numpy()
+            sl = slice(w * hop, w * hop + window)
+            r = bss_eval_sources(host[0][:, sl], host[1][:, sl], compute_permutation, flen)
+        else:
+            proj_one = np.stack([y[i][w] for i in range(nsrc)], axis=1)
+            r = _metrics_from_gram(energy[w, nsrc:], proj_one, y[nsrc][w] if nsrc == 2 else proj_one[:, 0],
+                                   compute_permutation)
+        for o, v in zip(out, r):
+            o[:, w] = v
+    return tuple(out)
+
+
+def _metrics_framewise_gpu(mix, vocal_ref, vocal_est, window, hop, ws_budget):
+    """metrics_from_waveforms_framewise(device="gpu"): one windowed correlation pass over the rows of
+    _metrics_from_waveforms_gpu, then per window K = 1 on (vocal; est, acc_est, mix) and (acc; est, acc_est) and K = 2.
+    Fewer than two windows: the same machinery on one window, the whole track, without the silence rule."""
+    import torch
+    window, hop = _frame_args(window, hop)
+    m, v, ve = _device_f64(mix), _device_f64(vocal_ref), _device_f64(vocal_est)
+    v, ve = v.to(m.device), ve.to(m.device)
+    if m.dim() != 1 or v.shape != m.shape or ve.shape != m.shape:
+        raise ValueError(f"mix {tuple(m.shape)}, vocal {tuple(v.shape)} and estimate {tuple(ve.shape)} must be 1-D of "
+                         "one length")
+    n = m.shape[0]
+    nwin = frame_count(n, window, hop)
+    whole = nwin < 2
+    if whole:
+        window, hop, nwin = n, n, 1
+    sig = torch.stack([v, m - v, ve, m - ve, m])     # rows: vocal, accompaniment, their estimates, mixture
+    energy, (p_v, p_a, p_all), status = _gpu_framewise_projections(
+        sig, window, hop, nwin, [((0,), [2, 3, 4]), ((1,), [2, 3]), ((0, 1), [2, 3])], [0, 1, 2, 3, 4], FILTER_LEN,
+        ws_budget)
+    sdr, sir, sar, sdr_mix = (np.full(nwin, np.nan) for _ in range(4))
+    host = None
+    for w in range(nwin):
+        silent = not whole and bool((energy[w, :4] == 0).any())
+        mix_silent = not whole and (energy[w, 0] == 0 or energy[w, 4] == 0)
+        main_bad = not silent and bool(status[0][w] or status[1][w] or status[2][w])
+        mix_bad = not mix_silent and bool(status[0][w])
+        if (main_bad or mix_bad) and host is None:
+            _warn_framewise_fallback()
+            host = [t.cpu().numpy() for t in (m, v, ve)]
+        sl = slice(w * hop, w * hop + window)
+        if main_bad:
+            hm, hv, he = (x[sl] for x in host)
+            r = bss_eval_sources(np.stack([hv, hm - hv]), np.stack([he, hm - he]), compute_permutation=False)
+            sdr[w], sir[w], sar[w] = r[0][0], r[1][0], r[2][0]
+        elif not silent:
+            r = _metrics_from_gram(energy[w, 2:4], np.stack([p_v[w, :2], p_a[w]], axis=1), p_all[w],
+                                   compute_permutation=False)
+            sdr[w], sir[w], sar[w] = r[0][0], r[1][0], r[2][0]
+        if mix_bad:
+            sdr_mix[w] = bss_eval_sources(host[1][None, sl], host[0][None, sl], compute_permutation=False)[0][0]
+        elif not mix_silent:
+            sdr_mix[w] = _metrics_from_gram(energy[w, 4:5], p_v[w, 2:3, None], p_v[w, 2:3], compute_permutation=False)[0][0]
+    return _frames(sdr, sir, sar, sdr_mix, hop)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Evaluate SVS results with SDR / SIR / SAR / NSDR (vocal only).")
     parser.add_argument("--est", type=str, required=True, help="folder of predicted vocal wav files")
@@ -306,7 +568,21 @@ def main(argv=None):
     parser.add_argument("--out_csv", type=str, default=None)
     parser.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
                         help="gpu: BSS-eval with the fp64 gfx950 kernels (same metrics and CSV)")
+    parser.add_argument("--frame_window", type=float, default=None, metavar="SECONDS",
+                        help="framewise BSS-eval over windows of this length: each track reports the median over its "
+                             "valid frames and their number")
+    parser.add_argument("--frame_hop", type=float, default=None, metavar="SECONDS",
+                        help="hop between frames (default: the window)")
+    parser.add_argument("--frames_csv", type=str, default=None, metavar="PATH",
+                        help="write every frame: track, frame, start_s, SDR, SIR, SAR, NSDR")
     args = parser.parse_args(argv)
+    framewise = args.frame_window is not None
+    if framewise and not args.frame_window > 0:
+        parser.error("--frame_window must be > 0")
+    if args.frame_hop is not None and not (framewise and args.frame_hop > 0):
+        parser.error("--frame_hop must be > 0 and needs --frame_window")
+    if args.frames_csv is not None and not framewise:
+        parser.error("--frames_csv needs --frame_window")
     if args.device == "gpu":
         import torch
         if not torch.cuda.is_available():
@@ -318,7 +594,7 @@ def main(argv=None):
         return
     print("=== Start Evaluation ===")
     print(f"#tracks = {len(pred_files)}\n")
-    results = []
+    results, frame_rows = [], []
     for pred_path in pred_files:
         base = os.path.basename(pred_path)
         mix_path, ref_path = os.path.join(args.mix, base), os.path.join(args.ref, base)
@@ -329,25 +605,45 @@ def main(argv=None):
             print(f"[Warning] Vocal ref file not found, skip: {ref_path}")
             continue
         try:
-            m = compute_metrics_for_track(mix_path, ref_path, pred_path, args.device)
+            if framewise:
+                frames = compute_frame_metrics_for_track(mix_path, ref_path, pred_path, args.frame_window, args.frame_hop,
+                                                         args.device)
+                m = frame_summary(frames)
+            else:
+                m = compute_metrics_for_track(mix_path, ref_path, pred_path, args.device)
         except Exception as e:                          # evaluate.py:127-131
             print(f"[Error] Failed on {base}: {e}")
             continue
         name = os.path.splitext(base)[0]
-        print(f"{name[:20]}:\tSDR={m['SDR']:.3f} dB,\tSIR={m['SIR']:.3f} dB,\tSAR={m['SAR']:.3f} dB,\tNSDR={m['NSDR']:.3f} dB")
+        line = f"{name[:20]}:\tSDR={m['SDR']:.3f} dB,\tSIR={m['SIR']:.3f} dB,\tSAR={m['SAR']:.3f} dB,\tNSDR={m['NSDR']:.3f} dB"
+        if framewise:
+            if m["frames"] == 0:
+                print(f"[Error] No valid frame in {base} ({frames['SDR'].size} frames, all silent)")
+                continue
+            line += f",\tframes={m['frames']}/{frames['SDR'].size}"
+            frame_rows += [{"track": name, "frame": i, "start_s": float(frames["start_s"][i]),
+                            **{k: float(frames[k][i]) for k in METRICS}} for i in range(frames["SDR"].size)]
+        print(line)
         results.append({"track": name, **m})
     if not results:
         print("\n[Error] No valid tracks evaluated.")
         return
-    print("\n=== Overall Mean Metrics (vocal) ===")
+    print("\n=== Overall Mean Metrics (vocal) ===" if not framewise else
+          "\n=== Overall Mean Metrics (vocal, per-track medians over frames) ===")
     for k in ("SDR", "SIR", "SAR", "NSDR"):
         print(f"Mean {k:4s}: {float(np.mean([r[k] for r in results])):.3f} dB")
     if args.out_csv is not None:
         with open(args.out_csv, "w", newline="", encoding="utf-8") as f:
-            w = csv.DictWriter(f, fieldnames=["track", "SDR", "SIR", "SAR", "NSDR"])
+            w = csv.DictWriter(f, fieldnames=["track", "SDR", "SIR", "SAR", "NSDR"] + (["frames"] if framewise else []))
             w.writeheader()
             w.writerows(results)
         print(f"\n[Info] Results saved to {args.out_csv}")
+    if args.frames_csv is not None:
+        with open(args.frames_csv, "w", newline="", encoding="utf-8") as f:
+            w = csv.DictWriter(f, fieldnames=["track", "frame", "start_s", *METRICS])
+            w.writeheader()
+            w.writerows(frame_rows)
+        print(f"[Info] Frame results saved to {args.frames_csv}")
     return results
 
 

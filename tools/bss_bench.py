@@ -5,6 +5,7 @@ and the numpy path, on a seeded synthetic 240 s track at 8192 Hz and at 44,100 H
     python tools/bss_bench.py [--rates 8192 44100] [--seconds 240] [--reps 5] [--no-numpy]
     rocprofv3 --kernel-trace --stats -d DIR -o bss --output-format csv -- python tools/bss_bench.py --rates 8192 --no-numpy
     python tools/bss_bench.py --kernel-stats DIR --rates 8192 --seconds 240
+    python tools/bss_bench.py --frame_window 1 [--frame_hop 1] [--ws-budget BYTES]   # framewise metrics instead
 
 Timing: host clock around metrics_from_waveforms(device="gpu") followed by a device synchronise (the call ends with a
 copy back to the host anyway), after one warm-up call; median and minimum of --reps calls.  The numpy path is timed once.
@@ -54,6 +55,39 @@ def time_gpu(mix, vocal, est, reps):
     return ts, m
 
 
+def time_gpu_frames(mix, vocal, est, window, hop, reps, ws_budget):
+    import torch
+    ev.metrics_from_waveforms_framewise(mix, vocal, est, window, hop, device="gpu", ws_budget=ws_budget)
+    torch.cuda.synchronize()
+    ts, fr = [], None
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fr = ev.metrics_from_waveforms_framewise(mix, vocal, est, window, hop, device="gpu", ws_budget=ws_budget)
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return ts, fr
+
+
+def frames_record(args, rate, mix, vocal, est):
+    """--frame_window: GPU and numpy metrics_from_waveforms_framewise on the same track; max |delta| over the frames both
+    score, and whether their NaN frames agree."""
+    window = ev.frame_samples(args.frame_window, rate)
+    hop = ev.frame_samples(args.frame_window if args.frame_hop is None else args.frame_hop, rate)
+    ts, g = time_gpu_frames(mix, vocal, est, window, hop, args.reps, args.ws_budget)
+    rec = {"rate": rate, "seconds": args.seconds, "n": mix.size, "window": window, "hop": hop, "frames": int(g["SDR"].size),
+           "gpu_ms_median": 1e3 * statistics.median(ts), "gpu_ms_min": 1e3 * min(ts), "reps": args.reps,
+           "ws_budget": args.ws_budget, "gpu_median_sdr": ev.frame_summary(g)["SDR"]}
+    if not args.no_numpy:
+        t0 = time.perf_counter()
+        c = ev.metrics_from_waveforms_framewise(mix, vocal, est, window, hop)
+        rec["numpy_s"] = time.perf_counter() - t0
+        rec["nan_frames_equal"] = all(np.array_equal(np.isnan(g[k]), np.isnan(c[k])) for k in ev.METRICS)
+        ok = {k: ~np.isnan(c[k]) for k in ev.METRICS}
+        rec["max_abs_diff_db"] = max(float(np.max(np.abs(g[k][ok[k]] - c[k][ok[k]]), initial=0.0)) for k in ev.METRICS)
+        rec["speedup"] = rec["numpy_s"] / (rec["gpu_ms_median"] / 1e3)
+    return rec
+
+
 def kernel_stats(path, n):
     files = glob.glob(os.path.join(path, "**", "*kernel_stats.csv"), recursive=True) if os.path.isdir(path) else [path]
     if not files:
@@ -82,6 +116,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-numpy", action="store_true", help="GPU path only (profiling runs)")
     ap.add_argument("--kernel-stats", default=None, help="rocprofv3 --stats CSV (or its directory) of a run at one rate")
+    ap.add_argument("--frame_window", type=float, default=None, help="seconds: time the framewise metrics instead")
+    ap.add_argument("--frame_hop", type=float, default=None, help="seconds (default: the window)")
+    ap.add_argument("--ws-budget", type=int, default=ev.WS_BUDGET, help="workspace bytes of one batch of factorisations")
     args = ap.parse_args()
     if args.kernel_stats:
         n = args.seconds * args.rates[0]
@@ -92,6 +129,9 @@ def main():
         raise SystemExit("bss_bench.py needs a ROCm device")
     for rate in args.rates:
         mix, vocal, est = track(args.seconds, rate)
+        if args.frame_window is not None:
+            print(json.dumps(frames_record(args, rate, mix, vocal, est)), flush=True)
+            continue
         ts, m_gpu = time_gpu(mix, vocal, est, args.reps)
         rec = {"rate": rate, "seconds": args.seconds, "n": mix.size, "gpu_ms_median": 1e3 * statistics.median(ts),
                "gpu_ms_min": 1e3 * min(ts), "reps": args.reps, "corr_gflop": LAG_PRODUCTS * mix.size * 2 / 1e9,
