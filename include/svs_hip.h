@@ -374,6 +374,38 @@ int svs_bss_solve_batched(const double* corr, int64_t nbatch, int K, int flen, c
                           const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, void* ws, size_t ws_bytes,
                           hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Resampling to the network rate (csrc/resample.hip): the arithmetic half of librosa.load(path, sr=8192, mono=True),
+ * data.py:78,94 -- downmix and polyphase FIR resampling; decoding the file stays host code.  The filter is the caller's
+ * (svs_unet_pytorch_amd/resample.py designs scipy.signal.resample_poly's Kaiser low-pass, the project's host path; the
+ * reference's librosa resamples with soxr, whose filter this does not reproduce).  With half = (ntaps - 1) / 2:
+ *   y[i] = sum_j x[j] * taps[i*down - j*up + half],   0 <= j < n_in,   0 <= i < svs_resample_out_len = ceil(n_in*up/down).
+ * ntaps is odd; 1 <= up, down <= 2^24 (pass them divided by their gcd: the table has `up` rows).  fp32 taps and fp32
+ * accumulation; each output is summed in one fixed order that depends only on i % up (no atomics), so results are bitwise
+ * reproducible and do not depend on the batch, on n_in or on where a sample lies in the signal.  Indices are 64-bit.
+ * svs_resample_out_len is host arithmetic (-1 for invalid arguments). */
+#define SVS_PCM_F32 0 /* float32 samples as they are */
+#define SVS_PCM_I16 1 /* int16 / 32768 */
+#define SVS_PCM_I32 2 /* int32 / 2^31 (24-bit files arrive left-justified in int32) */
+int64_t svs_resample_out_len(int64_t n_in, int up, int down);
+/* Packed tap table for svs_resample_poly: ceil(ntaps / up) x up floats, [k][q] = taps[(q*down + half) % up + k*up] (0 past
+ * ntaps) -- row q serves every output i with i % up == q, and consecutive outputs read consecutive floats.  `taps` is a
+ * device array of ntaps floats.  The query is 0 for invalid arguments. */
+size_t svs_resample_table_bytes(int up, int down, int ntaps);
+int svs_resample_pack_taps(const float* taps, int ntaps, int up, int down, void* table, hipStream_t stream);
+/* x: `batch` signals of n_in sample frames, signal b at element b*ld_in, frame j of it at j*channels (interleaved as a wav
+ * file stores them; channels = 1: planar), elements of format fmt (SVS_PCM_*).  downmix != 0: every frame becomes one fp32
+ * sample as data.py's load_wav_mono forms it (each channel converted to fp32, added in channel order in fp32, divided
+ * by `channels`) and y has `batch` rows; downmix == 0: channel c of signal b is resampled on its own into row
+ * b*channels + c.  y row r at y + r*ld_out, n_out floats each.  Needs no workspace.  channels <= 64, at most 65535 rows;
+ * filters too long for the LDS (down / up above about 90) are refused. */
+int svs_resample_poly(const void* x, int fmt, int channels, int downmix, int64_t n_in, int64_t ld_in, int batch,
+                      const void* table, int ntaps, int up, int down, float* y, int64_t ld_out, hipStream_t stream);
+/* The launch svs_resample_poly makes for `rows` output rows (host arithmetic, for benchmarks and DESIGN.md section 10):
+ * plan[0..8) = outputs per segment W, segments per step S, blocks along i % up, blocks along the signal, steps per block,
+ * input samples staged per segment, LDS bytes per block, tap bytes all blocks together read from the packed table. */
+int svs_resample_plan(int64_t n_in, int up, int down, int ntaps, int rows, int64_t* plan);
+
 #ifdef __cplusplus
 }
 #endif

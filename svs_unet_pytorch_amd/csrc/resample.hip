@@ -1,0 +1,239 @@
+// Polyphase FIR resampler with the PCM front end fused into its load (include/svs_hip.h: svs_resample_*).
+//
+// Replaces the resampling half of librosa.load(path, sr=8192, mono=True) (reference data.py:78,94) with the arithmetic of
+// scipy.signal.resample_poly (the project's host path, svs_unet_pytorch_amd/data.py: load_wav_mono):
+//
+//   y[i] = sum_j x[j] * h[i*down - j*up + half],   half = (ntaps - 1) / 2,   0 <= j < n_in,   n_out = ceil(n_in*up/down).
+//
+// With pos = i*down + half, n0 = pos / up and p = pos % up this is the T = ceil(ntaps / up) term dot product
+//   y[i] = sum_{k=0}^{T-1} x[n0 - k] * h[p + k*up]           (x = 0 outside [0, n_in), h = 0 past ntaps),
+// summed for k = 0, 1, ... T-1 with one fmaf per term: the order depends on nothing but the output, so results are
+// bitwise reproducible and independent of the batch, the grid and the signal length.
+//
+// Layout.  p depends on i % up only, so the packed table has one row per q = i % up, stored
+// [k][q]: consecutive outputs read consecutive floats.  A block keeps the rows of W consecutive q in LDS ([k][W]) and walks
+// over many periods i = q + m*up with them, S = 256 / W periods at a time; per period segment it stages the
+// (W-1)*down/up + T + 1 input samples its outputs read -- converted to fp32 and downmixed once -- in LDS.  When up <= 256
+// the whole table is the block's and a segment is 256 / up whole periods of consecutive outputs.  Index arithmetic is
+// 64-bit: one division per thread at the start, then (quotient, remainder) increments per step.
+#include "common.h"
+
+namespace {
+
+enum { RS_F32 = 0, RS_I16 = 1, RS_I32 = 2 };
+constexpr int RS_THREADS = 256;
+constexpr size_t RS_LDS_FOUR_BLOCKS = 40 * 1024;     // four blocks (16 waves) per CU: measured 1.4x faster than two blocks of twice the rows
+constexpr size_t RS_LDS_MAX = 160 * 1024;
+
+struct RsPlan {
+  int W;            // outputs per segment (= tap rows a block owns when up > 256)
+  int Wt;           // tap rows in LDS
+  int S;            // segments per step
+  int nqb;          // blocks along q
+  int span;         // input samples staged per segment
+  int64_t stride;   // distance in outputs between the starts of consecutive segments
+  int64_t nsteps;   // steps that cover n_out
+  int ipc;          // steps per block
+  int chunks;       // blocks along the steps
+  int64_t dq, dr;   // (S * stride * down) / up and % up: what one step adds to (n0, pos % up)
+  size_t lds;
+};
+
+struct RsArgs {
+  const void* x; int fmt, channels, downmix, rps; int64_t n_in, ld_in;
+  const float* table; int T, up, down; int64_t half;
+  float* y; int64_t ld_out, n_out;
+  RsPlan p;
+};
+
+static inline int rs_taps_per_phase(int ntaps, int up) { return (ntaps + up - 1) / up; }
+
+static size_t rs_lds_bytes(int Wt, int W, int S, int T, int up, int down, int* span) {
+  *span = (int)(((int64_t)(W - 1) * down) / up) + T + 2;
+  return ((size_t)Wt * T + (size_t)S * *span) * sizeof(float);
+}
+
+// false: no block shape fits the LDS (the filter is too long for this kernel: about down / up > 90)
+static bool rs_plan(int64_t n_out, int T, int up, int down, int rows, RsPlan* p) {
+  bool ok = false;
+  if (up <= RS_THREADS) {
+    p->W = RS_THREADS / up * up; p->Wt = up; p->S = 1; p->nqb = 1; p->stride = p->W;
+    // a long filter over few phases: shorter segments (still whole periods) leave room for the taps
+    for (; p->W >= up; p->W = (p->W / up / 2) * up) {
+      p->stride = p->W;
+      p->lds = rs_lds_bytes(p->Wt, p->W, 1, T, up, down, &p->span);
+      if (p->lds <= RS_LDS_MAX) { ok = true; break; }
+      if (p->W == up) break;
+    }
+  } else {
+    for (int pass = 0; pass < 2 && !ok; ++pass)
+      for (int W = RS_THREADS; W >= 16 && !ok; W >>= 1) {
+        p->W = p->Wt = W; p->S = RS_THREADS / W;
+        p->lds = rs_lds_bytes(W, W, p->S, T, up, down, &p->span);
+        ok = p->lds <= (pass ? RS_LDS_MAX : RS_LDS_FOUR_BLOCKS);
+      }
+    p->nqb = (up + p->W - 1) / p->W; p->stride = up;
+  }
+  if (!ok) return false;
+  const int64_t per_step = p->S * p->stride;                         // outputs (of all q) one step advances
+  p->nsteps = (n_out + per_step - 1) / per_step;
+  int64_t chunks = 1024 / ((int64_t)p->nqb * rows);                  // about four blocks per CU in all
+  if (chunks < 1) chunks = 1;
+  if (chunks > p->nsteps) chunks = p->nsteps;
+  p->ipc = (int)((p->nsteps + chunks - 1) / chunks);
+  p->chunks = (int)((p->nsteps + p->ipc - 1) / p->ipc);
+  const int64_t dpos = per_step * down;
+  p->dq = dpos / up; p->dr = dpos % up;
+  return true;
+}
+
+// sample j of output row `row`: format conversion and downmix as load_wav_mono does them (each channel to fp32, the
+// channels added in channel order in fp32, divided by their count)
+__device__ __forceinline__ float rs_cvt(const void* x, int fmt, int64_t e) {
+  if (fmt == RS_I16) return (float)((const int16_t*)x)[e] * (1.0f / 32768.0f);
+  if (fmt == RS_I32) return (float)((const int32_t*)x)[e] * (1.0f / 2147483648.0f);
+  return ((const float*)x)[e];
+}
+__device__ __forceinline__ float rs_load(const RsArgs& a, int64_t sig_base, int chan, int64_t j) {
+  if (j < 0 || j >= a.n_in) return 0.0f;
+  const int64_t e = sig_base + j * a.channels;
+  if (!a.downmix) return rs_cvt(a.x, a.fmt, e + chan);
+  float s = rs_cvt(a.x, a.fmt, e);
+  for (int c = 1; c < a.channels; ++c) s += rs_cvt(a.x, a.fmt, e + c);
+  return s / (float)a.channels;
+}
+
+__global__ void __launch_bounds__(RS_THREADS) resample_poly_kernel(const RsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float rs_smem[];
+  const RsPlan& p = a.p;
+  float* taps = rs_smem;                                   // [T][Wt]
+  float* xs = rs_smem + (size_t)p.Wt * a.T;                // [S][span]
+  const int t = threadIdx.x;
+  const int64_t q0 = (int64_t)blockIdx.x * (p.nqb > 1 ? p.W : 0);
+  const int lseg = p.nqb > 1 ? (int)min((int64_t)p.W, a.up - q0) : p.W;
+  const int seg = t / p.W, r = t % p.W;
+  const bool active = seg < p.S && r < lseg;
+  const int row = blockIdx.z;
+  const int64_t sig_base = (int64_t)(row / a.rps) * a.ld_in;
+  const int chan = row % a.rps;
+
+  for (int e = t; e < p.Wt * a.T; e += RS_THREADS) {       // this block's tap rows
+    const int k = e / p.Wt, c = e % p.Wt;
+    taps[e] = q0 + c < a.up ? a.table[(int64_t)k * a.up + q0 + c] : 0.0f;
+  }
+
+  const int64_t it0 = (int64_t)blockIdx.y * p.ipc;
+  const int64_t it1 = min(it0 + p.ipc, p.nsteps);
+  // first output of this thread's segment and the thread's own output, as (n0, pos % up)
+  int64_t i_f = ((it0 * p.S + seg) * p.stride) + q0;
+  int64_t n0f, remf, n0, rem;
+  {
+    const int64_t posf = i_f * a.down + a.half;
+    n0f = posf / a.up; remf = posf % a.up;
+    const int64_t pos = posf + (int64_t)r * a.down;
+    n0 = pos / a.up; rem = pos % a.up;
+  }
+  const float* tp = taps + r % p.Wt;
+  float* xseg = xs + (size_t)seg * p.span;
+  const int64_t di = (int64_t)p.S * p.stride;
+
+  for (int64_t it = it0; it < it1; ++it) {
+    const bool live = active && i_f < a.n_out;
+    __syncthreads();                                       // taps complete (first step); xs free again (later steps)
+    if (live) {
+      const int64_t lo = n0f - (a.T - 1);
+      for (int e = r; e < p.span; e += lseg) xseg[e] = rs_load(a, sig_base, chan, lo + e);
+    }
+    __syncthreads();
+    if (live && i_f + r < a.n_out) {
+      const float* xp = xseg + (int)(n0 - n0f) + a.T - 1;
+      float acc = 0.0f;
+#pragma unroll 4
+      for (int k = 0; k < a.T; ++k) acc = fmaf(xp[-k], tp[(size_t)k * p.Wt], acc);
+      a.y[(int64_t)row * a.ld_out + i_f + r] = acc;
+    }
+    i_f += di;
+    n0f += p.dq; remf += p.dr; if (remf >= a.up) { remf -= a.up; ++n0f; }
+    n0 += p.dq; rem += p.dr; if (rem >= a.up) { rem -= a.up; ++n0; }
+  }
+}
+
+// table[k][q] = h[(q*down + half) % up + k*up]   (0 past ntaps)
+__global__ void __launch_bounds__(256) resample_pack_kernel(const float* __restrict__ taps, int ntaps, int up, int down, int T,
+                                                            float* __restrict__ table) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)T * up) return;
+  const int64_t k = e / up, q = e % up;
+  const int64_t idx = (q * down + (ntaps - 1) / 2) % up + k * up;
+  table[e] = idx < ntaps ? taps[idx] : 0.0f;
+}
+
+bool rs_filter_ok(int ntaps, int up, int down) {
+  return up >= 1 && down >= 1 && ntaps >= 1 && (ntaps & 1) && up <= (1 << 24) && down <= (1 << 24);
+}
+
+}  // namespace
+
+extern "C" int64_t svs_resample_out_len(int64_t n_in, int up, int down) {
+  if (n_in < 0 || up < 1 || down < 1 || n_in > (INT64_MAX >> 26)) return -1;
+  return (n_in * up + down - 1) / down;
+}
+
+extern "C" size_t svs_resample_table_bytes(int up, int down, int ntaps) {
+  if (!rs_filter_ok(ntaps, up, down)) return 0;
+  return (size_t)rs_taps_per_phase(ntaps, up) * up * sizeof(float);
+}
+
+extern "C" int svs_resample_pack_taps(const float* taps, int ntaps, int up, int down, void* table, hipStream_t stream) {
+  SVS_REQUIRE(taps && table && rs_filter_ok(ntaps, up, down),
+              "svs_resample_pack_taps: bad arguments (need an odd number of taps, 1 <= up, down <= 2^24)");
+  const int T = rs_taps_per_phase(ntaps, up);
+  const int64_t n = (int64_t)T * up;
+  SVS_REQUIRE(n <= ((int64_t)1 << 31), "svs_resample_pack_taps: table of %lld floats is too large", (long long)n);
+  hipLaunchKernelGGL(resample_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, taps, ntaps, up, down, T,
+                     (float*)table);
+  SVS_CHECK_LAUNCH("resample_pack");
+  return SVS_OK;
+}
+
+extern "C" int svs_resample_plan(int64_t n_in, int up, int down, int ntaps, int rows, int64_t* plan) {
+  SVS_REQUIRE(plan && rs_filter_ok(ntaps, up, down) && rows >= 1 && rows <= 65535, "svs_resample_plan: bad arguments");
+  const int64_t n_out = svs_resample_out_len(n_in, up, down);
+  SVS_REQUIRE(n_in >= 1 && n_out >= 1, "svs_resample_plan: n_in %lld out of range", (long long)n_in);
+  const int T = rs_taps_per_phase(ntaps, up);
+  RsPlan p{};
+  SVS_REQUIRE(rs_plan(n_out, T, up, down, rows, &p), "svs_resample_plan: %d taps per output at %d/%d do not fit the LDS", T, up, down);
+  const int64_t blocks = (int64_t)p.nqb * p.chunks * rows;
+  plan[0] = p.W; plan[1] = p.S; plan[2] = p.nqb; plan[3] = p.chunks; plan[4] = p.ipc; plan[5] = p.span; plan[6] = (int64_t)p.lds;
+  plan[7] = blocks * p.Wt * T * (int64_t)sizeof(float);
+  return SVS_OK;
+}
+
+extern "C" int svs_resample_poly(const void* x, int fmt, int channels, int downmix, int64_t n_in, int64_t ld_in, int batch,
+                                 const void* table, int ntaps, int up, int down, float* y, int64_t ld_out, hipStream_t stream) {
+  SVS_REQUIRE(x && table && y, "svs_resample_poly: null pointer");
+  SVS_REQUIRE(fmt == RS_F32 || fmt == RS_I16 || fmt == RS_I32, "svs_resample_poly: fmt %d (0 float32, 1 int16, 2 int32)", fmt);
+  SVS_REQUIRE(rs_filter_ok(ntaps, up, down), "svs_resample_poly: bad filter (need an odd number of taps, 1 <= up, down <= 2^24)");
+  SVS_REQUIRE(channels >= 1 && channels <= 64 && batch >= 1, "svs_resample_poly: channels %d (1..64), batch %d", channels, batch);
+  const int64_t n_out = svs_resample_out_len(n_in, up, down);
+  SVS_REQUIRE(n_in >= 1 && n_out >= 1, "svs_resample_poly: n_in %lld out of range", (long long)n_in);
+  SVS_REQUIRE(n_in <= INT64_MAX / channels && (batch == 1 || ld_in >= n_in * channels),
+              "svs_resample_poly: ld_in %lld is shorter than a signal (%lld x %d)", (long long)ld_in, (long long)n_in, channels);
+  const int rps = downmix ? 1 : channels;
+  const int64_t rows = (int64_t)batch * rps;
+  SVS_REQUIRE(rows <= 65535, "svs_resample_poly: %lld output rows (at most 65535 per call)", (long long)rows);
+  SVS_REQUIRE(rows == 1 || ld_out >= n_out, "svs_resample_poly: ld_out %lld < n_out %lld", (long long)ld_out, (long long)n_out);
+  RsArgs a{};
+  a.x = x; a.fmt = fmt; a.channels = channels; a.downmix = downmix ? 1 : 0; a.rps = rps; a.n_in = n_in; a.ld_in = ld_in;
+  a.table = (const float*)table; a.T = rs_taps_per_phase(ntaps, up); a.up = up; a.down = down; a.half = (ntaps - 1) / 2;
+  a.y = y; a.ld_out = ld_out; a.n_out = n_out;
+  SVS_REQUIRE(rs_plan(n_out, a.T, up, down, (int)rows, &a.p),
+              "svs_resample_poly: %d taps per output at %d/%d do not fit the LDS (down / up above about 90 is not built)",
+              a.T, up, down);
+  SVS_REQUIRE(a.p.chunks <= 65535, "svs_resample_poly: grid too large");
+  SVS_HIP(hipFuncSetAttribute((const void*)resample_poly_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.p.lds));
+  hipLaunchKernelGGL(resample_poly_kernel, dim3((unsigned)a.p.nqb, (unsigned)a.p.chunks, (unsigned)rows), dim3(RS_THREADS), a.p.lds,
+                     stream, a);
+  SVS_CHECK_LAUNCH("resample_poly");
+  return SVS_OK;
+}

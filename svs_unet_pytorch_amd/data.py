@@ -12,10 +12,14 @@ NNNN_<song>_phase.npy (complex64 unit phasors) under <tar>/mixture and <tar>/voc
 to_wave (data.py:117-169): <name>_spec.npy times its phase -> inverse STFT -> peak-normalise to 0.9 ->
 <name>.wav at --sr.
 
-Out of the accelerated path: wav decoding + resampling to --sr (the
-reference uses librosa.load / soxr; here scipy.io.wavfile + scipy.signal.resample_poly on the CPU) and
-wav encoding (soundfile there, scipy.io.wavfile here).  Resampled audio therefore matches the reference
-only up to the resampler's filter; everything after the resampler follows the reference's arithmetic.
+Out of the accelerated path: wav decoding (scipy.io.wavfile) and wav
+encoding (soundfile there, scipy.io.wavfile here).  Downmix + resampling to --sr (the reference uses
+librosa.load / soxr) is scipy.signal.resample_poly on the CPU by default; with --resample gpu (or
+load_wav_mono(..., device=...)) the file's PCM is copied to the device as it is stored and one gfx950
+kernel (csrc/resample.hip, svs_unet_pytorch_amd/resample.py) converts, downmixes and resamples it with
+resample_poly's own filter, so the signal never visits the host between the file and the spectrogram.
+Either way resampled audio matches the reference only up to the resampler's filter (soxr is not
+reproduced); everything after the resampler follows the reference's arithmetic.
 """
 from __future__ import annotations
 
@@ -124,8 +128,13 @@ def istft_from_tiles(tiles: torch.Tensor, mask, phase_fm: torch.Tensor, frames: 
 # ------------------------------------------------------------------------------------------------
 # host-side file glue (not on the accelerated path)
 # ------------------------------------------------------------------------------------------------
-def load_wav_mono(path: str, sr: int) -> np.ndarray:
+def load_wav_mono(path: str, sr: int, device=None):
+    """Mono float32 samples of a wav file at rate `sr`.  device=None: numpy array, decoded, downmixed and resampled on the
+    host.  With a device: the PCM goes to the device as the file stores it (one copy) and svs_resample_poly converts,
+    downmixes and resamples it there; returns a device tensor."""
     from scipy.io import wavfile
+    if device is not None:
+        return _load_wav_mono_device(path, sr, device)
     from scipy.signal import resample_poly
     rate, data = wavfile.read(path)
     if data.dtype.kind == "i":
@@ -140,6 +149,20 @@ def load_wav_mono(path: str, sr: int) -> np.ndarray:
         fr = Fraction(sr, rate)
         data = resample_poly(data, fr.numerator, fr.denominator).astype(np.float32)
     return np.ascontiguousarray(data, dtype=np.float32)
+
+
+def _load_wav_mono_device(path: str, sr: int, device) -> torch.Tensor:
+    from scipy.io import wavfile
+    from .resample import resample_poly_gpu
+    rate, data = wavfile.read(path)
+    if data.dtype.kind == "u":                                 # 8-bit files: offset binary, converted on the host
+        data = (data.astype(np.float32) - 128.0) / 128.0
+    elif data.dtype not in (np.int16, np.int32):               # float files (and int64, which wavfile never returns)
+        data = data.astype(np.float32)
+    channels = data.shape[1] if data.ndim == 2 else 1
+    pcm = torch.from_numpy(np.ascontiguousarray(data)).to(device)
+    fr = Fraction(sr, rate)                                    # 1/1 (rate == sr): the call only converts and downmixes
+    return resample_poly_gpu(pcm, fr.numerator, fr.denominator, channels=channels, downmix=True)
 
 
 def write_wav(path: str, y: np.ndarray, sr: int):
@@ -164,8 +187,9 @@ def to_spec(args, device):
         if not os.path.exists(mix_path):
             continue
         try:
-            y_mix = load_wav_mono(mix_path, args.sr)
-            spec_mix, _ = stft_magphase(torch.from_numpy(y_mix).to(device), args.win_size, args.hop_size)
+            on_gpu = getattr(args, "resample", "cpu") == "gpu"
+            y_mix = load_wav_mono(mix_path, args.sr, device if on_gpu else None)
+            spec_mix, _ = stft_magphase(y_mix if on_gpu else torch.from_numpy(y_mix).to(device), args.win_size, args.hop_size)
             norm = torch.empty(1, dtype=torch.float32, device=device)     # max magnitude, 0 -> 1 (data.py:84-85)
             _lib.check(_lib.lib().svs_absmax(spec_mix.data_ptr(), spec_mix.numel(), norm.data_ptr(), ws.data_ptr(), ws.numel(),
                                              _lib.stream_ptr()), "svs_absmax")
@@ -173,9 +197,14 @@ def to_spec(args, device):
                 track = os.path.join(song_path, wav_file)
                 if not os.path.exists(track):
                     continue
-                y = load_wav_mono(track, args.sr)
-                y = y[: len(y_mix)] if len(y) > len(y_mix) else np.pad(y, (0, len(y_mix) - len(y)))   # data.py:97-98
-                spec, phase = stft_magphase(torch.from_numpy(y).to(device), args.win_size, args.hop_size)
+                if on_gpu:
+                    y = load_wav_mono(track, args.sr, device)
+                    y = y[: len(y_mix)] if len(y) > len(y_mix) else torch.nn.functional.pad(y, (0, len(y_mix) - len(y)))
+                else:
+                    y = load_wav_mono(track, args.sr)
+                    y = y[: len(y_mix)] if len(y) > len(y_mix) else np.pad(y, (0, len(y_mix) - len(y)))   # data.py:97-98
+                    y = torch.from_numpy(y).to(device)
+                spec, phase = stft_magphase(y, args.win_size, args.hop_size)
                 _lib.check(_lib.lib().svs_scale_by_inv(spec.data_ptr(), spec.numel(), norm.data_ptr(), 1.0, _lib.stream_ptr()),
                            "svs_scale_by_inv")
                 base = f"{num2str(audio_idx)}_{song}"
@@ -220,6 +249,8 @@ def main(argv=None):
     parser.add_argument("--hop_size", type=int, default=HOP_SIZE)
     parser.add_argument("--sr", type=int, default=SAMPLE_RATE)
     parser.add_argument("--direction", default="to_spec", choices=["to_spec", "to_wave"])
+    parser.add_argument("--resample", default="cpu", choices=["cpu", "gpu"],
+                        help="to_spec: downmix + resample on the host (scipy, default) or on the device from the file's PCM")
     args = parser.parse_args(argv)
     if args.win_size != WINDOW_SIZE:             # data.py:24 lets it vary; the gfx950 transforms are built for the config's 1024 only
         parser.error(f"--win_size {args.win_size}: the STFT / iSTFT kernels are built for n_fft = {WINDOW_SIZE} (config.WINDOW_SIZE) only; "

@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .config import HOP_SIZE, INPUT_LEN, WINDOW_SIZE
+from .config import HOP_SIZE, INPUT_LEN, SAMPLE_RATE, WINDOW_SIZE
 from .data import istft_from_tiles, stft_to_tiles
 
 
@@ -46,14 +46,19 @@ def separate_spectrogram_device(model, mag: torch.Tensor, seg_len: int = INPUT_L
 
 @torch.no_grad()
 def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
-                      peak: float | None = 0.9, max_batch: int = 256, precision: str | None = None):
+                      peak: float | None = 0.9, max_batch: int = 256, precision: str | None = None, sr_in: int | None = None):
     """float32 samples (n,) or (channels, n) on the GPU -> separated samples (hop*(T-1),) or (channels, hop*(T-1)).
+    sr_in: the rate of y if it is not config.SAMPLE_RATE yet (a file's 44,100 Hz): every channel is first resampled to
+    SAMPLE_RATE on the device (resample.resample_poly_gpu, no downmix); None: y is at the network rate already.
     All channels go through ONE forward transform (which writes network tiles and frame-major phasors directly), one
     batched network forward per `max_batch` tiles and ONE inverse transform (which applies the mask on load and
     overlap-adds in LDS); the only other passes are the two per-channel normalisations."""
     squeeze = y.dim() == 1
     if squeeze:
         y = y[None]
+    if sr_in is not None and sr_in != SAMPLE_RATE:
+        from .resample import resample_poly_gpu
+        y = resample_poly_gpu(y.contiguous().float(), SAMPLE_RATE, sr_in)
     tiles, phase, norm, T = stft_to_tiles(y, n_fft, hop, INPUT_LEN)
     L = _lib.lib()
     C, n_tiles = tiles.shape[:2]
