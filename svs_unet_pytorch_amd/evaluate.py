@@ -15,11 +15,13 @@ is the one with the best mean SIR.  tests/test_host.py checks the defining prope
 reference scores > 100 dB, a known interference mix scores its mixing ratio, additive noise scores its SNR).
 wav files are read with scipy.io.wavfile (mono downmix, native sample rate: evaluate.py:15-23 passes sr=None).
 
-`bss_eval_sources_gpu` and `metrics_from_waveforms(..., device="gpu")` (CLI `--device gpu`) compute the same metrics with
-fp64 gfx950 kernels (csrc/bss.hip) from the Gram-matrix form below; the numpy functions stay the reference they are
-tested against.  `bss_eval_sources_framewise` / `metrics_from_waveforms_framewise` (CLI `--frame_window`) score windows of
-a track the way mir_eval.separation.bss_eval_sources_framewise does; their GPU forms make one windowed correlation pass
-and factor the Gram matrices of all windows in batches.
+`bss_eval_sources_framewise` / `metrics_from_waveforms_framewise` (CLI `--frame_window`) score windows of a track the way
+mir_eval.separation.bss_eval_sources_framewise does.  `bss_eval_sources_gpu`, `bss_eval_sources_framewise_gpu` and
+`device="gpu"` of the two metrics functions (CLI `--device gpu`) compute the same metrics with fp64 gfx950 kernels
+(csrc/bss.hip) from the Gram-matrix form below; the numpy functions stay the reference they are tested against.  The GPU
+path is one path over windows: one windowed correlation pass, then the Gram matrices of all windows factored in batches;
+a whole signal is its one-window case.  Per window, an output that needs a factorisation with a pivot that is not > 0
+comes from the numpy bss_eval_sources on that window's slice, with one RuntimeWarning per call.
 
 The Gram-matrix form of _project / _criteria.  References s_0 .. s_{K-1} and an estimate e of length n, zero outside
 [0, n); filter length F; x(.-p) is x delayed by p samples.  _project builds
@@ -177,89 +179,6 @@ def _metrics_from_gram(energy, proj_one, proj_all, compute_permutation=True):
     return sdr[popt, idx], sir[popt, idx], sar[popt, idx], np.asarray(popt)
 
 
-def _gpu_projections(sig, solves, energies, flen):
-    """Projection energies of the Gram form on the GPU, from ONE correlation pass over the rows of `sig` ((S, n) float64
-    on a ROCm device).  solves: [(reference rows, estimate rows)], one Cholesky factorisation each; energies: rows whose
-    |x|^2 is wanted.  Returns (energy, [|P e|^2 per estimate of each solve]) as numpy, or None when a factorisation met a
-    pivot that was not > 0 (singular G: _project then solves by least squares)."""
-    import ctypes
-    import torch
-    from . import _lib
-    L = _lib.lib()
-    pairs, off = [], {}
-
-    def need(a, b, nl):                              # offset of pair (a, b, nl) in the correlation output
-        if (a, b, nl) not in off:
-            off[(a, b, nl)] = sum(p[2] for p in pairs)
-            pairs.append((a, b, nl))
-        return off[(a, b, nl)]
-
-    plans = []
-    for refs, ests in solves:
-        gram = [need(i, j, flen) for i in refs for j in refs]
-        rhs = [need(e, i, flen) for e in ests for i in refs]
-        plans.append((len(refs), gram, rhs, len(ests)))
-    eoff = [need(e, e, 1) for e in energies]
-    flat = [v for p in pairs for v in p]
-    parr = (ctypes.c_int * len(flat))(*flat)
-    dev = sig.device
-    n = sig.shape[1]
-    ws_bytes = max([L.svs_bss_corr_workspace_bytes(n, len(pairs), parr)] +
-                   [L.svs_bss_solve_workspace_bytes(k, flen, nr) for k, _, _, nr in plans])
-    with torch.cuda.device(dev):
-        stream = _lib.stream_ptr()
-        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
-        corr = torch.empty(sum(p[2] for p in pairs), dtype=torch.float64, device=dev)
-        _lib.check(L.svs_bss_corr(sig.data_ptr(), sig.stride(0), sig.shape[0], n, parr, len(pairs), corr.data_ptr(),
-                                  ws.data_ptr(), ws.numel(), stream), "svs_bss_corr")
-        status = torch.empty(len(plans), dtype=torch.int32, device=dev)
-        ynorm2 = torch.empty(len(plans), max(p[3] for p in plans), dtype=torch.float64, device=dev)
-        for s, (k, gram, rhs, nr) in enumerate(plans):
-            _lib.check(L.svs_bss_solve(corr.data_ptr(), k, flen, (ctypes.c_int * len(gram))(*gram),
-                                       (ctypes.c_int * len(rhs))(*rhs), nr, ynorm2[s].data_ptr(), status[s:].data_ptr(),
-                                       ws.data_ptr(), ws.numel(), stream), "svs_bss_solve")
-        energy = corr[eoff].cpu().numpy()
-        y = ynorm2.cpu().numpy()
-        if status.cpu().numpy().any():
-            warnings.warn("BSS-eval: a Gram matrix has a pivot that is not > 0 in the GPU Cholesky (singular or "
-                          "numerically indefinite); this call falls back to the numpy path", RuntimeWarning, stacklevel=3)
-            return None
-    return energy, [y[s, :p[3]] for s, p in enumerate(plans)]
-
-
-def _device_f64(x):
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("the GPU BSS-eval needs a ROCm device (fp64 gfx950 kernels, no CPU path; use device='cpu')")
-    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-    return t.to(device=t.device if t.is_cuda else torch.device("cuda"), dtype=torch.float64)
-
-
-def bss_eval_sources_gpu(reference_sources, estimated_sources, compute_permutation=True, flen=FILTER_LEN):
-    """bss_eval_sources on the GPU (numpy or torch inputs, K = 1 or 2 sources, flen <= 512): the same (sdr, sir, sar,
-    perm).  A singular Gram matrix (e.g. a silent reference) makes the call return the numpy bss_eval_sources result."""
-    import torch
-    ref, est = _device_f64(reference_sources), _device_f64(estimated_sources)
-    ref, est = ref.reshape(1, -1) if ref.dim() == 1 else ref, est.reshape(1, -1) if est.dim() == 1 else est
-    if ref.shape != est.shape:
-        raise ValueError(f"reference {tuple(ref.shape)} and estimate {tuple(est.shape)} must have the same shape")
-    nsrc = ref.shape[0]
-    if nsrc not in (1, 2):
-        raise ValueError(f"bss_eval_sources_gpu handles 1 or 2 sources, got {nsrc} (use bss_eval_sources)")
-    if not 1 <= flen <= 512:
-        raise ValueError(f"flen = {flen}: the GPU path supports filter lengths 1 .. 512")
-    if est.device != ref.device:
-        est = est.to(ref.device)
-    refs, ests = list(range(nsrc)), [nsrc + a for a in range(nsrc)]
-    solves = [((i,), ests) for i in refs] + ([(tuple(refs), ests)] if nsrc == 2 else [])
-    q = _gpu_projections(torch.cat([ref, est]).contiguous(), solves, ests, flen)
-    if q is None:
-        return bss_eval_sources(ref.cpu().numpy(), est.cpu().numpy(), compute_permutation, flen)
-    energy, y = q
-    proj_one = np.stack(y[:nsrc], axis=1)
-    return _metrics_from_gram(energy, proj_one, y[nsrc] if nsrc == 2 else proj_one[:, 0], compute_permutation)
-
-
 def _load_track(mix_path, vocal_ref_path, vocal_est_path):
     mix, sr_mix = load_mono_audio(mix_path)
     vocal_ref, sr_ref = load_mono_audio(vocal_ref_path)
@@ -307,10 +226,11 @@ def frame_summary(frames):
 
 
 def metrics_from_waveforms(mix, vocal_ref, vocal_est, device="cpu"):
-    """{"SDR", "SIR", "SAR", "NSDR"} of the vocal.  device="gpu": one correlation pass over (vocal, mix - vocal, estimate,
-    mix - estimate, mix) on the GPU serves all four (the accompaniments are formed on the device, as numpy does)."""
+    """{"SDR", "SIR", "SAR", "NSDR"} of the vocal.  device="gpu": the one-window case of _vocal_metrics_gpu, with the
+    permutation."""
     if device == "gpu":
-        return _metrics_from_waveforms_gpu(mix, vocal_ref, vocal_est)
+        frames = _vocal_metrics_gpu(mix, vocal_ref, vocal_est, None, None, compute_permutation=True)
+        return {k: float(frames[k][0]) for k in METRICS}
     if device != "cpu":
         raise ValueError(f"device must be 'cpu' or 'gpu', got {device!r}")
     sources_ref = np.stack([vocal_ref, mix - vocal_ref], axis=0)
@@ -319,21 +239,6 @@ def metrics_from_waveforms(mix, vocal_ref, vocal_est, device="cpu"):
     v = int(perm[0])                                   # estimate matched to the vocal reference (evaluate.py:62)
     sdr_mix, _, _, _ = bss_eval_sources(vocal_ref[None, :], mix[None, :])
     return {"SDR": float(sdr[v]), "SIR": float(sir[v]), "SAR": float(sar[v]), "NSDR": float(sdr[v]) - float(sdr_mix[0])}
-
-
-def _metrics_from_waveforms_gpu(mix, vocal_ref, vocal_est):
-    import torch
-    m, v, ve = _device_f64(mix), _device_f64(vocal_ref), _device_f64(vocal_est)
-    v, ve = v.to(m.device), ve.to(m.device)
-    sig = torch.stack([v, m - v, ve, m - ve, m])     # rows: vocal, accompaniment, their estimates, mixture
-    q = _gpu_projections(sig, [((0,), [2, 3, 4]), ((1,), [2, 3]), ((0, 1), [2, 3])], [2, 3, 4], FILTER_LEN)
-    if q is None:
-        return metrics_from_waveforms(*(t.cpu().numpy() for t in (m, v, ve)))
-    energy, (p_v, p_a, p_all) = q
-    sdr, sir, sar, perm = _metrics_from_gram(energy[:2], np.stack([p_v[:2], p_a], axis=1), p_all)
-    j = int(perm[0])
-    sdr_mix = _metrics_from_gram(energy[2:], p_v[2:, None], p_v[2:])[0]
-    return {"SDR": float(sdr[j]), "SIR": float(sir[j]), "SAR": float(sar[j]), "NSDR": float(sdr[j]) - float(sdr_mix[0])}
 
 
 # ---- framewise ------------------------------------------------------------------------------
@@ -396,7 +301,7 @@ def metrics_from_waveforms_framewise(mix, vocal_ref, vocal_est, window, hop, dev
     the vocal estimate), NaN where the vocal or the mixture is silent.  device="gpu": one windowed correlation pass and
     batched factorisations; ws_budget caps the workspace of one batch (the results do not depend on it)."""
     if device == "gpu":
-        return _metrics_framewise_gpu(mix, vocal_ref, vocal_est, window, hop, ws_budget)
+        return _vocal_metrics_gpu(mix, vocal_ref, vocal_est, window, hop, False, ws_budget)
     if device != "cpu":
         raise ValueError(f"device must be 'cpu' or 'gpu', got {device!r}")
     mix, vocal_ref, vocal_est = (np.asarray(x, dtype=np.float64) for x in (mix, vocal_ref, vocal_est))
@@ -406,11 +311,26 @@ def metrics_from_waveforms_framewise(mix, vocal_ref, vocal_est, window, hop, dev
     return _frames(sdr[0], sir[0], sar[0], sdr_mix, _frame_args(window, hop)[1])
 
 
-def _gpu_framewise_projections(sig, window, hop, nwin, solves, energies, flen, ws_budget):
-    """_gpu_projections for every window [w*hop, w*hop + window) of the rows of sig: ONE windowed correlation pass, then
-    per solve batched factorisations over all windows, in batches whose workspace stays within ws_budget bytes (at least
-    one system).  Returns numpy (energy (nwin, len(energies)), [|P e|^2 (nwin, nrhs) per solve], [status (nwin,) per
-    solve]); a status that is not 0 marks a window whose factorisation met a pivot that was not > 0."""
+# ---- the GPU path ---------------------------------------------------------------------------
+# A whole signal is one window (window = hop = n); the windows of bss_eval_sources_framewise are the same call with more of
+# them.  Per window: a silent row -> NaN (only with two or more windows); a factorisation that met a bad pivot -> the
+# outputs that need it come from the numpy bss_eval_sources on that window's slice (_host_windows).
+
+def _device_f64(x):
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("the GPU BSS-eval needs a ROCm device (fp64 gfx950 kernels, no CPU path; use device='cpu')")
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    return t.to(device=t.device if t.is_cuda else torch.device("cuda"), dtype=torch.float64)
+
+
+def _gpu_window_projections(sig, window, hop, nwin, solves, energies, flen, ws_budget):
+    """Projection energies of the Gram form for every window [w*hop, w*hop + window) of the rows of `sig` ((S, n) float64 on
+    a ROCm device): ONE windowed correlation pass, then per solve batched factorisations over all windows, in batches whose
+    workspace stays within ws_budget bytes (at least one system).  solves: [(reference rows, estimate rows)], one Cholesky
+    factorisation per window each; energies: rows whose |x|^2 is wanted.  Returns numpy (energy (nwin, len(energies)),
+    [|P e|^2 (nwin, nrhs) per solve], [status (nwin,) per solve]); a status that is not 0 marks a window whose factorisation
+    met a pivot that was not > 0 (singular G: _project then solves by least squares)."""
     import torch
     from . import _lib
     L = _lib.lib()
@@ -422,11 +342,14 @@ def _gpu_framewise_projections(sig, window, hop, nwin, solves, energies, flen, w
             pairs.append((a, b, nl))
         return off[(a, b, nl)]
 
-    plans = []
+    plans, ycols = [], 0
     for refs, ests in solves:
         gram = [need(i, j, flen) for i in refs for j in refs]
         rhs = [need(e, i, flen) for e in ests for i in refs]
-        plans.append((len(refs), np.asarray(gram, dtype=np.int64), np.asarray(rhs, dtype=np.int64), len(ests)))
+        k, nr = len(refs), len(ests)
+        nb = int(max(1, min(nwin, MAX_BATCH, ws_budget // L.svs_bss_solve_batched_workspace_bytes(1, k, flen, nr))))
+        plans.append((k, np.asarray(gram, dtype=np.int64), np.asarray(rhs, dtype=np.int64), nr, nb, ycols))
+        ycols += nr
     eoff = [need(e, e, 1) for e in energies]
     stride = sum(p[2] for p in pairs)
     flat = np.asarray([v for p in pairs for v in p], dtype=np.int32)
@@ -437,35 +360,96 @@ def _gpu_framewise_projections(sig, window, hop, nwin, solves, energies, flen, w
         ws_bytes = L.svs_bss_corr_windows_workspace_bytes(window, nwin, len(pairs), flat.ctypes.data)
         if ws_bytes == 0:
             raise ValueError(f"{nwin} windows of {window} samples do not fit one correlation launch")
+        # one workspace and one result buffer of each kind for the whole call: the launches share a stream, and every
+        # copy back to the host is a synchronisation
+        ws_bytes = max([ws_bytes] +
+                       [L.svs_bss_solve_batched_workspace_bytes(nb, k, flen, nr) for k, _, _, nr, nb, _ in plans])
         ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
         corr = torch.empty(nwin, stride, dtype=torch.float64, device=dev)
         _lib.check(L.svs_bss_corr_windows(sig.data_ptr(), sig.stride(0), sig.shape[0], n, window, hop, nwin,
                                           flat.ctypes.data, len(pairs), corr.data_ptr(), stride, ws.data_ptr(),
                                           ws.numel(), stream), "svs_bss_corr_windows")
-        del ws
-        ys, sts = [], []
-        for k, gram, rhs, nr in plans:
-            nb = int(max(1, min(nwin, MAX_BATCH, ws_budget // L.svs_bss_solve_workspace_bytes(k, flen, nr))))
-            ws = torch.empty(int(L.svs_bss_solve_batched_workspace_bytes(nb, k, flen, nr)), dtype=torch.uint8, device=dev)
-            y = torch.empty(nwin, nr, dtype=torch.float64, device=dev)
-            status = torch.empty(nwin, dtype=torch.int32, device=dev)
+        y = torch.empty(nwin * ycols, dtype=torch.float64, device=dev)      # per solve a contiguous (nwin, nrhs) block
+        status = torch.empty(len(plans), nwin, dtype=torch.int32, device=dev)
+        for s, (k, gram, rhs, nr, nb, y0) in enumerate(plans):
             for w0 in range(0, nwin, nb):
                 b = min(nb, nwin - w0)
                 base = np.arange(w0, w0 + b, dtype=np.int64)[:, None] * stride
                 g, r = np.ascontiguousarray(base + gram), np.ascontiguousarray(base + rhs)
                 _lib.check(L.svs_bss_solve_batched(corr.data_ptr(), b, k, flen, g.ctypes.data, r.ctypes.data, nr,
-                                                   y[w0].data_ptr(), status[w0:].data_ptr(), ws.data_ptr(), ws.numel(),
-                                                   stream), "svs_bss_solve_batched")
-            ys.append(y)
-            sts.append(status)
-            del ws
-        energy = corr[:, eoff].cpu().numpy()
-        return energy, [y.cpu().numpy() for y in ys], [s.cpu().numpy() for s in sts]
+                                                   y[nwin * y0 + w0 * nr:].data_ptr(), status[s, w0:].data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), stream), "svs_bss_solve_batched")
+        energy, y, status = (t.cpu().numpy() for t in (corr[:, eoff], y, status))
+    return energy, [y[nwin * y0:nwin * (y0 + nr)].reshape(nwin, nr) for _, _, _, nr, _, y0 in plans], list(status)
 
 
-def _warn_framewise_fallback():
-    warnings.warn("BSS-eval: a Gram matrix has a pivot that is not > 0 in the GPU Cholesky (singular or numerically "
-                  "indefinite); the windows concerned fall back to the numpy path", RuntimeWarning, stacklevel=4)
+def _windows(n, window, hop):
+    """(window, hop, nwin, framed) of a signal of n samples.  window None, or fewer than two windows: one window that is the
+    whole signal, not framed (no silence rule)."""
+    if window is not None:
+        window, hop = _frame_args(window, hop)
+        nwin = frame_count(n, window, hop)
+        if nwin >= 2:
+            return window, hop, nwin, True
+    return n, n, 1, False
+
+
+def _host_windows(signals, window, hop):
+    """slices(w) -> window w of each of `signals` as numpy, for the windows that numpy has to score.  The first use copies
+    the signals to the host and gives the one RuntimeWarning of the call (attributed to the caller of the public function)."""
+    host = []
+
+    def slices(w):
+        if not host:
+            warnings.warn("BSS-eval: a Gram matrix has a pivot that is not > 0 in the GPU Cholesky (singular or numerically "
+                          "indefinite); scoring of the affected window(s) falls back to the numpy path", RuntimeWarning,
+                          stacklevel=4)
+            host.extend(t.cpu().numpy() for t in signals)
+        return [x[..., w * hop:w * hop + window] for x in host]
+    return slices
+
+
+def _sources_gpu(reference_sources, estimated_sources, window, hop, compute_permutation, flen, ws_budget=WS_BUDGET):
+    """(sdr, sir, sar, perm), each (nsrc, nwin), of K = 1 or 2 references and K estimates over the windows of _windows
+    (perm: float64 when framed, since a silent window is NaN).  Every output of a window needs every solve of that window."""
+    import torch
+    ref, est = (x.reshape(1, -1) if x.dim() == 1 else x for x in map(_device_f64, (reference_sources, estimated_sources)))
+    if ref.dim() != 2 or ref.shape != est.shape:
+        raise ValueError(f"reference {tuple(ref.shape)} and estimate {tuple(est.shape)} must have the same 2-D shape")
+    nsrc, n = ref.shape
+    if nsrc not in (1, 2):
+        raise ValueError(f"the GPU BSS-eval handles 1 or 2 sources, got {nsrc} (use bss_eval_sources)")
+    if not 1 <= flen <= 512:
+        raise ValueError(f"flen = {flen}: the GPU path supports filter lengths 1 .. 512")
+    window, hop, nwin, framed = _windows(n, window, hop)
+    est = est.to(ref.device)
+    refs, ests = list(range(nsrc)), [nsrc + a for a in range(nsrc)]
+    solves = [((i,), ests) for i in refs] + ([(tuple(refs), ests)] if nsrc == 2 else [])
+    energy, y, status = _gpu_window_projections(torch.cat([ref, est]).contiguous(), window, hop, nwin, solves, refs + ests,
+                                                flen, ws_budget)
+    host = _host_windows((ref, est), window, hop)
+    out = [np.full((nsrc, nwin), np.nan) for _ in range(4)]
+    for w in range(nwin):
+        if framed and (energy[w] == 0).any():          # a silent reference or estimate
+            continue
+        if any(s[w] for s in status):
+            r = bss_eval_sources(*host(w), compute_permutation, flen)
+        else:
+            proj_one = np.stack([y[i][w] for i in range(nsrc)], axis=1)
+            r = _metrics_from_gram(energy[w, nsrc:], proj_one, y[nsrc][w] if nsrc == 2 else proj_one[:, 0],
+                                   compute_permutation)
+        for o, v in zip(out, r):
+            o[:, w] = v
+    if not framed:                                     # no NaN: an integer perm, as bss_eval_sources gives
+        out[3] = out[3].astype(np.int64)
+    return tuple(out)
+
+
+def bss_eval_sources_gpu(reference_sources, estimated_sources, compute_permutation=True, flen=FILTER_LEN):
+    """bss_eval_sources on the GPU (numpy or torch inputs, K = 1 or 2 sources, flen <= 512): the same (sdr, sir, sar,
+    perm).  A singular Gram matrix (e.g. a silent reference) makes the call return the numpy bss_eval_sources result, with
+    a RuntimeWarning."""
+    return tuple(v[:, 0] for v in _sources_gpu(reference_sources, estimated_sources, None, None, compute_permutation, flen))
 
 
 def bss_eval_sources_framewise_gpu(reference_sources, estimated_sources, window=30 * 44100, hop=15 * 44100,
@@ -473,89 +457,42 @@ def bss_eval_sources_framewise_gpu(reference_sources, estimated_sources, window=
     """bss_eval_sources_framewise on the GPU (numpy or torch inputs, K = 1 or 2 sources, flen <= 512): the same
     (sdr, sir, sar, perm).  Silent windows are NaN from the per-window energies; a window whose Gram matrix is singular
     although no row is silent is scored by the numpy bss_eval_sources, with a RuntimeWarning."""
-    import torch
-    ref, est = _device_f64(reference_sources), _device_f64(estimated_sources)
-    ref, est = ref.reshape(1, -1) if ref.dim() == 1 else ref, est.reshape(1, -1) if est.dim() == 1 else est
-    if ref.dim() != 2 or ref.shape != est.shape:
-        raise ValueError(f"reference {tuple(ref.shape)} and estimate {tuple(est.shape)} must have the same 2-D shape")
-    window, hop = _frame_args(window, hop)
-    nsrc, n = ref.shape
-    if nsrc not in (1, 2):
-        raise ValueError(f"bss_eval_sources_framewise_gpu handles 1 or 2 sources, got {nsrc}")
-    if not 1 <= flen <= 512:
-        raise ValueError(f"flen = {flen}: the GPU path supports filter lengths 1 .. 512")
-    nwin = frame_count(n, window, hop)
-    if nwin < 2:
-        return tuple(np.expand_dims(v, -1) for v in bss_eval_sources_gpu(ref, est, compute_permutation, flen))
-    est = est.to(ref.device)
-    refs, ests = list(range(nsrc)), [nsrc + a for a in range(nsrc)]
-    solves = [((i,), ests) for i in refs] + ([(tuple(refs), ests)] if nsrc == 2 else [])
-    energy, y, status = _gpu_framewise_projections(torch.cat([ref, est]).contiguous(), window, hop, nwin, solves,
-                                                   refs + ests, flen, ws_budget)
-    bad = np.any(np.stack(status) != 0, axis=0)
-    out = [np.full((nsrc, nwin), np.nan) for _ in range(4)]
-    host = None
-    for w in range(nwin):
-        if (energy[w] == 0).any():                     # a silent reference or estimate
-            continue
-        if bad[w]:
-            if host is None:
-                _warn_framewise_fallback()
-                host = ref.cpu().numpy(), est.cpu().numpy()
-            sl = slice(w * hop, w * hop + window)
-            r = bss_eval_sources(host[0][:, sl], host[1][:, sl], compute_permutation, flen)
-        else:
-            proj_one = np.stack([y[i][w] for i in range(nsrc)], axis=1)
-            r = _metrics_from_gram(energy[w, nsrc:], proj_one, y[nsrc][w] if nsrc == 2 else proj_one[:, 0],
-                                   compute_permutation)
-        for o, v in zip(out, r):
-            o[:, w] = v
-    return tuple(out)
+    return _sources_gpu(reference_sources, estimated_sources, window, hop, compute_permutation, flen, ws_budget)
 
 
-def _metrics_framewise_gpu(mix, vocal_ref, vocal_est, window, hop, ws_budget):
-    """metrics_from_waveforms_framewise(device="gpu"): one windowed correlation pass over the rows of
-    _metrics_from_waveforms_gpu, then per window K = 1 on (vocal; est, acc_est, mix) and (acc; est, acc_est) and K = 2.
-    Fewer than two windows: the same machinery on one window, the whole track, without the silence rule."""
+def _vocal_metrics_gpu(mix, vocal_ref, vocal_est, window, hop, compute_permutation, ws_budget=WS_BUDGET):
+    """The frames of metrics_from_waveforms_framewise over the windows of _windows: one windowed correlation pass over
+    (vocal, mix - vocal, estimate, mix - estimate, mix), the accompaniments formed on the device as numpy forms them, then
+    per window K = 1 on (vocal; est, acc_est, mix) and (acc; est, acc_est) and K = 2.  SDR / SIR / SAR of a window need all
+    three solves, the mixture's SDR only the vocal-alone one."""
     import torch
-    window, hop = _frame_args(window, hop)
     m, v, ve = _device_f64(mix), _device_f64(vocal_ref), _device_f64(vocal_est)
     v, ve = v.to(m.device), ve.to(m.device)
     if m.dim() != 1 or v.shape != m.shape or ve.shape != m.shape:
         raise ValueError(f"mix {tuple(m.shape)}, vocal {tuple(v.shape)} and estimate {tuple(ve.shape)} must be 1-D of "
                          "one length")
-    n = m.shape[0]
-    nwin = frame_count(n, window, hop)
-    whole = nwin < 2
-    if whole:
-        window, hop, nwin = n, n, 1
+    window, hop, nwin, framed = _windows(m.shape[0], window, hop)
     sig = torch.stack([v, m - v, ve, m - ve, m])     # rows: vocal, accompaniment, their estimates, mixture
-    energy, (p_v, p_a, p_all), status = _gpu_framewise_projections(
+    energy, (p_v, p_a, p_all), status = _gpu_window_projections(
         sig, window, hop, nwin, [((0,), [2, 3, 4]), ((1,), [2, 3]), ((0, 1), [2, 3])], [0, 1, 2, 3, 4], FILTER_LEN,
         ws_budget)
+    host = _host_windows((m, v, ve), window, hop)
     sdr, sir, sar, sdr_mix = (np.full(nwin, np.nan) for _ in range(4))
-    host = None
     for w in range(nwin):
-        silent = not whole and bool((energy[w, :4] == 0).any())
-        mix_silent = not whole and (energy[w, 0] == 0 or energy[w, 4] == 0)
-        main_bad = not silent and bool(status[0][w] or status[1][w] or status[2][w])
-        mix_bad = not mix_silent and bool(status[0][w])
-        if (main_bad or mix_bad) and host is None:
-            _warn_framewise_fallback()
-            host = [t.cpu().numpy() for t in (m, v, ve)]
-        sl = slice(w * hop, w * hop + window)
-        if main_bad:
-            hm, hv, he = (x[sl] for x in host)
-            r = bss_eval_sources(np.stack([hv, hm - hv]), np.stack([he, hm - he]), compute_permutation=False)
-            sdr[w], sir[w], sar[w] = r[0][0], r[1][0], r[2][0]
-        elif not silent:
-            r = _metrics_from_gram(energy[w, 2:4], np.stack([p_v[w, :2], p_a[w]], axis=1), p_all[w],
-                                   compute_permutation=False)
-            sdr[w], sir[w], sar[w] = r[0][0], r[1][0], r[2][0]
-        if mix_bad:
-            sdr_mix[w] = bss_eval_sources(host[1][None, sl], host[0][None, sl], compute_permutation=False)[0][0]
-        elif not mix_silent:
-            sdr_mix[w] = _metrics_from_gram(energy[w, 4:5], p_v[w, 2:3, None], p_v[w, 2:3], compute_permutation=False)[0][0]
+        if not (framed and (energy[w, :4] == 0).any()):
+            if status[0][w] or status[1][w] or status[2][w]:
+                hm, hv, he = host(w)
+                r = bss_eval_sources(np.stack([hv, hm - hv]), np.stack([he, hm - he]), compute_permutation)
+            else:
+                r = _metrics_from_gram(energy[w, 2:4], np.stack([p_v[w, :2], p_a[w]], axis=1), p_all[w], compute_permutation)
+            j = int(r[3][0])                           # estimate matched to the vocal reference (evaluate.py:62)
+            sdr[w], sir[w], sar[w] = r[0][j], r[1][j], r[2][j]
+        if not (framed and (energy[w, 0] == 0 or energy[w, 4] == 0)):
+            if status[0][w]:
+                hm, hv, _ = host(w)
+                sdr_mix[w] = bss_eval_sources(hv[None], hm[None], compute_permutation=False)[0][0]
+            else:
+                sdr_mix[w] = _metrics_from_gram(energy[w, 4:5], p_v[w, 2:3, None], p_v[w, 2:3], compute_permutation=False)[0][0]
     return _frames(sdr, sir, sar, sdr_mix, hop)
 
 

@@ -1,14 +1,20 @@
 """Framewise BSS-eval on the host (evaluate.bss_eval_sources_framewise, metrics_from_waveforms_framewise, the
 --frame_window / --frame_hop / --frames_csv options) against the whole-signal bss_eval_sources on each window's slices,
-and the argument checks of the framewise C entry points.  No GPU needed."""
+the argument checks of the framewise C entry points, and the window rules of the device="gpu" entry points (silent window,
+bad pivot, which solves an output needs) with the one library-calling function replaced by numpy.  No GPU needed."""
 import csv
 import ctypes
+import warnings
 
 import numpy as np
 import pytest
+import torch
+from scipy.linalg import LinAlgError, cholesky, solve_triangular
 
 from svs_unet_pytorch_amd import _lib
 from svs_unet_pytorch_amd import evaluate as ev
+from test_bss_gram import assert_bss_close, corr
+from test_gpu_bss_framewise import assert_frames_close, track_with_silence, two_sources
 
 FLEN = 16                                            # the window rules do not depend on flen; short filters keep numpy fast
 
@@ -257,3 +263,151 @@ def test_framewise_entry_points_reject_invalid_calls_without_touching_the_gpu(li
     assert b"negative offset (system 1)" in err()
     assert lib.svs_bss_solve_batched(fake, 2, 1, 512, g, r, 2, fake, fake, fake, 1000, None) == -2
     assert b"workspace too small" in err()
+
+
+# ---- the window rules of the GPU path, with numpy in place of the library ---------------------
+
+class NumpyProjections:
+    """float64 numpy stand-in for evaluate._gpu_window_projections: per window and solve the block-Toeplitz Gram matrix from
+    lagged correlations, scipy's Cholesky and a forward solve, |y|^2.  A matrix that scipy cannot factor, or a (window,
+    solve) in force_bad, has status 1."""
+
+    def __init__(self, force_bad=()):
+        self.force_bad = set(force_bad)
+
+    def __call__(self, sig, window, hop, nwin, solves, energies, flen, ws_budget):
+        x = sig.numpy()
+        d = np.arange(flen)[None, :] - np.arange(flen)[:, None]
+        energy = np.empty((nwin, len(energies)))
+        ys = [np.zeros((nwin, len(ests))) for _, ests in solves]
+        status = [np.zeros(nwin, dtype=np.int32) for _ in solves]
+        for w in range(nwin):
+            s = x[:, w * hop:w * hop + window]
+            energy[w] = [corr(s[e], s[e], 1)[0] for e in energies]
+            for q, (refs, ests) in enumerate(solves):
+                c = {(i, j): corr(s[i], s[j], flen) for i in refs for j in refs}
+                G = np.block([[np.where(d >= 0, c[i, j][np.abs(d)], c[j, i][np.abs(d)]) for j in refs] for i in refs])
+                D = np.stack([np.concatenate([corr(s[e], s[i], flen) for i in refs]) for e in ests], axis=1)
+                try:
+                    if (w, q) in self.force_bad:
+                        raise LinAlgError("forced")
+                    Y = solve_triangular(cholesky(G, lower=True), D, lower=True)
+                    ys[q][w] = (Y * Y).sum(axis=0)
+                except LinAlgError:
+                    status[q][w] = 1
+        return energy, ys, status
+
+
+def host_f64(x):
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    return t.to(dtype=torch.float64)
+
+
+def use_numpy_projections(mp, force_bad=()):
+    mp.setattr(ev, "_gpu_window_projections", NumpyProjections(force_bad))
+    mp.setattr(ev, "_device_f64", host_f64)
+
+
+def fallback_warnings(rec):
+    """The RuntimeWarnings of a recorded call, all of which must be the fallback warning."""
+    got = [str(r.message) for r in rec if issubclass(r.category, RuntimeWarning)]
+    assert all("falls back to the numpy path" in m for m in got), got
+    return got
+
+
+SR = 8192
+
+
+def test_gpu_window_rules_silent_windows_are_nan(monkeypatch):
+    mix, vocal, est = track_with_silence(7, seed=50)
+    want = ev.metrics_from_waveforms_framewise(mix, vocal, est, SR, SR)
+    assert list(np.isnan(want["SDR"])) == [False, True, False, False, False, False, True]      # silent vocal; all silent
+    use_numpy_projections(monkeypatch)
+    monkeypatch.setattr(ev, "bss_eval_sources", None)                        # no fallback: not called at all
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        got = ev.metrics_from_waveforms_framewise(mix, vocal, est, SR, SR, device="gpu")
+    assert_frames_close(got, want)
+
+
+@pytest.mark.parametrize("perm", [False, True])
+def test_gpu_window_rules_sources_framewise(perm, monkeypatch):
+    refs, ests = two_sources(24000, 53)
+    want = ev.bss_eval_sources_framewise(refs, ests, 4000, 2000, perm, 64)
+    assert np.isnan(want[0][:, 4]).all() and not np.isnan(want[0][:, 3]).any()
+    use_numpy_projections(monkeypatch)
+    monkeypatch.setattr(ev, "bss_eval_sources", None)
+    got = ev.bss_eval_sources_framewise_gpu(refs, ests, 4000, 2000, perm, 64)
+    for g, w in zip(got, want):
+        assert g.shape == w.shape == (2, 11) and g.dtype == np.float64
+        assert np.array_equal(np.isnan(g), np.isnan(w))
+    for k in np.flatnonzero(~np.isnan(want[0][0])):
+        assert_bss_close(tuple(v[:, k] for v in got), tuple(v[:, k] for v in want))
+
+
+@pytest.mark.parametrize("solve,numpy_calls", [(2, 1), (1, 1), (0, 2)])
+def test_gpu_window_rules_bad_pivot_rescores_that_window_with_numpy(solve, numpy_calls, monkeypatch):
+    """SDR / SIR / SAR need all three solves of a window, the mixture's SDR only solve 0 (the vocal alone)."""
+    mix, vocal, est = track_with_silence(7, seed=50)
+    want = ev.metrics_from_waveforms_framewise(mix, vocal, est, SR, SR)
+    use_numpy_projections(monkeypatch)
+    clean = ev.metrics_from_waveforms_framewise(mix, vocal, est, SR, SR, device="gpu")
+    use_numpy_projections(monkeypatch, force_bad=[(3, solve)])
+    calls, numpy_bss = [], ev.bss_eval_sources
+
+    def spy(refs, ests, *args, **kwargs):
+        calls.append((np.array(refs), np.array(ests)))
+        return numpy_bss(refs, ests, *args, **kwargs)
+
+    monkeypatch.setattr(ev, "bss_eval_sources", spy)
+    with warnings.catch_warnings(record=True) as rec:
+        warnings.simplefilter("always")
+        got = ev.metrics_from_waveforms_framewise(mix, vocal, est, SR, SR, device="gpu")
+    assert len(fallback_warnings(rec)) == 1
+    others = np.arange(7) != 3
+    for k in ev.METRICS:
+        assert np.array_equal(got[k][others], clean[k][others], equal_nan=True), k
+    for k in ("SDR", "SIR", "SAR"):
+        assert got[k][3] == want[k][3], k                                      # bitwise the numpy result
+    sl = slice(3 * SR, 4 * SR)
+    sdr_mix = want["SDR"][3] - want["NSDR"][3] if solve == 0 else clean["SDR"][3] - clean["NSDR"][3]
+    assert abs(got["NSDR"][3] - (want["SDR"][3] - sdr_mix)) <= 1e-9
+    assert len(calls) == numpy_calls
+    assert np.array_equal(calls[0][0], np.stack([vocal[sl], (mix - vocal)[sl]]))
+    assert np.array_equal(calls[0][1], np.stack([est[sl], (mix - est)[sl]]))
+    if numpy_calls == 2:
+        assert got["NSDR"][3] == want["NSDR"][3]
+        assert np.array_equal(calls[1][0], vocal[None, sl]) and np.array_equal(calls[1][1], mix[None, sl])
+
+
+def test_gpu_window_rules_one_window_is_the_whole_track(monkeypatch):
+    mix, vocal, est = track_with_silence(7, seed=50)
+    n = mix.size
+    assert list(ev.bss_eval_sources(np.stack([vocal, mix - vocal]), np.stack([est, mix - est]))[3]) == [0, 1]
+    want = ev.metrics_from_waveforms(mix, vocal, est)
+    use_numpy_projections(monkeypatch)
+    monkeypatch.setattr(ev, "bss_eval_sources", None)
+    whole = ev.metrics_from_waveforms(mix, vocal, est, device="gpu")
+    for window, hop in [(n, n), (n + 5, 100), (2 * n, SR)]:
+        fr = ev.metrics_from_waveforms_framewise(mix, vocal, est, window, hop, device="gpu")
+        assert list(fr["start"]) == [0]
+        for k in ev.METRICS:
+            assert fr[k].shape == (1,) and fr[k][0] == whole[k], (k, window, hop)
+    assert whole.keys() == want.keys() and all(isinstance(v, float) for v in whole.values())
+    for k in want:
+        assert abs(whole[k] - want[k]) <= 1e-3, (k, whole[k], want[k])
+
+
+def test_gpu_window_rules_silent_reference_falls_back_to_numpy(monkeypatch):
+    rng = np.random.default_rng(4)
+    refs = np.stack([np.zeros(8000), rng.standard_normal(8000)])
+    ests = np.stack([0.01 * rng.standard_normal(8000), refs[1] + 0.1 * rng.standard_normal(8000)])
+    use_numpy_projections(monkeypatch)
+    with np.errstate(all="ignore"):
+        with pytest.warns(RuntimeWarning, match="falls back to the numpy path"):
+            got = ev.bss_eval_sources_gpu(refs, ests)
+        want = ev.bss_eval_sources(refs, ests)
+    for g, w in zip(got, want):
+        assert g.shape == (2,)
+        np.testing.assert_array_equal(g, w)
+    assert np.issubdtype(got[3].dtype, np.integer)

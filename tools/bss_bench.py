@@ -10,7 +10,7 @@ and the numpy path, on a seeded synthetic 240 s track at 8192 Hz and at 44,100 H
 Timing: host clock around metrics_from_waveforms(device="gpu") followed by a device synchronise (the call ends with a
 copy back to the host anyway), after one warm-up call; median and minimum of --reps calls.  The numpy path is timed once.
 With --kernel-stats the tool instead reads a rocprofv3 --stats CSV of a run at ONE rate and reports the correlation
-kernel's time and fp64 rate: lag products x n x 2 FLOP (9 pairs x 512 lags + 3 energies per sample).
+kernel's time and fp64 rate: lag products x n x 2 FLOP (9 pairs x 512 lags + 5 energies per sample).
 """
 import argparse
 import csv
@@ -27,7 +27,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from svs_unet_pytorch_amd import evaluate as ev  # noqa: E402
 
-LAG_PRODUCTS = 9 * ev.FILTER_LEN + 3       # the pairs metrics_from_waveforms(device="gpu") asks of svs_bss_corr
+# the pairs metrics_from_waveforms(device="gpu") asks of svs_bss_corr_windows: the Gram and right-hand-side pairs of the
+# three solves and the energy of each of the five rows (a whole track is one window and asks what every window asks)
+LAG_PRODUCTS = 9 * ev.FILTER_LEN + 5
 
 
 def track(seconds, rate, seed=0):
