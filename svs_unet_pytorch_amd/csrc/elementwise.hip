@@ -2,7 +2,7 @@
 // apply (+ LeakyReLU/ReLU + Dropout2d), BatchNorm backward, the L1 mask loss, Adam, weight packing,
 // eval-mode BN folding, synthetic data.  All tensors are fp32 NHWC (pixel-major), read and written
 // as float4 by C/4 adjacent lanes per pixel.  Bound: HBM (each tensor once per pass).
-#include "internal.h"
+#include "unet_desc.h"
 
 // ------------------------------------------------------------------------------------------------
 // per-channel block reduction shared by bn_stats (sum x, sum x^2) and bn_bwd (sum dz, sum dz*xhat)
@@ -874,6 +874,7 @@ __global__ void dropout_masks_all_kernel(float* out, int B, uint32_t seed, int s
   const uint64_t off = ((uint64_t)layer << 56) | ((uint64_t)(rank & 0xFF) << 48) | ((uint64_t)(step & 0xFFFFFF) << 24);
   out[i] = (float)(svs_u32(seed, off + (uint64_t)(i - base)) >> 31) * 2.f;
 }
+static_assert(DROPOUT_CHANNELS == 496 && LAYERS[6].N == 256, "dropout_masks_all_kernel walks the outputs of deconv1..deconv5: 256, 128, .. 16 channels");
 extern "C" int svs_dropout_masks_all(float* out, int B, uint32_t seed, int step, int rank, hipStream_t stream) {
   SVS_REQUIRE(out && B > 0 && (long)B * 496 < (1L << 31), "svs_dropout_masks_all: bad arguments");
   const int n = B * 496;

@@ -16,7 +16,7 @@
 // 32 bytes of every 64.  Bound: HBM / launch at streaming batch sizes (bf16 MFMA peak ~2.5 PFLOP/s: 16x the fp32 rate).
 #include <type_traits>
 
-#include "internal.h"
+#include "unet_desc.h"
 
 typedef unsigned short u16;
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -992,23 +992,18 @@ static int conv_bf16_run(int mode, const u16* x, long ldx, int B, int H, int W, 
   return SVS_OK;
 }
 
-// ---- whole network ---------------------------------------------------------------------------------
-static const int BCH[7] = {1, 16, 32, 64, 128, 256, 512};
-static const int BDEC_C[6] = {512, 512, 256, 128, 64, 32};
-static const int BDEC_N[6] = {256, 128, 64, 32, 16, 1};
+// ---- whole network (described in unet_desc.h) ------------------------------------------------------
 struct Bf16Prepared { long w[12], shift[11], w1, w2k, w6, bias6, total; };          // byte offsets into the prepared blob
 static Bf16Prepared bf16_prepared_layout() {
   Bf16Prepared L{};
-  long off = 0;
-  auto take = [&](long bytes) { long o = off; off += (bytes + 255) / 256 * 256; return o; };
-  L.w1 = take(16 * 32 * 2);                                    // conv1: bf16 [16 n][32 taps (25 used)], scale folded
-  for (int k = 3; k <= 6; ++k) L.w[k - 1] = take((long)BCH[k] * BCH[k - 1] * 25 * 2);      // (conv2 has its own form: w2k)
-  for (int j = 0; j < 5; ++j) L.w[6 + j] = take((long)BDEC_C[j] * BDEC_N[j] * 25 * 2);
-  L.w2k = take(13 * 32 * 32 * 2);                              // conv2, window kernel: bf16 [13 steps][32 n][2 taps x 16 channels]
-  L.w6 = take(9 * 16 * 32 * 2);                                // deconv6: bf16 [9 positions][16 columns (4 parities used)][32 channels]
-  for (int l = 0; l < 11; ++l) L.shift[l] = take((l < 6 ? BCH[l + 1] : BDEC_N[l - 6]) * 4);
-  L.bias6 = take(4);
-  L.total = off;
+  Arena a{};
+  L.w1 = a.skip(16 * 32 * 2);                                  // conv1: bf16 [16 n][32 taps (25 used)], scale folded
+  for (int l = 2; l <= 10; ++l) L.w[l] = a.skip(param_numel(4 * l) * 2);    // conv3..deconv5 (conv2 has its own form: w2k)
+  L.w2k = a.skip(13 * 32 * 32 * 2);                            // conv2, window kernel: bf16 [13 steps][32 n][2 taps x 16 channels]
+  L.w6 = a.skip(9 * 16 * 32 * 2);                              // deconv6: bf16 [9 positions][16 columns (4 parities used)][32 channels]
+  for (int l = 0; l < 11; ++l) L.shift[l] = a.skip(bn_channels(l) * 4);
+  L.bias6 = a.skip(4);
+  L.total = a.used;
   return L;
 }
 extern "C" size_t svs_unet_prepared_bf16_bytes(void) { return (size_t)bf16_prepared_layout().total; }
@@ -1017,112 +1012,101 @@ extern "C" size_t svs_unet_prepared_bf16_bytes(void) { return (size_t)bf16_prepa
 extern "C" int svs_unet_prepare_eval_bf16(const void* prepared_f32, void* prepared_bf16, hipStream_t stream) {
   SVS_REQUIRE(prepared_f32 && prepared_bf16 && svs_aligned16(prepared_bf16), "svs_unet_prepare_eval_bf16: bad pointers");
   const Bf16Prepared L = bf16_prepared_layout();
+  const Prepared F = prepared_layout();
   char* out = (char*)prepared_bf16;
   const float* blob = (const float*)prepared_f32;
-  long wp[12], scale[11], shift[11], bias6;
-  svs_unet_prepared_offsets(wp, scale, shift, &bias6);
-  hipLaunchKernelGGL(conv1_pack_kernel, dim3(2), dim3(256), 0, stream, blob + wp[0], blob + scale[0], (u16*)(out + L.w1));
+  hipLaunchKernelGGL(conv1_pack_kernel, dim3(2), dim3(256), 0, stream, blob + F.wp[0], blob + F.scale[0], (u16*)(out + L.w1));
   SVS_CHECK_LAUNCH("conv1_pack");
-  for (int k = 3; k <= 6; ++k) {
-    const int N = BCH[k], C = BCH[k - 1];
-    hipLaunchKernelGGL(pack_bf16_kernel, dim3(512), dim3(256), 0, stream, blob + wp[k - 1], blob + scale[k - 1], (u16*)(out + L.w[k - 1]), N, C, C, 0);
+  for (int l = 2; l <= 10; ++l) {
+    const Layer& D = LAYERS[l];
+    hipLaunchKernelGGL(pack_bf16_kernel, dim3(512), dim3(256), 0, stream, blob + F.wp[l], blob + F.scale[l], (u16*)(out + L.w[l]), D.N, D.C, D.C, (int)D.up);
     SVS_CHECK_LAUNCH("pack_bf16");
   }
-  for (int j = 0; j < 5; ++j) {
-    hipLaunchKernelGGL(pack_bf16_kernel, dim3(512), dim3(256), 0, stream, blob + wp[6 + j], blob + scale[6 + j], (u16*)(out + L.w[6 + j]), BDEC_N[j],
-                       BDEC_C[j], BDEC_C[j], 1);
-    SVS_CHECK_LAUNCH("pack_bf16");
-  }
-  hipLaunchKernelGGL(conv2_pack_kernel, dim3(52), dim3(256), 0, stream, blob + wp[1], blob + scale[1], (u16*)(out + L.w2k));
+  hipLaunchKernelGGL(conv2_pack_kernel, dim3(52), dim3(256), 0, stream, blob + F.wp[1], blob + F.scale[1], (u16*)(out + L.w2k));
   SVS_CHECK_LAUNCH("conv2_pack");
-  hipLaunchKernelGGL(deconv6_pack_kernel, dim3(18), dim3(256), 0, stream, blob + wp[11], (u16*)(out + L.w6));
+  hipLaunchKernelGGL(deconv6_pack_kernel, dim3(18), dim3(256), 0, stream, blob + F.wp[11], (u16*)(out + L.w6));
   SVS_CHECK_LAUNCH("deconv6_pack");
-  SVS_HIP(hipMemcpyAsync(out + L.bias6, blob + bias6, 4, hipMemcpyDeviceToDevice, stream));
+  SVS_HIP(hipMemcpyAsync(out + L.bias6, blob + F.bias6, 4, hipMemcpyDeviceToDevice, stream));
   for (int l = 0; l < 11; ++l)
-    SVS_HIP(hipMemcpyAsync(out + L.shift[l], blob + shift[l], (l < 6 ? BCH[l + 1] : BDEC_N[l - 6]) * 4, hipMemcpyDeviceToDevice, stream));
+    SVS_HIP(hipMemcpyAsync(out + L.shift[l], blob + F.shift[l], bn_channels(l) * 4, hipMemcpyDeviceToDevice, stream));
   return SVS_OK;
 }
 
-struct Bf16Ws { u16* cat[6]; u16* c6; void* scratch; size_t scratch_bytes; size_t total; int h[7], w[7]; long P[7]; };
-static int bf16_ws_layout(int B, int H, int W, void* ws, Bf16Ws& e) {
-  SVS_REQUIRE(B > 0 && H > 0 && W > 0, "bad tile geometry B=%d H=%d W=%d", B, H, W);
-  e.h[0] = H; e.w[0] = W;
-  for (int k = 1; k <= 6; ++k) { e.h[k] = svs_conv_out(e.h[k - 1]); e.w[k] = svs_conv_out(e.w[k - 1]); }
-  for (int k = 0; k <= 6; ++k) e.P[k] = (long)B * e.h[k] * e.w[k];
-  size_t used = 0;
-  auto take = [&](size_t bytes) { void* p = ws ? (char*)ws + used : nullptr; used += svs_align_up(bytes, 256); return p; };
-  for (int k = 1; k <= 5; ++k) e.cat[k] = (u16*)take((size_t)e.P[k] * 2 * BCH[k] * 2);
-  e.c6 = (u16*)take((size_t)e.P[6] * 512 * 2);
-  size_t sb = 0;
-  for (int k = 3; k <= 6; ++k) { const size_t s = bf16_layer_ws(BF_GATHER, B, e.h[k - 1], e.w[k - 1], BCH[k - 1], e.h[k], e.w[k], BCH[k]); if (s > sb) sb = s; }
-  for (int j = 0; j < 5; ++j) { const size_t s = bf16_layer_ws(BF_PARITY, B, e.h[6 - j], e.w[6 - j], BDEC_C[j], e.h[5 - j], e.w[5 - j], BDEC_N[j]); if (s > sb) sb = s; }
-  e.scratch_bytes = sb;
-  e.scratch = take(sb + 256);
-  e.total = used;
-  return SVS_OK;
+struct Bf16Ws { u16* cat[6]; u16* c6; void* scratch; size_t scratch_bytes; size_t total; };
+static Bf16Ws bf16_ws_layout(const Geo& g, void* ws) {
+  Bf16Ws e{};
+  Arena a{(char*)ws, 0};
+  for (int k = 1; k <= 5; ++k) e.cat[k] = a.take<u16>((size_t)g.P[k] * 2 * CH[k]);
+  e.c6 = a.take<u16>((size_t)g.P[6] * CH[6]);
+  e.scratch_bytes = max_layer_bytes(2, 10, [&](const Layer& L) {            // conv3..deconv5: conv1 and conv2 have kernels of their own
+    return bf16_layer_ws(L.up ? BF_PARITY : BF_GATHER, g.B, g.h[L.lin], g.w[L.lin], L.C, g.h[L.lout], g.w[L.lout], L.N);
+  });
+  e.scratch = a.take<char>(e.scratch_bytes + 256);
+  e.total = a.used;
+  return e;
 }
 extern "C" size_t svs_unet_eval_bf16_workspace_bytes(int B, int H, int W) {
-  Bf16Ws e;
-  if (bf16_ws_layout(B, H, W, nullptr, e)) return 0;
-  return e.total;
+  Geo g;
+  if (make_geo(B, H, W, g)) return 0;
+  return bf16_ws_layout(g, nullptr).total;
 }
 
 extern "C" int svs_unet_forward_eval_bf16(const void* prepared_bf16, const float* mix, float* mask, int B, int H, int W, void* ws,
                                           size_t ws_bytes, hipStream_t stream) {
-  Bf16Ws e;
-  int rc = bf16_ws_layout(B, H, W, ws, e);
+  Geo g;
+  int rc = make_geo(B, H, W, g);
   if (rc) return rc;
   SVS_REQUIRE(prepared_bf16 && mix && mask && svs_aligned16(mix) && svs_aligned16(mask), "svs_unet_forward_eval_bf16: bad pointers");
   // conv1 / deconv6 address the input tiles and the two level-1 planes with 32-bit byte offsets (buffer loads)
-  SVS_REQUIRE(((long)B * H * W + 4L * W) * 4 < (1L << 31) && (e.P[1] * 32 + 4L * e.w[1] * 16) * 2 < (1L << 31),
+  SVS_REQUIRE(((long)B * H * W + 4L * W) * 4 < (1L << 31) && (g.P[1] * 32 + 4L * g.w[1] * 16) * 2 < (1L << 31),
               "svs_unet_forward_eval_bf16: %d tiles of %dx%d need 64-bit offsets; split the batch", B, H, W);
+  const Bf16Ws e = bf16_ws_layout(g, ws);
   if (!ws || ws_bytes < e.total || !svs_aligned16(ws)) { svs_set_error("svs_unet_forward_eval_bf16: workspace too small (%zu < %zu)", ws_bytes, e.total); return SVS_ERR_WORKSPACE; }
   const Bf16Prepared L = bf16_prepared_layout();
   const char* blob = (const char*)prepared_bf16;
   auto SH = [&](int l) { return (const float*)(blob + L.shift[l]); };
-  // encoder (model.py:176-181).  Levels 2..5 are one interleaved buffer [decoder half | skip half] each; conv_k writes the skip half
-  // of level k and reads the skip half of level k - 1.  Level 1 is PLANAR (decoder plane, then skip plane, 16 channels = 32 bytes per
-  // pixel each): interleaved, each producer wrote -- and conv2 read -- 32 bytes of every 64, i.e. half of every HBM burst
-  // (conv1 72 us for 170 MB at 216 tiles).  conv1 and conv2 have kernels of their own (1 and 16 input channels)
+  // encoder (model.py:176-181): conv_k writes the skip half of level k and reads the skip half of level k - 1 (cat_half: levels
+  // 2..5 interleaved, level 1 planar -- interleaved, each producer wrote, and conv2 read, 32 bytes of every 64, i.e. half of every
+  // HBM burst: conv1 72 us for 170 MB at 216 tiles).  conv1 and conv2 have kernels of their own (1 and 16 input channels)
+  const HalfView<u16> skip1 = cat_half(e.cat, g, 1, 1), skip2 = cat_half(e.cat, g, 2, 1);
   {
-    Conv1Args c{mix, B, H, W, (const u16*)(blob + L.w1), SH(0), 0.2f, e.cat[1] + e.P[1] * 16, 16L, e.h[1], e.w[1]};
-    const long tiles = (long)B * ((e.h[1] + 15) / 16) * ((e.w[1] + 31) / 32);
+    Conv1Args c{mix, B, H, W, (const u16*)(blob + L.w1), SH(0), 0.2f, skip1.p, skip1.ld, g.h[1], g.w[1]};
+    const long tiles = (long)B * ((g.h[1] + 15) / 16) * ((g.w[1] + 31) / 32);
     hipLaunchKernelGGL(conv1_mfma_bf16_kernel, dim3((unsigned)(tiles < 2048 ? tiles : 2048)), dim3(256), 0, stream, c);      // persistent: 8 blocks per CU
     SVS_CHECK_LAUNCH("conv1_mfma_bf16");
   }
   {
-    Conv2WinArgs c{e.cat[1] + e.P[1] * 16, 16L, B, e.h[1], e.w[1], (const u16*)(blob + L.w2k), SH(1), 0.2f, e.cat[2] + 32, 64L, e.h[2], e.w[2]};
-    const long tiles = (long)B * ((e.h[2] + 7) / 8) * ((e.w[2] + 15) / 16);
+    Conv2WinArgs c{skip1.p, skip1.ld, B, g.h[1], g.w[1], (const u16*)(blob + L.w2k), SH(1), 0.2f, skip2.p, skip2.ld, g.h[2], g.w[2]};
+    const long tiles = (long)B * ((g.h[2] + 7) / 8) * ((g.w[2] + 15) / 16);
     hipLaunchKernelGGL(conv2_window_bf16_kernel, dim3((unsigned)(tiles < 768 ? tiles : 768)), dim3(256), 0, stream, c);
     SVS_CHECK_LAUNCH("conv2_window_bf16");
   }
   for (int k = 3; k <= 6; ++k) {
-    const u16* x = e.cat[k - 1] + BCH[k - 1];
-    const long ldx = 2L * BCH[k - 1];
-    u16* y = k == 6 ? e.c6 : e.cat[k] + BCH[k];
-    const long ldy = k == 6 ? 512 : 2L * BCH[k];
+    const HalfView<u16> xi = cat_half(e.cat, g, k - 1, 1);
+    const HalfView<u16> yo = k == 6 ? HalfView<u16>{e.c6, CH[6]} : cat_half(e.cat, g, k, 1);
     if (k == 3) {                                                       // LDS-window form
-      Conv3WinArgs c{x, ldx, B, e.h[2], e.w[2], (const u16*)(blob + L.w[2]), SH(2), 0.2f, y, ldy, e.h[3], e.w[3]};
-      const long tiles = (long)B * ((e.h[3] + 7) / 8) * ((e.w[3] + 15) / 16);
+      Conv3WinArgs c{xi.p, xi.ld, B, g.h[2], g.w[2], (const u16*)(blob + L.w[2]), SH(2), 0.2f, yo.p, yo.ld, g.h[3], g.w[3]};
+      const long tiles = (long)B * ((g.h[3] + 7) / 8) * ((g.w[3] + 15) / 16);
       SVS_HIP(hipFuncSetAttribute((const void*)conv3_window_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CONV3_WIN_LDS));
       hipLaunchKernelGGL(conv3_window_bf16_kernel, dim3((unsigned)(tiles < 256 ? tiles : 256)), dim3(256), CONV3_WIN_LDS, stream, c);
       SVS_CHECK_LAUNCH("conv3_window_bf16");
       continue;
     }
-    if ((rc = conv_bf16_run(BF_GATHER, x, ldx, B, e.h[k - 1], e.w[k - 1], BCH[k - 1], (const u16*)(blob + L.w[k - 1]), SH(k - 1), 0.2f, y, ldy, e.h[k], e.w[k],
-                            BCH[k], e.scratch, e.scratch_bytes, stream))) return rc;
+    if ((rc = conv_bf16_run(BF_GATHER, xi.p, xi.ld, B, g.h[k - 1], g.w[k - 1], CH[k - 1], (const u16*)(blob + L.w[k - 1]), SH(k - 1), 0.2f, yo.p, yo.ld,
+                            g.h[k], g.w[k], CH[k], e.scratch, e.scratch_bytes, stream))) return rc;
   }
   // decoder (model.py:183-196); Dropout2d is the identity in eval
-  for (int j = 0; j < 5; ++j) {
-    const int lin = 6 - j, lout = 5 - j;
-    const u16* x = j == 0 ? e.c6 : e.cat[lin];
-    if ((rc = conv_bf16_run(BF_PARITY, x, BDEC_C[j], B, e.h[lin], e.w[lin], BDEC_C[j], (const u16*)(blob + L.w[6 + j]), SH(6 + j), 0.f, e.cat[lout],
-                            lout == 1 ? 16L : 2L * BCH[lout], e.h[lout], e.w[lout], BDEC_N[j], e.scratch, e.scratch_bytes, stream))) return rc;
+  for (int l = 6; l <= 10; ++l) {
+    const Layer& D = LAYERS[l];
+    const u16* x = l == 6 ? e.c6 : e.cat[D.lin];
+    const HalfView<u16> yo = cat_half(e.cat, g, D.lout, 0);
+    if ((rc = conv_bf16_run(BF_PARITY, x, D.C, B, g.h[D.lin], g.w[D.lin], D.C, (const u16*)(blob + L.w[l]), SH(l), 0.f, yo.p, yo.ld,
+                            g.h[D.lout], g.w[D.lout], D.N, e.scratch, e.scratch_bytes, stream))) return rc;
   }
   // deconv6 + sigmoid (model.py:198-200)
   {
-    Deconv6Args d{e.cat[1], 16L, B, e.h[1], e.w[1], (const u16*)(blob + L.w6), (const float*)(blob + L.bias6), mask, H, W, e.P[1] * 16};
-    const long tiles = (long)B * ((e.h[1] + 7) / 8) * ((e.w[1] + 15) / 16);
+    Deconv6Args d{e.cat[1], (long)CH[1], B, g.h[1], g.w[1], (const u16*)(blob + L.w6), (const float*)(blob + L.bias6), mask, H, W, level1_plane(g)};
+    const long tiles = (long)B * ((g.h[1] + 7) / 8) * ((g.w[1] + 15) / 16);
     hipLaunchKernelGGL(deconv6_mfma_bf16_kernel, dim3((unsigned)(tiles < 2048 ? tiles : 2048)), dim3(256), 0, stream, d);
     SVS_CHECK_LAUNCH("deconv6_mfma_bf16");
   }

@@ -12,13 +12,14 @@
 // Training additionally keeps the pre-BatchNorm ("raw") output of every block, the batch statistics,
 // both weight packings, and gradient images dcat[k] / dc6 of the same shapes.
 #include <math.h>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "internal.h"
+#include "unet_desc.h"
 
 // ---------------------------------------------------------------------------------------------
 // error string
@@ -155,31 +156,18 @@ extern "C" int svs_describe_plan(int kind, int B, int H, int W, int C, int Ho, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// network description
+// network description (unet_desc.h) as the C ABI shows it
 // ---------------------------------------------------------------------------------------------
-static const int CH[7] = {1, 16, 32, 64, 128, 256, 512};                 // model.py:47-76
-static const int DEC_C[6] = {512, 512, 256, 128, 64, 32};                // model.py:79-109 (in)
-static const int DEC_N[6] = {256, 128, 64, 32, 16, 1};                   //                 (out)
 #define BN_EPS 1e-5f
 #define BN_MOMENTUM 0.1f
 #define LEAKY 0.2f
 
-// parameter tensor index: enc k (1..6): 4*(k-1) + {0 w, 1 b, 2 gamma, 3 beta}; dec j (1..6): 24 + 4*(j-1) + {...}
-static long param_numel(int idx) {
-  if (idx < 24) {
-    const int k = idx / 4 + 1, f = idx % 4;
-    return f == 0 ? (long)CH[k] * CH[k - 1] * 25 : CH[k];
-  }
-  const int j = (idx - 24) / 4, f = (idx - 24) % 4;
-  return f == 0 ? (long)DEC_C[j] * DEC_N[j] * 25 : DEC_N[j];
-}
 extern "C" int64_t svs_unet_param_offset(int tensor_index) {
   if (tensor_index < 0 || tensor_index > SVS_UNET_NUM_PARAMS) return -1;
   long off = 0;
   for (int i = 0; i < tensor_index; ++i) off += param_numel(i);
   return off;
 }
-static int bn_channels(int bn) { return bn < 6 ? CH[bn + 1] : DEC_N[bn - 6]; }
 extern "C" int64_t svs_unet_buffer_offset(int bn_index, int which) {
   if (bn_index < 0 || bn_index > SVS_UNET_NUM_BN) return -1;
   long off = 0;
@@ -205,59 +193,23 @@ static ParamView view_params(const float* params) {
   return v;
 }
 
-struct Geo { int B; int h[7], w[7]; long P[7]; };
-static int make_geo(int B, int H, int W, Geo& g) {
-  SVS_REQUIRE(B > 0 && H > 0 && W > 0, "bad tile geometry B=%d H=%d W=%d", B, H, W);
-  g.B = B; g.h[0] = H; g.w[0] = W;
-  for (int k = 1; k <= 6; ++k) { g.h[k] = svs_conv_out(g.h[k - 1]); g.w[k] = svs_conv_out(g.w[k - 1]); }
-  for (int k = 0; k <= 6; ++k) g.P[k] = (long)B * g.h[k] * g.w[k];
-  return SVS_OK;
-}
+typedef HalfView<float> View;
 
-// One channel half of the level-k concat buffer (which: 0 = decoder output, 1 = encoder/skip output).
-// Levels 2..5 interleave the halves inside a pixel (ld = 2*ch, a half is >= 128 B so accesses are whole lines).
-// Level 1 has 16-channel halves (64 B): interleaved, every access of a half would touch half a 128-byte line and
-// drag the other half through the caches, so level 1 is PLANAR -- two dense (P, 16) planes back to back; the three
-// kernels that need all 32 channels of a pixel (deconv6 forward / weight gradient / data gradient) take the plane
-// distance as `half` (special.hip: chan_off).
-struct View { float* p; long ld; };
-static View cat_half(float* const* cat, const Geo& g, int k, int which) {
-  if (k == 1) return View{cat[1] + (long)which * g.P[1] * 16, 16};
-  return View{cat[k] + (long)which * CH[k], 2L * CH[k]};
+// workspace of the forward GEMM of a layer, and of the GEMMs that carry gradients back through it
+static size_t fwd_ws(const Geo& g, const Layer& L) {
+  return svs_conv_gemm_workspace(L.up ? SVS_MODE_PARITY : SVS_MODE_GATHER, g.B, g.h[L.lin], g.w[L.lin], L.C, g.h[L.lout], g.w[L.lout], L.N);
 }
-
-// bump allocator over the caller's workspace (every block 256-byte aligned)
-struct Arena {
-  char* base; size_t used;
-  float* take(size_t nfloats) {
-    float* p = base ? (float*)(base + used) : nullptr;
-    used += svs_align_up(nfloats * sizeof(float), 256);
-    return p;
-  }
-};
+static size_t bwd_data_ws(const Geo& g, const Layer& L) {
+  return svs_conv_gemm_workspace(L.up ? SVS_MODE_GATHER : SVS_MODE_PARITY, g.B, g.h[L.lout], g.w[L.lout], L.N, g.h[L.lin], g.w[L.lin], L.C);
+}
+static size_t bwd_weight_ws(const Geo& g, const Layer& L) {      // (strided image and its channels, channels of the windowed image)
+  return L.up ? svs_block_bwd_weight_workspace_bytes(g.B, g.h[L.lin], g.w[L.lin], L.C, L.N)
+              : svs_block_bwd_weight_workspace_bytes(g.B, g.h[L.lout], g.w[L.lout], L.N, L.C);
+}
 
 // ---------------------------------------------------------------------------------------------
 // eval
 // ---------------------------------------------------------------------------------------------
-struct Prepared {      // offsets in floats into the prepared blob
-  long wp[12], scale[11], shift[11], bias6, total;
-};
-static Prepared prepared_layout() {
-  Prepared p{};
-  long off = 0;
-  auto take = [&](long n) { long o = off; off += (n + 63) / 64 * 64; return o; };
-  for (int l = 0; l < 12; ++l) p.wp[l] = take(param_numel(4 * l));
-  for (int l = 0; l < 11; ++l) { p.scale[l] = take(bn_channels(l)); p.shift[l] = take(bn_channels(l)); }
-  p.bias6 = take(1);
-  p.total = off;
-  return p;
-}
-void svs_unet_prepared_offsets(long wp[12], long scale[11], long shift[11], long* bias6) {
-  const Prepared L = prepared_layout();
-  for (int l = 0; l < 12; ++l) wp[l] = L.wp[l];
-  for (int l = 0; l < 11; ++l) { scale[l] = L.scale[l]; shift[l] = L.shift[l]; }
-  *bias6 = L.bias6;
-}
 extern "C" size_t svs_unet_prepared_bytes(void) { return (size_t)prepared_layout().total * sizeof(float); }
 
 extern "C" int svs_unet_prepare_eval(const float* params, const float* bn_buffers, void* prepared, hipStream_t stream) {
@@ -270,8 +222,7 @@ extern "C" int svs_unet_prepare_eval(const float* params, const float* bn_buffer
   SVS_HIP(hipMemcpyAsync(blob + L.wp[0], v.w[0], param_numel(0) * sizeof(float), hipMemcpyDeviceToDevice, stream));
   {
     SvsPackJobs jobs{};
-    for (int k = 2; k <= 6; ++k) jobs.j[jobs.n++] = SvsPackJob{v.w[k - 1], blob + L.wp[k - 1], CH[k], CH[k - 1], 0, 0};
-    for (int j = 0; j < 5; ++j) jobs.j[jobs.n++] = SvsPackJob{v.w[6 + j], blob + L.wp[6 + j], DEC_N[j], DEC_C[j], 1, 0};
+    for (int l = 1; l <= 10; ++l) jobs.j[jobs.n++] = SvsPackJob{v.w[l], blob + L.wp[l], LAYERS[l].N, LAYERS[l].C, LAYERS[l].up, 0};
     if ((rc = svs_pack_all_run(jobs, stream))) return rc;
   }
   SVS_HIP(hipMemcpyAsync(blob + L.wp[11], v.w[11], param_numel(44) * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -288,19 +239,11 @@ struct EvalWs { float* cat[6]; float* c6; float* scratch; size_t scratch_bytes; 
 static EvalWs eval_layout(const Geo& g, void* ws) {
   EvalWs e{};
   Arena a{(char*)ws, 0};
-  for (int k = 1; k <= 5; ++k) e.cat[k] = a.take((size_t)g.P[k] * 2 * CH[k]);
-  e.c6 = a.take((size_t)g.P[6] * 512);
-  size_t sb = 0;
-  for (int k = 2; k <= 6; ++k) {
-    size_t s = svs_conv_gemm_workspace(SVS_MODE_GATHER, g.B, g.h[k - 1], g.w[k - 1], CH[k - 1], g.h[k], g.w[k], CH[k]);
-    if (s > sb) sb = s;
-  }
-  for (int j = 0; j < 5; ++j) {
-    size_t s = svs_conv_gemm_workspace(SVS_MODE_PARITY, g.B, g.h[6 - j], g.w[6 - j], DEC_C[j], g.h[5 - j], g.w[5 - j], DEC_N[j]);
-    if (s > sb) sb = s;
-  }
+  for (int k = 1; k <= 5; ++k) e.cat[k] = a.take<float>((size_t)g.P[k] * 2 * CH[k]);
+  e.c6 = a.take<float>((size_t)g.P[6] * CH[6]);
+  const size_t sb = max_layer_bytes(1, 10, [&](const Layer& L) { return fwd_ws(g, L); });
   e.scratch_bytes = sb;
-  e.scratch = a.take(sb / sizeof(float) + 64);
+  e.scratch = a.take<float>(sb / sizeof(float) + 64);
   e.total = a.used;
   return e;
 }
@@ -323,26 +266,23 @@ extern "C" int svs_unet_forward_eval(const void* prepared, const float* mix, flo
   // encoder (model.py:176-181): BN folded, LeakyReLU(0.2) in the epilogue
   for (int k = 1; k <= 6; ++k) {
     const View xi = (k == 1) ? View{const_cast<float*>(mix), 1} : cat_half(e.cat, g, k - 1, 1);
-    const View yo = (k == 6) ? View{e.c6, 512} : cat_half(e.cat, g, k, 1);
-    const float* x = xi.p; const long ldx = xi.ld;
-    float* y = yo.p; const long ldy = yo.ld;
-    rc = svs_enc_block_fwd(x, ldx, B, g.h[k - 1], g.w[k - 1], CH[k - 1], blob + L.wp[k - 1], nullptr,
-                           blob + L.scale[k - 1], blob + L.shift[k - 1], LEAKY, y, ldy, CH[k], 0, e.scratch, e.scratch_bytes, stream);
+    const View yo = (k == 6) ? View{e.c6, CH[6]} : cat_half(e.cat, g, k, 1);
+    rc = svs_enc_block_fwd(xi.p, xi.ld, B, g.h[k - 1], g.w[k - 1], CH[k - 1], blob + L.wp[k - 1], nullptr,
+                           blob + L.scale[k - 1], blob + L.shift[k - 1], LEAKY, yo.p, yo.ld, CH[k], 0, e.scratch, e.scratch_bytes, stream);
     if (rc) return rc;
   }
   // decoder (model.py:183-196): BN folded, ReLU; Dropout2d is the identity in eval
-  for (int j = 0; j < 5; ++j) {
-    const int lin = 6 - j, lout = 5 - j;
-    const float* x = (j == 0) ? e.c6 : e.cat[lin];
-    const View yo = cat_half(e.cat, g, lout, 0);
-    rc = svs_dec_block_fwd(x, DEC_C[j], B, g.h[lin], g.w[lin], DEC_C[j], blob + L.wp[6 + j], nullptr, blob + L.scale[6 + j],
-                           blob + L.shift[6 + j], 0.f, yo.p, yo.ld, g.h[lout], g.w[lout], DEC_N[j], 0,
-                           e.scratch, e.scratch_bytes, stream);
+  for (int l = 6; l <= 10; ++l) {
+    const Layer& D = LAYERS[l];
+    const float* x = (l == 6) ? e.c6 : e.cat[D.lin];
+    const View yo = cat_half(e.cat, g, D.lout, 0);
+    rc = svs_dec_block_fwd(x, D.C, B, g.h[D.lin], g.w[D.lin], D.C, blob + L.wp[l], nullptr, blob + L.scale[l], blob + L.shift[l], 0.f,
+                           yo.p, yo.ld, g.h[D.lout], g.w[D.lout], D.N, 0, e.scratch, e.scratch_bytes, stream);
     if (rc) return rc;
   }
   // deconv6 + sigmoid (model.py:198-200)
-  return svs_deconv_to1_run(e.cat[1], 16, B, g.h[1], g.w[1], 32, blob + L.wp[11], blob + L.bias6, mask, H, W, 1, stream,
-                            "svs_unet_forward_eval", g.P[1] * 16);
+  return svs_deconv_to1_run(e.cat[1], CH[1], B, g.h[1], g.w[1], LAYERS[11].C, blob + L.wp[11], blob + L.bias6, mask, H, W, 1, stream,
+                            "svs_unet_forward_eval", level1_plane(g));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -350,7 +290,7 @@ extern "C" int svs_unet_forward_eval(const void* prepared, const float* mix, flo
 // ---------------------------------------------------------------------------------------------
 struct TrainWs {
   float* cat[6]; float* c6;
-  float* raw_e[7]; float* raw_d[5];
+  float* raw[11];                         // pre-BatchNorm output of layer l (conv1..conv6, deconv1..deconv5)
   float* mean[11]; float* invstd[11];
   float* wfwd[12]; float* wbwd[12];       // packed weights (null where torch's layout is read directly)
   float* dcat[6]; float* dc6;
@@ -359,64 +299,40 @@ struct TrainWs {
   float* bnws; size_t bnws_bytes;
   float* dbias_part[11];                  // per-layer partial sums of d_raw (bias gradients), reduced in one batched pass
   float* scratch; size_t scratch_bytes;
-  float* scratch2; size_t scratch2_bytes;     // split-K slabs of the weight-gradient GEMMs (side stream)
+  float* scratch2; size_t scratch2_bytes;
   size_t total;
 };
 #define SVS_FUSED_STATS_ROWS 512          // rows of BatchNorm partials the split-K epilogue may write into bnws
 static TrainWs train_layout(const Geo& g, void* ws) {
   TrainWs t{};
   Arena a{(char*)ws, 0};
-  const int B = g.B;
-  for (int k = 1; k <= 5; ++k) t.cat[k] = a.take((size_t)g.P[k] * 2 * CH[k]);
-  t.c6 = a.take((size_t)g.P[6] * 512);
-  for (int k = 1; k <= 6; ++k) t.raw_e[k] = a.take((size_t)g.P[k] * CH[k]);
-  for (int j = 0; j < 5; ++j) t.raw_d[j] = a.take((size_t)g.P[5 - j] * DEC_N[j]);
-  for (int l = 0; l < 11; ++l) { t.mean[l] = a.take(bn_channels(l)); t.invstd[l] = a.take(bn_channels(l)); }
-  for (int k = 2; k <= 6; ++k) { t.wfwd[k - 1] = a.take(param_numel(4 * (k - 1))); t.wbwd[k - 1] = a.take(param_numel(4 * (k - 1))); }
-  for (int j = 0; j < 5; ++j) { t.wfwd[6 + j] = a.take(param_numel(24 + 4 * j)); t.wbwd[6 + j] = a.take(param_numel(24 + 4 * j)); }
-  for (int k = 1; k <= 5; ++k) t.dcat[k] = a.take((size_t)g.P[k] * 2 * CH[k]);
-  t.dc6 = a.take((size_t)g.P[6] * 512);
+  auto take = [&](size_t nfloats) { return a.take<float>(nfloats); };
+  for (int k = 1; k <= 5; ++k) t.cat[k] = take((size_t)g.P[k] * 2 * CH[k]);
+  t.c6 = take((size_t)g.P[6] * CH[6]);
+  for (int l = 0; l < 11; ++l) t.raw[l] = take((size_t)g.P[bn_level(l)] * bn_channels(l));
+  for (int l = 0; l < 11; ++l) { t.mean[l] = take(bn_channels(l)); t.invstd[l] = take(bn_channels(l)); }
+  for (int l = 1; l <= 10; ++l) { t.wfwd[l] = take(param_numel(4 * l)); t.wbwd[l] = take(param_numel(4 * l)); }
+  for (int k = 1; k <= 5; ++k) t.dcat[k] = take((size_t)g.P[k] * 2 * CH[k]);
+  t.dc6 = take((size_t)g.P[6] * CH[6]);
   size_t dmax = 0;
   for (int k = 1; k <= 6; ++k) if ((size_t)g.P[k] * CH[k] > dmax) dmax = (size_t)g.P[k] * CH[k];
-  t.d_raw = a.take(dmax);
-  for (int l = 0; l < 11; ++l) {
-    const int lvl = (l < 6) ? l + 1 : 5 - (l - 6);
-    t.d_raw_l[l] = a.take((size_t)g.P[lvl] * bn_channels(l));
-  }
-  t.d_logit = a.take((size_t)g.P[0]);
-  t.mask = a.take((size_t)g.P[0]);
+  t.d_raw = take(dmax);
+  for (int l = 0; l < 11; ++l) t.d_raw_l[l] = take((size_t)g.P[bn_level(l)] * bn_channels(l));
+  t.d_logit = take((size_t)g.P[0]);
+  t.mask = take((size_t)g.P[0]);
   size_t bb = 0;
   for (int k = 1; k <= 6; ++k) { size_t s = svs_bn_workspace_bytes(g.P[k], CH[k]); if (s > bb) bb = s; }
-  if (bb < (size_t)SVS_FUSED_STATS_ROWS * 2 * 512 * sizeof(float)) bb = (size_t)SVS_FUSED_STATS_ROWS * 2 * 512 * sizeof(float);
+  if (bb < (size_t)SVS_FUSED_STATS_ROWS * 2 * CH[6] * sizeof(float)) bb = (size_t)SVS_FUSED_STATS_ROWS * 2 * CH[6] * sizeof(float);
   t.bnws_bytes = bb + 4096;
-  t.bnws = a.take(t.bnws_bytes / sizeof(float));
-  for (int l = 0; l < 11; ++l) {
-    const int lvl = (l < 6) ? l + 1 : 5 - (l - 6);
-    t.dbias_part[l] = a.take(svs_bn_partial_floats(g.P[lvl], bn_channels(l)));
-  }
-  size_t sb = 4096;
-  auto upd = [&](size_t s) { if (s > sb) sb = s; };
-  for (int k = 2; k <= 6; ++k) {
-    upd(svs_conv_gemm_workspace(SVS_MODE_GATHER, B, g.h[k - 1], g.w[k - 1], CH[k - 1], g.h[k], g.w[k], CH[k]));
-    upd(svs_conv_gemm_workspace(SVS_MODE_PARITY, B, g.h[k], g.w[k], CH[k], g.h[k - 1], g.w[k - 1], CH[k - 1]));   // bwd data
-    upd(svs_block_bwd_weight_workspace_bytes(B, g.h[k], g.w[k], CH[k], CH[k - 1]));
-  }
-  upd(svs_block_bwd_weight_workspace_bytes(B, g.h[1], g.w[1], 16, 1));
-  for (int j = 0; j < 6; ++j) {
-    const int lin = 6 - j, lout = 5 - j;
-    if (j < 5) {
-      upd(svs_conv_gemm_workspace(SVS_MODE_PARITY, B, g.h[lin], g.w[lin], DEC_C[j], g.h[lout], g.w[lout], DEC_N[j]));
-      upd(svs_conv_gemm_workspace(SVS_MODE_GATHER, B, g.h[lout], g.w[lout], DEC_N[j], g.h[lin], g.w[lin], DEC_C[j]));  // bwd data
-    }
-    upd(svs_block_bwd_weight_workspace_bytes(B, g.h[lin], g.w[lin], DEC_C[j], DEC_N[j]));
-  }
-  t.scratch_bytes = sb;
-  t.scratch = a.take(sb / sizeof(float) + 64);
-  size_t sb2 = svs_block_bwd_weight_workspace_bytes(B, g.h[1], g.w[1], 16, 1);
-  for (int k = 2; k <= 6; ++k) { const size_t s2 = svs_block_bwd_weight_workspace_bytes(B, g.h[k], g.w[k], CH[k], CH[k - 1]); if (s2 > sb2) sb2 = s2; }
-  for (int j = 0; j < 6; ++j) { const size_t s2 = svs_block_bwd_weight_workspace_bytes(B, g.h[6 - j], g.w[6 - j], DEC_C[j], DEC_N[j]); if (s2 > sb2) sb2 = s2; }
-  t.scratch2_bytes = sb2;
-  t.scratch2 = a.take(sb2 / sizeof(float) + 64);
+  t.bnws = take(t.bnws_bytes / sizeof(float));
+  for (int l = 0; l < 11; ++l) t.dbias_part[l] = take(svs_bn_partial_floats(g.P[bn_level(l)], bn_channels(l)));
+  // scratch2: the weight-gradient GEMMs of all twelve layers (side stream); scratch: the forward and backward-data GEMMs of
+  // conv2..deconv5, and the weight gradients when there is no side stream
+  t.scratch2_bytes = max_layer_bytes(0, 11, [&](const Layer& L) { return bwd_weight_ws(g, L); });
+  t.scratch_bytes = std::max({(size_t)4096, t.scratch2_bytes,
+                              max_layer_bytes(1, 10, [&](const Layer& L) { return std::max(fwd_ws(g, L), bwd_data_ws(g, L)); })});
+  t.scratch = take(t.scratch_bytes / sizeof(float) + 64);
+  t.scratch2 = take(t.scratch2_bytes / sizeof(float) + 64);
   t.total = a.used;
   return t;
 }
@@ -461,34 +377,73 @@ extern "C" size_t svs_unet_train_workspace_bytes(int B, int H, int W) {
   return train_layout(g, nullptr).total;
 }
 
+// names of svs_unet_ws_offset: stem<first> .. stem<first + count - 1> are p[0 .. count - 1]; count 0 is the bare stem, *p
+struct WsName { const char* stem; int first, count; float* const* p; };
+static int64_t ws_find(const WsName* tab, size_t n, const char* name, const char* base) {
+  for (size_t i = 0; i < n; ++i) {
+    const size_t len = strlen(tab[i].stem);
+    if (strncmp(name, tab[i].stem, len)) continue;
+    if (!tab[i].count) {
+      if (!name[len]) return (const char*)*tab[i].p - base;
+      continue;
+    }
+    char* end;
+    const long idx = strtol(name + len, &end, 10) - tab[i].first;
+    if (end != name + len && !*end && idx >= 0 && idx < tab[i].count) return (const char*)tab[i].p[idx] - base;
+  }
+  return -1;
+}
 extern "C" int64_t svs_unet_ws_offset(const char* name, int B, int H, int W, int training) {
   Geo g;
   if (!name || make_geo(B, H, W, g)) return -1;
   char* const base = (char*)256;   // non-null dummy so the arena hands out addresses
-  auto rel = [&](const float* p) { return p ? (int64_t)((const char*)p - base) : (int64_t)-1; };
-  int idx = 0;
   if (training) {
     const TrainWs t = train_layout(g, base);
-    if (sscanf(name, "cat%d", &idx) == 1 && idx >= 1 && idx <= 5 && name[0] == 'c') return rel(t.cat[idx]);
-    if (!strcmp(name, "c6")) return rel(t.c6);
-    if (sscanf(name, "raw_e%d", &idx) == 1 && idx >= 1 && idx <= 6) return rel(t.raw_e[idx]);
-    if (sscanf(name, "raw_d%d", &idx) == 1 && idx >= 1 && idx <= 5) return rel(t.raw_d[idx - 1]);
-    if (sscanf(name, "dcat%d", &idx) == 1 && idx >= 1 && idx <= 5) return rel(t.dcat[idx]);
-    if (!strcmp(name, "dc6")) return rel(t.dc6);
-    if (!strcmp(name, "d_logit")) return rel(t.d_logit);
-    if (!strcmp(name, "mask")) return rel(t.mask);
-    if (sscanf(name, "mean%d", &idx) == 1 && idx >= 0 && idx < 11) return rel(t.mean[idx]);
-    if (sscanf(name, "invstd%d", &idx) == 1 && idx >= 0 && idx < 11) return rel(t.invstd[idx]);
-    return -1;
+    const WsName tab[] = {{"cat", 1, 5, t.cat + 1}, {"c6", 0, 0, &t.c6},         {"raw_e", 1, 6, t.raw},  {"raw_d", 1, 5, t.raw + 6},
+                          {"dcat", 1, 5, t.dcat + 1}, {"dc6", 0, 0, &t.dc6},     {"d_logit", 0, 0, &t.d_logit}, {"mask", 0, 0, &t.mask},
+                          {"mean", 0, 11, t.mean},  {"invstd", 0, 11, t.invstd}};
+    return ws_find(tab, sizeof(tab) / sizeof(tab[0]), name, base);
   }
   const EvalWs e = eval_layout(g, base);
-  if (sscanf(name, "cat%d", &idx) == 1 && idx >= 1 && idx <= 5) return rel(e.cat[idx]);
-  if (!strcmp(name, "c6")) return rel(e.c6);
-  return -1;
+  const WsName tab[] = {{"cat", 1, 5, e.cat + 1}, {"c6", 0, 0, &e.c6}};
+  return ws_find(tab, sizeof(tab) / sizeof(tab[0]), name, base);
 }
 
-static int train_forward_impl(const ParamView& v, float* bn_buffers, int64_t* nbt, const float* mix, const float* drop,
-                              const Geo& g, const TrainWs& t, float* mask, hipStream_t stream) {
+// everything a training entry point derives from its arguments
+struct TrainCall { Geo g; TrainWs t; ParamView v; };
+static int train_prologue(const char* who, const float* params, int B, int H, int W, void* ws, size_t ws_bytes, TrainCall& c) {
+  const int rc = make_geo(B, H, W, c.g);
+  if (rc) return rc;
+  c.t = train_layout(c.g, ws);
+  if (!ws || ws_bytes < c.t.total || !svs_aligned16(ws)) {
+    svs_set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, c.t.total);
+    return SVS_ERR_WORKSPACE;
+  }
+  c.v = view_params(params);
+  return SVS_OK;
+}
+
+// The tail of a training block: batch statistics of raw[l] unless the GEMM's epilogue left them in bnws (stat_rows > 0),
+// then finalise (running statistics included) + BatchNorm + activation (+ Dropout2d) -> y
+static int train_bn_act(const TrainCall& c, int l, int stat_rows, float* bn_buffers, int64_t* nbt, float slope, const float* drop,
+                        View y, hipStream_t stream) {
+  const TrainWs& t = c.t;
+  const int N = bn_channels(l), lvl = bn_level(l);
+  const long P = c.g.P[lvl];
+  if (!stat_rows) {
+    const int rc = svs_bn_stats(t.raw[l], N, P, N, t.bnws, t.bnws_bytes, stream);
+    if (rc) return rc;
+    stat_rows = svs_bn_partial_rows(P, N);
+  }
+  return svs_bn_fin_act_apply_run(t.bnws, stat_rows, t.raw[l], N, P, N, (long)c.g.h[lvl] * c.g.w[lvl], c.v.gamma[l], c.v.beta[l], BN_EPS,
+                                  BN_MOMENTUM, bn_buffers ? bn_buffers + svs_unet_buffer_offset(l, 0) : nullptr,
+                                  bn_buffers ? bn_buffers + svs_unet_buffer_offset(l, 1) : nullptr,
+                                  nbt ? (long long*)(nbt + l) : nullptr, t.mean[l], t.invstd[l], slope, drop, y.p, y.ld, stream);
+}
+
+static int train_forward_impl(const TrainCall& c, float* bn_buffers, int64_t* nbt, const float* mix, const float* drop, float* mask,
+                              hipStream_t stream) {
+  const Geo& g = c.g; const TrainWs& t = c.t; const ParamView& v = c.v;
   const int B = g.B;
   int rc;
   const int fused_rows = svs_tune_flag(SVS_TUNE_TRAIN_UNFUSED) ? 0 : (int)(t.bnws_bytes / sizeof(float));     // capacity (floats) for fused BatchNorm partials; A/B switch
@@ -498,14 +453,12 @@ static int train_forward_impl(const ParamView& v, float* bn_buffers, int64_t* nb
   // weight packings for this step (weights change every optimiser step)
   {
     SvsPackJobs jobs{};
-    auto add = [&](const float* w, float* wp, int N, int C, int kind) { jobs.j[jobs.n++] = SvsPackJob{w, wp, N, C, kind, 0}; };
-    for (int k = 2; k <= 6; ++k) {
-      add(v.w[k - 1], t.wfwd[k - 1], CH[k], CH[k - 1], 0);          // conv forward: gather packing
-      add(v.w[k - 1], t.wbwd[k - 1], CH[k - 1], CH[k], 1);          // conv bwd-data: (N,C,..) read as (in=N,out=C): one row per C
-    }
-    for (int j = 0; j < 5; ++j) {
-      add(v.w[6 + j], t.wfwd[6 + j], DEC_N[j], DEC_C[j], 1);        // convT forward: parity packing, one row per output channel
-      add(v.w[6 + j], t.wbwd[6 + j], DEC_C[j], DEC_N[j], 0);        // convT bwd-data: (C,N,..) read as (n=C,c=N)
+    for (int l = 1; l <= 10; ++l) {
+      const Layer& L = LAYERS[l];
+      // forward: gather packing for a conv, parity packing (one row per output channel) for a convT; backward-data: the
+      // other packing of the same tensor with the channel roles swapped ((N,C,..) read as (in=N,out=C) and the reverse)
+      jobs.j[jobs.n++] = SvsPackJob{v.w[l], t.wfwd[l], L.N, L.C, L.up, 0};
+      jobs.j[jobs.n++] = SvsPackJob{v.w[l], t.wbwd[l], L.C, L.N, !L.up, 0};
     }
     // conv1 reads torch's layout directly, so the packing runs beside it on the side stream (joined before conv2)
     if (sd) {
@@ -518,58 +471,40 @@ static int train_forward_impl(const ParamView& v, float* bn_buffers, int64_t* nb
   // encoder: conv (+bias) -> raw; batch stats; BN + LeakyReLU -> second half of cat[k]
   for (int k = 1; k <= 6; ++k) {
     if (k == 2 && sd) SVS_HIP(hipStreamWaitEvent(stream, sd->done[0], 0));
+    const int l = k - 1;
     const View xi = (k == 1) ? View{const_cast<float*>(mix), 1} : cat_half(t.cat, g, k - 1, 1);
-    const float* x = xi.p; const long ldx = xi.ld;
-    const float* wp = (k == 1) ? v.w[0] : t.wfwd[k - 1];
     int stat_rows = 0;                       // > 0: the split-K epilogue already left the BatchNorm partials in bnws
-    if (k == 1) rc = svs_enc_block_fwd(x, ldx, B, g.h[0], g.w[0], 1, wp, v.b[0], nullptr, nullptr, 0.f, t.raw_e[1], CH[1], CH[1], 0,
+    if (k == 1) rc = svs_enc_block_fwd(xi.p, xi.ld, B, g.h[0], g.w[0], 1, v.w[0], v.b[0], nullptr, nullptr, 0.f, t.raw[0], CH[1], CH[1], 0,
                                        t.scratch, t.scratch_bytes, stream);
-    else rc = svs_conv_gemm_run(SVS_MODE_GATHER, x, ldx, B, g.h[k - 1], g.w[k - 1], CH[k - 1], wp, v.b[k - 1], nullptr, nullptr, 0.f,
-                                t.raw_e[k], CH[k], g.h[k], g.w[k], CH[k], 0, t.scratch, t.scratch_bytes, stream, "conv forward",
+    else rc = svs_conv_gemm_run(SVS_MODE_GATHER, xi.p, xi.ld, B, g.h[k - 1], g.w[k - 1], CH[k - 1], t.wfwd[l], v.b[l], nullptr, nullptr, 0.f,
+                                t.raw[l], CH[k], g.h[k], g.w[k], CH[k], 0, t.scratch, t.scratch_bytes, stream, "conv forward",
                                 t.bnws, fused_rows, &stat_rows);
     if (rc) return rc;
-    const int l = k - 1;
-    if (!stat_rows) {
-      if ((rc = svs_bn_stats(t.raw_e[k], CH[k], g.P[k], CH[k], t.bnws, t.bnws_bytes, stream))) return rc;
-      stat_rows = svs_bn_partial_rows(g.P[k], CH[k]);
-    }
-    const View yo = (k == 6) ? View{t.c6, 512} : cat_half(t.cat, g, k, 1);
-    float* y = yo.p; const long ldy = yo.ld;
-    if ((rc = svs_bn_fin_act_apply_run(t.bnws, stat_rows, t.raw_e[k], CH[k], g.P[k], CH[k], (long)g.h[k] * g.w[k], v.gamma[l], v.beta[l],
-                                       BN_EPS, BN_MOMENTUM, bn_buffers ? bn_buffers + svs_unet_buffer_offset(l, 0) : nullptr,
-                                       bn_buffers ? bn_buffers + svs_unet_buffer_offset(l, 1) : nullptr,
-                                       nbt ? (long long*)(nbt + l) : nullptr, t.mean[l], t.invstd[l], LEAKY, nullptr, y, ldy, stream))) return rc;
+    const View yo = (k == 6) ? View{t.c6, CH[6]} : cat_half(t.cat, g, k, 1);
+    if ((rc = train_bn_act(c, l, stat_rows, bn_buffers, nbt, LEAKY, nullptr, yo, stream))) return rc;
   }
   // decoder: convT (+bias) -> raw; batch stats; BN + ReLU + Dropout2d -> first half of cat[lout]
   const float* dp = drop;
-  for (int j = 0; j < 5; ++j) {
-    const int lin = 6 - j, lout = 5 - j, l = 6 + j;
-    const float* x = (j == 0) ? t.c6 : t.cat[lin];
+  for (int l = 6; l <= 10; ++l) {
+    const Layer& D = LAYERS[l];
+    const float* x = (l == 6) ? t.c6 : t.cat[D.lin];
     int stat_rows = 0;
-    rc = svs_conv_gemm_run(SVS_MODE_PARITY, x, DEC_C[j], B, g.h[lin], g.w[lin], DEC_C[j], t.wfwd[l], v.b[l], nullptr, nullptr, 0.f,
-                           t.raw_d[j], DEC_N[j], g.h[lout], g.w[lout], DEC_N[j], 0, t.scratch, t.scratch_bytes, stream,
+    rc = svs_conv_gemm_run(SVS_MODE_PARITY, x, D.C, B, g.h[D.lin], g.w[D.lin], D.C, t.wfwd[l], v.b[l], nullptr, nullptr, 0.f,
+                           t.raw[l], D.N, g.h[D.lout], g.w[D.lout], D.N, 0, t.scratch, t.scratch_bytes, stream,
                            "deconv forward", t.bnws, fused_rows, &stat_rows);
     if (rc) return rc;
-    if (!stat_rows) {
-      if ((rc = svs_bn_stats(t.raw_d[j], DEC_N[j], g.P[lout], DEC_N[j], t.bnws, t.bnws_bytes, stream))) return rc;
-      stat_rows = svs_bn_partial_rows(g.P[lout], DEC_N[j]);
-    }
-    const View yo = cat_half(t.cat, g, lout, 0);
-    if ((rc = svs_bn_fin_act_apply_run(t.bnws, stat_rows, t.raw_d[j], DEC_N[j], g.P[lout], DEC_N[j], (long)g.h[lout] * g.w[lout], v.gamma[l],
-                                       v.beta[l], BN_EPS, BN_MOMENTUM, bn_buffers ? bn_buffers + svs_unet_buffer_offset(l, 0) : nullptr,
-                                       bn_buffers ? bn_buffers + svs_unet_buffer_offset(l, 1) : nullptr,
-                                       nbt ? (long long*)(nbt + l) : nullptr, t.mean[l], t.invstd[l], 0.f, dp, yo.p, yo.ld, stream))) return rc;
-    if (dp) dp += (long)B * DEC_N[j];
+    if ((rc = train_bn_act(c, l, stat_rows, bn_buffers, nbt, 0.f, dp, cat_half(t.cat, g, D.lout, 0), stream))) return rc;
+    if (dp) dp += (long)B * D.N;
   }
-  return svs_deconv_to1_run(t.cat[1], 16, B, g.h[1], g.w[1], 32, v.w[11], v.b[11], mask, g.h[0], g.w[0], 1, stream,
-                            "svs_unet_train_forward", g.P[1] * 16);
+  return svs_deconv_to1_run(t.cat[1], CH[1], B, g.h[1], g.w[1], LAYERS[11].C, v.w[11], v.b[11], mask, g.h[0], g.w[0], 1, stream,
+                            "svs_unet_train_forward", level1_plane(g));
 }
 
 // parts: bit 0 = decoder half (deconv6..deconv1: gradients of parameter tensors 24..45, produced FIRST),
 //        bit 1 = encoder half (conv6..conv1: tensors 0..23).  A data-parallel caller runs them as two calls and
 //        all-reduces the decoder half of the flat gradient buffer while the encoder half is still being computed.
-static int train_backward_impl(const ParamView& v, float* grads, const float* mix, const float* drop, const Geo& g,
-                               const TrainWs& t, hipStream_t stream, int parts = 15) {
+static int train_backward_impl(const TrainCall& c, float* grads, const float* mix, const float* drop, hipStream_t stream, int parts = 15) {
+  const Geo& g = c.g; const TrainWs& t = c.t; const ParamView& v = c.v;
   const int B = g.B;
   int rc;
   auto G = [&](int idx) { return grads + svs_unet_param_offset(idx); };
@@ -605,31 +540,31 @@ static int train_backward_impl(const ParamView& v, float* grads, const float* mi
   };
   if (parts & 1) {
   // deconv6 (model.py:109,198): dw, db, dx -> dcat[1]
-  const long half1 = g.P[1] * 16;     // level 1 is planar (cat_half)
+  const long half1 = level1_plane(g);
   if ((rc = fork())) return rc;
-  if ((rc = svs_wgrad_c1_run(t.cat[1], 16, B, g.h[1], g.w[1], 32, t.d_logit, g.h[0], g.w[0], G(44), wscratch, wscratch_bytes, wstream,
+  if ((rc = svs_wgrad_c1_run(t.cat[1], CH[1], B, g.h[1], g.w[1], LAYERS[11].C, t.d_logit, g.h[0], g.w[0], G(44), wscratch, wscratch_bytes, wstream,
                              "deconv6 bwd_weight", half1))) return rc;
   if ((rc = svs_sum_run(t.d_logit, g.P[0], G(45), wscratch, wscratch_bytes, wstream))) return rc;      // deconv6 bias gradient
   if ((rc = forked())) return rc;
-  if ((rc = svs_conv_c1_run(t.d_logit, B, g.h[0], g.w[0], v.w[11], nullptr, nullptr, nullptr, 0.f, t.dcat[1], 16, 32, 0, stream,
+  if ((rc = svs_conv_c1_run(t.d_logit, B, g.h[0], g.w[0], v.w[11], nullptr, nullptr, nullptr, 0.f, t.dcat[1], CH[1], LAYERS[11].C, 0, stream,
                             "deconv6 bwd_data", half1))) return rc;
   // decoders 5..1
-  long drop_off[5];
-  { long o = 0; for (int j = 0; j < 5; ++j) { drop_off[j] = o; o += (long)B * DEC_N[j]; } }
-  for (int j = 4; j >= 0; --j) {
-    const int lin = 6 - j, lout = 5 - j, l = 6 + j, N = DEC_N[j], C = DEC_C[j];
-    const float* x = (j == 0) ? t.c6 : t.cat[lin];
+  long drop_off[11];                         // start of layer l's Dropout2d mask in `drop`
+  { long o = 0; for (int l = 6; l <= 10; ++l) { drop_off[l] = o; o += (long)B * LAYERS[l].N; } }
+  for (int l = 10; l >= 6; --l) {
+    const int lin = LAYERS[l].lin, lout = LAYERS[l].lout, N = LAYERS[l].N, C = LAYERS[l].C;
+    const float* x = (l == 6) ? t.c6 : t.cat[lin];
     const View dyv = cat_half(t.dcat, g, lout, 0);
     float* const d_raw = layer_draw(l);
-    rc = svs_bn_bwd_run(dyv.p, dyv.ld, t.raw_d[j], N, g.P[lout], N, (long)g.h[lout] * g.w[lout], v.gamma[l], v.beta[l],
-                        t.mean[l], t.invstd[l], 0.f, drop ? drop + drop_off[j] : nullptr, d_raw, G(24 + 4 * j + 2), G(24 + 4 * j + 3),
-                        G(24 + 4 * j + 1), t.bnws, t.bnws_bytes, stream, unfused ? nullptr : t.dbias_part[l], &sums);   // + bias gradient (sum of d_raw)
+    rc = svs_bn_bwd_run(dyv.p, dyv.ld, t.raw[l], N, g.P[lout], N, (long)g.h[lout] * g.w[lout], v.gamma[l], v.beta[l],
+                        t.mean[l], t.invstd[l], 0.f, drop ? drop + drop_off[l] : nullptr, d_raw, G(4 * l + 2), G(4 * l + 3),
+                        G(4 * l + 1), t.bnws, t.bnws_bytes, stream, unfused ? nullptr : t.dbias_part[l], &sums);   // + bias gradient (sum of d_raw)
     if (rc) return rc;
     if ((rc = fork())) return rc;
-    if ((rc = svs_dec_block_bwd_weight(x, C, B, g.h[lin], g.w[lin], C, d_raw, N, g.h[lout], g.w[lout], N, G(24 + 4 * j), nullptr,
+    if ((rc = svs_dec_block_bwd_weight(x, C, B, g.h[lin], g.w[lin], C, d_raw, N, g.h[lout], g.w[lout], N, G(4 * l), nullptr,
                                        wscratch, wscratch_bytes, wstream))) return rc;
     if ((rc = forked())) return rc;
-    float* dx = (j == 0) ? t.dc6 : t.dcat[lin];
+    float* dx = (l == 6) ? t.dc6 : t.dcat[lin];
     if ((rc = svs_dec_block_bwd_data(d_raw, N, B, g.h[lout], g.w[lout], N, t.wbwd[l], dx, C, g.h[lin], g.w[lin], C, 0,
                                      t.scratch, t.scratch_bytes, stream))) return rc;
   }
@@ -642,10 +577,9 @@ static int train_backward_impl(const ParamView& v, float* grads, const float* mi
   for (int k = 6; k >= 1; --k) {
     if (!(parts & (k == 6 ? 2 : k >= 4 ? 4 : 8))) continue;
     const int l = k - 1, N = CH[k], C = CH[k - 1];
-    const View dyv = (k == 6) ? View{t.dc6, 512} : cat_half(t.dcat, g, k, 1);
-    const float* dy = dyv.p; const long lddy = dyv.ld;
+    const View dyv = (k == 6) ? View{t.dc6, CH[6]} : cat_half(t.dcat, g, k, 1);
     float* const d_raw = layer_draw(l);
-    rc = svs_bn_bwd_run(dy, lddy, t.raw_e[k], N, g.P[k], N, (long)g.h[k] * g.w[k], v.gamma[l], v.beta[l], t.mean[l], t.invstd[l],
+    rc = svs_bn_bwd_run(dyv.p, dyv.ld, t.raw[l], N, g.P[k], N, (long)g.h[k] * g.w[k], v.gamma[l], v.beta[l], t.mean[l], t.invstd[l],
                         LEAKY, nullptr, d_raw, G(4 * l + 2), G(4 * l + 3), G(4 * l + 1), t.bnws, t.bnws_bytes, stream,
                         unfused ? nullptr : t.dbias_part[l], &sums);
     if (rc) return rc;
@@ -684,53 +618,47 @@ extern "C" int svs_unet_train_bwd_sync(hipStream_t consumer) {
   return SVS_OK;
 }
 
-static int check_train_ws(const char* who, const Geo& g, void* ws, size_t ws_bytes, TrainWs& t) {
-  t = train_layout(g, ws);
-  if (!ws || ws_bytes < t.total || !svs_aligned16(ws)) {
-    svs_set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, t.total);
-    return SVS_ERR_WORKSPACE;
-  }
-  return SVS_OK;
-}
-
 extern "C" int svs_unet_train_forward(const float* params, float* bn_buffers, int64_t* num_batches_tracked, const float* mix,
                                       const float* drop, int B, int H, int W, float* mask, void* ws, size_t ws_bytes,
                                       hipStream_t stream) {
-  Geo g; TrainWs t;
-  int rc = make_geo(B, H, W, g);
-  if (rc) return rc;
   SVS_REQUIRE(params && mix && mask && svs_aligned16(params) && svs_aligned16(mix) && svs_aligned16(mask), "svs_unet_train_forward: bad pointers");
-  if ((rc = check_train_ws("svs_unet_train_forward", g, ws, ws_bytes, t))) return rc;
-  return train_forward_impl(view_params(params), bn_buffers, num_batches_tracked, mix, drop, g, t, mask, stream);
+  TrainCall c;
+  const int rc = train_prologue("svs_unet_train_forward", params, B, H, W, ws, ws_bytes, c);
+  if (rc) return rc;
+  return train_forward_impl(c, bn_buffers, num_batches_tracked, mix, drop, mask, stream);
 }
 
 extern "C" int svs_unet_train_backward(const float* params, float* grads, const float* mix, const float* mask,
                                        const float* d_mask, const float* drop, int B, int H, int W, void* ws,
                                        size_t ws_bytes, hipStream_t stream) {
-  Geo g; TrainWs t;
-  int rc = make_geo(B, H, W, g);
-  if (rc) return rc;
   SVS_REQUIRE(params && grads && mix && mask && d_mask && svs_aligned16(grads), "svs_unet_train_backward: bad pointers");
-  if ((rc = check_train_ws("svs_unet_train_backward", g, ws, ws_bytes, t))) return rc;
-  if ((rc = svs_sigmoid_bwd_run(mask, d_mask, g.P[0], t.d_logit, stream))) return rc;
-  return train_backward_impl(view_params(params), grads, mix, drop, g, t, stream);
+  TrainCall c;
+  int rc = train_prologue("svs_unet_train_backward", params, B, H, W, ws, ws_bytes, c);
+  if (rc) return rc;
+  if ((rc = svs_sigmoid_bwd_run(mask, d_mask, c.g.P[0], c.t.d_logit, stream))) return rc;
+  return train_backward_impl(c, grads, mix, drop, stream);
+}
+
+// forward + L1 mask loss (scaled by loss_scale) + d(loss)/d(logit) -> d_logit; the mask goes to the workspace when the caller keeps none
+static int train_fwd_loss_impl(const TrainCall& c, float* bn_buffers, int64_t* nbt, const float* mix, const float* voc, const float* drop,
+                               float loss_scale, float* mask, float* loss, hipStream_t stream) {
+  float* m = mask ? mask : c.t.mask;
+  const int rc = train_forward_impl(c, bn_buffers, nbt, mix, drop, m, stream);
+  if (rc) return rc;
+  return svs_l1_mask_loss_fwd_bwd(m, mix, voc, c.g.P[0], loss_scale, c.t.d_logit, loss, c.t.bnws, c.t.bnws_bytes, stream);
 }
 
 extern "C" int svs_unet_train_fwd_bwd(const float* params, float* grads, float* bn_buffers, int64_t* num_batches_tracked,
                                       const float* mix, const float* voc, const float* drop, int B, int H, int W,
                                       float loss_scale, float* mask, float* loss, void* ws, size_t ws_bytes,
                                       hipStream_t stream) {
-  Geo g; TrainWs t;
-  int rc = make_geo(B, H, W, g);
-  if (rc) return rc;
   SVS_REQUIRE(params && grads && mix && voc && loss && svs_aligned16(params) && svs_aligned16(grads) && svs_aligned16(mix),
               "svs_unet_train_fwd_bwd: bad pointers");
-  if ((rc = check_train_ws("svs_unet_train_fwd_bwd", g, ws, ws_bytes, t))) return rc;
-  float* m = mask ? mask : t.mask;
-  const ParamView v = view_params(params);
-  if ((rc = train_forward_impl(v, bn_buffers, num_batches_tracked, mix, drop, g, t, m, stream))) return rc;
-  if ((rc = svs_l1_mask_loss_fwd_bwd(m, mix, voc, g.P[0], loss_scale, t.d_logit, loss, t.bnws, t.bnws_bytes, stream))) return rc;
-  return train_backward_impl(v, grads, mix, drop, g, t, stream);
+  TrainCall c;
+  int rc = train_prologue("svs_unet_train_fwd_bwd", params, B, H, W, ws, ws_bytes, c);
+  if (rc) return rc;
+  if ((rc = train_fwd_loss_impl(c, bn_buffers, num_batches_tracked, mix, voc, drop, loss_scale, mask, loss, stream))) return rc;
+  return train_backward_impl(c, grads, mix, drop, stream);
 }
 
 // Split form of svs_unet_train_fwd_bwd for gradient-exchange overlap: forward + loss, then the backward in
@@ -738,14 +666,11 @@ extern "C" int svs_unet_train_fwd_bwd(const float* params, float* grads, float* 
 extern "C" int svs_unet_train_fwd_loss(const float* params, float* bn_buffers, int64_t* num_batches_tracked, const float* mix,
                                        const float* voc, const float* drop, int B, int H, int W, float loss_scale, float* mask,
                                        float* loss, void* ws, size_t ws_bytes, hipStream_t stream) {
-  Geo g; TrainWs t;
-  int rc = make_geo(B, H, W, g);
-  if (rc) return rc;
   SVS_REQUIRE(params && mix && voc && loss && svs_aligned16(params) && svs_aligned16(mix), "svs_unet_train_fwd_loss: bad pointers");
-  if ((rc = check_train_ws("svs_unet_train_fwd_loss", g, ws, ws_bytes, t))) return rc;
-  float* m = mask ? mask : t.mask;
-  if ((rc = train_forward_impl(view_params(params), bn_buffers, num_batches_tracked, mix, drop, g, t, m, stream))) return rc;
-  return svs_l1_mask_loss_fwd_bwd(m, mix, voc, g.P[0], loss_scale, t.d_logit, loss, t.bnws, t.bnws_bytes, stream);
+  TrainCall c;
+  const int rc = train_prologue("svs_unet_train_fwd_loss", params, B, H, W, ws, ws_bytes, c);
+  if (rc) return rc;
+  return train_fwd_loss_impl(c, bn_buffers, num_batches_tracked, mix, voc, drop, loss_scale, mask, loss, stream);
 }
 
 // The reference's full objective (train.py:274-296): alpha_L1 * (L1 vocal + L1 accompaniment) + alpha_MR * MR-STFT(
@@ -758,11 +683,11 @@ static MrTrainWs mr_train_layout(int B, int W, int hop, void* ws) {
   MrTrainWs m{};
   Arena a{(char*)ws, 0};
   const size_t L = (size_t)hop * (W - 1);
-  m.wav_pred = a.take((size_t)B * L);
-  m.wav_tgt = a.take((size_t)B * L);
-  m.d_wav = a.take((size_t)B * L);
+  m.wav_pred = a.take<float>((size_t)B * L);
+  m.wav_tgt = a.take<float>((size_t)B * L);
+  m.d_wav = a.take<float>((size_t)B * L);
   m.mr_bytes = svs_mrstft_workspace_bytes(B, (int64_t)L);
-  m.mr = a.take(m.mr_bytes / sizeof(float) + 64);
+  m.mr = a.take<float>(m.mr_bytes / sizeof(float) + 64);
   m.total = a.used;
   return m;
 }
@@ -774,19 +699,17 @@ extern "C" int svs_unet_train_fwd_loss_mr(const float* params, float* bn_buffers
                                           const float* voc, const float* mix_phase, const float* voc_phase, const float* drop,
                                           int B, int H, int W, int hop, float alpha_l1, float alpha_mr, float* mask, float* losses,
                                           void* ws, size_t ws_bytes, void* mr_ws, size_t mr_ws_bytes, hipStream_t stream) {
-  Geo g; TrainWs t;
-  int rc = make_geo(B, H, W, g);
-  if (rc) return rc;
   SVS_REQUIRE(params && mix && voc && mix_phase && voc_phase && losses && svs_aligned16(params) && svs_aligned16(mix),
               "svs_unet_train_fwd_loss_mr: bad pointers");
   SVS_REQUIRE(H == 512 && W >= 2 && hop >= 512 && hop <= 1024, "svs_unet_train_fwd_loss_mr: needs H = 512 (n_fft 1024) and 512 <= hop <= 1024");
-  if ((rc = check_train_ws("svs_unet_train_fwd_loss_mr", g, ws, ws_bytes, t))) return rc;
+  TrainCall c;
+  int rc = train_prologue("svs_unet_train_fwd_loss_mr", params, B, H, W, ws, ws_bytes, c);
+  if (rc) return rc;
   const MrTrainWs m = mr_train_layout(B, W, hop, mr_ws);
   if (!mr_ws || mr_ws_bytes < m.total || !svs_aligned16(mr_ws)) { svs_set_error("svs_unet_train_fwd_loss_mr: MR workspace too small (%zu < %zu)", mr_ws_bytes, m.total); return SVS_ERR_WORKSPACE; }
-  float* mk = mask ? mask : t.mask;
-  if ((rc = train_forward_impl(view_params(params), bn_buffers, num_batches_tracked, mix, drop, g, t, mk, stream))) return rc;
   // d_logit = alpha_l1 * d(L1)/d(logit)                                                   (train.py:281-283,296)
-  if ((rc = svs_l1_mask_loss_fwd_bwd(mk, mix, voc, g.P[0], alpha_l1, t.d_logit, losses, t.bnws, t.bnws_bytes, stream))) return rc;
+  if ((rc = train_fwd_loss_impl(c, bn_buffers, num_batches_tracked, mix, voc, drop, alpha_l1, mask, losses, stream))) return rc;
+  const float* mk = mask ? mask : c.t.mask;
   // waveforms: predicted magnitude (mask * mix, fused into the inverse's load) with the MIXTURE phase, target with its own
   const int64_t cs = (int64_t)H * W;
   const long L = (long)hop * (W - 1);
@@ -794,17 +717,16 @@ extern "C" int svs_unet_train_fwd_loss_mr(const float* params, float* bn_buffers
   if ((rc = svs_istft_tiles(voc, cs, W, H, 1, nullptr, 0, voc_phase, 3, B, 2 * H, hop, W, m.wav_tgt, nullptr, stream))) return rc; // train.py:291
   if ((rc = svs_mrstft_loss_fwd_bwd(m.wav_pred, m.wav_tgt, B, L, alpha_mr, losses + 1, m.d_wav, m.mr, m.mr_bytes, stream))) return rc;  // train.py:293
   // d_logit += d(alpha_mr * MR)/d(wav) through the inverse STFT and |S| = mask * mix
-  return svs_istft_bwd_mask(m.d_wav, mix_phase, mix, mk, t.d_logit, 1.0f, B, 2 * H, hop, W, stream);
+  return svs_istft_bwd_mask(m.d_wav, mix_phase, mix, mk, c.t.d_logit, 1.0f, B, 2 * H, hop, W, stream);
 }
 
 extern "C" int svs_unet_train_bwd_part(const float* params, float* grads, const float* mix, const float* drop, int B, int H, int W,
                                        int part, void* ws, size_t ws_bytes, hipStream_t stream) {
-  Geo g; TrainWs t;
-  int rc = make_geo(B, H, W, g);
-  if (rc) return rc;
   SVS_REQUIRE(params && grads && mix && part >= 0 && part <= 6, "svs_unet_train_bwd_part: bad arguments");
-  if ((rc = check_train_ws("svs_unet_train_bwd_part", g, ws, ws_bytes, t))) return rc;
+  TrainCall c;
+  const int rc = train_prologue("svs_unet_train_bwd_part", params, B, H, W, ws, ws_bytes, c);
+  if (rc) return rc;
   // decoder | whole encoder | conv6 block | conv5..conv1 blocks | everything | conv5 + conv4 blocks | conv3..conv1 blocks
   static const int bits[7] = {1, 2 | 4 | 8, 2, 4 | 8, 15, 4, 8};
-  return train_backward_impl(view_params(params), grads, mix, drop, g, t, stream, bits[part]);
+  return train_backward_impl(c, grads, mix, drop, stream, bits[part]);
 }

@@ -28,6 +28,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, lib, ptr
+from .synth import DEC_IO, ENC_CHANNELS          # the channel tables live with the state_dict spec
 
 
 def _on_model_device(fn):
@@ -45,8 +46,6 @@ def _on_model_device(fn):
             return fn(self, *a, **k)
     return wrapped
 
-ENC_CHANNELS = (1, 16, 32, 64, 128, 256, 512)                                   # model.py:47-76
-DEC_IO = ((512, 256), (512, 128), (256, 64), (128, 32), (64, 16), (32, 1))      # model.py:79-109
 ALPHA_L1 = 166.66                                                                # train.py:24
 ALPHA_MR = 0.66                                                                  # train.py:25
 

@@ -12,7 +12,7 @@ import torch
 from oracle import unet_oracle as uo
 from svs_unet_pytorch_amd import _lib, synth
 from svs_unet_pytorch_amd.inference import segment_plan, separate
-from svs_unet_pytorch_amd.model import DEC_IO, UNet
+from svs_unet_pytorch_amd.model import DEC_IO, ENC_CHANNELS, UNet
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -55,7 +55,6 @@ def test_eval_forward_golden(golden, report):
     hw = [(512, 128)]
     for _ in range(6):
         hw.append(((hw[-1][0] + 1) // 2, (hw[-1][1] + 1) // 2))
-    ch = (1, 16, 32, 64, 128, 256, 512)
     for k in range(1, 7):
         h, w = hw[k]
         if k == 6:
@@ -63,7 +62,7 @@ def test_eval_forward_golden(golden, report):
         elif k == 1:        # level 1 is planar: [decoder plane | skip plane], each (B, h, w, 16)
             t = ws_view(model, "eval", "cat1", B, H, W, (2, B, h, w, 16))[1]
         else:
-            t = ws_view(model, "eval", f"cat{k}", B, H, W, (B, h, w, 2 * ch[k]))[..., ch[k]:]
+            t = ws_view(model, "eval", f"cat{k}", B, H, W, (B, h, w, 2 * ENC_CHANNELS[k]))[..., ENC_CHANNELS[k]:]
         nchw = t.permute(0, 3, 1, 2).contiguous().cpu()
         key = f"tap.conv{k}.out"
         assert tuple(g[key + ".shape"]) == tuple(nchw.shape)

@@ -15,8 +15,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from svs_unet_pytorch_amd import _lib  # noqa: E402
+from svs_unet_pytorch_amd.synth import ENC_CHANNELS as CH  # noqa: E402
 
-CH = (1, 16, 32, 64, 128, 256, 512)
 DEC = ((512, 256), (512, 128), (256, 64), (128, 32), (64, 16))
 CFG = {0: (128, 128), 1: (128, 64), 2: (256, 32), 3: (256, 16), 4: (32, 128), 5: (64, 64), 6: (64, 128)}
 

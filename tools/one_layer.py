@@ -11,8 +11,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from svs_unet_pytorch_amd import _lib  # noqa: E402
+from svs_unet_pytorch_amd.synth import ENC_CHANNELS as CH  # noqa: E402
 
-CH = (1, 16, 32, 64, 128, 256, 512)
 DEC = ((512, 256), (512, 128), (256, 64), (128, 32), (64, 16))
 
 
