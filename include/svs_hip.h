@@ -45,23 +45,24 @@ extern "C" {
 
 int svs_version(void);
 const char* svs_last_error_string(void);
-/* Planner overrides for sweeps, A/B runs and tests -- never needed in production.  `name` is one of CONV_CFG,
- * CONV_KSPLIT, CONV_WINDOW, CONV_SKIP, CONV_KORDER, CONV_DIRECT, SKIP_REDUCE, WGRAD_CFG, WGRAD_KSPLIT, WGRAD_SKIP,
- * WGRAD_WINDOW, WGRAD_C1_VALU, SIDE_PRIORITY, TRAIN_UNFUSED, TRAIN_ONE_STREAM, CONV_PLAN (0: batch-64 tile table for the
- * inference calls too), MFMA_SPLIT (1: the fp32 GEMM kernels form their products on the bf16 MFMA from exact three-limb
- * splits of the fp32 operands -- fp32-accurate, see csrc/mfma_split.h; default off), CONV_BALANCE (0: one K-split count per
- * layer instead of per-position counts on the tap-skipping layers), CONV_C1_TILED (0: the thread-per-pixel form of the
- * single-channel convolution), BF16_KB (K-tiles per barrier of the bf16 GEMM: 1, 2 or 4), BF16_CFG / BF16_KSPLIT (its tile / K-split),
- * CONV_PF / WGRAD_PF (K-tiles the fp32 conv / weight-gradient GEMMs request ahead: 1 or 2; CONV_PF 3: on every tile shape),
- * CONV_GWINDOW (0: conv2 forward on the GEMM kernel instead of the LDS-window kernel; 2: the window kernel whenever the layer is
- * eligible; >= 16: that many blocks), BF16_CONV3_WINDOW / BF16_DECONV3_WINDOW (0: conv3 / deconv3 of the bf16 network in the GEMM form),
- * BN_INLINE (most partial rows a BatchNorm apply kernel folds itself instead of waiting for a finalise launch; 0: never;
- * default 128), BN_BLOCKS (blocks of the BatchNorm reduce / apply kernels, <= 1024; default 512),
- * or "*" for all; value -1 = planner
- * default ("*", -1: every switch back to what the environment gave at load).  The boolean switches (SKIP_REDUCE,
- * WGRAD_C1_VALU, TRAIN_UNFUSED, TRAIN_ONE_STREAM, MFMA_SPLIT) are ON for values > 0 only -- 0 and -1 both mean off; the
- * others are valued (0 is a value).  The table is initialised from the environment (SVS_<NAME>) at first use; no compute
- * path reads the environment; entries are atomics (a setter may run beside compute threads). */
+/* Planner overrides for sweeps, A/B runs and tests -- never needed in production.  `name` is one of
+ *   CONV_CFG / CONV_KSPLIT (tile / K-split of the fp32 conv GEMM), CONV_WINDOW (0: the GEMM form of the layers that have an
+ *   LDS-window kernel, in the fp32 and the bf16 network; 2 / 3: the fp32 parity window kernel whenever the layer is eligible),
+ *   CONV_SKIP (tap skipping of the fp32 conv GEMM, 0: never, 2: wherever the tile allows), SKIP_REDUCE (the split-K reduction
+ *   is left out, so that bench.py can time a GEMM kernel alone), WGRAD_CFG / WGRAD_KSPLIT / WGRAD_SKIP / WGRAD_WINDOW (the
+ *   same for the weight-gradient GEMM and its window kernel), TRAIN_UNFUSED (one launch per BatchNorm reduction),
+ *   TRAIN_ONE_STREAM (weight gradients on the caller's stream), MFMA_SPLIT (1: the fp32 GEMM kernels form their products on
+ *   the bf16 MFMA from exact three-limb splits of the fp32 operands -- fp32-accurate, see csrc/mfma_split.h; default off),
+ *   CONV_C1_TILED (0: the thread-per-pixel form of the single-channel convolution, 2: the tiled form always),
+ *   BF16_CFG / BF16_KSPLIT (tile -- 0: 128x128, 1: 128x64, 4: 64x128 -- and K-split of the bf16 GEMM), BN_INLINE (most partial
+ *   rows a BatchNorm apply kernel folds itself instead of waiting for a finalise launch; 0: never; default 128),
+ *   CONV_GWINDOW (0: conv2 forward on the GEMM kernel instead of the LDS-window kernel; 2: the window kernel whenever the
+ *   layer is eligible; >= 16: that many blocks),
+ * or "*" for all; value -1 = planner default ("*", -1: every switch back to what the environment gave at load).  Any other
+ * name is refused.  The boolean switches (SKIP_REDUCE, TRAIN_UNFUSED, TRAIN_ONE_STREAM, MFMA_SPLIT) are ON for values > 0
+ * only -- 0 and -1 both mean off; the others are valued (0 is a value).  The table is initialised from the environment
+ * (SVS_<NAME>) at first use; no compute path reads the environment; entries are atomics (a setter may run beside compute
+ * threads). */
 int svs_tuning_set(const char* name, long value);
 
 /* ---------------------------------------------------------------------------------------------
@@ -157,8 +158,10 @@ int svs_dec_block_bwd_weight(const float* x, int64_t ldx, int B, int H, int W, i
 
 /* Which kernel (name as rocprofv3 prints it) and K-split the planner uses for a block call of the given geometry:
  * kind 0 = gather GEMM (svs_enc_block_fwd / svs_dec_block_bwd_data), 1 = parity GEMM (svs_dec_block_fwd /
- * svs_enc_block_bwd_data), 2 = weight gradient (H,W,C: the strided image, N: channels of the windowed image).
- * Lets bench.py attribute its live HIP-event timings to the kernels of the rocprofv3 summary. */
+ * svs_enc_block_bwd_data), 2 = weight gradient (H,W,C: the strided image, N: channels of the windowed image), 3 / 4 = a gather
+ * (conv4..conv6) / parity (deconv1..deconv5) layer of the bf16 eval network (svs_unet_forward_eval_bf16): conv_gemm_bf16_kernel
+ * with its tile, or the parity_window_bf16_kernel instantiation; <0 for channel counts no bf16 layer has.  Host arithmetic
+ * only: no GPU is touched.  Lets bench.py attribute its live HIP-event timings to the kernels of the rocprofv3 summary. */
 int svs_describe_plan(int kind, int B, int H, int W, int C, int Ho, int Wo, int N, char* buf, size_t buflen);
 
 /* ---------------------------------------------------------------------------------------------
@@ -263,12 +266,21 @@ int svs_unet_train_fwd_loss_mr(const float* params, float* bn_buffers, int64_t* 
                                const float* voc, const float* mix_phase, const float* voc_phase, const float* drop, int B, int H,
                                int W, int hop, float alpha_l1, float alpha_mr, float* mask, float* losses, void* ws, size_t ws_bytes,
                                void* mr_ws, size_t mr_ws_bytes, hipStream_t stream);
+/* training = 0: the workspace of svs_unet_forward_eval, 1: of the svs_unet_train_* calls, 2: of svs_unet_forward_eval_bf16
+ * (names "cat1" .. "cat5" and "c6" only; see below what they hold). */
 int64_t svs_unet_ws_offset(const char* name, int B, int H, int W, int training);  /* bytes, <0 unknown */
 
 /* bf16 eval forward (BASELINE configs[4]: "bf16 convs on MFMA"): the same network with bf16 NHWC activations and bf16
  * weights on v_mfma_f32_16x16x32_bf16, fp32 accumulation, BatchNorm folded, mix and mask still fp32.  Not bit-comparable with
  * the fp32 path (activations are rounded to 8 significant bits per layer); tests report its mask L1 against the fp32 forward.
- * prepared_f32 is the blob of svs_unet_prepare_eval. */
+ * prepared_f32 is the blob of svs_unet_prepare_eval.
+ * After a forward every layer's output is still in ws, at svs_unet_ws_offset(name, B, H, W, 2) bytes: elements are uint16
+ * bf16, NHWC, level k = the input ceil-halved k times, ch[k] = {16, 32, 64, 128, 256, 512}[k - 1] channels per half.
+ *   "cat2" .. "cat5": (B, h[k], w[k], 2 ch[k]) -- a pixel is [decoder half | skip half] (pixel pitch 2 ch[k]): the output of
+ *                     deconv(6-k) then the output of conv k;
+ *   "cat1":           two dense planes of (P1 = B h[1] w[1], 16): the output of deconv5, then the output of conv1;
+ *   "c6":             (B, h[6], w[6], 512), the output of conv6.
+ * Each buffer starts 256-byte aligned; no kernel writes the padding between one buffer's end and the next one's start. */
 size_t svs_unet_prepared_bf16_bytes(void);
 int svs_unet_prepare_eval_bf16(const void* prepared_f32, void* prepared_bf16, hipStream_t stream);
 size_t svs_unet_eval_bf16_workspace_bytes(int B, int H, int W);

@@ -14,6 +14,7 @@
 // Levels 2..5 are interleaved ([decoder half | skip half] per pixel); level 1 is PLANAR (a 16-channel decoder plane and a
 // 16-channel skip plane, 32 bytes per pixel each), so that conv1 / deconv5 write and conv2 reads whole HBM bursts instead of
 // 32 bytes of every 64.  Bound: HBM / launch at streaming batch sizes (bf16 MFMA peak ~2.5 PFLOP/s: 16x the fp32 rate).
+#include <string.h>
 #include <type_traits>
 
 #include "unet_desc.h"
@@ -950,6 +951,19 @@ static int launch_window_bf16(const ConvBf16Args& a, const Bf16Plan& pl, hipStre
   hipLaunchKernelGGL((parity_window_bf16_kernel<C, TN, TW>), pl.grid, dim3(256), pl.lds, stream, a);
   return SVS_OK;
 }
+// svs_describe_plan kinds 3 / 4: the kernel plan_bf16 picks, named as rocprofv3 prints it, and its K-split (host arithmetic only)
+int svs_conv_bf16_describe(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, char* buf, size_t n) {
+  static const int TILE[5][5] = {{128, 128, 2, 2, 2}, {128, 64, 2, 2, 2}, {256, 32, 4, 1, 1}, {256, 16, 4, 1, 1}, {64, 128, 2, 2, 2}};   // launch_gemm_bf16's cases
+  if (B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || C % 32 || !(N == 16 || N == 32 || N == 64 || (N > 0 && N % 128 == 0))) {
+    svs_set_error("svs_describe_plan: no bf16 layer has B=%d %dx%d C=%d -> %dx%d N=%d", B, H, W, C, Ho, Wo, N);
+    return SVS_ERR_INVALID;
+  }
+  const Bf16Plan pl = plan_bf16(mode, B, H, W, C, Ho, Wo, N, C);
+  if (pl.kind == BF16_WINDOW) { snprintf(buf, n, "parity_window_bf16_kernel<%d, %d, %d>", pl.wC, pl.wTN, pl.wTW); return 1; }
+  const int* t = TILE[pl.cfg];
+  snprintf(buf, n, "conv_gemm_bf16_kernel<%d, %d, %d, %d, %d, %d>", mode, t[0], t[1], t[2], t[3], t[4]);
+  return pl.ksplit;
+}
 template <int MODE>
 static void launch_gemm_bf16(const ConvBf16Args& a, const Bf16Plan& pl, hipStream_t stream) {
   switch (pl.cfg) {        // two K-tiles per barrier where the tile is 64 or 128 columns wide
@@ -1049,6 +1063,14 @@ extern "C" size_t svs_unet_eval_bf16_workspace_bytes(int B, int H, int W) {
   Geo g;
   if (make_geo(B, H, W, g)) return 0;
   return bf16_ws_layout(g, nullptr).total;
+}
+// svs_unet_ws_offset(..., training = 2): "cat1" .. "cat5", "c6" of the layout above (bytes; -1: unknown name)
+long svs_unet_bf16_ws_offset(const char* name, const Geo& g) {
+  char* const base = (char*)256;   // non-null dummy so the arena hands out addresses
+  const Bf16Ws e = bf16_ws_layout(g, base);
+  if (!strcmp(name, "c6")) return (long)((char*)e.c6 - base);
+  if (!strncmp(name, "cat", 3) && name[3] >= '1' && name[3] <= '5' && !name[4]) return (long)((char*)e.cat[name[3] - '0'] - base);
+  return -1;
 }
 
 extern "C" int svs_unet_forward_eval_bf16(const void* prepared_bf16, const float* mix, float* mask, int B, int H, int W, void* ws,

@@ -148,10 +148,12 @@ extern "C" int svs_dec_block_bwd_weight(const float* x, int64_t ldx, int B, int 
 }
 
 // kind 0: gather GEMM (enc fwd / dec bwd_data), 1: parity GEMM (dec fwd / enc bwd_data), 2: weight-gradient GEMM
-// (then H,W,C = the strided image S and N = channels of the windowed image).  Returns the K-split.
+// (then H,W,C = the strided image S and N = channels of the windowed image), 3 / 4: gather / parity layer of the bf16 eval
+// network.  Returns the K-split.
 extern "C" int svs_describe_plan(int kind, int B, int H, int W, int C, int Ho, int Wo, int N, char* buf, size_t buflen) {
   if (!buf || !buflen) return SVS_ERR_INVALID;
   if (kind == 2) return svs_wgrad_gemm_describe(B, H, W, C, N, buf, buflen);
+  if (kind == 3 || kind == 4) return svs_conv_bf16_describe(kind == 4 ? SVS_MODE_PARITY : SVS_MODE_GATHER, B, H, W, C, Ho, Wo, N, buf, buflen);
   return svs_conv_gemm_describe(kind == 1 ? SVS_MODE_PARITY : SVS_MODE_GATHER, B, H, W, C, Ho, Wo, N, C, buf, buflen);
 }
 
@@ -396,6 +398,7 @@ static int64_t ws_find(const WsName* tab, size_t n, const char* name, const char
 extern "C" int64_t svs_unet_ws_offset(const char* name, int B, int H, int W, int training) {
   Geo g;
   if (!name || make_geo(B, H, W, g)) return -1;
+  if (training == 2) return svs_unet_bf16_ws_offset(name, g);      // the bf16 eval workspace
   char* const base = (char*)256;   // non-null dummy so the arena hands out addresses
   if (training) {
     const TrainWs t = train_layout(g, base);

@@ -30,6 +30,9 @@ static int make_geo(int B, int H, int W, Geo& g) {
   return SVS_OK;
 }
 
+// bf16 eval workspace (gemm_bf16.hip: bf16_ws_layout): byte offset of "cat1" .. "cat5" / "c6", -1 for any other name
+long svs_unet_bf16_ws_offset(const char* name, const Geo& g);
+
 // bump allocator of every workspace and prepared blob (each block 256-byte aligned); a null base only measures
 struct Arena {
   char* base; size_t used;

@@ -77,11 +77,12 @@ def test_workspace_queries_are_consistent(lib):
     assert lib.svs_stft_frames(97536, 768) == 128 and lib.svs_stft_frames(100000, 768) == 131 and lib.svs_stft_frames(81920, 768) == 107
 
 
-@pytest.mark.parametrize("training", [0, 1])
+@pytest.mark.parametrize("training", [0, 1, 2])
 def test_named_workspace_buffers_are_aligned_disjoint_and_inside(lib, training):
     """What holds for svs_unet_ws_offset whatever the sizes are, at a shape that is odd at every level: each named
-    buffer (fp32, shapes of csrc/net.hip's header comment) starts 256-byte aligned, overlaps no other and ends inside
-    the workspace; names outside the table are unknown."""
+    buffer (fp32, shapes of csrc/net.hip's header comment; training = 2: the bf16 eval workspace, the same shapes in
+    2-byte elements) starts 256-byte aligned, overlaps no other and ends inside the workspace; names outside the table
+    are unknown."""
     B, H, W = 2, 513, 100
     hw = [(H, W)]
     for _ in range(6):
@@ -90,20 +91,21 @@ def test_named_workspace_buffers_are_aligned_disjoint_and_inside(lib, training):
     bn = list(ENC_CHANNELS[1:]) + [n for _, n in DEC_IO[:5]]                   # channels of the 11 BatchNorm layers
     numel = {f"cat{k}": P[k] * 2 * ENC_CHANNELS[k] for k in range(1, 6)}
     numel["c6"] = P[6] * ENC_CHANNELS[6]
-    if training:
+    esize = 2 if training == 2 else 4
+    if training == 1:
         numel.update({f"raw_e{k}": P[k] * ENC_CHANNELS[k] for k in range(1, 7)})
         numel.update({f"raw_d{j}": P[6 - j] * DEC_IO[j - 1][1] for j in range(1, 6)})      # deconv j writes level 6 - j
         numel.update({"d" + name: n for name, n in list(numel.items()) if name.startswith("c")})   # dcat1..5, dc6
         numel.update({"d_logit": P[0], "mask": P[0]})
         numel.update({f"mean{i}": c for i, c in enumerate(bn)})
         numel.update({f"invstd{i}": c for i, c in enumerate(bn)})
-    total = (lib.svs_unet_train_workspace_bytes if training else lib.svs_unet_eval_workspace_bytes)(B, H, W)
+    total = (lib.svs_unet_eval_workspace_bytes, lib.svs_unet_train_workspace_bytes, lib.svs_unet_eval_bf16_workspace_bytes)[training](B, H, W)
     spans = []
     for name, n in numel.items():
         off = lib.svs_unet_ws_offset(name.encode(), B, H, W, training)
         assert off >= 0 and off % 256 == 0, (name, off)
-        assert off + 4 * n <= total, (name, off, n, total)
-        spans.append((off, off + 4 * n, name))
+        assert off + esize * n <= total, (name, off, n, total)
+        spans.append((off, off + esize * n, name))
     spans.sort()
     for (_, end, a), (start, _, b) in zip(spans, spans[1:]):
         assert end <= start, (a, b)
@@ -111,8 +113,8 @@ def test_named_workspace_buffers_are_aligned_disjoint_and_inside(lib, training):
         assert lib.svs_unet_ws_offset(name.encode(), B, H, W, training) == -1, name
     for k in range(1, 6):          # "dcatK" is a name of its own (training) or unknown (eval), never read as "catK"
         assert lib.svs_unet_ws_offset(b"dcat%d" % k, B, H, W, training) != lib.svs_unet_ws_offset(b"cat%d" % k, B, H, W, training)
-    if not training:
-        assert lib.svs_unet_ws_offset(b"dcat3", B, H, W, 0) == lib.svs_unet_ws_offset(b"raw_e1", B, H, W, 0) == -1
+    if training != 1:
+        assert lib.svs_unet_ws_offset(b"dcat3", B, H, W, training) == lib.svs_unet_ws_offset(b"raw_e1", B, H, W, training) == -1
 
 
 def test_invalid_arguments_are_reported_without_touching_the_gpu(lib):
