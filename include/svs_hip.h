@@ -418,6 +418,24 @@ int svs_resample_poly(const void* x, int fmt, int channels, int downmix, int64_t
  * input samples staged per segment, LDS bytes per block, tap bytes all blocks together read from the packed table. */
 int svs_resample_plan(int64_t n_in, int up, int down, int ntaps, int rows, int64_t* plan);
 
+/* The way out (csrc/resample.hip): planar fp32 rows (channel c at x + c*ld_in, n_in samples each; 1 <= channels <= 8) are
+ * resampled with the same table, plan and summation order as svs_resample_poly -- acc_c below is bitwise the float that
+ * svs_resample_poly writes for that row -- and leave as the interleaved frames a wav file stores: frame i is `channels`
+ * consecutive elements at out + i*channels,
+ *   v_c = acc_c * gain[c]                       one fp32 multiply; gain (device, `channels` floats) NULL: no multiply
+ *   SVS_PCM_F32: v    SVS_PCM_I16: clamp(rintf(v * 32767.0f), -32768, 32767), fp32 multiply, ties to even
+ *   SVS_PCM_I32: clamp(rint((double)v * 2147483647.0), -2^31, 2^31 - 1);   NaN -> 0 and +-inf clamp in both integer formats
+ * (the I16 rule is libsndfile's float -> short conversion as recalled; parity with the reference's writer, data.py:166, is
+ * unpinned).  svs_resample_peaks writes peaks[c] = max_i |acc_c| -- the reference normalises at the rate it writes,
+ * data.py:162-166 -- from per-block partials in ws and one reduce launch (no atomics).  1/1 with the one-tap table is a
+ * pure encode.  The workspace query is 0 for invalid arguments. */
+size_t svs_resample_peaks_workspace_bytes(int64_t n_in, int channels, int up, int down, int ntaps);
+int svs_resample_peaks(const float* x, int channels, int64_t n_in, int64_t ld_in, const void* table, int ntaps, int up, int down,
+                       float* peaks /* [channels], device */, void* ws, size_t ws_bytes, hipStream_t stream);
+int svs_resample_encode(const float* x, int channels, int64_t n_in, int64_t ld_in, const void* table, int ntaps, int up, int down,
+                        const float* gain /* [channels] device, nullable */, int out_fmt /* SVS_PCM_* */,
+                        void* out /* svs_resample_out_len(n_in, up, down) x channels, interleaved */, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

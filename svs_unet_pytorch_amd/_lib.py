@@ -107,6 +107,9 @@ _SIGS = {
     "svs_resample_pack_taps": (I, [P, I, I, I, P, P]),
     "svs_resample_plan": (I, [L, I, I, I, I, P]),
     "svs_resample_poly": (I, [P, I, I, I, L, L, I, P, I, I, I, P, L, P]),
+    "svs_resample_peaks_workspace_bytes": (Z, [L, I, I, I, I]),
+    "svs_resample_peaks": (I, [P, I, L, L, P, I, I, I, P, P, Z, P]),
+    "svs_resample_encode": (I, [P, I, L, L, P, I, I, I, P, I, P, P]),
 }
 
 

@@ -48,20 +48,21 @@ struct RsArgs {
 
 static inline int rs_taps_per_phase(int ntaps, int up) { return (ntaps + up - 1) / up; }
 
-static size_t rs_lds_bytes(int Wt, int W, int S, int T, int up, int down, int* span) {
+// nch: input rows a block stages per segment (1: resample_poly_kernel; the channel count: resample_encode_kernel)
+static size_t rs_lds_bytes(int Wt, int W, int S, int T, int up, int down, int nch, int* span) {
   *span = (int)(((int64_t)(W - 1) * down) / up) + T + 2;
-  return ((size_t)Wt * T + (size_t)S * *span) * sizeof(float);
+  return ((size_t)Wt * T + (size_t)S * nch * *span) * sizeof(float);
 }
 
 // false: no block shape fits the LDS (the filter is too long for this kernel: about down / up > 90)
-static bool rs_plan(int64_t n_out, int T, int up, int down, int rows, RsPlan* p) {
+static bool rs_plan(int64_t n_out, int T, int up, int down, int rows, int nch, RsPlan* p) {
   bool ok = false;
   if (up <= RS_THREADS) {
     p->W = RS_THREADS / up * up; p->Wt = up; p->S = 1; p->nqb = 1; p->stride = p->W;
     // a long filter over few phases: shorter segments (still whole periods) leave room for the taps
     for (; p->W >= up; p->W = (p->W / up / 2) * up) {
       p->stride = p->W;
-      p->lds = rs_lds_bytes(p->Wt, p->W, 1, T, up, down, &p->span);
+      p->lds = rs_lds_bytes(p->Wt, p->W, 1, T, up, down, nch, &p->span);
       if (p->lds <= RS_LDS_MAX) { ok = true; break; }
       if (p->W == up) break;
     }
@@ -69,7 +70,7 @@ static bool rs_plan(int64_t n_out, int T, int up, int down, int rows, RsPlan* p)
     for (int pass = 0; pass < 2 && !ok; ++pass)
       for (int W = RS_THREADS; W >= 16 && !ok; W >>= 1) {
         p->W = p->Wt = W; p->S = RS_THREADS / W;
-        p->lds = rs_lds_bytes(W, W, p->S, T, up, down, &p->span);
+        p->lds = rs_lds_bytes(W, W, p->S, T, up, down, nch, &p->span);
         ok = p->lds <= (pass ? RS_LDS_MAX : RS_LDS_FOUR_BLOCKS);
       }
     p->nqb = (up + p->W - 1) / p->W; p->stride = up;
@@ -158,6 +159,188 @@ __global__ void __launch_bounds__(RS_THREADS) resample_poly_kernel(const RsArgs 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Egress: resample planar fp32 rows and write the frames as a wav file stores them (svs_resample_encode), or only take
+// max |y| per channel (svs_resample_peaks).  Same plan, same tap rows, same (n0, pos % up) walk and the same k = 0 .. T-1
+// fmaf chain as resample_poly_kernel -- the value before the gain is bitwise svs_resample_poly's -- but frame-major: a
+// thread owns one output FRAME, the block stages the span of every channel ([S][NCH][span]) next to its tap rows, which
+// all channels share, and the thread's NCH samples leave in one store where a frame is 4, 8 or 16 bytes.
+//
+// Sample formats.  F32: v.  I16: clamp(rintf(v * 32767.0f), -32768, 32767), the multiply in fp32, ties to even.  I32:
+// clamp(rint((double)v * 2147483647.0), -2^31, 2^31 - 1).  NaN -> 0, +-inf clamp.  The I16 rule is libsndfile's float ->
+// short conversion (what the reference's sf.write(path, y, sr) runs for a wav file, data.py:166) as recalled: soundfile
+// is not importable where this was written, so parity with the reference's writer is unpinned.
+// ------------------------------------------------------------------------------------------------
+constexpr int RS_MAX_CH = 8;
+
+struct RsEncArgs {
+  const float* x; int64_t n_in, ld_in;
+  const float* table; int T, up, down; int64_t half;
+  const float* gain; int fmt; void* out;      // encode
+  float* partial; int nblocks;                // peaks: [NCH][nblocks]
+  int64_t n_out;
+  RsPlan p;
+};
+
+__device__ __forceinline__ int16_t rs_enc_i16(float v) {
+  const float s = rintf(v * 32767.0f);
+  if (s != s) return 0;
+  return (int16_t)(int)fminf(fmaxf(s, -32768.0f), 32767.0f);
+}
+__device__ __forceinline__ int32_t rs_enc_i32(float v) {
+  const double s = rint((double)v * 2147483647.0);
+  if (s != s) return 0;
+  return (int32_t)fmin(fmax(s, -2147483648.0), 2147483647.0);
+}
+
+template <int BYTES> struct RsWord { typedef void type; };
+template <> struct RsWord<4> { typedef uint32_t type; };
+template <> struct RsWord<8> { typedef uint2 type; };
+template <> struct RsWord<16> { typedef uint4 type; };
+
+// the NCH samples of frame i, as one store where the frame is 4, 8 or 16 bytes (`out` is 16-byte aligned)
+template <int NCH, typename S>
+__device__ __forceinline__ void rs_store_frame(void* out, int64_t i, const S (&s)[NCH]) {
+  constexpr int BYTES = NCH * (int)sizeof(S);
+  S* p = (S*)out + i * NCH;
+  if constexpr (BYTES == 4 || BYTES == 8 || BYTES == 16) {
+    typename RsWord<BYTES>::type w;
+    __builtin_memcpy(&w, s, BYTES);
+    *reinterpret_cast<typename RsWord<BYTES>::type*>(p) = w;
+  } else {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) p[c] = s[c];
+  }
+}
+
+template <int NCH, bool PEAK>
+__global__ void __launch_bounds__(RS_THREADS) resample_encode_kernel(const RsEncArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float rs_smem[];
+  const RsPlan& p = a.p;
+  float* taps = rs_smem;                                   // [T][Wt]
+  float* xs = rs_smem + (size_t)p.Wt * a.T;                // [S][NCH][span]
+  const int t = threadIdx.x;
+  const int64_t q0 = (int64_t)blockIdx.x * (p.nqb > 1 ? p.W : 0);
+  const int lseg = p.nqb > 1 ? (int)min((int64_t)p.W, a.up - q0) : p.W;
+  const int seg = t / p.W, r = t % p.W;
+  const bool active = seg < p.S && r < lseg;
+
+  for (int e = t; e < p.Wt * a.T; e += RS_THREADS) {       // this block's tap rows
+    const int k = e / p.Wt, c = e % p.Wt;
+    taps[e] = q0 + c < a.up ? a.table[(int64_t)k * a.up + q0 + c] : 0.0f;
+  }
+
+  const int64_t it0 = (int64_t)blockIdx.y * p.ipc;
+  const int64_t it1 = min(it0 + p.ipc, p.nsteps);
+  int64_t i_f = ((it0 * p.S + seg) * p.stride) + q0;
+  int64_t n0f, remf, n0, rem;
+  {
+    const int64_t posf = i_f * a.down + a.half;
+    n0f = posf / a.up; remf = posf % a.up;
+    const int64_t pos = posf + (int64_t)r * a.down;
+    n0 = pos / a.up; rem = pos % a.up;
+  }
+  const float* tp = taps + r % p.Wt;
+  float* xseg = xs + (size_t)seg * NCH * p.span;
+  const int64_t di = (int64_t)p.S * p.stride;
+  float g[NCH], mx[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) { g[c] = (!PEAK && a.gain) ? a.gain[c] : 1.0f; mx[c] = 0.0f; }
+
+  for (int64_t it = it0; it < it1; ++it) {
+    const bool live = active && i_f < a.n_out;
+    __syncthreads();                                       // taps complete (first step); xs free again (later steps)
+    if (live) {
+      const int64_t lo = n0f - (a.T - 1);
+      for (int e = r; e < p.span; e += lseg) {
+        const int64_t j = lo + e;
+        const bool in = j >= 0 && j < a.n_in;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) xseg[c * p.span + e] = in ? a.x[(int64_t)c * a.ld_in + j] : 0.0f;
+      }
+    }
+    __syncthreads();
+    if (live && i_f + r < a.n_out) {
+      const float* xp = xseg + (int)(n0 - n0f) + a.T - 1;
+      float acc[NCH];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) acc[c] = 0.0f;
+#pragma unroll 4
+      for (int k = 0; k < a.T; ++k) {
+        const float tap = tp[(size_t)k * p.Wt];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) acc[c] = fmaf(xp[c * p.span - k], tap, acc[c]);
+      }
+      if constexpr (PEAK) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) mx[c] = fmaxf(mx[c], fabsf(acc[c]));
+      } else {
+        const int64_t i = i_f + r;
+        if (a.fmt == RS_I16) {
+          int16_t s[NCH];
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) s[c] = rs_enc_i16(acc[c] * g[c]);
+          rs_store_frame<NCH>(a.out, i, s);
+        } else if (a.fmt == RS_I32) {
+          int32_t s[NCH];
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) s[c] = rs_enc_i32(acc[c] * g[c]);
+          rs_store_frame<NCH>(a.out, i, s);
+        } else {
+          float s[NCH];
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) s[c] = acc[c] * g[c];
+          rs_store_frame<NCH>(a.out, i, s);
+        }
+      }
+    }
+    i_f += di;
+    n0f += p.dq; remf += p.dr; if (remf >= a.up) { remf -= a.up; ++n0f; }
+    n0 += p.dq; rem += p.dr; if (rem >= a.up) { rem -= a.up; ++n0; }
+  }
+
+  if constexpr (PEAK) {                                    // partial[c][block]: max |y_c| over this block's frames
+    __syncthreads();                                       // every wave is done with the LDS; the launch gives >= 4 * NCH floats
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      float m = mx[c];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+      if ((t & 63) == 0) rs_smem[c * 4 + (t >> 6)] = m;
+    }
+    __syncthreads();
+    if (t < NCH) {
+      const float* sh = rs_smem + t * 4;
+      a.partial[(int64_t)t * a.nblocks + (int64_t)blockIdx.y * gridDim.x + blockIdx.x] = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+    }
+  }
+}
+
+// peaks[c] = max of partial[c][0 .. nblocks): one wave per channel, no atomics
+__global__ void __launch_bounds__(64) resample_peaks_reduce_kernel(const float* __restrict__ partial, int nblocks, float* __restrict__ peaks) {
+  const float* row = partial + (int64_t)blockIdx.x * nblocks;
+  float m = 0.0f;
+  for (int i = threadIdx.x; i < nblocks; i += 64) m = fmaxf(m, row[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  if (threadIdx.x == 0) peaks[blockIdx.x] = m;
+}
+
+template <bool PEAK>
+static const void* rs_encode_kernel_for(int channels) {
+  switch (channels) {
+    case 1: return (const void*)resample_encode_kernel<1, PEAK>;
+    case 2: return (const void*)resample_encode_kernel<2, PEAK>;
+    case 3: return (const void*)resample_encode_kernel<3, PEAK>;
+    case 4: return (const void*)resample_encode_kernel<4, PEAK>;
+    case 5: return (const void*)resample_encode_kernel<5, PEAK>;
+    case 6: return (const void*)resample_encode_kernel<6, PEAK>;
+    case 7: return (const void*)resample_encode_kernel<7, PEAK>;
+    case 8: return (const void*)resample_encode_kernel<8, PEAK>;
+  }
+  return nullptr;
+}
+
 // table[k][q] = h[(q*down + half) % up + k*up]   (0 past ntaps)
 __global__ void __launch_bounds__(256) resample_pack_kernel(const float* __restrict__ taps, int ntaps, int up, int down, int T,
                                                             float* __restrict__ table) {
@@ -202,7 +385,7 @@ extern "C" int svs_resample_plan(int64_t n_in, int up, int down, int ntaps, int 
   SVS_REQUIRE(n_in >= 1 && n_out >= 1, "svs_resample_plan: n_in %lld out of range", (long long)n_in);
   const int T = rs_taps_per_phase(ntaps, up);
   RsPlan p{};
-  SVS_REQUIRE(rs_plan(n_out, T, up, down, rows, &p), "svs_resample_plan: %d taps per output at %d/%d do not fit the LDS", T, up, down);
+  SVS_REQUIRE(rs_plan(n_out, T, up, down, rows, 1, &p), "svs_resample_plan: %d taps per output at %d/%d do not fit the LDS", T, up, down);
   const int64_t blocks = (int64_t)p.nqb * p.chunks * rows;
   plan[0] = p.W; plan[1] = p.S; plan[2] = p.nqb; plan[3] = p.chunks; plan[4] = p.ipc; plan[5] = p.span; plan[6] = (int64_t)p.lds;
   plan[7] = blocks * p.Wt * T * (int64_t)sizeof(float);
@@ -227,7 +410,7 @@ extern "C" int svs_resample_poly(const void* x, int fmt, int channels, int downm
   a.x = x; a.fmt = fmt; a.channels = channels; a.downmix = downmix ? 1 : 0; a.rps = rps; a.n_in = n_in; a.ld_in = ld_in;
   a.table = (const float*)table; a.T = rs_taps_per_phase(ntaps, up); a.up = up; a.down = down; a.half = (ntaps - 1) / 2;
   a.y = y; a.ld_out = ld_out; a.n_out = n_out;
-  SVS_REQUIRE(rs_plan(n_out, a.T, up, down, (int)rows, &a.p),
+  SVS_REQUIRE(rs_plan(n_out, a.T, up, down, (int)rows, 1, &a.p),
               "svs_resample_poly: %d taps per output at %d/%d do not fit the LDS (down / up above about 90 is not built)",
               a.T, up, down);
   SVS_REQUIRE(a.p.chunks <= 65535, "svs_resample_poly: grid too large");
@@ -236,4 +419,72 @@ extern "C" int svs_resample_poly(const void* x, int fmt, int channels, int downm
                      stream, a);
   SVS_CHECK_LAUNCH("resample_poly");
   return SVS_OK;
+}
+
+// ---- egress: svs_resample_peaks / svs_resample_encode ---------------------------------------------------------------
+namespace {
+
+// argument checks and the launch geometry the two entry points share (host arithmetic only)
+int rs_encode_setup(const char* who, const float* x, int channels, int64_t n_in, int64_t ld_in, const void* table, int ntaps, int up,
+                    int down, RsEncArgs* a) {
+  SVS_REQUIRE(x && table, "%s: null pointer", who);
+  SVS_REQUIRE(rs_filter_ok(ntaps, up, down), "%s: bad filter (need an odd number of taps, 1 <= up, down <= 2^24)", who);
+  SVS_REQUIRE(channels >= 1 && channels <= RS_MAX_CH, "%s: channels %d (1..%d)", who, channels, RS_MAX_CH);
+  const int64_t n_out = svs_resample_out_len(n_in, up, down);
+  SVS_REQUIRE(n_in >= 1 && n_out >= 1, "%s: n_in %lld out of range", who, (long long)n_in);
+  SVS_REQUIRE(ld_in >= n_in, "%s: ld_in %lld is shorter than a row (%lld)", who, (long long)ld_in, (long long)n_in);
+  a->x = x; a->n_in = n_in; a->ld_in = ld_in;
+  a->table = (const float*)table; a->T = rs_taps_per_phase(ntaps, up); a->up = up; a->down = down; a->half = (ntaps - 1) / 2;
+  a->n_out = n_out;
+  SVS_REQUIRE(rs_plan(n_out, a->T, up, down, 1, channels, &a->p),
+              "%s: %d taps per output at %d/%d with %d channels do not fit the LDS", who, a->T, up, down, channels);
+  SVS_REQUIRE(a->p.chunks <= 65535, "%s: grid too large", who);
+  a->nblocks = a->p.nqb * a->p.chunks;
+  return SVS_OK;
+}
+
+int rs_encode_launch(const void* kernel, const RsEncArgs& a, size_t lds, hipStream_t stream) {
+  SVS_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  void* args[] = {(void*)&a};
+  SVS_HIP(hipLaunchKernel(kernel, dim3((unsigned)a.p.nqb, (unsigned)a.p.chunks), dim3(RS_THREADS), args, lds, stream));
+  return SVS_OK;
+}
+
+}  // namespace
+
+extern "C" size_t svs_resample_peaks_workspace_bytes(int64_t n_in, int channels, int up, int down, int ntaps) {
+  if (!rs_filter_ok(ntaps, up, down) || channels < 1 || channels > RS_MAX_CH || n_in < 1) return 0;
+  const int64_t n_out = svs_resample_out_len(n_in, up, down);
+  RsPlan p{};
+  if (n_out < 1 || !rs_plan(n_out, rs_taps_per_phase(ntaps, up), up, down, 1, channels, &p)) return 0;
+  return (size_t)channels * p.nqb * p.chunks * sizeof(float);
+}
+
+extern "C" int svs_resample_peaks(const float* x, int channels, int64_t n_in, int64_t ld_in, const void* table, int ntaps, int up,
+                                  int down, float* peaks, void* ws, size_t ws_bytes, hipStream_t stream) {
+  RsEncArgs a{};
+  SVS_REQUIRE(peaks, "svs_resample_peaks: null pointer");
+  if (int rc = rs_encode_setup("svs_resample_peaks", x, channels, n_in, ld_in, table, ntaps, up, down, &a)) return rc;
+  if (!ws || ws_bytes < (size_t)channels * a.nblocks * sizeof(float)) {
+    svs_set_error("svs_resample_peaks: workspace too small");
+    return SVS_ERR_WORKSPACE;
+  }
+  a.partial = (float*)ws;
+  const size_t reduce_lds = 4 * RS_MAX_CH * sizeof(float);                  // the block reduction reuses the staging LDS
+  if (int rc = rs_encode_launch(rs_encode_kernel_for<true>(channels), a, a.p.lds > reduce_lds ? a.p.lds : reduce_lds, stream)) return rc;
+  hipLaunchKernelGGL(resample_peaks_reduce_kernel, dim3((unsigned)channels), dim3(64), 0, stream, (const float*)ws, a.nblocks, peaks);
+  SVS_CHECK_LAUNCH("resample_peaks_reduce");
+  return SVS_OK;
+}
+
+extern "C" int svs_resample_encode(const float* x, int channels, int64_t n_in, int64_t ld_in, const void* table, int ntaps, int up,
+                                   int down, const float* gain, int out_fmt, void* out, hipStream_t stream) {
+  RsEncArgs a{};
+  SVS_REQUIRE(out, "svs_resample_encode: null pointer");
+  SVS_REQUIRE(svs_aligned16(out), "svs_resample_encode: out must be 16-byte aligned");
+  SVS_REQUIRE(out_fmt == RS_F32 || out_fmt == RS_I16 || out_fmt == RS_I32, "svs_resample_encode: out_fmt %d (0 float32, 1 int16, 2 int32)",
+              out_fmt);
+  if (int rc = rs_encode_setup("svs_resample_encode", x, channels, n_in, ld_in, table, ntaps, up, down, &a)) return rc;
+  a.gain = gain; a.fmt = out_fmt; a.out = out;
+  return rs_encode_launch(rs_encode_kernel_for<false>(channels), a, a.p.lds, stream);
 }

@@ -10,10 +10,14 @@ data.py:84-85); mixture.wav and vocals.wav are STFT'd (n_fft=--win_size, hop=--h
 centred), divided by that maximum (data.py:105) and saved as NNNN_<song>_spec.npy (float32 (513,T)) and
 NNNN_<song>_phase.npy (complex64 unit phasors) under <tar>/mixture and <tar>/vocal (data.py:107-109).
 to_wave (data.py:117-169): <name>_spec.npy times its phase -> inverse STFT -> peak-normalise to 0.9 ->
-<name>.wav at --sr.
+<name>.wav at --sr, float32 samples.  With --sr_out RATE and / or --subtype PCM_16 | PCM_32 the waveform is instead
+up-sampled to RATE, peak-normalised at that rate and converted to the subtype's samples by one gfx950 kernel
+(csrc/resample.hip: svs_resample_encode, save_wav_device below), and only the bytes the file stores cross to the
+host.  --subtype PCM_16 is the reference's format: its sf.write(path, y, sr) (data.py:166) picks 16-bit PCM for a
+.wav name; FLOAT, the default here, is what this project has always written.
 
-Out of the accelerated path: wav decoding (scipy.io.wavfile) and wav
-encoding (soundfile there, scipy.io.wavfile here).  Downmix + resampling to --sr (the reference uses
+Out of the accelerated path: wav decoding (scipy.io.wavfile) and the wav
+container write (soundfile there, scipy.io.wavfile here).  Downmix + resampling to --sr (the reference uses
 librosa.load / soxr) is scipy.signal.resample_poly on the CPU by default; with --resample gpu (or
 load_wav_mono(..., device=...)) the file's PCM is copied to the device as it is stored and one gfx950
 kernel (csrc/resample.hip, svs_unet_pytorch_amd/resample.py) converts, downmixes and resamples it with
@@ -170,6 +174,19 @@ def write_wav(path: str, y: np.ndarray, sr: int):
     wavfile.write(path, sr, np.asarray(y, dtype=np.float32))
 
 
+def save_wav_device(path: str, y_dev: torch.Tensor, sr: int, sr_out: int | None = None, subtype: str = "PCM_16", peak: float | None = 0.9):
+    """float32 device samples (n,) or (channels, n) at rate `sr` -> a wav file at `sr_out` (default: sr) with the samples of
+    `subtype` ("PCM_16", the reference's sf.write format for a .wav name, "PCM_32" or "FLOAT"), peak-normalised to `peak` at
+    the rate that is written (data.py:162-166; None: not normalised; one gain for all channels).  Resampling, gain, sample
+    conversion and interleaving are resample.resample_encode_gpu; one device -> host copy of the encoded samples follows."""
+    from scipy.io import wavfile
+    from .resample import resample_encode_gpu
+    sr_out = int(sr if sr_out is None else sr_out)
+    fr = Fraction(sr_out, int(sr))
+    pcm = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=subtype, peak=peak, common_gain=True)
+    wavfile.write(path, sr_out, pcm.cpu().numpy())
+
+
 def to_spec(args, device):
     os.makedirs(args.tar, exist_ok=True)
     for folder in TRACK_MAP.values():
@@ -232,10 +249,17 @@ def to_wave(args, device):
             if phase is None:
                 phase = np.exp(2j * np.pi * np.random.rand(*mag.shape))                                        # data.py:148
             m = min(mag.shape[1], phase.shape[1])                                                              # data.py:151-153
+            sr_out = getattr(args, "sr_out", None) or args.sr
+            subtype = getattr(args, "subtype", "FLOAT")
+            encode = sr_out != args.sr or subtype != "FLOAT"          # else: float32 at --sr, written as it always was
             y = istft(torch.from_numpy(np.ascontiguousarray(mag[:, :m])).to(device),
                       torch.from_numpy(np.ascontiguousarray(phase[:, :m]).astype(np.complex64)).to(device),
-                      args.win_size, args.hop_size, peak=0.9)
-            write_wav(os.path.join(args.tar, spec_name.replace("_spec.npy", ".wav")), y.cpu().numpy(), args.sr)
+                      args.win_size, args.hop_size, peak=None if encode else 0.9)
+            wav_path = os.path.join(args.tar, spec_name.replace("_spec.npy", ".wav"))
+            if encode:
+                save_wav_device(wav_path, y, args.sr, sr_out, subtype, peak=0.9)
+            else:
+                write_wav(wav_path, y.cpu().numpy(), args.sr)
         except Exception as e:                                          # data.py:168-169
             print(f"Restore failed {spec_name}: {e}")
 
@@ -251,7 +275,12 @@ def main(argv=None):
     parser.add_argument("--direction", default="to_spec", choices=["to_spec", "to_wave"])
     parser.add_argument("--resample", default="cpu", choices=["cpu", "gpu"],
                         help="to_spec: downmix + resample on the host (scipy, default) or on the device from the file's PCM")
+    parser.add_argument("--sr_out", type=int, default=None, help="to_wave: rate of the written files (default: --sr)")
+    parser.add_argument("--subtype", default="FLOAT", choices=["FLOAT", "PCM_16", "PCM_32"],
+                        help="to_wave: sample format of the written files (PCM_16 is the reference's)")
     args = parser.parse_args(argv)
+    if args.sr_out is not None and args.sr_out < 1:
+        parser.error(f"--sr_out {args.sr_out}: must be positive")
     if args.win_size != WINDOW_SIZE:             # data.py:24 lets it vary; the gfx950 transforms are built for the config's 1024 only
         parser.error(f"--win_size {args.win_size}: the STFT / iSTFT kernels are built for n_fft = {WINDOW_SIZE} (config.WINDOW_SIZE) only; "
                      "--hop_size may be anything in 1..win_size")

@@ -170,3 +170,110 @@ def resample_poly_gpu(x, up: int, down: int, *, channels: int = 1, downmix: bool
     if rps > 1:
         return y.view(batch, rps, n_out) if batched else y
     return y if batched else y[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# the way out: planar fp32 at the network rate -> the interleaved PCM a wav file stores, at the file's rate
+# ------------------------------------------------------------------------------------------------
+_PCM = {"float32": (PCM_F32, np.float32), "int16": (PCM_I16, np.int16), "int32": (PCM_I32, np.int32)}
+_SUBTYPE = {"FLOAT": "float32", "PCM_16": "int16", "PCM_32": "int32"}       # soundfile's names for the wav subtypes
+
+
+def pcm_format(fmt):
+    """(SVS_PCM_* code, numpy dtype) of "float32" / "int16" / "int32", of a wav subtype name ("FLOAT", "PCM_16", "PCM_32")
+    or of a code."""
+    if isinstance(fmt, str):
+        fmt = _SUBTYPE.get(fmt, fmt)
+        if fmt in _PCM:
+            return _PCM[fmt]
+    else:
+        for code, dtype in _PCM.values():
+            if code == fmt:
+                return code, dtype
+    raise ValueError(f"sample format {fmt!r}: one of {sorted(_PCM)} or {sorted(_SUBTYPE)}")
+
+
+def encode_pcm_reference(y, gain, fmt):
+    """numpy restatement of what svs_resample_encode does after the FIR (include/svs_hip.h).  y: (n, channels) or (n,)
+    float32; gain: None, a scalar or `channels` float32 values.  v = y * gain is one float32 multiply, then
+        float32: v        int16: clip(rint(v * float32(32767)), -32768, 32767), the multiply in float32
+        int32: clip(rint(float64(v) * 2147483647), -2^31, 2^31 - 1)
+    with rint rounding ties to even, NaN -> 0 and +-inf clipped in the integer formats."""
+    code, dtype = pcm_format(fmt)
+    v = np.asarray(y, dtype=np.float32)
+    if gain is not None:
+        v = v * np.asarray(gain, dtype=np.float32)
+    if code == PCM_F32:
+        return np.ascontiguousarray(v, dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if code == PCM_I16:
+            s = np.rint(v * np.float32(32767.0))
+            lo, hi = -32768.0, 32767.0
+        else:
+            s = np.rint(v.astype(np.float64) * 2147483647.0)
+            lo, hi = -2147483648.0, 2147483647.0
+        s = np.where(np.isnan(s), 0.0, np.clip(s, lo, hi))
+    return np.ascontiguousarray(s.astype(dtype))
+
+
+def resample_peaks_gpu(y, up: int, down: int):
+    """max |resample_poly_gpu(y, up, down)| per row of a planar float32 device tensor (channels, n), as a device tensor
+    (channels,), without writing the resampled signal (svs_resample_peaks)."""
+    import torch
+    up, down = reduced(up, down)
+    channels, n_in = y.shape
+    L = _lib.lib()
+    table, ntaps = tap_table(up, down, y.device)
+    nbytes = int(L.svs_resample_peaks_workspace_bytes(n_in, channels, up, down, ntaps))
+    if nbytes == 0:
+        raise _lib.SvsError(f"svs_resample_peaks_workspace_bytes({n_in}, {channels}, {up}, {down}, {ntaps}): invalid arguments")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=y.device)
+    peaks = torch.empty(channels, dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        _lib.check(L.svs_resample_peaks(y.data_ptr(), channels, n_in, n_in, table.data_ptr(), ntaps, up, down, peaks.data_ptr(),
+                                        ws.data_ptr(), nbytes, _lib.stream_ptr(y.device)), "svs_resample_peaks")
+    return peaks
+
+
+def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | None = 0.9, common_gain: bool = True):
+    """float32 device tensor (n,) or (channels, n), planar -> device tensor (n_out,) or (n_out, channels) of int16 / int32 /
+    float32 at rate * up / down, interleaved as a wav file stores it (svs_resample_encode; the rules: encode_pcm_reference).
+    peak=None: the samples are encoded as they are.  Otherwise they are scaled by peak / max |resampled signal| on the way
+    (data.py:162-164, at the rate that is written): the maximum comes from a first run of the FIR that stores nothing
+    (svs_resample_peaks; measured against materialising the float32 signal once: DESIGN.md section 10b) and the gain is formed
+    on the device, so nothing waits for the host.  common_gain=True: one gain
+    for all channels, from the loudest (a stereo file keeps its balance; mono is the reference's rule); False: every channel
+    is normalised on its own, as istft_from_tiles(peak=) does.  A silent signal (maximum 0) is divided by 1, the rule of
+    svs_scale_by_inv, and stays silent."""
+    import torch
+    if not y.is_cuda:
+        raise ValueError("resample_encode_gpu needs a device tensor (there is no CPU path)")
+    if y.dtype != torch.float32:
+        raise TypeError(f"resample_encode_gpu: dtype {y.dtype} (float32)")
+    if y.dim() not in (1, 2) or y.shape[-1] < 1:
+        raise ValueError(f"input must be (n,) or (channels, n), got {tuple(y.shape)}")
+    code, dtype = pcm_format(fmt)
+    up, down = reduced(up, down)
+    squeeze = y.dim() == 1
+    y = (y[None] if squeeze else y).contiguous()
+    channels, n_in = y.shape
+    L = _lib.lib()
+    n_out = int(L.svs_resample_out_len(n_in, up, down))
+    table, ntaps = tap_table(up, down, y.device)
+    out = torch.empty((n_out, channels), dtype=getattr(torch, np.dtype(dtype).name), device=y.device)
+    with torch.cuda.device(y.device):
+        s = _lib.stream_ptr(y.device)
+        gain = None
+        if peak is not None:
+            peaks = resample_peaks_gpu(y, up, down)
+            gain = torch.full((channels,), float(peak), dtype=torch.float32, device=y.device)
+            if common_gain:
+                top = torch.empty(1, dtype=torch.float32, device=y.device)
+                _lib.check(L.svs_max(peaks.data_ptr(), channels, top.data_ptr(), s), "svs_max")
+                _lib.check(L.svs_scale_by_inv(gain.data_ptr(), channels, top.data_ptr(), 1.0, s), "svs_scale_by_inv")
+            else:
+                for c in range(channels):
+                    _lib.check(L.svs_scale_by_inv(gain[c:].data_ptr(), 1, peaks[c:].data_ptr(), 1.0, s), "svs_scale_by_inv")
+        _lib.check(L.svs_resample_encode(y.data_ptr(), channels, n_in, n_in, table.data_ptr(), ntaps, up, down, _lib.ptr(gain), code,
+                                         out.data_ptr(), s), "svs_resample_encode")
+    return out[:, 0] if squeeze else out

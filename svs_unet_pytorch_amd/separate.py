@@ -1,0 +1,66 @@
+"""wav -> separated wav in one command: the file's PCM goes to the device as it is stored, every channel is resampled to
+the network rate, separated (STFT -> U-Net mask -> inverse STFT), resampled back to the file's rate, peak-normalised to 0.9
+and converted to the written sample format there (streaming.separate_to_wav; csrc/resample.hip); only the encoded samples
+return to the host.  The output has the source's rate, channel count and (unless --no_keep_length) frame count, so
+evaluate.py accepts it beside the source's stems.
+
+    python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src song.wav --tar out.wav
+    python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src wav_folder --tar out_folder \
+        [--vocal_solo 0|1] [--precision bf16] [--subtype PCM_16|PCM_32|FLOAT] [--no_keep_length]
+
+A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
+default) is what the reference's data.py writes (data.py:166).  The reference has no such command: it goes through
+data.py to_spec, inference.py and data.py to_wave with .npy files in between.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import torch
+
+from .model import UNet
+from .streaming import separate_to_wav
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--model_path", type=str, required=True)
+    parser.add_argument("--src", type=str, required=True, help="a wav file, or a folder of *.wav files")
+    parser.add_argument("--tar", type=str, required=True, help="the wav file to write, or the target folder when --src is a folder")
+    parser.add_argument("--vocal_solo", type=int, default=1, help="1: keep the vocal, 0: remove it")
+    parser.add_argument("--precision", default=None, choices=["fp32", "bf16"], help="eval precision of the network (default: the model's)")
+    parser.add_argument("--subtype", default="PCM_16", choices=["PCM_16", "PCM_32", "FLOAT"], help="sample format of the written files")
+    parser.add_argument("--no_keep_length", action="store_true", help="do not cut / pad the output to the source's frame count")
+    args = parser.parse_args(argv)
+
+    if not torch.cuda.is_available():
+        print("separate.py needs a ROCm device (hand-written gfx950 kernels, no CPU path).")
+        sys.exit(1)
+    device = torch.device("cuda")
+    model = UNet().to(device)
+    try:                                                        # as inference.py loads it
+        checkpoint = torch.load(args.model_path, map_location=device)
+        if isinstance(checkpoint, dict) and "model_state_dict" in checkpoint:
+            model.load_state_dict(checkpoint["model_state_dict"])
+    except Exception as e:
+        print(f"Failed to load the model: {e}")
+        sys.exit(1)
+    model.eval()
+
+    if os.path.isdir(args.src):
+        os.makedirs(args.tar, exist_ok=True)
+        jobs = [(os.path.join(args.src, f), os.path.join(args.tar, f)) for f in sorted(os.listdir(args.src)) if f.endswith(".wav")]
+    else:
+        jobs = [(args.src, args.tar)]
+    print(f"Found {len(jobs)} files, separating...")
+    for src, dst in jobs:
+        frames, channels = separate_to_wav(model, src, dst, vocal_solo=bool(args.vocal_solo), precision=args.precision,
+                                           subtype=args.subtype, keep_length=not args.no_keep_length)
+        print(f"{dst}: {frames} frames x {channels}")
+    print("Separation finished!")
+
+
+if __name__ == "__main__":
+    main()

@@ -46,10 +46,14 @@ def separate_spectrogram_device(model, mag: torch.Tensor, seg_len: int = INPUT_L
 
 @torch.no_grad()
 def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
-                      peak: float | None = 0.9, max_batch: int = 256, precision: str | None = None, sr_in: int | None = None):
+                      peak: float | None = 0.9, max_batch: int = 256, precision: str | None = None, sr_in: int | None = None,
+                      sr_out: int | None = None):
     """float32 samples (n,) or (channels, n) on the GPU -> separated samples (hop*(T-1),) or (channels, hop*(T-1)).
     sr_in: the rate of y if it is not config.SAMPLE_RATE yet (a file's 44,100 Hz): every channel is first resampled to
     SAMPLE_RATE on the device (resample.resample_poly_gpu, no downmix); None: y is at the network rate already.
+    sr_out: the rate to return (a file's 44,100 Hz): the separated channels are resampled from SAMPLE_RATE on the device and
+    peak-normalised per channel at THAT rate -> (channels, ceil(hop*(T-1) * sr_out / SAMPLE_RATE)) float32; None: the
+    network rate, as always.
     All channels go through ONE forward transform (which writes network tiles and frame-major phasors directly), one
     batched network forward per `max_batch` tiles and ONE inverse transform (which applies the mask on load and
     overlap-adds in LDS); the only other passes are the two per-channel normalisations."""
@@ -76,5 +80,73 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     finally:                                                     # a failing forward must not leave the model in another mode
         model.eval_precision = was_precision
         model.train(was_training)
-    out = istft_from_tiles(tiles, mask, phase, T, invert=not vocal_solo, n_fft=n_fft, hop=hop, peak=peak)
+    out = istft_from_tiles(tiles, mask, phase, T, invert=not vocal_solo, n_fft=n_fft, hop=hop, peak=None if sr_out is not None else peak)
+    if sr_out is not None:
+        from .resample import resample_poly_gpu
+        out = resample_poly_gpu(out, int(sr_out), SAMPLE_RATE)
+        if peak is not None:                                     # data.py:162-164 at the rate that is returned
+            ws = torch.empty(4096, dtype=torch.uint8, device=out.device)
+            pk = torch.empty(C, dtype=torch.float32, device=out.device)
+            for c in range(C):
+                _lib.check(L.svs_absmax(out[c].data_ptr(), out.shape[1], pk[c:].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "svs_absmax")
+                _lib.check(L.svs_scale_by_inv(out[c].data_ptr(), out.shape[1], pk[c:].data_ptr(), float(peak), _lib.stream_ptr()), "svs_scale_by_inv")
     return out[0] if squeeze else out
+
+
+def kept_length(n_encoded: int, n_source: int):
+    """(frames to keep, zero frames to append) that turn n_encoded written frames into exactly n_source: a separated signal
+    is short of its source by less than one hop at the network rate (the inverse STFT returns hop * (T - 1) samples; STFT ->
+    iSTFT and the zero-phase FIR add no delay), and rounding up twice in the two rate changes can leave it a frame long."""
+    n_encoded, n_source = int(n_encoded), int(n_source)
+    if n_encoded < 0 or n_source < 0:
+        raise ValueError(f"frame counts must not be negative, got {n_encoded}, {n_source}")
+    keep = min(n_encoded, n_source)
+    return keep, n_source - keep
+
+
+def separated_frames(n_source: int, sr: int, hop: int = HOP_SIZE):
+    """Frames separate_to_wav encodes for a file of n_source frames at rate sr, before keep_length: to the network rate
+    (ceil), whole hops of it (the centred STFT has 1 + n // hop frames, the inverse returns hop * (T - 1) samples), and back
+    (ceil)."""
+    n8 = -((-int(n_source) * SAMPLE_RATE) // int(sr))
+    return -((-(hop * (n8 // hop)) * int(sr)) // SAMPLE_RATE)
+
+
+@torch.no_grad()
+def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = True, precision: str | None = None,
+                    subtype: str = "PCM_16", keep_length: bool = True):
+    """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
+    the PCM is copied as the file stores it, resample.resample_poly_gpu (no downmix) brings every channel to SAMPLE_RATE,
+    separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
+    peak-normalises to 0.9 with one gain for all channels (data.py:162-164), converts to `subtype` ("PCM_16", "PCM_32",
+    "FLOAT") and interleaves; only those samples return to the host.  keep_length: the frames are cut or zero-padded to the
+    source's frame count (kept_length), so the file lines up sample for sample with the source's stems.  Returns the
+    (frames, channels) written."""
+    from fractions import Fraction
+
+    import numpy as np
+    from scipy.io import wavfile
+
+    from .resample import resample_encode_gpu, resample_poly_gpu
+    rate, data = wavfile.read(src_path)
+    if data.dtype.kind == "u":                                   # 8-bit files: offset binary, converted on the host
+        data = (data.astype(np.float32) - 128.0) / 128.0
+    elif data.dtype not in (np.int16, np.int32):
+        data = data.astype(np.float32)
+    n_source = data.shape[0]
+    channels = data.shape[1] if data.ndim == 2 else 1
+    dev = model._flat.device
+    if separated_frames(n_source, rate) == 0:
+        raise ValueError(f"{src_path}: {n_source} frames at {rate} Hz are shorter than one hop ({HOP_SIZE} samples at {SAMPLE_RATE} Hz)")
+    pcm = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+    fr = Fraction(SAMPLE_RATE, int(rate))
+    y = resample_poly_gpu(pcm, fr.numerator, fr.denominator, channels=channels, downmix=False)
+    y = y[None] if y.dim() == 1 else y                            # (channels, n) at the network rate
+    sep = separate_waveform(model, y, vocal_solo=vocal_solo, peak=None, precision=precision)
+    enc = resample_encode_gpu(sep, fr.denominator, fr.numerator, fmt=subtype, peak=0.9, common_gain=True)
+    if keep_length:
+        keep, pad = kept_length(enc.shape[0], n_source)
+        enc = torch.nn.functional.pad(enc[:keep], (0, 0, 0, pad))
+    out = enc.cpu().numpy()
+    wavfile.write(dst_path, int(rate), out[:, 0] if channels == 1 else out)
+    return out.shape

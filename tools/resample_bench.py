@@ -6,6 +6,7 @@ at 48,000 Hz.
     python tools/resample_bench.py [--rates 44100 48000] [--seconds 240] [--reps 5] [--no-separate]
     rocprofv3 --kernel-trace --stats -d DIR -o rs --output-format csv -- python tools/resample_bench.py --rates 44100 --gpu-only
     python tools/resample_bench.py --kernel-stats DIR --rates 44100 --seconds 240
+    python tools/resample_bench.py --egress [--rates 44100 48000] [--seconds 240] [--reps 5]
 
 Per rate, medians of --reps synchronised calls after one warm-up call, all in one run on one box:
   (a) gpu_ms          resample_poly_gpu(int16 stereo PCM already on the device, downmix) -> mono float32 at 8,192 Hz
@@ -15,6 +16,15 @@ Per rate, medians of --reps synchronised calls after one warm-up call, all in on
   (c) separate_*      streaming.separate_waveform(model, stereo float32 at the file rate, sr_in=rate) against resample_poly of
                       both channels on the host + copy + today's separate_waveform (44,100 Hz only, skipped by --no-separate)
 and max |d| of (a) and (b) against float64 scipy on the same samples.
+With --egress the tool times the way OUT instead: --seconds of separated stereo float32 at 8,192 Hz on the device -> peak-normalised
+interleaved int16 at the file rate on the host, medians of --reps after one warm-up:
+  (a) resample.resample_encode_gpu (FIR twice: svs_resample_peaks, then svs_resample_encode) -- peaks_ms / encode_ms / device_ms
+      from device events, to_host_ms the wall time until the int16 bytes are in host memory; encode_store_gbps = the bytes the
+      encode launch stores over encode_ms; materialised_device_ms is the other peak strategy (svs_resample_poly to float32 once,
+      then peaks and encode of that buffer at 1/1);
+  (b) what the parent of that feature offers: resample_poly_gpu to float32, abs().amax(), scale, .cpu(), then numpy rint /
+      clip / astype / interleave -- parent_to_host_ms;
+and asserts that (a), the materialised form and (b) give the same int16 samples.
 With --kernel-stats the tool instead reads a rocprofv3 --stats CSV of a --gpu-only run at ONE rate and reports the kernel's
 time and its achieved bytes/s against (i) the input + output bytes (HBM) and (ii) the tap bytes the launch reads from the
 packed table (L2), as svs_resample_plan counts them.
@@ -122,6 +132,78 @@ def record(args, rate):
     return rec
 
 
+def event_median(fn, reps):
+    """median device ms between events around fn(), after one warm-up call; fn's last result"""
+    import torch
+    out = fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return statistics.median(ts), out
+
+
+def egress_record(args, rate):
+    import torch
+    fr = Fraction(rate, SAMPLE_RATE)
+    up, down = fr.numerator, fr.denominator
+    dev = torch.device("cuda")
+    y = torch.from_numpy(np.ascontiguousarray((track(args.seconds, SAMPLE_RATE).astype(np.float32) / 32768.0).T)).to(dev)   # (2, n) planar
+    channels, n_in = y.shape
+    n_out = rs.out_len(n_in, up, down)
+    L = _lib.lib()
+    table, ntaps = rs.tap_table(up, down, dev)
+    one, one_taps = rs.tap_table(1, 1, dev)
+    rec = {"mode": "egress", "rate": rate, "seconds": args.seconds, "channels": channels, "n_in": n_in, "n_out": n_out, "up": up, "down": down,
+           "reps": args.reps, "fmt": "int16", "peak_strategy": "fir_twice"}
+
+    def gain_of(peaks):
+        top = torch.empty(1, dtype=torch.float32, device=dev)
+        gain = torch.full((channels,), 0.9, dtype=torch.float32, device=dev)
+        _lib.check(L.svs_max(peaks.data_ptr(), channels, top.data_ptr(), _lib.stream_ptr()), "svs_max")
+        _lib.check(L.svs_scale_by_inv(gain.data_ptr(), channels, top.data_ptr(), 1.0, _lib.stream_ptr()), "svs_scale_by_inv")
+        return gain
+
+    def encode(x, u, d, tab, nt, gain):
+        out = torch.empty((rs.out_len(x.shape[1], u, d), channels), dtype=torch.int16, device=dev)
+        _lib.check(L.svs_resample_encode(x.data_ptr(), channels, x.shape[1], x.shape[1], tab.data_ptr(), nt, u, d, gain.data_ptr(), rs.PCM_I16,
+                                         out.data_ptr(), _lib.stream_ptr()), "svs_resample_encode")
+        return out
+
+    def materialised():
+        f = rs.resample_poly_gpu(y, up, down)                                   # (2, n_out) float32, written once
+        return encode(f, 1, 1, one, one_taps, gain_of(rs.resample_peaks_gpu(f, 1, 1)))
+
+    rec["peaks_ms"], peaks = event_median(lambda: rs.resample_peaks_gpu(y, up, down), args.reps)
+    gain = gain_of(peaks)
+    rec["encode_ms"], _ = event_median(lambda: encode(y, up, down, table, ntaps, gain), args.reps)
+    rec["encode_store_gbps"] = n_out * channels * 2 / (rec["encode_ms"] * 1e-3) / 1e9
+    rec["device_ms"], a_dev = event_median(lambda: rs.resample_encode_gpu(y, up, down, fmt="int16", peak=0.9), args.reps)
+    rec["materialised_device_ms"], m_dev = event_median(materialised, args.reps)
+    med, mn, a = median_of(lambda: rs.resample_encode_gpu(y, up, down, fmt="int16", peak=0.9).cpu().numpy(), args.reps)
+    rec.update(to_host_ms=1e3 * med, to_host_ms_min=1e3 * mn)
+
+    def parent():
+        f = rs.resample_poly_gpu(y, up, down)
+        g = np.float32(0.9) / np.float32(f.abs().amax().item())                 # one gain for both channels; 0 does not occur here
+        v = (f * float(g)).cpu().numpy()
+        s = np.clip(np.rint(v * np.float32(32767.0)), -32768.0, 32767.0).astype(np.int16)
+        return np.ascontiguousarray(s.T)
+    med, mn, b = median_of(parent, args.reps)
+    rec.update(parent_to_host_ms=1e3 * med, parent_to_host_ms_min=1e3 * mn)
+    assert a.shape == b.shape == (n_out, channels) and a.dtype == b.dtype == np.int16
+    assert np.array_equal(a, b), "the fused path and the parent path disagree"
+    assert np.array_equal(a, a_dev.cpu().numpy()) and np.array_equal(a, m_dev.cpu().numpy()), "the two peak strategies disagree"
+    rec["max_abs_sample"] = int(np.abs(a.astype(np.int32)).max())
+    rec["speedup_to_host"] = rec["parent_to_host_ms"] / rec["to_host_ms"]
+    return rec
+
+
 def kernel_stats(path, args):
     files = glob.glob(os.path.join(path, "**", "*kernel_stats.csv"), recursive=True) if os.path.isdir(path) else [path]
     if not files:
@@ -153,6 +235,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--gpu-only", action="store_true", help="only the device-resident GPU call (profiling runs)")
     ap.add_argument("--no-separate", action="store_true", help="skip the separate_waveform comparison")
+    ap.add_argument("--egress", action="store_true", help="time the way out (8,192 Hz float32 -> int16 at the file rate on the host) instead")
     ap.add_argument("--kernel-stats", default=None, help="rocprofv3 --stats CSV (or its directory) of a --gpu-only run at one rate")
     args = ap.parse_args()
     if args.kernel_stats:
@@ -162,7 +245,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("resample_bench.py needs a ROCm device")
     for rate in args.rates:
-        print(json.dumps(record(args, rate)), flush=True)
+        print(json.dumps(egress_record(args, rate) if args.egress else record(args, rate)), flush=True)
 
 
 if __name__ == "__main__":
