@@ -319,11 +319,35 @@ int svs_stft_groups(int frames_alloc);
 /* svs_istft_tiles: y (channels, hop * (frames - 1)) = istft(mag [* mask or * (1 - mask)] * phase).  mask (optional, same
  *   layout as mag) fuses inference.py:100-107.  phase_mode 1: frame-major phasors; 3: angles in the layout of mag
  *   (train.py:33-60, `specific_istft`: the DC row that train.py:41-42 pads back is the absent first_bin row).
- *   n_fft / 2 <= hop <= n_fft.  absmax_partial (optional): [channels][svs_istft_groups(hop, frames, channels)] maxima of |y|. */
+ *   0 < hop <= n_fft.  absmax_partial (optional): [channels][svs_istft_groups(hop, frames, channels)] maxima of |y|. */
 int svs_istft_tiles(const float* mag, int64_t chan_stride, int seg, int rows, int first_bin, const float* mask, int invert,
                     const float* phase, int phase_mode, int channels, int n_fft, int hop, int frames, float* y,
                     float* absmax_partial, hipStream_t stream);
 int svs_istft_groups(int hop, int frames, int channels);
+/* The same two transforms for n_fft = 512, 1024 or 2048 -- data.py:24 (`--win_size`, handed to librosa.stft / librosa.istft at
+ *   data.py:79,100,159) and the 2048-sample windows of config.py:18-44.  Arguments, layouts and results as svs_stft_tiles /
+ *   svs_istft_tiles with 513 -> n_fft / 2 + 1 and 512 -> n_fft / 2 (rows == n_fft / 2 + 1 - first_bin); any other n_fft is an
+ *   error that names the three sizes, and so is hop > n_fft.  At n_fft = 1024 they ARE the two functions above (which
+ *   require 1024 and forward here), so results are bitwise the same through either name; the 1024-only entry points
+ *   (svs_stft_fwd, svs_istft, svs_istft_bwd_mask, the training losses) keep rejecting any other n_fft. */
+int svs_stft_tiles_n(const float* y, int64_t n_samples, int channels, int n_fft, int hop, float* mag, int64_t chan_stride,
+                     int seg, int rows, int first_bin, int frames_alloc, float* phase, int phase_mode,
+                     float* absmax_partial, hipStream_t stream);
+int svs_istft_tiles_n(const float* mag, int64_t chan_stride, int seg, int rows, int first_bin, const float* mask, int invert,
+                      const float* phase, int phase_mode, int channels, int n_fft, int hop, int frames, float* y,
+                      float* absmax_partial, hipStream_t stream);
+/* absmax partials per channel of the two calls above (data.py:84-85,162-164 reduce them); -1 and an error for an n_fft that
+ * is not built or a hop outside 1..n_fft */
+int svs_stft_groups_n(int n_fft, int frames_alloc);
+int svs_istft_groups_n(int n_fft, int hop, int frames, int channels);
+/* Host-only query of the inverse's launch plan for (n_fft, hop), read by the launch and by svs_istft_groups_n alike
+ * (librosa.istft's overlap-add, data.py:159, for any --hop_size of data.py:25): hops of output that one block owns, rounds of
+ * frames it walks for them (16 frames per round; 8 for n_fft = 2048 with hop < 1024, whose blocks have four waves) and the
+ * dynamic LDS of a block in bytes.  hop >= n_fft / 2 is the two-frames-per-sample kernel (15 hops, one round). */
+int svs_istft_plan_n(int n_fft, int hop, int* hops_per_block, int* rounds, size_t* lds_bytes);
+/* Host-only: the periodic Hann window the forward transform multiplies by (librosa.stft's default window, data.py:79,100):
+ * out[m] = sin^2(pi m / n_fft) for m = 0 .. n_fft / 2 (n_fft / 2 + 1 floats; w[n_fft - m] = w[m]), rounded from double. */
+int svs_hann_table(int n_fft, float* out);
 /* (rows, cols) complex64 -> (cols, rows): f-major phasor files <-> the frame-major form */
 int svs_transpose_c64(const float* in, float* out, int rows, int cols, hipStream_t stream);
 /* Backward of `specific_istft` (train.py:33-60) fused with the chain rule of |S| = mask * mix (train.py:275,288):

@@ -61,6 +61,8 @@ int svs_bn_bwd_run(const float* dy, long lddy, const float* raw, long ldr, long 
 // device pointer to fft_wave.h's twiddle table for n_fft = 512 / 1024 / 2048 (FftSize<n>::TW float2), built once per device;
 // work queued on `stream` after the call sees the table complete
 int svs_fft_twiddles(int n, hipStream_t stream, const float2** out);
+// the same for the periodic Hann window of n samples, entries 0 .. n / 2 (fft_tables.hip)
+int svs_fft_hann(int n, hipStream_t stream, const float** out);
 
 int svs_conv_gemm_describe(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, long ldx, char* buf, size_t n);
 int svs_wgrad_gemm_describe(int B, int Hs, int Ws, int Cs, int Cl, char* buf, size_t n);

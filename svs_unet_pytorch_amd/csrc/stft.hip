@@ -1,11 +1,12 @@
 // Windowed STFT / inverse STFT on the GPU (gfx950) as bandwidth kernels.
 // Replaces librosa.stft / librosa.magphase / librosa.istft (reference data.py:79-80,100-101,159) and torch.istft
-// (train.py:51-58): periodic Hann window of n_fft = 1024 samples, centred frames with zero padding,
+// (train.py:51-58): periodic Hann window of n_fft samples, centred frames with zero padding,
 // frames = 1 + n_samples / hop; inverse = irfft, window, overlap-add, divide by the window sum-of-squares, trim
-// n_fft/2 from both ends.
+// n_fft/2 from both ends.  Every kernel is a template on N = n_fft, instantiated for 512, 1024 (the reference's config.py:47)
+// and 2048 (data.py:24 lets --win_size vary); the numbers in the comments below are those of N = 1024.
 //
 // Structure (both directions): a 512-thread block owns 16 consecutive frames (hops) of one channel.
-//   * FFT: one 1024-point complex FFT per WAVE in LDS (fft_wave.h: three register-radix passes, no block barriers),
+//   * FFT: one N-point complex FFT per WAVE in LDS (fft_wave.h: three register-radix passes, no block barriers),
 //     and TWO real frames per transform (frame t in the real part, frame t+1 in the imaginary part; the two spectra
 //     separate by Hermitian symmetry) -- half the arithmetic of a complex transform per real frame.
 //   * Layout: spectrograms are f-major with time fastest ((513, T) files of data.py:107-109, (tiles, 1, 512, 128)
@@ -22,8 +23,6 @@
 #include "internal.h"
 #include "fft_wave.h"
 
-#define NFFT 1024
-#define NBIN 513
 #define GROUP 16                  // forward: frames per block (8 waves x 2)
 #define SROW (GROUP + 1)          // floats per staged angle row (odd -> conflict-free column access)
 #define IGROUP 15                 // inverse: hops per step; they touch 16 frames = 8 waves x 2 (one of 16 transforms is halo)
@@ -44,19 +43,25 @@ struct SpecLayout {
   }
 };
 
-__device__ __forceinline__ float hann_at(int m) { return 0.5f - 0.5f * cospif((float)m * (2.0f / NFFT)); }
-// the same value from the FFT's pass-2 twiddle table (tw2[256 + k] = exp(-2 pi i k / 1024), k < 256: exact sincospi
-// entries), by symmetry: an LDS read and three selects instead of a ~40-instruction cospif
+// Window of the forward transform, N = 1024: from the FFT's pass-2 twiddle table (tw2[256 + k] = exp(-2 pi i k / 1024),
+// k < 256: exact sincospi entries), by symmetry: an LDS read and three selects instead of a ~40-instruction cospif
 __device__ __forceinline__ float hann_tw(const float2* tw2, int m) {
+  constexpr int NFFT = 1024;
   const int r = m <= NFFT / 2 ? m : NFFT - m;
   const float c = r < 256 ? tw2[256 + r].x : (r == 256 ? 0.f : -tw2[256 + (512 - r)].x);
   return 0.5f - 0.5f * c;
 }
+// N = 512 / 2048: the pass-2 tables of those plans hold less than a quarter circle (k < 64 of 512; an eighth of 2048), so the
+// window comes from the device-wide table of svs_fft_hann (fft_tables.hip: sin^2(pi m / N) rounded from double, m <= N / 2)
+template <int NFFT>
+__device__ __forceinline__ float hann_tab(const float* __restrict__ tab, int m) { return tab[m <= NFFT / 2 ? m : NFFT - m]; }
 // one-instruction form (v_cos_f32 takes revolutions; absolute error ~1e-6): used where the window also divides out again
 // (the inverse's overlap-add / envelope), not for the forward magnitudes
+template <int NFFT>
 __device__ __forceinline__ float hann_fast(int m) { return 0.5f - 0.5f * __builtin_amdgcn_cosf((float)m * (1.0f / NFFT)); }
 
 // window sum-of-squares at padded position q (= sample index + n_fft/2) for T frames of hop `hop`
+template <int NFFT>
 __device__ __forceinline__ float envelope_at(int q, int hop, int T) {      // (32-bit: two 64-bit divisions per sample were most of the caller)
   if (q < 0) return 0.f;
   int t1 = (int)((unsigned)q / (unsigned)hop);
@@ -64,7 +69,7 @@ __device__ __forceinline__ float envelope_at(int q, int hop, int T) {      // (3
   int t0 = q - (NFFT - 1);
   t0 = t0 <= 0 ? 0 : (int)((unsigned)(t0 + hop - 1) / (unsigned)hop);
   float env = 0.f;
-  for (int t = t0; t <= t1; ++t) { const float w = hann_fast(q - t * hop); env += w * w; }
+  for (int t = t0; t <= t1; ++t) { const float w = hann_fast<NFFT>(q - t * hop); env += w * w; }
   return env;
 }
 
@@ -72,6 +77,9 @@ __device__ __forceinline__ float envelope_at(int q, int hop, int T) {      // (3
 // holds) go through the waves' own FFT buffers: wave w keeps the two values (frame 2w, frame 2w+1) of bin k as ONE
 // float2 at raw element k + w of its buffer (the + w skews the waves by one bank pair, so the 16 values of a row -- two
 // from each of the 8 buffers, BUF * 2 floats apart = 0 mod 32 banks -- come from 16 different banks).
+// The second plane of a transposed round (phasors of the odd frames, angles) lies BUF / 2 elements higher: k + w <= N / 2 + 7
+// stays below BUF / 2 = N / 2 + N / 32 for every N >= 512.
+template <int NFFT>
 __device__ __forceinline__ int xpose_at(int wave, int k) { return wave * FftSize<NFFT>::BUF + k + wave; }
 
 // ------------------------------------------------------------------------------------------------
@@ -86,12 +94,14 @@ struct StftArgs {
   float* absmax_partial;                                            // [gridDim.y * gridDim.x] or null
   // SINK_DMAG: d_logit[idx] += alpha * d|S| * mix[idx] * mask[idx] * (1 - mask[idx]), all in layout `lay`
   const float* angle; const float* mix; const float* mask; float* d_logit; float alpha;
-  const float2* twiddles;                                           // svs_fft_twiddles(NFFT): the device-wide table
+  const float2* twiddles;                                           // svs_fft_twiddles(N): the device-wide table
+  const float* hann;                                                // svs_fft_hann(N), N != 1024
 };
 
-template <int SRC, int SINK>
+template <int NFFT, int SRC, int SINK>
 __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int NBIN = NFFT / 2 + 1, NR = NFFT / 128 + 1;   // bins; bins per lane (9 = ceil(513 / 64))
   constexpr int BUF = FftSize<NFFT>::BUF, TW = FftSize<NFFT>::TW;
   float2* const fbuf = (float2*)smem;                       // [8][BUF]
   float2* const tw = fbuf + 8 * BUF;                        // [TW]
@@ -127,7 +137,7 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
       }
       if (SRC == SRC_ENVDIV) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { const float env = envelope_at((int)(q0 + j), p.hop, p.T); if (env > 1.1754944e-38f) v[r][h][j] *= __builtin_amdgcn_rcpf(env); }   // (as the inverse itself divides)
+        for (int j = 0; j < 4; ++j) { const float env = envelope_at<NFFT>((int)(q0 + j), p.hop, p.T); if (env > 1.1754944e-38f) v[r][h][j] *= __builtin_amdgcn_rcpf(env); }   // (as the inverse itself divides)
       }
     }
   }
@@ -138,13 +148,17 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
   for (int r = 0; r < NFFT / 256; ++r) {
     const int m0 = 4 * lane + 256 * r;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { const float w = hann_tw(tw2, m0 + j); buf[fft_pad(m0 + j)] = float2{v[r][0][j] * w, v[r][1][j] * w}; }
+    for (int j = 0; j < 4; ++j) {
+      float w;
+      if constexpr (NFFT == 1024) w = hann_tw(tw2, m0 + j); else w = hann_tab<NFFT>(p.hann, m0 + j);
+      buf[fft_pad(m0 + j)] = float2{v[r][0][j] * w, v[r][1][j] * w};
+    }
   }
   fft_wave<NFFT>(buf, tw, lane);
-  // ---- separate the two spectra, bins k = 0 .. 512, into registers (every Z is read before the buffer is reused)
-  float2 A[9], B[9];
+  // ---- separate the two spectra, bins k = 0 .. N / 2, into registers (every Z is read before the buffer is reused)
+  float2 A[NR], B[NR];
 #pragma unroll
-  for (int r = 0; r < 9; ++r) {
+  for (int r = 0; r < NR; ++r) {
     const int k = lane + 64 * r;
     A[r] = B[r] = float2{0.f, 0.f};
     if (k > NFFT / 2) continue;
@@ -155,7 +169,7 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
   fft_wave_sync();                                          // every lane has read Z before the buffer is rewritten below
   float vmax = 0.f;
 #pragma unroll
-  for (int r = 0; r < 9; ++r) {
+  for (int r = 0; r < NR; ++r) {
     const int k = lane + 64 * r;
     if (k > NFFT / 2) continue;
     float2 out;
@@ -181,7 +195,7 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
       const float sa = __builtin_amdgcn_sinf(ra), ca = __builtin_amdgcn_cosf(ra), sb = __builtin_amdgcn_sinf(rb), cb = __builtin_amdgcn_cosf(rb);
       out = float2{ck * (A[r].x * ca + (edge ? 0.f : A[r].y * sa)), ck * (B[r].x * cb + (edge ? 0.f : B[r].y * sb))};
     }
-    fbuf[xpose_at(wave, k)] = out;
+    fbuf[xpose_at<NFFT>(wave, k)] = out;
   }
   __syncthreads();
   // ---- rows out: 16 consecutive frames of a bin = one 64-byte run
@@ -192,7 +206,7 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
       const long cbase = p.lay.col(c, t);
       for (int k = tid >> 4; k < NBIN; k += 512 / GROUP) {
         if (k < p.lay.first_bin) continue;
-        const float v = t < p.T ? xp[2 * xpose_at(col >> 1, k) + (col & 1)] : 0.f;   // tile padding beyond the last frame is written as zeros
+        const float v = t < p.T ? xp[2 * xpose_at<NFFT>(col >> 1, k) + (col & 1)] : 0.f;   // tile padding beyond the last frame is written as zeros
         const long idx = cbase + (long)k * p.lay.seg;
         if (SINK == SINK_MAGPHASE) p.mag[idx] = v;
         else if (t < p.T) { const float m = p.mask[idx]; p.d_logit[idx] += p.alpha * v * p.mix[idx] * m * (1.f - m); }
@@ -201,21 +215,21 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
   }
   if (SINK == SINK_MAGPHASE && p.phase_mode == 2) {
     // f-major phasors (the .npy layout of data.py:108-109): a second transposed round, phasor of frame 2w at raw
-    // element k + w, of frame 2w+1 at 544 + k + w of the wave's buffer
+    // element k + w, of frame 2w+1 at BUF / 2 + k + w (544 + k + w) of the wave's buffer
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < 9; ++r) {
+    for (int r = 0; r < NR; ++r) {
       const int k = lane + 64 * r;
       if (k > NFFT / 2) continue;
       const float ma = sqrtf(A[r].x * A[r].x + A[r].y * A[r].y), mb = sqrtf(B[r].x * B[r].x + B[r].y * B[r].y);
-      fbuf[xpose_at(wave, k)] = ma == 0.f ? float2{1.f, 0.f} : float2{A[r].x / ma, A[r].y / ma};
-      fbuf[xpose_at(wave, k) + 544] = mb == 0.f ? float2{1.f, 0.f} : float2{B[r].x / mb, B[r].y / mb};
+      fbuf[xpose_at<NFFT>(wave, k)] = ma == 0.f ? float2{1.f, 0.f} : float2{A[r].x / ma, A[r].y / ma};
+      fbuf[xpose_at<NFFT>(wave, k) + BUF / 2] = mb == 0.f ? float2{1.f, 0.f} : float2{B[r].x / mb, B[r].y / mb};
     }
     __syncthreads();
     float2* ph = (float2*)p.phase;
     for (int e = tid; e < NBIN * GROUP; e += 512) {
       const int k = e / GROUP, col = e - k * GROUP, t = t0 + col;
-      if (t < p.T) ph[((long)c * NBIN + k) * p.T + t] = fbuf[xpose_at(col >> 1, k) + 544 * (col & 1)];
+      if (t < p.T) ph[((long)c * NBIN + k) * p.T + t] = fbuf[xpose_at<NFFT>(col >> 1, k) + (BUF / 2) * (col & 1)];
     }
   }
   if (p.absmax_partial) {
@@ -243,7 +257,7 @@ struct IstftArgs {
   int channels, T, hop;
   float* y; long n_out;                           // (channels, hop * (T - 1))
   float* absmax_partial;
-  const float2* twiddles;                         // svs_fft_twiddles(NFFT)
+  const float2* twiddles;                         // svs_fft_twiddles(N)
 };
 
 // A 512-thread block (8 waves) owns the padded samples [hop * t0, hop * (t0 + 15)) of one channel: exactly the 16 frames
@@ -255,11 +269,13 @@ struct IstftArgs {
 // blocks per CU, so one block's loads overlap the other's transform.
 // (Measured alternatives, 240 s stereo: one block per CU with per-element divisions 0.29 ms; persistent blocks with register
 // prefetch of the next group, 239 VGPRs, one block per CU 0.165 ms.)
-template <int PMODE>                                        // phase_mode as a template argument: only its registers exist
-__global__ __launch_bounds__(512, 2) void istft_kernel(IstftArgs p, int ngroups) {
+// N = 2048: 157,696 B of LDS, one block per CU (and its 256 VGPRs); N = 512: 39,424 B.
+template <int NFFT, int PMODE>                              // phase_mode as a template argument: only its registers exist
+__global__ __launch_bounds__(512, NFFT == 2048 ? 1 : 2) void istft_kernel(IstftArgs p, int ngroups) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int BUF = FftSize<NFFT>::BUF, TW = FftSize<NFFT>::TW, NW = 8, NF = 2 * NW;
-  constexpr int NIT = (NBIN * NF + 511) / 512;              // staged values per thread (17: 513 * 16 / 512)
+  constexpr int NBIN = NFFT / 2 + 1, NR = NFFT / 128 + 1;
+  constexpr int BUF = FftSize<NFFT>::BUF, NW = 8, NF = 2 * NW;
+  constexpr int NIT = (NBIN * NF + 511) / 512;             // staged values per thread (17: 513 * 16 / 512)
   float2* const fbuf = (float2*)smem;                       // [8][BUF]
   float2* const tw = fbuf + NW * BUF;
   float* const raw = (float*)fbuf;
@@ -293,12 +309,12 @@ __global__ __launch_bounds__(512, 2) void istft_kernel(IstftArgs p, int ngroups)
       if (PMODE == 3) sa[PMODE == 3 ? it : 0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rph, (int)off, 0, 0));
     }
   }
-  float2 pa[PMODE == 1 ? 9 : 1], pb[PMODE == 1 ? 9 : 1];
+  float2 pa[PMODE == 1 ? NR : 1], pb[PMODE == 1 ? NR : 1];
   const int ta = t0 - 1 + 2 * wave;
   if (PMODE == 1) {
     struct F2 { float x, y; };                              // (bit_cast: whatever 8-byte type the builtin returns)
 #pragma unroll
-    for (int r = 0; r < 9; ++r) {
+    for (int r = 0; r < NR; ++r) {
       const int k = lane + 64 * r;
       const bool oka = k <= NFFT / 2 && ta >= 0 && ta < p.T, okb = k <= NFFT / 2 && ta + 1 >= 0 && ta + 1 < p.T;
       const unsigned oa = oka ? (unsigned)(((long)c * p.T + ta) * NBIN + k) * 8u : OOB;
@@ -321,9 +337,9 @@ __global__ __launch_bounds__(512, 2) void istft_kernel(IstftArgs p, int ngroups)
   }
   __syncthreads();
   // spectra of this wave's two frames into registers (imaginary parts of DC / Nyquist dropped, as irfft does)
-  float2 Sa[9], Sb[9];
+  float2 Sa[NR], Sb[NR];
 #pragma unroll
-  for (int r = 0; r < 9; ++r) {
+  for (int r = 0; r < NR; ++r) {
     const int k = lane + 64 * r;
     Sa[r] = Sb[r] = float2{0.f, 0.f};
     if (k > NFFT / 2) continue;
@@ -344,7 +360,7 @@ __global__ __launch_bounds__(512, 2) void istft_kernel(IstftArgs p, int ngroups)
   // conj(Z) with Z = Sa + i Sb (Hermitian-extended): the forward transform of conj(Z) is conj(ifft(Z)) = a - i b
   fft_wave_sync();                                          // every lane has read its staged values before the buffer is refilled
 #pragma unroll
-  for (int r = 0; r < 9; ++r) {
+  for (int r = 0; r < NR; ++r) {
     const int k = lane + 64 * r;
     if (k > NFFT / 2) continue;
     buf[fft_pad(k)] = float2{Sa[r].x - Sb[r].y, -(Sa[r].y + Sb[r].x)};
@@ -361,7 +377,7 @@ __global__ __launch_bounds__(512, 2) void istft_kernel(IstftArgs p, int ngroups)
     const long ilo = NFFT / 2 - (long)p.hop * t0, ihi = p.n_out + ilo;       // valid e: ilo <= e < ihi
     auto emit = [&](int m, int fh_lo, int fh_hi) __attribute__((always_inline)) {
       const bool two = m + p.hop < NFFT;                    // frame fh - 1 still covers this position
-      const float w1 = hann_fast(m) * (1.0f / NFFT), w0 = two ? hann_fast(m + p.hop) * (1.0f / NFFT) : 0.f;
+      const float w1 = hann_fast<NFFT>(m) * (1.0f / NFFT), w0 = two ? hann_fast<NFFT>(m + p.hop) * (1.0f / NFFT) : 0.f;
       const float e1 = w1 * w1 * (float)(NFFT * NFFT), e0 = w0 * w0 * (float)(NFFT * NFFT);
       const int a1 = fft_pad(m), a0 = fft_pad(two ? m + p.hop : 0);
 #pragma unroll 4
@@ -407,16 +423,19 @@ __global__ __launch_bounds__(512, 2) void istft_kernel(IstftArgs p, int ngroups)
 
 // General overlap-add for ANY 0 < hop <= n_fft (data.py:24-25 lets --hop_size override the config, and config.py:14-25 records
 // runs at HOP_SIZE = 256: four frames per sample).  A block owns G hops = G * hop padded samples of one channel and walks the
-// frames that touch them, floor((n_fft - 1) / hop) + G of them, in rounds of 16 (two per wave, the same transform as above);
+// frames that touch them, floor((n_fft - 1) / hop) + G of them, in rounds of NF = 16 (two per wave, the same transform as above);
 // after each round every thread adds the round's frames into ITS OWN positions of an LDS accumulator (windowed sample and
 // squared window side by side: fixed frame order, no atomics), and after the last round divides and stores.  Slower than the
 // two-frames-per-sample kernel (one block per CU, divisions per position and round); that one keeps hop >= n_fft / 2.
-template <int PMODE>
-__global__ __launch_bounds__(512) void istft_general_kernel(IstftArgs p, int ngroups, int G, int rounds) {
+// NW waves per block (NF = 2 NW frames per round): 8, except N = 2048, where eight buffers and the twiddles fill 157,696 of the
+// CU's 163,840 B and leave no room for the accumulator -- four waves (88,064 B) leave 75,776 B (istft_plan below).
+template <int NFFT, int NW, int PMODE>
+__global__ __launch_bounds__(64 * NW) void istft_general_kernel(IstftArgs p, int ngroups, int G, int rounds) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int BUF = FftSize<NFFT>::BUF, TW = FftSize<NFFT>::TW, NW = 8, NF = 2 * NW;
-  constexpr int NIT = (NBIN * NF + 511) / 512;
-  float2* const fbuf = (float2*)smem;                       // [8][BUF]
+  constexpr int NBIN = NFFT / 2 + 1, NR = NFFT / 128 + 1, NT = 64 * NW;
+  constexpr int BUF = FftSize<NFFT>::BUF, TW = FftSize<NFFT>::TW, NF = 2 * NW;
+  constexpr int NIT = (NBIN * NF + NT - 1) / NT;
+  float2* const fbuf = (float2*)smem;                       // [NW][BUF]
   float2* const tw = fbuf + NW * BUF;
   float2* const acc = tw + TW;                              // [G * hop]: (sum of windowed samples, sum of squared windows)
   float* const raw = (float*)fbuf;
@@ -429,18 +448,18 @@ __global__ __launch_bounds__(512) void istft_general_kernel(IstftArgs p, int ngr
   const __amdgpu_buffer_rsrc_t rmask = __builtin_amdgcn_make_buffer_rsrc((void*)(p.mask ? p.mask : p.mag), 0, OOB, 0x00020000);
   const __amdgpu_buffer_rsrc_t rph = __builtin_amdgcn_make_buffer_rsrc((void*)p.phase, 0, OOB, 0x00020000);
   const bool has_mask = p.mask != nullptr;
-  fft_load_twiddles<NFFT>(tw, p.twiddles, tid, 512);
-  for (int i = tid; i < seg_len; i += 512) acc[i] = float2{0.f, 0.f};
+  fft_load_twiddles<NFFT>(tw, p.twiddles, tid, NT);
+  for (int i = tid; i < seg_len; i += NT) acc[i] = float2{0.f, 0.f};
   for (int r = 0; r < rounds; ++r) {
     const int tb = t0 - halo + NF * r;                      // first frame of this round
     __syncthreads();                                        // the previous round's buffers have been consumed (and, r = 0: twiddles)
-    // ---- stage: this thread's frame column (16 frames x 513 bins through the waves' buffers, as in istft_kernel)
+    // ---- stage: this thread's frame column (NF frames x NBIN bins through the waves' buffers, as in istft_kernel)
     {
       const int tf = tb + (tid & (NF - 1));
       const bool tok = tf >= 0 && tf < p.T;
       const unsigned cbase = tok ? (unsigned)p.lay.col(c, tf) : 0u;
       for (int it = 0; it < NIT; ++it) {
-        const int k = (tid >> 4) + (512 / NF) * it;
+        const int k = tid / NF + (NT / NF) * it;
         if (k >= NBIN) continue;
         const bool ok = tok && k >= p.lay.first_bin;
         const unsigned off = ok ? (cbase + (unsigned)(k * p.lay.seg)) * 4u : OOB;
@@ -457,9 +476,9 @@ __global__ __launch_bounds__(512) void istft_general_kernel(IstftArgs p, int ngr
     __syncthreads();
     // ---- spectra of this wave's two frames, Hermitian-extended conj(Sa + i Sb), one transform
     const int ta = tb + 2 * wave;
-    float2 Sa[9], Sb[9];
+    float2 Sa[NR], Sb[NR];
 #pragma unroll
-    for (int q = 0; q < 9; ++q) {
+    for (int q = 0; q < NR; ++q) {
       const int k = lane + 64 * q;
       Sa[q] = Sb[q] = float2{0.f, 0.f};
       if (k > NFFT / 2) continue;
@@ -486,7 +505,7 @@ __global__ __launch_bounds__(512) void istft_general_kernel(IstftArgs p, int ngr
     }
     fft_wave_sync();                                        // every lane has read its staged values before the buffer is refilled
 #pragma unroll
-    for (int q = 0; q < 9; ++q) {
+    for (int q = 0; q < NR; ++q) {
       const int k = lane + 64 * q;
       if (k > NFFT / 2) continue;
       buf[fft_pad(k)] = float2{Sa[q].x - Sb[q].y, -(Sa[q].y + Sb[q].x)};
@@ -495,7 +514,7 @@ __global__ __launch_bounds__(512) void istft_general_kernel(IstftArgs p, int ngr
     fft_wave<NFFT>(buf, tw, lane);
     __syncthreads();
     // ---- accumulate: position i (padded sample hop * t0 + i) takes every frame of this round that covers it, ascending
-    for (int i = tid; i < seg_len; i += 512) {
+    for (int i = tid; i < seg_len; i += NT) {
       const int q = p.hop * t0 + i;
       int lo = q - (NFFT - 1);
       lo = lo <= 0 ? 0 : (int)((unsigned)(lo + p.hop - 1) / (unsigned)p.hop);
@@ -507,7 +526,7 @@ __global__ __launch_bounds__(512) void istft_general_kernel(IstftArgs p, int ngr
       for (int t = lo; t <= hi; ++t) {
         const int f = t - tb, m = q - t * p.hop;
         const float2 z = fbuf[(f >> 1) * BUF + fft_pad(m)];
-        const float w = hann_fast(m);
+        const float w = hann_fast<NFFT>(m);
         a.x += ((f & 1) ? -z.y : z.x) * (w * (1.0f / NFFT));
         a.y += w * w;
       }
@@ -516,7 +535,7 @@ __global__ __launch_bounds__(512) void istft_general_kernel(IstftArgs p, int ngr
   }
   // ---- divide by the window envelope, store, |.|max
   float vmax = 0.f;
-  for (int i = tid; i < seg_len; i += 512) {
+  for (int i = tid; i < seg_len; i += NT) {
     const long e = (long)p.hop * t0 + i - NFFT / 2;
     if (e < 0 || e >= p.n_out) continue;
     const float2 a = acc[i];
@@ -556,109 +575,171 @@ __global__ __launch_bounds__(256) void transpose_c64_kernel(const float2* __rest
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static size_t fwd_lds_bytes(bool dmag) {       // 79,872 B: two blocks per CU
-  return (size_t)8 * FftSize<NFFT>::BUF * 8 + FftSize<NFFT>::TW * 8 + (dmag ? NBIN * SROW * 4 : 0);
+static bool nfft_built(int n) { return n == 512 || n == 1024 || n == 2048; }
+#define SVS_REQUIRE_NFFT(who, n) SVS_REQUIRE(nfft_built(n), who ": n_fft must be 512, 1024 or 2048 (the sizes that are built), got %d", n)
+static size_t fft_lds_bytes(int n_fft, int waves) {       // the waves' buffers and the twiddle table
+  const size_t buf = n_fft == 512 ? FftSize<512>::BUF : n_fft == 1024 ? FftSize<1024>::BUF : FftSize<2048>::BUF;
+  const size_t tw = n_fft == 512 ? FftSize<512>::TW : n_fft == 1024 ? FftSize<1024>::TW : FftSize<2048>::TW;
+  return (size_t)waves * buf * 8 + tw * 8;
 }
-static size_t inv_lds_bytes() { return (size_t)8 * FftSize<NFFT>::BUF * 8 + FftSize<NFFT>::TW * 8; }    // 79,872 B: two blocks per CU
+// forward and two-frames-per-sample inverse, eight waves: 39,424 B (512), 79,872 B (1024: two blocks per CU), 157,696 B (2048)
+static size_t fwd_lds_bytes(int n_fft, bool dmag) { return fft_lds_bytes(n_fft, 8) + (dmag ? (size_t)(n_fft / 2 + 1) * SROW * 4 : 0); }
 template <class K>
 static int allow_lds(K kernel, size_t bytes) {
   SVS_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   return SVS_OK;
 }
-static int check_layout(const char* who, int seg, int rows, int first_bin, int frames_alloc, int T) {
-  SVS_REQUIRE(seg > 0 && (first_bin == 0 || first_bin == 1) && rows == NBIN - first_bin && frames_alloc >= T,
+static int check_layout(const char* who, int n_fft, int seg, int rows, int first_bin, int frames_alloc, int T) {
+  SVS_REQUIRE(seg > 0 && (first_bin == 0 || first_bin == 1) && rows == n_fft / 2 + 1 - first_bin && frames_alloc >= T,
               "%s: bad spectrogram layout (seg=%d rows=%d first_bin=%d frames_alloc=%d T=%d)", who, seg, rows, first_bin, frames_alloc, T);
   return SVS_OK;
 }
 
 extern "C" int svs_stft_frames(int64_t n_samples, int hop) { return hop > 0 && n_samples >= 0 ? (int)(1 + n_samples / hop) : -1; }
 
-extern "C" int svs_stft_tiles(const float* y, int64_t n_samples, int channels, int n_fft, int hop, float* mag, int64_t chan_stride,
-                              int seg, int rows, int first_bin, int frames_alloc, float* phase, int phase_mode,
-                              float* absmax_partial, hipStream_t stream) {
+template <int N>
+static int launch_stft_fwd(StftArgs& a, int frames_alloc, hipStream_t stream) {
+  int rc = svs_fft_twiddles(N, stream, &a.twiddles);
+  if (rc) return rc;
+  if (N != 1024 && (rc = svs_fft_hann(N, stream, &a.hann))) return rc;
+  const size_t lds = fwd_lds_bytes(N, false);
+  if ((rc = allow_lds(stft_fwd_kernel<N, SRC_SIGNAL, SINK_MAGPHASE>, lds))) return rc;
+  dim3 grid((unsigned)((frames_alloc + GROUP - 1) / GROUP), (unsigned)a.channels);
+  hipLaunchKernelGGL((stft_fwd_kernel<N, SRC_SIGNAL, SINK_MAGPHASE>), grid, dim3(512), lds, stream, a);
+  SVS_CHECK_LAUNCH("stft_fwd");
+  return SVS_OK;
+}
+
+extern "C" int svs_stft_tiles_n(const float* y, int64_t n_samples, int channels, int n_fft, int hop, float* mag, int64_t chan_stride,
+                                int seg, int rows, int first_bin, int frames_alloc, float* phase, int phase_mode,
+                                float* absmax_partial, hipStream_t stream) {
   SVS_REQUIRE(y && mag && n_samples > 0 && channels > 0 && hop > 0, "svs_stft_tiles: bad arguments");
-  SVS_REQUIRE(n_fft == NFFT, "svs_stft_tiles: only n_fft=1024 (reference config.py:47) is built, got %d", n_fft);
+  SVS_REQUIRE_NFFT("svs_stft_tiles_n", n_fft);
   SVS_REQUIRE(phase_mode >= 0 && phase_mode <= 2 && (phase_mode == 0 || (phase && (((uintptr_t)phase) & 7u) == 0)), "svs_stft_tiles: bad phase arguments");
   const int T = (int)(1 + n_samples / hop);
-  int rc = check_layout("svs_stft_tiles", seg, rows, first_bin, frames_alloc, T);
+  int rc = check_layout("svs_stft_tiles", n_fft, seg, rows, first_bin, frames_alloc, T);
   if (rc) return rc;
   StftArgs a{};
   a.y = y; a.n_samples = n_samples; a.channels = channels; a.hop = hop; a.T = T;
   a.mag = mag; a.lay = SpecLayout{chan_stride, seg, rows, first_bin, frames_alloc};
   a.phase = phase; a.phase_mode = phase_mode; a.absmax_partial = absmax_partial;
-  if ((rc = svs_fft_twiddles(NFFT, stream, &a.twiddles))) return rc;
-  const size_t lds = fwd_lds_bytes(false);
-  if ((rc = allow_lds(stft_fwd_kernel<SRC_SIGNAL, SINK_MAGPHASE>, lds))) return rc;
-  dim3 grid((unsigned)((frames_alloc + GROUP - 1) / GROUP), (unsigned)channels);
-  hipLaunchKernelGGL((stft_fwd_kernel<SRC_SIGNAL, SINK_MAGPHASE>), grid, dim3(512), lds, stream, a);
-  SVS_CHECK_LAUNCH("stft_fwd");
-  return SVS_OK;
+  return n_fft == 512 ? launch_stft_fwd<512>(a, frames_alloc, stream)
+       : n_fft == 1024 ? launch_stft_fwd<1024>(a, frames_alloc, stream) : launch_stft_fwd<2048>(a, frames_alloc, stream);
 }
+extern "C" int svs_stft_tiles(const float* y, int64_t n_samples, int channels, int n_fft, int hop, float* mag, int64_t chan_stride,
+                              int seg, int rows, int first_bin, int frames_alloc, float* phase, int phase_mode,
+                              float* absmax_partial, hipStream_t stream) {
+  SVS_REQUIRE(y && mag && n_samples > 0 && channels > 0 && hop > 0, "svs_stft_tiles: bad arguments");
+  SVS_REQUIRE(n_fft == 1024, "svs_stft_tiles: only n_fft=1024 (reference config.py:47) is built, got %d", n_fft);
+  return svs_stft_tiles_n(y, n_samples, channels, n_fft, hop, mag, chan_stride, seg, rows, first_bin, frames_alloc, phase, phase_mode,
+                          absmax_partial, stream);
+}
+// blocks per channel of the forward = absmax partials per channel: 16 frames per block at every n_fft
 extern "C" int svs_stft_groups(int frames_alloc) { return (frames_alloc + GROUP - 1) / GROUP; }
+extern "C" int svs_stft_groups_n(int n_fft, int frames_alloc) {
+  SVS_REQUIRE_NFFT("svs_stft_groups_n", n_fft);
+  return svs_stft_groups(frames_alloc);
+}
 
 extern "C" int svs_stft_fwd(const float* y, int64_t n_samples, int n_fft, int hop, float* mag, float* phase, hipStream_t stream) {
   SVS_REQUIRE(y && mag && n_samples > 0 && hop > 0, "svs_stft_fwd: bad arguments");
   const int T = (int)(1 + n_samples / hop);
-  return svs_stft_tiles(y, n_samples, 1, n_fft, hop, mag, (int64_t)NBIN * T, T, NBIN, 0, T, phase, phase ? 2 : 0, nullptr, stream);
+  return svs_stft_tiles(y, n_samples, 1, n_fft, hop, mag, (int64_t)513 * T, T, 513, 0, T, phase, phase ? 2 : 0, nullptr, stream);
 }
 
-// hops per block and rounds of 16 frames of the general kernel: G + floor((n_fft - 1) / hop) frames touch G hops; one round
-// while the halo leaves at least 4 hops of it (hop >= 86), else enough rounds that at least half of every round is new hops
-static void istft_general_plan(int hop, int* G, int* rounds) {
-  const int halo = (NFFT - 1) / hop;
-  *rounds = halo <= 12 ? 1 : (halo + 7) / 8;
-  *G = 16 * *rounds - halo;
+// The inverse's launch plan: the one value that the launch, svs_istft_groups_n and svs_istft_plan_n read.
+//   hop >= n_fft / 2: istft_kernel, eight waves, 15 hops per block (they touch 16 frames), one round.
+//   hop <  n_fft / 2: istft_general_kernel.  G + halo frames touch G hops, halo = floor((n_fft - 1) / hop); they are walked in
+//     rounds of NF = 2 * waves frames: one round while the halo leaves at least 4 hops of it (n_fft 1024: hop >= 86), else enough
+//     rounds that at least half of every round is new hops.  waves = 8, except n_fft = 2048, where eight buffers leave 6 KB of the
+//     CU's 160 KiB and the accumulator (G * hop * 8 B, up to 6 * 1023 * 8) needs 49 KB: four waves, eight frames per round.
+struct IstftPlan { bool general; int waves, G, rounds; size_t lds; };
+static IstftPlan istft_plan(int n_fft, int hop) {
+  IstftPlan pl{};
+  pl.general = hop < n_fft / 2;
+  if (!pl.general) { pl.waves = 8; pl.G = IGROUP; pl.rounds = 1; pl.lds = fft_lds_bytes(n_fft, 8); return pl; }
+  pl.waves = n_fft == 2048 ? 4 : 8;
+  const int nf = 2 * pl.waves, halo = (n_fft - 1) / hop;
+  pl.rounds = halo <= nf - 4 ? 1 : (halo + nf / 2 - 1) / (nf / 2);
+  pl.G = nf * pl.rounds - halo;
+  pl.lds = fft_lds_bytes(n_fft, pl.waves) + (size_t)pl.G * hop * 8;
+  return pl;
 }
-// padded length n_fft + hop * (T - 1): the last samples belong to group floor((padded - 1) / (G hop)), G = 15 hops per block
-// of the two-frames-per-sample kernel (hop >= n_fft / 2), istft_general_plan's below it
-static int svs_istft_groups_per_channel(int hop, int frames) {
-  int G = IGROUP, rounds;
-  if (hop < NFFT / 2) istft_general_plan(hop, &G, &rounds);
-  return (int)((NFFT + (long)hop * (frames - 1) + (long)G * hop - 1) / ((long)G * hop));
+// padded length n_fft + hop * (T - 1): the last samples belong to group floor((padded - 1) / (G hop))
+static int svs_istft_groups_per_channel(int n_fft, int hop, int frames) {
+  const long span = (long)istft_plan(n_fft, hop).G * hop;
+  return (int)((n_fft + (long)hop * (frames - 1) + span - 1) / span);
 }
 // blocks per channel of svs_istft_tiles = absmax partials per channel (layout [channel][group])
-extern "C" int svs_istft_groups(int hop, int frames, int channels) { (void)channels; return svs_istft_groups_per_channel(hop, frames); }
+extern "C" int svs_istft_groups(int hop, int frames, int channels) { (void)channels; return svs_istft_groups_per_channel(1024, hop, frames); }
+extern "C" int svs_istft_groups_n(int n_fft, int hop, int frames, int channels) {
+  (void)channels;
+  SVS_REQUIRE_NFFT("svs_istft_groups_n", n_fft);
+  SVS_REQUIRE(hop > 0 && hop <= n_fft && frames > 0, "svs_istft_groups_n: need 0 < hop <= n_fft and frames > 0 (hop=%d frames=%d)", hop, frames);
+  return svs_istft_groups_per_channel(n_fft, hop, frames);
+}
+extern "C" int svs_istft_plan_n(int n_fft, int hop, int* hops_per_block, int* rounds, size_t* lds_bytes) {
+  SVS_REQUIRE_NFFT("svs_istft_plan_n", n_fft);
+  SVS_REQUIRE(hop > 0 && hop <= n_fft, "svs_istft_plan_n: hop %d is not in 1..n_fft (a larger hop leaves samples that no frame covers)", hop);
+  const IstftPlan pl = istft_plan(n_fft, hop);
+  if (hops_per_block) *hops_per_block = pl.G;
+  if (rounds) *rounds = pl.rounds;
+  if (lds_bytes) *lds_bytes = pl.lds;
+  return SVS_OK;
+}
 
-extern "C" int svs_istft_tiles(const float* mag, int64_t chan_stride, int seg, int rows, int first_bin, const float* mask, int invert,
-                               const float* phase, int phase_mode, int channels, int n_fft, int hop, int frames, float* y,
-                               float* absmax_partial, hipStream_t stream) {
+template <int N, int NW>
+static int launch_istft(IstftArgs& a, const IstftPlan& pl, int ngroups, hipStream_t stream) {
+  int rc = svs_fft_twiddles(N, stream, &a.twiddles);
+  if (rc) return rc;
+  const dim3 grid((unsigned)((long)ngroups * a.channels));
+  if (pl.general) {                               // more than two frames per sample: the general overlap-add
+    if ((rc = a.phase_mode == 1 ? allow_lds(istft_general_kernel<N, NW, 1>, pl.lds) : allow_lds(istft_general_kernel<N, NW, 3>, pl.lds))) return rc;
+    if (a.phase_mode == 1) hipLaunchKernelGGL((istft_general_kernel<N, NW, 1>), grid, dim3(64 * NW), pl.lds, stream, a, ngroups, pl.G, pl.rounds);
+    else hipLaunchKernelGGL((istft_general_kernel<N, NW, 3>), grid, dim3(64 * NW), pl.lds, stream, a, ngroups, pl.G, pl.rounds);
+    SVS_CHECK_LAUNCH("istft_general");
+    return SVS_OK;
+  }
+  if ((rc = a.phase_mode == 1 ? allow_lds(istft_kernel<N, 1>, pl.lds) : allow_lds(istft_kernel<N, 3>, pl.lds))) return rc;
+  if (a.phase_mode == 1) hipLaunchKernelGGL((istft_kernel<N, 1>), grid, dim3(512), pl.lds, stream, a, ngroups);
+  else hipLaunchKernelGGL((istft_kernel<N, 3>), grid, dim3(512), pl.lds, stream, a, ngroups);
+  SVS_CHECK_LAUNCH("istft");
+  return SVS_OK;
+}
+
+extern "C" int svs_istft_tiles_n(const float* mag, int64_t chan_stride, int seg, int rows, int first_bin, const float* mask, int invert,
+                                 const float* phase, int phase_mode, int channels, int n_fft, int hop, int frames, float* y,
+                                 float* absmax_partial, hipStream_t stream) {
   SVS_REQUIRE(mag && phase && y && hop > 0 && frames > 1 && channels > 0, "svs_istft_tiles: bad arguments (need >= 2 frames)");
-  SVS_REQUIRE(n_fft == NFFT, "svs_istft_tiles: only n_fft=1024 (reference config.py:47) is built, got %d", n_fft);
-  SVS_REQUIRE(hop <= NFFT, "svs_istft_tiles: hop %d > n_fft leaves samples that no frame covers", hop);
+  SVS_REQUIRE_NFFT("svs_istft_tiles_n", n_fft);
+  SVS_REQUIRE(hop <= n_fft, "svs_istft_tiles: hop %d > n_fft leaves samples that no frame covers", hop);
   SVS_REQUIRE(phase_mode == 1 || phase_mode == 3, "svs_istft_tiles: phase_mode must be 1 (frame-major phasors) or 3 (angles)");
-  SVS_REQUIRE((long)channels * (chan_stride > (long)frames * NBIN ? chan_stride : (long)frames * NBIN) * 8 < (1L << 31),
+  const long nbin = n_fft / 2 + 1;
+  SVS_REQUIRE((long)channels * (chan_stride > (long)frames * nbin ? chan_stride : (long)frames * nbin) * 8 < (1L << 31),
               "svs_istft_tiles: a spectrogram view of more than 2 GiB needs 64-bit offsets; split the channels");
-  int rc = check_layout("svs_istft_tiles", seg, rows, first_bin, frames, frames);
+  int rc = check_layout("svs_istft_tiles", n_fft, seg, rows, first_bin, frames, frames);
   if (rc) return rc;
   IstftArgs a{};
   a.mag = mag; a.lay = SpecLayout{chan_stride, seg, rows, first_bin, frames};
   a.mask = mask; a.invert = invert; a.phase = phase; a.phase_mode = phase_mode;
   a.channels = channels; a.T = frames; a.hop = hop; a.y = y; a.n_out = (long)hop * (frames - 1);
   a.absmax_partial = absmax_partial;
-  if ((rc = svs_fft_twiddles(NFFT, stream, &a.twiddles))) return rc;
-  const int ngroups = svs_istft_groups_per_channel(hop, frames);
-  const long total = (long)ngroups * channels;
-  const dim3 grid((unsigned)total);
-  if (hop < NFFT / 2) {                          // more than two frames per sample: the general overlap-add
-    int G, rounds;
-    istft_general_plan(hop, &G, &rounds);
-    const size_t lds = inv_lds_bytes() + (size_t)G * hop * 8;
-    if ((rc = phase_mode == 1 ? allow_lds(istft_general_kernel<1>, lds) : allow_lds(istft_general_kernel<3>, lds))) return rc;
-    if (phase_mode == 1) hipLaunchKernelGGL(istft_general_kernel<1>, grid, dim3(512), lds, stream, a, ngroups, G, rounds);
-    else hipLaunchKernelGGL(istft_general_kernel<3>, grid, dim3(512), lds, stream, a, ngroups, G, rounds);
-    SVS_CHECK_LAUNCH("istft_general");
-    return SVS_OK;
-  }
-  const size_t lds = inv_lds_bytes();
-  if ((rc = phase_mode == 1 ? allow_lds(istft_kernel<1>, lds) : allow_lds(istft_kernel<3>, lds))) return rc;
-  if (phase_mode == 1) hipLaunchKernelGGL(istft_kernel<1>, grid, dim3(512), lds, stream, a, ngroups);
-  else hipLaunchKernelGGL(istft_kernel<3>, grid, dim3(512), lds, stream, a, ngroups);
-  SVS_CHECK_LAUNCH("istft");
-  return SVS_OK;
+  const IstftPlan pl = istft_plan(n_fft, hop);
+  const int ngroups = svs_istft_groups_per_channel(n_fft, hop, frames);
+  return n_fft == 512 ? launch_istft<512, 8>(a, pl, ngroups, stream)
+       : n_fft == 1024 ? launch_istft<1024, 8>(a, pl, ngroups, stream) : launch_istft<2048, 4>(a, pl, ngroups, stream);
+}
+extern "C" int svs_istft_tiles(const float* mag, int64_t chan_stride, int seg, int rows, int first_bin, const float* mask, int invert,
+                               const float* phase, int phase_mode, int channels, int n_fft, int hop, int frames, float* y,
+                               float* absmax_partial, hipStream_t stream) {
+  SVS_REQUIRE(mag && phase && y && hop > 0 && frames > 1 && channels > 0, "svs_istft_tiles: bad arguments (need >= 2 frames)");
+  SVS_REQUIRE(n_fft == 1024, "svs_istft_tiles: only n_fft=1024 (reference config.py:47) is built, got %d", n_fft);
+  return svs_istft_tiles_n(mag, chan_stride, seg, rows, first_bin, mask, invert, phase, phase_mode, channels, n_fft, hop, frames, y,
+                           absmax_partial, stream);
 }
 extern "C" size_t svs_istft_workspace_bytes(int n_fft, int hop, int frames) {
-  (void)n_fft; (void)hop;
-  return (size_t)frames * NBIN * 8 + 256;           // frame-major copy of f-major phasors
+  (void)hop;
+  return (size_t)frames * (n_fft / 2 + 1) * 8 + 256;           // frame-major copy of f-major phasors
 }
 
 extern "C" int svs_transpose_c64(const float* in, float* out, int rows, int cols, hipStream_t stream) {
@@ -672,6 +753,8 @@ extern "C" int svs_transpose_c64(const float* in, float* out, int rows, int cols
 extern "C" int svs_istft(const float* mag, const float* phase, int phase_is_angle, int n_fft, int hop, int frames, float* y,
                          void* ws, size_t ws_bytes, hipStream_t stream) {
   SVS_REQUIRE(mag && phase && y && hop > 0 && frames > 1, "svs_istft: bad arguments (need >= 2 frames)");
+  SVS_REQUIRE(n_fft == 1024, "svs_istft: only n_fft=1024 (reference config.py:47) is built, got %d", n_fft);
+  constexpr int NBIN = 513;
   if (phase_is_angle)
     return svs_istft_tiles(mag, (int64_t)NBIN * frames, frames, NBIN, 0, nullptr, 0, phase, 3, 1, n_fft, hop, frames, y, nullptr, stream);
   if (!ws || ws_bytes < svs_istft_workspace_bytes(n_fft, hop, frames) || !svs_aligned16(ws)) { svs_set_error("svs_istft: workspace too small"); return SVS_ERR_WORKSPACE; }
@@ -682,21 +765,23 @@ extern "C" int svs_istft(const float* mag, const float* phase, int phase_is_angl
 
 // Transpose of the differentiable inverse of train.py:33-60 (`specific_istft`), fused with the mask's chain rule:
 //   d_logit[b, f, t] += alpha * dL/d|S|[b, f+1, t] * mix * mask * (1 - mask),   |S| = mask * mix (train.py:275,288)
-// d_wav: (B, hop * (T - 1)); angle / mix / mask / d_logit: (B, 1, 512, T) training tiles.
+// d_wav: (B, hop * (T - 1)); angle / mix / mask / d_logit: (B, 1, 512, T) training tiles.  n_fft = 1024 only: training runs at
+// the config's window (ResidentSpectrograms' 512-row tiles, the multi-resolution objective's H == 512).
 extern "C" int svs_istft_bwd_mask(const float* d_wav, const float* angle, const float* mix, const float* mask, float* d_logit,
                                   float alpha, int B, int n_fft, int hop, int frames, hipStream_t stream) {
   SVS_REQUIRE(d_wav && angle && mix && mask && d_logit && B > 0 && frames > 1 && hop > 0, "svs_istft_bwd_mask: bad arguments");
-  SVS_REQUIRE(n_fft == NFFT, "svs_istft_bwd_mask: only n_fft=1024 is built, got %d", n_fft);
+  SVS_REQUIRE(n_fft == 1024, "svs_istft_bwd_mask: only n_fft=1024 is built, got %d", n_fft);
+  constexpr int NFFT = 1024, NBIN = NFFT / 2 + 1;
   StftArgs a{};
   a.y = d_wav; a.n_samples = (long)hop * (frames - 1); a.channels = B; a.hop = hop; a.T = frames;
   a.lay = SpecLayout{(long)(NBIN - 1) * frames, frames, NBIN - 1, 1, frames};
   a.angle = angle; a.mix = mix; a.mask = mask; a.d_logit = d_logit; a.alpha = alpha;
-  const size_t lds = fwd_lds_bytes(true);
-  int rc = allow_lds(stft_fwd_kernel<SRC_ENVDIV, SINK_DMAG>, lds);
+  const size_t lds = fwd_lds_bytes(NFFT, true);
+  int rc = allow_lds(stft_fwd_kernel<NFFT, SRC_ENVDIV, SINK_DMAG>, lds);
   if (rc) return rc;
   if ((rc = svs_fft_twiddles(NFFT, stream, &a.twiddles))) return rc;
   dim3 grid((unsigned)((frames + GROUP - 1) / GROUP), (unsigned)B);
-  hipLaunchKernelGGL((stft_fwd_kernel<SRC_ENVDIV, SINK_DMAG>), grid, dim3(512), lds, stream, a);
+  hipLaunchKernelGGL((stft_fwd_kernel<NFFT, SRC_ENVDIV, SINK_DMAG>), grid, dim3(512), lds, stream, a);
   SVS_CHECK_LAUNCH("istft_bwd");
   return SVS_OK;
 }

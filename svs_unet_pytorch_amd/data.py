@@ -7,7 +7,7 @@ normalisations running in the gfx950 kernels of csrc/stft.hip instead of librosa
 
 to_spec (data.py:46-112): per song folder, mixture.wav fixes the normalisation (its maximum magnitude,
 data.py:84-85); mixture.wav and vocals.wav are STFT'd (n_fft=--win_size, hop=--hop_size, periodic Hann,
-centred), divided by that maximum (data.py:105) and saved as NNNN_<song>_spec.npy (float32 (513,T)) and
+centred), divided by that maximum (data.py:105) and saved as NNNN_<song>_spec.npy (float32 (win_size/2+1,T)) and
 NNNN_<song>_phase.npy (complex64 unit phasors) under <tar>/mixture and <tar>/vocal (data.py:107-109).
 to_wave (data.py:117-169): <name>_spec.npy times its phase -> inverse STFT -> peak-normalise to 0.9 ->
 <name>.wav at --sr, float32 samples.  With --sr_out RATE and / or --subtype PCM_16 | PCM_32 the waveform is instead
@@ -39,34 +39,53 @@ from . import _lib
 from .config import HOP_SIZE, SAMPLE_RATE, WINDOW_SIZE, num2str
 
 TRACK_MAP = {"mixture.wav": "mixture", "vocals.wav": "vocal"}      # data.py:40-43
+WINDOW_SIZES = (512, 1024, 2048)                                    # the n_fft the transforms of csrc/stft.hip are built for
+
+
+def _check_window(n_fft: int, hop: int):
+    if n_fft not in WINDOW_SIZES:
+        raise ValueError(f"n_fft = {n_fft}: the STFT / iSTFT kernels are built for n_fft in {WINDOW_SIZES}")
+    if not 0 < hop <= n_fft:
+        raise ValueError(f"hop = {hop}: must be in 1..{n_fft} (a larger hop leaves samples that no frame covers)")
 
 
 # ------------------------------------------------------------------------------------------------
 # GPU signal path
 # ------------------------------------------------------------------------------------------------
 def stft_magphase(y: torch.Tensor, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE):
-    """float32 (n,) on the GPU -> (mag float32 (513,T), phase complex64 (513,T)), both on the GPU."""
+    """float32 (n,) on the GPU -> (mag float32 (n_fft/2+1,T), phase complex64 (n_fft/2+1,T)), both on the GPU."""
+    _check_window(n_fft, hop)                  # (the buffers below are sized by n_fft before the library sees it)
     L = _lib.lib()
     y = y.contiguous().float()
     T = int(L.svs_stft_frames(y.numel(), hop))
-    mag = torch.empty((n_fft // 2 + 1, T), dtype=torch.float32, device=y.device)
-    ph = torch.empty((n_fft // 2 + 1, T, 2), dtype=torch.float32, device=y.device)
-    _lib.check(L.svs_stft_fwd(y.data_ptr(), y.numel(), n_fft, hop, mag.data_ptr(), ph.data_ptr(), _lib.stream_ptr()), "svs_stft_fwd")
+    nbin = n_fft // 2 + 1
+    mag = torch.empty((nbin, T), dtype=torch.float32, device=y.device)
+    ph = torch.empty((nbin, T, 2), dtype=torch.float32, device=y.device)
+    _lib.check(L.svs_stft_tiles_n(y.data_ptr(), y.numel(), 1, n_fft, hop, mag.data_ptr(), nbin * T, T, nbin, 0, T, ph.data_ptr(), 2, None,
+                                  _lib.stream_ptr()), "svs_stft_tiles_n")
     return mag, torch.view_as_complex(ph)
 
 
 def istft(mag: torch.Tensor, phase: torch.Tensor, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE, peak: float | None = None):
-    """mag float32 (513,T) and phase (complex64 unit phasors, or float32 angles) -> float32 (hop*(T-1),).
+    """mag float32 (n_fft/2+1,T) and phase (complex64 unit phasors, or float32 angles) -> float32 (hop*(T-1),).
     `peak`: scale so that max|y| == peak (data.py:162-164); None leaves the amplitude alone."""
+    _check_window(n_fft, hop)
     L = _lib.lib()
     mag = mag.contiguous().float()
-    T = mag.shape[1]
+    nbin, T = mag.shape
+    if nbin != n_fft // 2 + 1 or tuple(phase.shape) != (nbin, T):
+        raise ValueError(f"istft: magnitude {tuple(mag.shape)} / phase {tuple(phase.shape)} are not ({n_fft // 2 + 1}, T) for n_fft = {n_fft}")
     is_angle = not torch.is_complex(phase)
     ph = phase.contiguous().float() if is_angle else torch.view_as_real(phase.contiguous().to(torch.complex64)).contiguous()
-    y = torch.empty(hop * (T - 1), dtype=torch.float32, device=mag.device)
+    y = torch.empty(hop * max(T - 1, 0), dtype=torch.float32, device=mag.device)
     ws = torch.empty(int(L.svs_istft_workspace_bytes(n_fft, hop, T)) + 4096, dtype=torch.uint8, device=mag.device)
-    _lib.check(L.svs_istft(mag.data_ptr(), ph.data_ptr(), 1 if is_angle else 0, n_fft, hop, T, y.data_ptr(), ws.data_ptr(), ws.numel(),
-                           _lib.stream_ptr()), "svs_istft")
+    if is_angle:
+        src, mode = ph, 3
+    else:                                      # f-major phasors of a .npy file -> the frame-major form the kernels stream
+        _lib.check(L.svs_transpose_c64(ph.data_ptr(), ws.data_ptr(), nbin, T, _lib.stream_ptr()), "svs_transpose_c64")
+        src, mode = ws, 1
+    _lib.check(L.svs_istft_tiles_n(mag.data_ptr(), nbin * T, T, nbin, 0, None, 0, src.data_ptr(), mode, 1, n_fft, hop, T, y.data_ptr(), None,
+                                   _lib.stream_ptr()), "svs_istft_tiles_n")
     if peak is not None:
         pk = torch.empty(1, dtype=torch.float32, device=mag.device)
         _lib.check(L.svs_absmax(y.data_ptr(), y.numel(), pk.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "svs_absmax")
@@ -75,14 +94,15 @@ def istft(mag: torch.Tensor, phase: torch.Tensor, n_fft: int = WINDOW_SIZE, hop:
 
 
 def specific_istft(magnitude: torch.Tensor, phase: torch.Tensor, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE):
-    """train.py:33-60: (B,1,512,T) magnitude and angle (DC row dropped) -> (B,1,hop*(T-1)) waveforms, ONE launch for the
+    """train.py:33-60: (B,1,n_fft/2,T) magnitude and angle (DC row dropped) -> (B,1,hop*(T-1)) waveforms, ONE launch for the
     whole batch (the DC row that train.py:41-42 pads back is the absent first row of the tile layout)."""
+    _check_window(n_fft, hop)
     B, _, F_, T = magnitude.shape
     m = magnitude.contiguous().float()
     a = phase.contiguous().float()
     out = torch.empty((B, 1, hop * (T - 1)), dtype=torch.float32, device=m.device)
-    _lib.check(_lib.lib().svs_istft_tiles(m.data_ptr(), F_ * T, T, F_, 1, None, 0, a.data_ptr(), 3, B, n_fft, hop, T, out.data_ptr(), None,
-                                          _lib.stream_ptr()), "svs_istft_tiles")
+    _lib.check(_lib.lib().svs_istft_tiles_n(m.data_ptr(), F_ * T, T, F_, 1, None, 0, a.data_ptr(), 3, B, n_fft, hop, T, out.data_ptr(), None,
+                                            _lib.stream_ptr()), "svs_istft_tiles_n")
     return out
 
 
@@ -90,6 +110,7 @@ def stft_to_tiles(y: torch.Tensor, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE
     """float32 (channels, n) on the GPU -> (tiles (channels, n_tiles, 1, n_fft/2, seg) magnitude with the DC row dropped and the
     last tile zero-padded (inference.py:68,84-92), frame-major unit phasors (channels, T, n_fft/2+1) complex64, the maximum
     magnitude per channel (channels,) incl. the DC row (data.py:84), T).  One launch; nothing is repacked afterwards."""
+    _check_window(n_fft, hop)
     L = _lib.lib()
     y = y.contiguous().float()
     C, n = y.shape
@@ -98,10 +119,10 @@ def stft_to_tiles(y: torch.Tensor, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE
     rows = n_fft // 2
     tiles = torch.empty((C, n_tiles, 1, rows, seg), dtype=torch.float32, device=y.device)
     phase = torch.empty((C, T, rows + 1, 2), dtype=torch.float32, device=y.device)
-    groups = int(L.svs_stft_groups(n_tiles * seg))
+    groups = int(L.svs_stft_groups_n(n_fft, n_tiles * seg))
     part = torch.empty((C, groups), dtype=torch.float32, device=y.device)
-    _lib.check(L.svs_stft_tiles(y.data_ptr(), n, C, n_fft, hop, tiles.data_ptr(), n_tiles * rows * seg, seg, rows, 1, n_tiles * seg,
-                                phase.data_ptr(), 1, part.data_ptr(), _lib.stream_ptr()), "svs_stft_tiles")
+    _lib.check(L.svs_stft_tiles_n(y.data_ptr(), n, C, n_fft, hop, tiles.data_ptr(), n_tiles * rows * seg, seg, rows, 1, n_tiles * seg,
+                                  phase.data_ptr(), 1, part.data_ptr(), _lib.stream_ptr()), "svs_stft_tiles_n")
     peak = torch.empty(C, dtype=torch.float32, device=y.device)
     for c in range(C):
         _lib.check(L.svs_max(part[c].data_ptr(), groups, peak[c:].data_ptr(), _lib.stream_ptr()), "svs_max")
@@ -110,17 +131,18 @@ def stft_to_tiles(y: torch.Tensor, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE
 
 def istft_from_tiles(tiles: torch.Tensor, mask, phase_fm: torch.Tensor, frames: int, invert: bool = False,
                      n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE, peak: float | None = None):
-    """(channels, n_tiles, 1, 512, seg) magnitude tiles [times mask or 1 - mask, fused: inference.py:100-107] and frame-major
-    phasors (channels, T, 513) -> (channels, hop*(T-1)) samples, optionally peak-normalised per channel (data.py:162-164)."""
+    """(channels, n_tiles, 1, n_fft/2, seg) magnitude tiles [times mask or 1 - mask, fused: inference.py:100-107] and frame-major
+    phasors (channels, T, n_fft/2+1) -> (channels, hop*(T-1)) samples, optionally peak-normalised per channel (data.py:162-164)."""
+    _check_window(n_fft, hop)
     L = _lib.lib()
     C, n_tiles, _, rows, seg = tiles.shape
     ph = torch.view_as_real(phase_fm.contiguous()).contiguous()
-    y = torch.empty((C, hop * (frames - 1)), dtype=torch.float32, device=tiles.device)
-    groups = int(L.svs_istft_groups(hop, frames, C))
+    y = torch.empty((C, hop * max(frames - 1, 0)), dtype=torch.float32, device=tiles.device)
+    groups = int(L.svs_istft_groups_n(n_fft, hop, max(frames, 1), C))
     part = torch.empty((C, groups), dtype=torch.float32, device=tiles.device) if peak is not None else None
-    _lib.check(L.svs_istft_tiles(tiles.data_ptr(), n_tiles * rows * seg, seg, rows, 1, None if mask is None else mask.data_ptr(),
-                                 1 if invert else 0, ph.data_ptr(), 1, C, n_fft, hop, frames, y.data_ptr(),
-                                 None if part is None else part.data_ptr(), _lib.stream_ptr()), "svs_istft_tiles")
+    _lib.check(L.svs_istft_tiles_n(tiles.data_ptr(), n_tiles * rows * seg, seg, rows, 1, None if mask is None else mask.data_ptr(),
+                                   1 if invert else 0, ph.data_ptr(), 1, C, n_fft, hop, frames, y.data_ptr(),
+                                   None if part is None else part.data_ptr(), _lib.stream_ptr()), "svs_istft_tiles_n")
     if peak is not None:
         pk = torch.empty(C, dtype=torch.float32, device=tiles.device)
         for c in range(C):
@@ -281,9 +303,9 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.sr_out is not None and args.sr_out < 1:
         parser.error(f"--sr_out {args.sr_out}: must be positive")
-    if args.win_size != WINDOW_SIZE:             # data.py:24 lets it vary; the gfx950 transforms are built for the config's 1024 only
-        parser.error(f"--win_size {args.win_size}: the STFT / iSTFT kernels are built for n_fft = {WINDOW_SIZE} (config.WINDOW_SIZE) only; "
-                     "--hop_size may be anything in 1..win_size")
+    if args.win_size not in WINDOW_SIZES:        # data.py:24 lets it vary; the gfx950 transforms are built for these three
+        parser.error(f"--win_size {args.win_size}: the STFT / iSTFT kernels are built for n_fft = {', '.join(map(str, WINDOW_SIZES))} "
+                     f"(default {WINDOW_SIZE}, config.WINDOW_SIZE); --hop_size may be anything in 1..win_size")
     if not 0 < args.hop_size <= args.win_size:
         parser.error(f"--hop_size {args.hop_size}: must be in 1..{args.win_size} (a larger hop leaves samples that no frame covers)")
     if not torch.cuda.is_available():

@@ -6,10 +6,13 @@ evaluate.py accepts it beside the source's stems.
 
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src song.wav --tar out.wav
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src wav_folder --tar out_folder \
-        [--vocal_solo 0|1] [--precision bf16] [--subtype PCM_16|PCM_32|FLOAT] [--no_keep_length]
+        [--vocal_solo 0|1] [--precision bf16] [--subtype PCM_16|PCM_32|FLOAT] [--no_keep_length] \
+        [--win_size 512|1024|2048] [--hop_size N]
 
 A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
-default) is what the reference's data.py writes (data.py:166).  The reference has no such command: it goes through
+default) is what the reference's data.py writes (data.py:166).  --win_size / --hop_size (the config's 1024 / 768 by default;
+data.py:24-25 takes the same two flags) are the window and hop of the two transforms, for a checkpoint trained at another
+geometry.  The reference has no such command: it goes through
 data.py to_spec, inference.py and data.py to_wave with .npy files in between.
 """
 from __future__ import annotations
@@ -20,6 +23,8 @@ import sys
 
 import torch
 
+from .config import HOP_SIZE, WINDOW_SIZE
+from .data import WINDOW_SIZES
 from .model import UNet
 from .streaming import separate_to_wav
 
@@ -33,7 +38,13 @@ def main(argv=None):
     parser.add_argument("--precision", default=None, choices=["fp32", "bf16"], help="eval precision of the network (default: the model's)")
     parser.add_argument("--subtype", default="PCM_16", choices=["PCM_16", "PCM_32", "FLOAT"], help="sample format of the written files")
     parser.add_argument("--no_keep_length", action="store_true", help="do not cut / pad the output to the source's frame count")
+    parser.add_argument("--win_size", type=int, default=WINDOW_SIZE, help="window of the STFT / inverse STFT (512, 1024 or 2048)")
+    parser.add_argument("--hop_size", type=int, default=HOP_SIZE, help="hop of the two transforms, 1..win_size")
     args = parser.parse_args(argv)
+    if args.win_size not in WINDOW_SIZES:
+        parser.error(f"--win_size {args.win_size}: the STFT / iSTFT kernels are built for n_fft = {', '.join(map(str, WINDOW_SIZES))}")
+    if not 0 < args.hop_size <= args.win_size:
+        parser.error(f"--hop_size {args.hop_size}: must be in 1..{args.win_size} (a larger hop leaves samples that no frame covers)")
 
     if not torch.cuda.is_available():
         print("separate.py needs a ROCm device (hand-written gfx950 kernels, no CPU path).")
@@ -57,7 +68,8 @@ def main(argv=None):
     print(f"Found {len(jobs)} files, separating...")
     for src, dst in jobs:
         frames, channels = separate_to_wav(model, src, dst, vocal_solo=bool(args.vocal_solo), precision=args.precision,
-                                           subtype=args.subtype, keep_length=not args.no_keep_length)
+                                           subtype=args.subtype, keep_length=not args.no_keep_length, n_fft=args.win_size,
+                                           hop=args.hop_size)
         print(f"{dst}: {frames} frames x {channels}")
     print("Separation finished!")
 

@@ -114,14 +114,15 @@ def separated_frames(n_source: int, sr: int, hop: int = HOP_SIZE):
 
 @torch.no_grad()
 def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = True, precision: str | None = None,
-                    subtype: str = "PCM_16", keep_length: bool = True):
+                    subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE):
     """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
     the PCM is copied as the file stores it, resample.resample_poly_gpu (no downmix) brings every channel to SAMPLE_RATE,
     separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
     peak-normalises to 0.9 with one gain for all channels (data.py:162-164), converts to `subtype` ("PCM_16", "PCM_32",
     "FLOAT") and interleaves; only those samples return to the host.  keep_length: the frames are cut or zero-padded to the
-    source's frame count (kept_length), so the file lines up sample for sample with the source's stems.  Returns the
-    (frames, channels) written."""
+    source's frame count (kept_length), so the file lines up sample for sample with the source's stems.  n_fft / hop: the
+    window and hop of the two transforms (data.WINDOW_SIZES; the network is fully convolutional, so a checkpoint trained at
+    another geometry runs on the n_fft / 2 rows of that window).  Returns the (frames, channels) written."""
     from fractions import Fraction
 
     import numpy as np
@@ -136,13 +137,13 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     n_source = data.shape[0]
     channels = data.shape[1] if data.ndim == 2 else 1
     dev = model._flat.device
-    if separated_frames(n_source, rate) == 0:
-        raise ValueError(f"{src_path}: {n_source} frames at {rate} Hz are shorter than one hop ({HOP_SIZE} samples at {SAMPLE_RATE} Hz)")
+    if separated_frames(n_source, rate, hop) == 0:
+        raise ValueError(f"{src_path}: {n_source} frames at {rate} Hz are shorter than one hop ({hop} samples at {SAMPLE_RATE} Hz)")
     pcm = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
     fr = Fraction(SAMPLE_RATE, int(rate))
     y = resample_poly_gpu(pcm, fr.numerator, fr.denominator, channels=channels, downmix=False)
     y = y[None] if y.dim() == 1 else y                            # (channels, n) at the network rate
-    sep = separate_waveform(model, y, vocal_solo=vocal_solo, peak=None, precision=precision)
+    sep = separate_waveform(model, y, vocal_solo=vocal_solo, n_fft=n_fft, hop=hop, peak=None, precision=precision)
     enc = resample_encode_gpu(sep, fr.denominator, fr.numerator, fmt=subtype, peak=0.9, common_gain=True)
     if keep_length:
         keep, pad = kept_length(enc.shape[0], n_source)
