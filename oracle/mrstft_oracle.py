@@ -68,6 +68,66 @@ def mrstft_loss_and_grad(x: torch.Tensor, y: torch.Tensor):
     return float(loss), x.grad.detach()
 
 
+def _shared_fft_mags(x: torch.Tensor, y: torch.Tensor, n_fft: int, hop: int, win: int):
+    """|X|, |Y| (clamped as stft_mag does) from ONE two-sided transform of z = x + i y:  Z_k = X_k + i Y_k and, x and y being
+    real, conj Z_{N-k} = X_k - i Y_k, so X_k = (Z_k + conj Z_{N-k}) / 2 and Y_k = (Z_k - conj Z_{N-k}) / 2i.  In float32 a bin of
+    the small signal then carries the rounding error of the large one."""
+    window = torch.hann_window(win, dtype=x.dtype, device=x.device)
+    pad = n_fft // 2                                    # torch.stft's center=True, pad_mode="reflect", done on the real parts
+    xp = torch.nn.functional.pad(x.unsqueeze(1), (pad, pad), mode="reflect").squeeze(1)
+    yp = torch.nn.functional.pad(y.unsqueeze(1), (pad, pad), mode="reflect").squeeze(1)
+    z = torch.stft(torch.complex(xp, yp), n_fft, hop, win, window, center=False, onesided=False, return_complex=True)
+    k = torch.arange(n_fft // 2 + 1, device=x.device)
+    zk, zn = z[:, k], torch.conj(z[:, (n_fft - k) % n_fft])
+    X, Y = 0.5 * (zk + zn), -0.5j * (zk - zn)
+
+    def mag(s):
+        return torch.sqrt(torch.clamp(s.real ** 2 + s.imag ** 2, min=EPS))
+    return mag(X), mag(Y)
+
+
+def _plain_mags(x: torch.Tensor, y: torch.Tensor, n_fft: int, hop: int, win: int):
+    return stft_mag(x, n_fft, hop, win), stft_mag(y, n_fft, hop, win)
+
+
+def _loss(x: torch.Tensor, y: torch.Tensor, mags, whole_batch_ratio: bool) -> torch.Tensor:
+    x, y = x.reshape(-1, x.shape[-1]), y.reshape(-1, y.shape[-1])
+    total = 0.0
+    for n_fft, hop, win in zip(FFT_SIZES, HOP_SIZES, WIN_LENGTHS):
+        xm, ym = mags(x, y, n_fft, hop, win)
+        if whole_batch_ratio:
+            sc = torch.norm(ym - xm, p="fro") / torch.norm(ym, p="fro")
+        else:
+            sc = (torch.norm(ym - xm, p="fro", dim=[-1, -2]) / torch.norm(ym, p="fro", dim=[-1, -2])).mean()
+        total = total + sc + torch.nn.functional.l1_loss(torch.log(xm), torch.log(ym))
+    return total / len(FFT_SIZES)
+
+
+def _loss_and_grad(x: torch.Tensor, y: torch.Tensor, mags, whole_batch_ratio: bool):
+    x = x.detach().clone().requires_grad_(True)
+    loss = _loss(x, y.detach(), mags, whole_batch_ratio)
+    loss.backward()
+    return float(loss.detach()), x.grad.detach()
+
+
+def mrstft_loss_shared_fft(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """mrstft_loss with the predicted and the target frame through ONE complex transform (_shared_fft_mags)."""
+    return _loss(x, y, _shared_fft_mags, whole_batch_ratio=False)
+
+
+def mrstft_loss_and_grad_shared_fft(x: torch.Tensor, y: torch.Tensor):
+    """(loss value, d loss / d x) of the SAME definition as mrstft_loss, with the predicted and the target frame through one
+    complex transform, at the dtype it is given.  In float64 it equals mrstft_loss_and_grad; in float32 it is the noise model
+    of an implementation that shares the transform -- built from the definition, not from any kernel."""
+    return _loss_and_grad(x, y, _shared_fft_mags, whole_batch_ratio=False)
+
+
+def mrstft_loss_and_grad_whole_batch_ratio(x: torch.Tensor, y: torch.Tensor):
+    """NOT the loss: the auraloss 0.2.x form, ONE spectral-convergence ratio of norms over the whole batch tensor.  It exists
+    so that a test can show that its inputs tell this form from the per-waveform one."""
+    return _loss_and_grad(x, y, _plain_mags, whole_batch_ratio=True)
+
+
 def specific_istft_torch(magnitude: torch.Tensor, phase: torch.Tensor, hop: int = 768) -> torch.Tensor:
     """train.py:33-60 restated on torch ops (differentiable): (B,1,512,T) magnitude / angle -> (B,1,hop*(T-1))."""
     m = torch.nn.functional.pad(magnitude, (0, 0, 1, 0))

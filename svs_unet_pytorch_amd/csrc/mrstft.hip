@@ -19,8 +19,8 @@
 //                   the spectral-convergence gradient coefficient per resolution and waveform.
 //   mr_pass_kernel  (when the gradient is wanted, instead of mr_sums) the same sums AND, from the same spectra, both unscaled
 //                   gradient parts of the frame brought back with ONE inverse FFT (real / imaginary part);
-//                   the 16 frames of a block are overlap-added in LDS (fixed order) and leave as ONE segment of
-//                   15 hop + win samples -- a quarter of the bytes of the 16 windowed frames (hop is win / 5).
+//                   the 8 frames of a block are overlap-added in LDS (fixed order) and leave as ONE segment of
+//                   7 hop + win samples -- a third of the bytes of the 8 windowed frames (hop is win / 5).
 //   mr_ola_kernel   gathers, per output sample, the (at most two) segments that cover it, for the sample itself and for the
 //                   two reflect-padding mirrors, in a fixed order -- no atomics, bitwise reproducible.
 // Bound: HBM + VALU (FFT); algorithmic FLOPs ~ 2.5 * 5 N log2 N per frame position.
@@ -49,7 +49,7 @@ struct MrArgs {
   int hop, win, F;                                   // this resolution: hop, window length, frames = 1 + L / hop
   float* partial;                                    // [B * gridDim.x][3]
   const float* coef;                                 // [1 + B]: log-magnitude coefficient, then the SC coefficient of every waveform (device)
-  float* frames;                                     // [B][ceil(F / 16)][15 hop + win]: the blocks' overlap-added frame gradients ("segments")
+  float* frames;                                     // [B][ceil(F / 8)][7 hop + win] (sc, log) pairs: the blocks' overlap-added frame gradients ("segments")
   const float2* twiddles;                            // this n_fft's table (svs_fft_twiddles)
 };
 
@@ -182,6 +182,7 @@ __global__ __launch_bounds__(64 * MrCfg<N>::WAVES) void mr_pass_kernel(MrArgs p)
   float2* const fbuf = (float2*)smem;
   float2* const tw = fbuf + WV * BUF;
   float* const red = (float*)(tw + TW);              // [WV][3]
+  float* const unbalance = red + 3 * WV;             // [WV]: what takes a frame's log part back to its scale (below)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.y, t = blockIdx.x * WV + wave;
   fft_load_twiddles<N>(tw, p.twiddles, tid, 64 * WV);
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(64 * MrCfg<N>::WAVES) void mr_pass_kernel(MrArgs p)
   mr_fill<N>(buf, p, b, t, lane);                    // (zeros past the last frame)
   __syncthreads();
   fft_wave<N>(buf, tw, lane);
-  float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  float s1 = 0.f, s2 = 0.f, s3 = 0.f, es = 0.f, el = 0.f;     // (es, el: energy of the frame's two gradient spectra, see below)
   float2 Hs[NR], Hl[NR];                             // Hermitian-weighted, unscaled dL/dX: spectral-convergence and log-magnitude parts
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
@@ -212,9 +213,26 @@ __global__ __launch_bounds__(64 * MrCfg<N>::WAVES) void mr_pass_kernel(MrArgs p)
         const float gs = -d * h, gl = (x2 > y2 ? 1.f : (x2 < y2 ? -1.f : 0.f)) * ix * h;      // sign(log|X| - log|Y|) = sign(|X|^2 - |Y|^2)
         Hs[r] = float2{gs * X.x, edge ? 0.f : gs * X.y};
         Hl[r] = float2{gl * X.x, edge ? 0.f : gl * X.y};
+        es += gs * gs * x2r;
+        el += gl * gl * x2r;
       }
     }
   }
+  // The two parts share one inverse transform, whose rounding error is relative to the LARGER part -- and unscaled they are
+  // |log part| / |sc part| ~ 1 / (|X| (|Y| - |X|)) apart: 1e8 for a waveform at -90 dBFS, where the spectral-convergence part
+  // came back as noise several times the whole gradient (and, the other way round, 1e-4 at full scale).  So the frame's log part
+  // goes through the transform times the power of two that brings its energy to the sc part's (exact), and the overlap-add
+  // below takes that factor out again.
+  es = svs_wave_sum(es); el = svs_wave_sum(el);      // (the same bits in every lane)
+  int bal = 0;                                       // half the difference of the two energies' binary exponents
+  if (es > 0.f && el > 0.f && es < INFINITY && el < INFINITY) {
+    bal = ((int)(__float_as_uint(es) >> 23) - (int)(__float_as_uint(el) >> 23)) / 2;
+    bal = bal < -48 ? -48 : (bal > 48 ? 48 : bal);
+  }
+  const float balance = __uint_as_float((unsigned)(127 + bal) << 23);      // 2^bal
+#pragma unroll
+  for (int r = 0; r < NR; ++r) { Hl[r].x *= balance; Hl[r].y *= balance; }
+  if (lane == 0) unbalance[wave] = __uint_as_float((unsigned)(127 - bal) << 23);
   fft_wave_sync();                                   // every lane has read the spectra before the buffer is refilled
   // conj(Z), Z = Hs + i Hl extended Hermitian; forward transform -> conj(ifft(Z)) = g_sc - i g_log
 #pragma unroll
@@ -254,7 +272,7 @@ __global__ __launch_bounds__(64 * MrCfg<N>::WAVES) void mr_pass_kernel(MrArgs p)
       const float2 z = fbuf[f * BUF + fft_pad(j + off)];
       const float w = mr_window_at(j, inv_win);
       s.x += z.x * w;
-      s.y -= z.y * w;
+      s.y -= z.y * (w * unbalance[f]);
     }
     seg[i] = s;
   }
@@ -307,7 +325,8 @@ __global__ __launch_bounds__(256) void mr_ola_kernel(MrOlaArgs a) {
 }
 
 // ---- host side -----------------------------------------------------------------------------------
-template <int N> static size_t mr_lds_bytes() { return (size_t)MrCfg<N>::WAVES * FftSize<N>::BUF * 8 + FftSize<N>::TW * 8 + 8 * 3 * 4 + 32; }
+// (wave buffers, twiddles, [WAVES][3] partial sums, [WAVES] log-part factors of mr_pass)
+template <int N> static size_t mr_lds_bytes() { return (size_t)MrCfg<N>::WAVES * FftSize<N>::BUF * 8 + FftSize<N>::TW * 8 + MrCfg<N>::WAVES * 3 * 4 + MrCfg<N>::WAVES * 4; }
 struct MrWs { float* partial[MR_NRES]; int nblk[MR_NRES]; float* frames[MR_NRES]; float* coef; double* terms; size_t total; };
 static MrWs mr_layout(int B, long L, void* ws) {
   MrWs w{};
