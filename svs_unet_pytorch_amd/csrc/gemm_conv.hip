@@ -603,6 +603,12 @@ __device__ __forceinline__ void svs_static_for(F&& f) {        // f(integral_con
   }
 }
 
+// x of lane R of the caller's quad of lanes (DPP quad_perm); every lane of the wave must be active
+template <int R>
+__device__ __forceinline__ float svs_quad_bcast(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), R * 0x55, 0xf, 0xf, true));
+}
+
 // ------------------------------------------------------------------------------------------------
 // LDS-window variant of the PARITY mode for the shallow layers (few channels, many pixels: deconv5 forward,
 // conv2 backward-data).  A block owns TH x TW anchor pixels of one image (= a 2TH x 2TW output patch, all four
@@ -611,11 +617,16 @@ __device__ __forceinline__ void svs_static_for(F&& f) {        // f(integral_con
 // per-tap address arithmetic, no validity masks, no re-fetch of the input through L1/L2 (the direct kernel
 // fetched 5-6x the algorithmic bytes on these layers, profiles/r01_pmc_traffic.json).  Each wave owns two anchor
 // rows (two 16-pixel row tiles); the weight fragments come straight from global memory (they are shared by
-// every block, so they live in L2/L1) and are prefetched one tap ahead.
+// every block, so they live in L2/L1) and are prefetched one tap ahead.  Weights are the FIRST MFMA operand, as in
+// gather_window_kernel: D = [channel][pixel], a lane's four registers are four consecutive channels of one pixel, so
+// the epilogue is one address, one 16-byte store (and, accumulating, one 16-byte load requested before the class's
+// last tap) per 16x16 tile and lane.  VEC = false: the same epilogue with 4-byte accesses, for an output view that is
+// not 16-byte aligned (y, ldy, bias / scale / shift).
 // ------------------------------------------------------------------------------------------------
-template <int C, int CW, int TN, int NT = TN>  // C input channels, CW of them per staging phase; N = 16 * NT, of which a block
+template <int C, int CW, int TN, int NT, bool VEC>     // C input channels, CW of them per staging phase; N = 16 * NT, of which a block
                                                // computes 16 * TN (blockIdx.y picks them: small batches get NT / TN x the blocks)
-__global__ __launch_bounds__(256) void parity_window_kernel(ConvGemmArgs p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C == 32 && NT == 1 ? 4 : C == 128 && TN == 2 ? 2 : 3)))
+void parity_window_kernel(ConvGemmArgs p) {      // (resident blocks per CU as before the weights-first epilogue: 4 / 2 / 3)
   constexpr int TH = 8, TW = 16, TM = 2;
   constexpr int LP = CW + 4;                   // floats per staged pixel: 16-byte aligned, conflict-free b128 reads
   constexpr int WW = TW + 2, NPX = (TH + 2) * WW;
@@ -696,54 +707,89 @@ __global__ __launch_bounds__(256) void parity_window_kernel(ConvGemmArgs p) {
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][k], fb[s_ & 1][cc][j][k], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[s_ & 1][cc][j][k], fa[i][k], acc[i][j], 0, 0, 0);
     }
   };
-  struct ColStat { float s[TN], q[TN]; };     // per-lane channel sums of what a class stores (BatchNorm statistics); returned
-                                              // by value: an array captured by reference in a lambda ends up in scratch
+  // D tile (i, j) of a class: this lane holds channels nl + 16 j .. + 3 of anchor (th0 + 2*wave + i, tw0 + lrow)
+  const int nl = n0 + 4 * q;
+  struct ColStat { f32x4 s[TN], q[TN]; };     // channel sums of what the block stores (BatchNorm statistics); passed and
+                                              // returned by value: an array captured by reference in a lambda ends up in scratch
+  struct Prev { f32x4 v[TM][TN]; };           // what y held (accumulate)
+  auto ld4 = [](const float* src) -> f32x4 {
+    if constexpr (VEC) return *(const f32x4*)src;
+    else return (f32x4){src[0], src[1], src[2], src[3]};
+  };
   ColStat wst;
 #pragma unroll
-  for (int j = 0; j < TN; ++j) { wst.s[j] = 0.f; wst.q[j] = 0.f; }
-  // rows q*4 + r of row tile i = anchor (th0 + 2*wave + i, tw0 + q*4 + r); column lrow (+16j) = output channel
-  auto store_class = [&](int par, const f32x4 (&acc)[TM][TN]) -> ColStat {
-    ColStat cs;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) { cs.s[j] = 0.f; cs.q[j] = 0.f; }
+  for (int j = 0; j < TN; ++j) wst.s[j] = wst.q[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  // where row tile i of class par puts this lane's pixel (channel nl); null: outside the output.  One 64-bit address per
+  // lane (output pixel (2 a0, 2 c0), never dereferenced as such) plus an offset that is the same for the whole wave.
+  const int a0 = th0 + 2 * __builtin_amdgcn_readfirstlane(wave), c0 = tw0 + lrow;
+  float* const ybase = p.y + ((b * p.Ho + 2 * a0) * p.Wo + 2 * c0) * p.ldy + nl;
+  auto out_ptr = [&](int par, int i) -> float* {
     const int ph = par >> 1, pw = par & 1;
+    if (a0 + i >= p.H || 2 * (a0 + i) + ph >= p.Ho || c0 >= p.W || 2 * c0 + pw >= p.Wo) return nullptr;
+    return ybase + ((long)(2 * i + ph) * p.Wo + pw) * p.ldy;
+  };
+  auto load_prev = [&](int par) -> Prev {
+    Prev pv;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
-      const int a = th0 + 2 * wave + i;
-      const int oh = 2 * a + ph;
-      if (a >= p.H || oh >= p.Ho) continue;
+      const float* src = p.accumulate ? out_ptr(par, i) : nullptr;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = tw0 + q * 4 + r;
-        const int ow = 2 * c + pw;
-        if (c >= p.W || ow >= p.Wo) continue;
-        const long opix = (b * p.Ho + oh) * p.Wo + ow;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int n = n0 + j * 16 + lrow;
-          float v = acc[i][j][r];
-          if (p.bias) v += p.bias[n];
-          if (p.scale) {
-            v = v * p.scale[n] + p.shift[n];
-            v = v > 0.f ? v : v * p.slope;
-          }
-          float* dst = p.y + opix * p.ldy + n;
-          if (p.accumulate) v += *dst;
-          *dst = v;
-          cs.s[j] += v;
-          cs.q[j] += v * v;
-        }
-      }
+      for (int j = 0; j < TN; ++j) pv.v[i][j] = src ? ld4(src + 16 * j) : (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-    return cs;
+    return pv;
   };
-  auto add_stat = [](ColStat a, const ColStat& b) -> ColStat {
+  // The statistics keep the summation order they had with pixel-major tiles, so their bits do not depend on the tile layout:
+  // per class the values of four adjacent pixels (a quad of lanes here) and both row tiles one after the other, v and the
+  // rounded v * v, then class sums into the block's; every lane of a quad carries the same sums.
+  auto store_class = [&](int par, const f32x4 (&acc)[TM][TN], const Prev& pv, ColStat ws) -> ColStat {
+    float* dst[TM];
 #pragma unroll
-    for (int j = 0; j < TN; ++j) { a.s[j] += b.s[j]; a.q[j] += b.q[j]; }
-    return a;
+    for (int i = 0; i < TM; ++i) dst[i] = out_ptr(par, i);
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      // (bias / scale / shift once per class and column tile, 16 bytes each: kept for the whole block they cost the
+      // 64-channel, 32-column form its third resident block)
+      f32x4 b4 = {0.f, 0.f, 0.f, 0.f}, sc4 = b4, sh4 = b4;
+      if (p.bias) b4 = ld4(p.bias + nl + 16 * j);
+      if (p.scale) { sc4 = ld4(p.scale + nl + 16 * j); sh4 = ld4(p.shift + nl + 16 * j); }
+      f32x4 val[TM];                           // what was stored, 0 outside the output
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        f32x4 v = acc[i][j];
+        if (p.bias) v += b4;
+        if (p.scale) {
+          v = v * sc4 + sh4;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[k] = v[k] > 0.f ? v[k] : v[k] * p.slope;
+        }
+        if (p.accumulate) v += pv.v[i][j];
+        if (dst[i]) {
+          if constexpr (VEC) *(f32x4*)(dst[i] + 16 * j) = v;
+          else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dst[i][16 * j + k] = v[k];
+          }
+        }
+        val[i] = dst[i] ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+      if (!p.stats) continue;
+      f32x4 cs = {0.f, 0.f, 0.f, 0.f}, cq = cs;
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const f32x4 sq = val[i] * val[i];
+        svs_static_for<4>([&](auto rc) {
+          constexpr int r_ = decltype(rc)::value;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) { cs[k] += svs_quad_bcast<r_>(val[i][k]); cq[k] += svs_quad_bcast<r_>(sq[k]); }
+        });
+      }
+      ws.s[j] += cs;
+      ws.q[j] += cq;
+    }
+    return ws;
   };
   auto zero = [&](f32x4 (&acc)[TM][TN]) {
 #pragma unroll
@@ -754,16 +800,19 @@ __global__ __launch_bounds__(256) void parity_window_kernel(ConvGemmArgs p) {
   if constexpr (C == CW) {                     // one phase: one class at a time, 2*TN accumulators live
     stage_window(0);
     f32x4 acc[TM][TN];
+    Prev pv;
     load_b(std::integral_constant<int, 0>{}, 0);
     svs_static_for<25>([&](auto sc) {
       constexpr int s_ = decltype(sc)::value;
       constexpr int par = s_ < 9 ? 0 : s_ < 15 ? 1 : s_ < 21 ? 2 : 3;
+      constexpr bool last = s_ == 24 || s_ + 1 == POFF[par < 3 ? par + 1 : 3];      // the class's last tap
       if constexpr (s_ == POFF[par]) zero(acc);
       if constexpr (s_ + 1 < 25) load_b(std::integral_constant<int, (s_ + 1 < 25 ? s_ + 1 : 0)>{}, 0);
-      if constexpr (CC >= 4) __builtin_amdgcn_sched_barrier(0);
+      if constexpr (last) pv = load_prev(par);                      // under this step's MFMAs
+      __builtin_amdgcn_sched_barrier(0);
       step(sc, acc);
-      if constexpr (s_ == 24 || s_ + 1 == POFF[par < 3 ? par + 1 : 3]) wst = add_stat(wst, store_class(par, acc));
-      if constexpr (CC >= 4) __builtin_amdgcn_sched_barrier(0);     // (32-channel steps are too short to fence)
+      if constexpr (last) wst = store_class(par, acc, pv, wst);
+      __builtin_amdgcn_sched_barrier(0);     // (the 32-channel form too: unfenced it needs 160 registers, fenced 82)
     });
   } else {                                     // several phases share the window buffer: all four classes stay live
     f32x4 acc[4][TM][TN];
@@ -783,17 +832,20 @@ __global__ __launch_bounds__(256) void parity_window_kernel(ConvGemmArgs p) {
       });
     }
 #pragma unroll
-    for (int par = 0; par < 4; ++par) wst = add_stat(wst, store_class(par, acc[par]));
+    for (int par = 0; par < 4; ++par) wst = store_class(par, acc[par], load_prev(par), wst);
   }
-  if (p.stats) {                               // this block's row of BatchNorm partials: [2][N]
+  if (p.stats) {                               // this block's row of BatchNorm partials [2][N]: the four quads of a row tile,
+                                               // (0 + 1) + (2 + 3), then the four waves likewise
     __shared__ float st[2][4][TN * 16];
 #pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      float a = wst.s[j], b2 = wst.q[j];
-      a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
-      b2 += __shfl_xor(b2, 16, 64); b2 += __shfl_xor(b2, 32, 64);
-      if (q == 0) { st[0][wave][j * 16 + lrow] = a; st[1][wave][j * 16 + lrow] = b2; }
-    }
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float a = wst.s[j][k], b2 = wst.q[j][k];
+#pragma unroll
+        for (int o = 4; o < 16; o <<= 1) { a += __shfl_xor(a, o, 64); b2 += __shfl_xor(b2, o, 64); }
+        if (lrow == 0) { st[0][wave][j * 16 + 4 * q + k] = a; st[1][wave][j * 16 + 4 * q + k] = b2; }
+      }
     __syncthreads();
     if (t < TN * 16) {
       float* out = p.stats + (long)blockIdx.x * 2 * (NT * 16) + n0;
@@ -1011,7 +1063,8 @@ struct ConvPlan {
   int cfg, BM, BN, WM, WN, pf;    // GEMM tile (cfg: the case of launch_conv_gemm_cfg), K-tiles requested ahead
   bool skip, split;               // tap skipping (batch-innermost rows), split-bf16 products (mfma_split.h)
   long mtiles; int grid_y;        // M-tiles per parity class, parity classes
-  int wC, wCW, wTN, wNT;          // parity_window_kernel<C, CW, TN, NT>
+  int wC, wCW, wTN, wNT;          // parity_window_kernel<C, CW, TN, NT, VEC>
+  bool wvec;                      // its 16-byte epilogue (set at launch from the output view)
   int tpb, gtiles;                // gather_window_kernel: tiles per block, tiles
   dim3 grid;
   int ksplit;                     // slabs of the split-K epilogue (1: the kernel writes y itself)
@@ -1196,9 +1249,9 @@ static int check_gemm_args(const char* who, const float* x, long ldx, int B, int
   SVS_REQUIRE(B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0, "%s: bad geometry B=%d H=%d W=%d", who, B, H, W);
   SVS_REQUIRE(C >= 16 && C % 16 == 0, "%s: C=%d must be a multiple of 16", who, C);
   SVS_REQUIRE(N >= 16 && (N == 16 || N == 32 || N == 64 || N % 128 == 0), "%s: unsupported N=%d", who, N);
-  SVS_REQUIRE(ldx >= C && ldx % 4 == 0 && ldy >= N && ldy % 4 == 0, "%s: bad ld (ldx=%ld ldy=%ld)", who, ldx, ldy);
-  SVS_REQUIRE(svs_aligned16(x) && svs_aligned16(wp) && svs_aligned16(y), "%s: pointers must be 16-byte aligned", who);
-  return SVS_OK;
+  SVS_REQUIRE(ldx >= C && ldx % 4 == 0 && ldy >= N, "%s: bad ld (ldx=%ld ldy=%ld)", who, ldx, ldy);
+  SVS_REQUIRE(svs_aligned16(x) && svs_aligned16(wp), "%s: pointers must be 16-byte aligned", who);
+  return SVS_OK;      // (the output view: svs_conv_gemm_run, once the kernel is known)
 }
 
 // The launch of one call.  Call facts beside the shape: `inference` (folded-BatchNorm epilogue) and `accumulate`.  `gemm_only`:
@@ -1302,7 +1355,11 @@ static void launch_conv_plan(const ConvGemmArgs& a, const ConvPlan& p, hipStream
   switch (p.kind) {
     case CONV_GATHER_WINDOW: hipLaunchKernelGGL(gather_window_kernel, p.grid, dim3(256), 0, stream, a, p.gtiles, p.tpb); break;
     case CONV_PARITY_WINDOW:
-#define SVS_LAUNCH_WINDOW(C_, CW_, TN_, NT_) hipLaunchKernelGGL((parity_window_kernel<C_, CW_, TN_, NT_>), p.grid, dim3(256), 0, stream, a)
+#define SVS_LAUNCH_WINDOW(C_, CW_, TN_, NT_)                                                                              \
+  do {                                                                                                                   \
+    if (p.wvec) hipLaunchKernelGGL((parity_window_kernel<C_, CW_, TN_, NT_, true>), p.grid, dim3(256), 0, stream, a);    \
+    else hipLaunchKernelGGL((parity_window_kernel<C_, CW_, TN_, NT_, false>), p.grid, dim3(256), 0, stream, a);          \
+  } while (0)
       if (p.wNT == 1) {
         if (p.wC == 32) SVS_LAUNCH_WINDOW(32, 32, 1, 1); else if (p.wC == 64) SVS_LAUNCH_WINDOW(64, 64, 1, 1); else SVS_LAUNCH_WINDOW(128, 64, 1, 1);
       } else if (p.wTN == 1) {
@@ -1339,6 +1396,10 @@ int svs_conv_gemm_run(int mode, const float* x, long ldx, int B, int H, int W, i
   SVS_REQUIRE(((long)B * H * W * ldx + 4L * (W + 2) * ldx) * 4 < (1L << 31) && (long)N * C * 25 * 4 < (1L << 31),
               "%s: input view of %ld bytes needs 64-bit offsets; split the batch", who, (long)B * H * W * ldx * 4);
   ConvPlan p = plan_conv_call(mode, B, H, W, C, Ho, Wo, N, ldx, scale != nullptr, accumulate != 0);
+  // 16-byte stores everywhere but in the window kernel's scalar-epilogue form
+  const bool y_vec = ldy % 4 == 0 && svs_aligned16(y);
+  SVS_REQUIRE(y_vec || p.kind == CONV_PARITY_WINDOW, "%s: output view must be 16-byte aligned (ldy=%ld)", who, ldy);
+  p.wvec = y_vec && svs_aligned16(bias) && svs_aligned16(scale) && svs_aligned16(shift);
   const size_t need = p.slab_bytes + p.rowtab_bytes;
   if (need && (!ws || ws_bytes < need || !svs_aligned16(ws))) {
     svs_set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
@@ -1414,7 +1475,7 @@ int svs_conv_gemm_describe(int mode, int B, int H, int W, int C, int Ho, int Wo,
   const ConvPlan p = plan_conv_call(mode, B, H, W, C, Ho, Wo, N, ldx, false, false);
   switch (p.kind) {
     case CONV_GATHER_WINDOW: snprintf(buf, n, "gather_window_kernel"); break;
-    case CONV_PARITY_WINDOW: snprintf(buf, n, "parity_window_kernel<%d, %d, %d, %d>", p.wC, p.wCW, p.wTN, p.wNT); break;
+    case CONV_PARITY_WINDOW: snprintf(buf, n, "parity_window_kernel<%d, %d, %d, %d, true>", p.wC, p.wCW, p.wTN, p.wNT); break;
     case CONV_DIRECT: snprintf(buf, n, "conv_direct_kernel<%d, 4, %d>", mode, N / 16); break;
     default:
       snprintf(buf, n, "conv_gemm_kernel<%d, %d, %d, %d, %d, %s, %s, %d>", mode, p.BM, p.BN, p.WM, p.WN, p.skip ? "true" : "false",
