@@ -74,8 +74,19 @@ __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >>
 // for all of them at once and its K-tiles are skipped outright (no loads, no MFMAs): -30% work on the 8x2 level,
 // -15% on 16x4.  Skipped products are exact zeros, so results do not change.  Needs tap-outer K order and C/16 a
 // power of two.
-template <int MODE, int BM, int BN, int WM, int WN, bool SKIP = false, bool SPLIT = false, int PF = 1>     // SPLIT: mfma_split.h (optional mode); PF: K-tiles requested ahead
+//
+// UNI (SKIP only, chosen on the host when B % BM == 0): an M-tile is then ONE pixel position of BM
+// consecutive images, so everything the block derives from a row's position is block-uniform and is derived once, with scalar
+// arithmetic: the position (h, w), the anchor, the tap mask (= the tile's mask: no per-row masks, no LDS atomic, no barriers), the
+// output pixel of image 0.  A thread keeps only its image index: an A row's offset and an output row's address are a scalar base plus
+// image * (image stride), and consecutive output rows of a lane differ by a constant.  The K-loop loads A rows with their offsets as
+// they are -- first_valid() visits only taps inside the tile's mask, and with one position per tile that is every row's mask.  Same
+// K-tiles in the same order and the same epilogue arithmetic as the generic form: outputs are bit-identical.  fp32 MFMA and VALU do
+// not overlap on a SIMD and all blocks of these launches run their prologues and epilogues together, so the generic form's two
+// divisions, 25-step mask loop and per-store 64-bit address products per ROW were time added to the launch.
+template <int MODE, int BM, int BN, int WM, int WN, bool UNI, bool SKIP, bool SPLIT, int PF>     // SPLIT: mfma_split.h (optional mode); PF: K-tiles requested ahead
 __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::conditional_t<SKIP, ConvBal, ConvNoBal> bal) {
+  static_assert(SKIP || !UNI, "the position-uniform form is a form of the tap-skipping kernel");
   constexpr int TM = BM / WM / 16;
   constexpr int TN = BN / WN / 16;
   constexpr int RA = (BM + 63) / 64;   // A rows staged per thread
@@ -95,6 +106,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;     // (tile, K-split, parity class)
   int nsplit = p.ksplit;                                     // K-splits of this block's M-tile
   bool balanced = false;
+  int upos = -1, ub0 = 0;                                    // UNI: the tile's position and first image (set here by the balanced grid)
   if constexpr (SKIP) {
     if (bal.enabled) {                                       // 1-D grid: (class, position, M-tile of the position, split, N-tile)
       balanced = true;
@@ -110,6 +122,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
       by = rem / ntn;
       bx = (pos * (p.B / BM) + i) * ntn + (rem - by * ntn);
       bz = c;
+      upos = pos; ub0 = i * BM;
     }
   }
   int ph = 0, pw = 0, nth = 5, ntw = 5;
@@ -153,6 +166,35 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
   const int chunk = t & 3;
   constexpr unsigned OOB = 0x80000000u;           // >= num_records of both descriptors
   unsigned a_voff[RA], a_mask[RA];
+  unsigned umask = 0x1FFFFFFu;                    // taps that at least one row of this tile needs (block-uniform)
+  int uhq = 0, uwq = 0;                           // UNI: the tile's position in the M grid
+  if constexpr (UNI) {
+    if (upos < 0) {                               // uniform grid: (32-bit: M < 2^31 follows from the host's 2 GiB view check)
+      upos = (int)((unsigned)m0 / (unsigned)p.B);
+      ub0 = (int)((unsigned)m0 - (unsigned)upos * (unsigned)p.B);
+    }
+    uwq = (int)((unsigned)upos / (unsigned)Ha);
+    uhq = upos - uwq * Ha;
+    const int h0 = (MODE == MODE_GATHER) ? 2 * uhq : uhq, w0 = (MODE == MODE_GATHER) ? 2 * uwq : uwq;
+    unsigned wbits = 0;                           // taps tw inside the image's columns, then one copy per tap th inside its rows
+    for (int tw = 0; tw < ntw; ++tw) {
+      const int iw = (MODE == MODE_GATHER) ? w0 - 2 + tw : w0 + 1 - tw;
+      if ((unsigned)iw < (unsigned)p.W) wbits |= 1u << tw;
+    }
+    umask = 0;
+    for (int th = 0; th < nth; ++th) {
+      const int ih = (MODE == MODE_GATHER) ? h0 - 2 + th : h0 + 1 - th;
+      if ((unsigned)ih < (unsigned)p.H) umask |= wbits << (th * ntw);
+    }
+    const unsigned base = (unsigned)((((long)h0 * p.W + w0) * p.ldx + chunk * 4) * 4);
+    const unsigned per_image = (unsigned)(((long)p.H * p.W * p.ldx) * 4);
+#pragma unroll
+    for (int r = 0; r < RA; ++r) {
+      const int row = (t >> 2) + 64 * r;
+      a_voff[r] = (BM % 64 == 0 || row < BM) ? base + (unsigned)(ub0 + row) * per_image : OOB;
+      a_mask[r] = 0;                              // (not read in this form)
+    }
+  } else {
 #pragma unroll
   for (int r = 0; r < RA; ++r) {
     const int row = (t >> 2) + 64 * r;
@@ -184,17 +226,19 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
       }
     a_mask[r] = mask;
   }
-  unsigned umask = 0x1FFFFFFu;                    // taps that at least one row of this tile needs (block-uniform)
+  }
   if (SKIP) {
-    __shared__ unsigned umask_s;
-    if (t == 0) umask_s = 0;
-    __syncthreads();
-    unsigned mine = 0;
+    if constexpr (!UNI) {
+      __shared__ unsigned umask_s;
+      if (t == 0) umask_s = 0;
+      __syncthreads();
+      unsigned mine = 0;
 #pragma unroll
-    for (int r = 0; r < RA; ++r) mine |= a_mask[r];
-    if (mine) atomicOr(&umask_s, mine);
-    __syncthreads();
-    umask = __builtin_amdgcn_readfirstlane(umask_s);
+      for (int r = 0; r < RA; ++r) mine |= a_mask[r];
+      if (mine) atomicOr(&umask_s, mine);
+      __syncthreads();
+      umask = __builtin_amdgcn_readfirstlane(umask_s);
+    }
     if (balanced) {                // this split's equal share of the VALID K-tiles: ranks [vb, ve) among the set taps of umask
       const int nvk = __builtin_popcount(umask) << p.cpt_shift;
       const int vb = (int)((long)nvk * by / nsplit), ve = (int)((long)nvk * (by + 1) / nsplit);
@@ -239,7 +283,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
     const int soff_b = __builtin_amdgcn_readfirstlane((int)(((long)tap * p.C + (cc << 4)) * 4));
 #pragma unroll
     for (int r = 0; r < RA; ++r) {
-      const unsigned vo = ((a_mask[r] >> tap) & 1u) ? a_voff[r] : OOB;
+      const unsigned vo = (UNI || ((a_mask[r] >> tap) & 1u)) ? a_voff[r] : OOB;       // (UNI: every tap visited is inside every row's mask)
       ra[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)vo, soff_a, 0));
     }
 #pragma unroll
@@ -388,6 +432,49 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
   float* const slab = split ? p.slab + (long)by * ((long)p.B * p.Ho * p.Wo) * p.N : nullptr;
   bool mark_rows = false;                // balanced: split 0 of N-tile 0 records how many slabs its rows have
   if constexpr (SKIP) mark_rows = balanced && by == 0 && n0 == 0 && wn == 0;
+  if constexpr (UNI) {
+    // the lane's rows are images ub0 + wm * (TM * 16) + 4 q + 16 i + r of ONE output pixel: a base and a constant step, no divisions;
+    // the per-column parameters once.  Values, stores and the order of the statistics' additions are the generic form's.
+    const long HoWo = (long)p.Ho * p.Wo;
+    const long pix0 = ((MODE == MODE_GATHER) ? (long)uhq * p.Wo + uwq : (long)(2 * uhq + ph) * p.Wo + 2 * uwq + pw) +
+                      (long)(ub0 + wm * (TM * 16) + q * 4) * HoWo;
+    const int ncol = n0 + wn * (TN * 16) + lrow;
+    const long rstride = HoWo * (split ? (long)p.N : p.ldy);
+    float* const out = split ? slab + pix0 * p.N + ncol : p.y + pix0 * p.ldy + ncol;
+    float cb[TN], csc[TN], csh[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      cb[j] = (!split && p.bias) ? p.bias[ncol + j * 16] : 0.f;
+      csc[j] = (!split && p.scale) ? p.scale[ncol + j * 16] : 0.f;
+      csh[j] = (!split && p.scale) ? p.shift[ncol + j * 16] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (mark_rows && lrow == 0) bal.rowsplit[pix0 + (i * 16 + r) * HoWo] = (unsigned char)nsplit;
+        float* const row = out + (i * 16 + r) * rstride;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          float v = acc[i][j][r];
+          if (split) {
+            row[j * 16] = v;
+          } else {
+            if (p.bias) v += cb[j];
+            if (p.scale) {
+              v = v * csc[j] + csh[j];
+              v = v > 0.f ? v : v * p.slope;
+            }
+            float* dst = row + j * 16;
+            if (p.accumulate) v += *dst;
+            *dst = v;
+            ssum[j] += v;
+            ssq[j] += v * v;
+          }
+        }
+      }
+    }
+  } else {
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -432,6 +519,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
         }
       }
     }
+  }
   }
   if (p.stats && !split) {
     // column sums of this tile: over the four 4-row groups of a wave (lanes 16 apart), then over the WM waves
@@ -1062,6 +1150,7 @@ struct ConvPlan {
   int kind;
   int cfg, BM, BN, WM, WN, pf;    // GEMM tile (cfg: the case of launch_conv_gemm_cfg), K-tiles requested ahead
   bool skip, split;               // tap skipping (batch-innermost rows), split-bf16 products (mfma_split.h)
+  bool uni;                       // tap skipping with one pixel position per M-tile (UNI)
   long mtiles; int grid_y;        // M-tiles per parity class, parity classes
   int wC, wCW, wTN, wNT;          // parity_window_kernel<C, CW, TN, NT, VEC>
   bool wvec;                      // its 16-byte epilogue (set at launch from the output view)
@@ -1189,7 +1278,9 @@ static int plan_balance_search(int mode, int B, int H, int W, int C, int Ho, int
   // Coarse cases (few splits per position, e.g. batch 128 with two M-tiles per position) do not come out even: keep the uniform
   // grid unless the most loaded CU is within 12 % of the mean, when the blocks go to the 256 CUs round-robin in launch order (how
   // the dispatcher is observed to place a grid that is resident at once) and each block pays a fixed prologue / epilogue share
-  // (units: one K-tile of one block; fixed cost per block ~ 3 K-tiles of a 64x64 tile).
+  // (units: one K-tile of one block; fixed cost per block ~ 3 K-tiles of a 64x64 tile).  That fit predates the position-uniform
+  // form (UNI), whose prologue and epilogue are less than half as many VALU instructions, so the fixed cost of the blocks planned
+  // here is now below it; the value stays, because another value is another plan and another summation order.
   const int NCU = 256;
   const double OVH = 3.0 * 4096.0 / (BM * BN);
   double load[NCU] = {};
@@ -1312,6 +1403,9 @@ static ConvPlan plan_conv_call(int mode, int B, int H, int W, int C, int Ho, int
   plan_gemm_tile(mode, Mmax, N, nkt_min, narrow_shape && cs < 0, inference, p);
   const bool can_skip = N > 32 /* tap-outer K order */ && (C & (C - 1)) == 0 && p.BN >= 64;
   p.skip = cs == 0 ? false : cs == 2 ? can_skip : can_skip && narrow_shape;
+  // (the split-bf16 mode keeps the generic form, and so does the 128x128 tile: its uniform form takes 105 registers against 99 and
+  // loses the third resident block)
+  p.uni = p.skip && B % p.BM == 0 && !p.split && p.cfg != 0;
   p.grid = dim3((unsigned)(p.mtiles * (N / p.BN)), (unsigned)p.ksplit, (unsigned)p.grid_y);      // (tiles, K-splits, parity classes)
   const int slabs = p.skip ? plan_balance(mode, B, H, W, C, Ho, Wo, N, p.BM, p.BN, p.ksplit, &p.bal) : 0;
   if (slabs) {                                 // the largest split count of any position; 1-D grid (class, position, M-tile, split, N-tile)
@@ -1329,14 +1423,20 @@ template <int MODE, bool SPLIT, int BM, int BN, int WM, int WN>
 static void launch_conv_gemm_tile(const ConvGemmArgs& a, const ConvPlan& p, hipStream_t stream) {
   constexpr int PF2 = (BM == 128 && BN == 128) || BM == 32 ? 1 : 2;
   if constexpr (BN >= 64) {
+    if constexpr (!SPLIT && !(BM == 128 && BN == 128)) {
+      if (p.uni) {
+        hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, true, true, false, PF2>), p.grid, dim3(256), 0, stream, a, p.bal);
+        return;
+      }
+    }
     if (p.skip) {
-      if (p.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, true, SPLIT, PF2>), p.grid, dim3(256), 0, stream, a, p.bal);
-      else hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, true, SPLIT, 1>), p.grid, dim3(256), 0, stream, a, p.bal);
+      if (p.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, true, SPLIT, PF2>), p.grid, dim3(256), 0, stream, a, p.bal);
+      else hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, true, SPLIT, 1>), p.grid, dim3(256), 0, stream, a, p.bal);
       return;
     }
   }
-  if (p.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, SPLIT, PF2>), p.grid, dim3(256), 0, stream, a, ConvNoBal{});
-  else hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, SPLIT, 1>), p.grid, dim3(256), 0, stream, a, ConvNoBal{});
+  if (p.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, false, SPLIT, PF2>), p.grid, dim3(256), 0, stream, a, ConvNoBal{});
+  else hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, false, SPLIT, 1>), p.grid, dim3(256), 0, stream, a, ConvNoBal{});
 }
 template <int MODE, bool SPLIT>
 static void launch_conv_gemm_cfg(const ConvGemmArgs& a, const ConvPlan& p, hipStream_t stream) {
@@ -1478,8 +1578,8 @@ int svs_conv_gemm_describe(int mode, int B, int H, int W, int C, int Ho, int Wo,
     case CONV_PARITY_WINDOW: snprintf(buf, n, "parity_window_kernel<%d, %d, %d, %d, true>", p.wC, p.wCW, p.wTN, p.wNT); break;
     case CONV_DIRECT: snprintf(buf, n, "conv_direct_kernel<%d, 4, %d>", mode, N / 16); break;
     default:
-      snprintf(buf, n, "conv_gemm_kernel<%d, %d, %d, %d, %d, %s, %s, %d>", mode, p.BM, p.BN, p.WM, p.WN, p.skip ? "true" : "false",
-               p.split ? "true" : "false", p.pf);
+      snprintf(buf, n, "conv_gemm_kernel<%d, %d, %d, %d, %d, %s, %s, %s, %d>", mode, p.BM, p.BN, p.WM, p.WN, p.uni ? "true" : "false",
+               p.skip ? "true" : "false", p.split ? "true" : "false", p.pf);
   }
   return p.ksplit;
 }
