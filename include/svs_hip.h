@@ -259,8 +259,11 @@ int svs_unet_train_bwd_part(const float* params, float* grads, const float* mix,
 int svs_unet_train_bwd_sync(hipStream_t consumer);
 /* The reference's FULL objective (train.py:274-296): alpha_l1 * L1 terms + alpha_mr * MultiResolutionSTFTLoss(
  * specific_istft(mask * mix, mix_phase), specific_istft(voc, voc_phase)) -- forward, both losses, d(total)/d(logit).
- * mix_phase / voc_phase: angles (B,1,512,W) (train.py:103-112).  Needs H = 512, W >= 2.  losses[0] = L1 part, losses[1] =
- * MR part, both unscaled.  Follow with svs_unet_train_bwd_part (part 4 = whole backward; or the split forms). */
+ * mix_phase / voc_phase: angles (B,1,H,W) (train.py:103-112).  H = n_fft / 2 = 256, 512 or 1024 (the window the tiles were
+ * made with, data.py:24), any 0 < hop <= n_fft, W >= 2 and hop * (W - 1) > 2048 (the loss's widest window, whatever the
+ * tiles' own: its resolutions are auraloss's 1024 / 2048 / 512); anything else is an error before the first launch.
+ * losses[0] = L1 part, losses[1] = MR part, both unscaled.  Follow with svs_unet_train_bwd_part (part 4 = whole backward;
+ * or the split forms). */
 size_t svs_unet_train_mr_workspace_bytes(int B, int W, int hop);
 int svs_unet_train_fwd_loss_mr(const float* params, float* bn_buffers, int64_t* num_batches_tracked, const float* mix,
                                const float* voc, const float* mix_phase, const float* voc_phase, const float* drop, int B, int H,
@@ -329,7 +332,7 @@ int svs_istft_groups(int hop, int frames, int channels);
  *   svs_istft_tiles with 513 -> n_fft / 2 + 1 and 512 -> n_fft / 2 (rows == n_fft / 2 + 1 - first_bin); any other n_fft is an
  *   error that names the three sizes, and so is hop > n_fft.  At n_fft = 1024 they ARE the two functions above (which
  *   require 1024 and forward here), so results are bitwise the same through either name; the 1024-only entry points
- *   (svs_stft_fwd, svs_istft, svs_istft_bwd_mask, the training losses) keep rejecting any other n_fft. */
+ *   (svs_stft_fwd, svs_istft) keep rejecting any other n_fft; svs_istft_bwd_mask and svs_unet_train_fwd_loss_mr take all three. */
 int svs_stft_tiles_n(const float* y, int64_t n_samples, int channels, int n_fft, int hop, float* mag, int64_t chan_stride,
                      int seg, int rows, int first_bin, int frames_alloc, float* phase, int phase_mode,
                      float* absmax_partial, hipStream_t stream);
@@ -351,7 +354,8 @@ int svs_hann_table(int n_fft, float* out);
 /* (rows, cols) complex64 -> (cols, rows): f-major phasor files <-> the frame-major form */
 int svs_transpose_c64(const float* in, float* out, int rows, int cols, hipStream_t stream);
 /* Backward of `specific_istft` (train.py:33-60) fused with the chain rule of |S| = mask * mix (train.py:275,288):
- *   d_logit[b,f,t] += alpha * dL/d|S|[b,f,t] * mix * mask * (1 - mask);   d_wav (B, hop*(frames-1)); the rest (B,1,512,frames) */
+ *   d_logit[b,f,t] += alpha * dL/d|S|[b,f,t] * mix * mask * (1 - mask);   d_wav (B, hop*(frames-1)); the rest
+ *   (B,1,n_fft/2,frames).  n_fft = 512, 1024 or 2048 (any other is an error that names them), 0 < hop <= n_fft, frames >= 2. */
 int svs_istft_bwd_mask(const float* d_wav, const float* angle, const float* mix, const float* mask, float* d_logit,
                        float alpha, int B, int n_fft, int hop, int frames, hipStream_t stream);
 /* Multi-resolution STFT loss of train.py:24-26,287-296 (auraloss.freq.MultiResolutionSTFTLoss with the reference's

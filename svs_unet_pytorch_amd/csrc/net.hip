@@ -683,7 +683,8 @@ extern "C" int svs_unet_train_fwd_loss(const float* params, float* bn_buffers, i
 
 // The reference's full objective (train.py:274-296): alpha_L1 * (L1 vocal + L1 accompaniment) + alpha_MR * MR-STFT(
 // specific_istft(mask * mix, mix_phase), specific_istft(voc, voc_phase)).  Forward + both losses + d(total)/d(logit); the
-// backward follows with svs_unet_train_bwd_part (part 4 = the whole pass, or the split forms).  Needs H = n_fft / 2 = 512.
+// backward follows with svs_unet_train_bwd_part (part 4 = the whole pass, or the split forms).  H = n_fft / 2 = 256, 512 or 1024
+// (the window the tiles were made with), any 0 < hop <= n_fft, hop * (W - 1) > 2048 (the loss's own resolutions do not follow the window).
 //   losses[0] = L1 part (unscaled), losses[1] = MR part (unscaled); total = alpha_l1 * losses[0] + alpha_mr * losses[1]
 //   mr_ws: svs_unet_train_mr_workspace_bytes(B, W, hop) bytes (waveforms, their gradient, the loss's frame buffers)
 struct MrTrainWs { float* wav_pred; float* wav_tgt; float* d_wav; void* mr; size_t mr_bytes; size_t total; };
@@ -709,7 +710,12 @@ extern "C" int svs_unet_train_fwd_loss_mr(const float* params, float* bn_buffers
                                           void* ws, size_t ws_bytes, void* mr_ws, size_t mr_ws_bytes, hipStream_t stream) {
   SVS_REQUIRE(params && mix && voc && mix_phase && voc_phase && losses && svs_aligned16(params) && svs_aligned16(mix),
               "svs_unet_train_fwd_loss_mr: bad pointers");
-  SVS_REQUIRE(H == 512 && W >= 2 && hop >= 512 && hop <= 1024, "svs_unet_train_fwd_loss_mr: needs H = 512 (n_fft 1024) and 512 <= hop <= 1024");
+  SVS_REQUIRE(H == 256 || H == 512 || H == 1024, "svs_unet_train_fwd_loss_mr: needs H = n_fft / 2 = 256, 512 or 1024 (n_fft 512, 1024 or 2048: the "
+              "sizes the inverse STFT and its transpose are built for), got H = %d", H);
+  SVS_REQUIRE(W >= 2 && hop > 0 && hop <= 2 * H, "svs_unet_train_fwd_loss_mr: needs W >= 2 and 0 < hop <= n_fft = %d (W = %d, hop = %d)", 2 * H, W, hop);
+  // the MR-STFT loss reflect-pads by half of its widest window (2048): the waveform must be longer than that
+  SVS_REQUIRE((long)hop * (W - 1) > 2048, "svs_unet_train_fwd_loss_mr: W = %d frames at hop = %d give waveforms of hop * (W - 1) = %ld samples; the "
+              "multi-resolution STFT loss needs more than 2048", W, hop, (long)hop * (W - 1));
   TrainCall c;
   int rc = train_prologue("svs_unet_train_fwd_loss_mr", params, B, H, W, ws, ws_bytes, c);
   if (rc) return rc;
@@ -721,8 +727,8 @@ extern "C" int svs_unet_train_fwd_loss_mr(const float* params, float* bn_buffers
   // waveforms: predicted magnitude (mask * mix, fused into the inverse's load) with the MIXTURE phase, target with its own
   const int64_t cs = (int64_t)H * W;
   const long L = (long)hop * (W - 1);
-  if ((rc = svs_istft_tiles(mix, cs, W, H, 1, mk, 0, mix_phase, 3, B, 2 * H, hop, W, m.wav_pred, nullptr, stream))) return rc;   // train.py:288
-  if ((rc = svs_istft_tiles(voc, cs, W, H, 1, nullptr, 0, voc_phase, 3, B, 2 * H, hop, W, m.wav_tgt, nullptr, stream))) return rc; // train.py:291
+  if ((rc = svs_istft_tiles_n(mix, cs, W, H, 1, mk, 0, mix_phase, 3, B, 2 * H, hop, W, m.wav_pred, nullptr, stream))) return rc;   // train.py:288
+  if ((rc = svs_istft_tiles_n(voc, cs, W, H, 1, nullptr, 0, voc_phase, 3, B, 2 * H, hop, W, m.wav_tgt, nullptr, stream))) return rc; // train.py:291
   if ((rc = svs_mrstft_loss_fwd_bwd(m.wav_pred, m.wav_tgt, B, L, alpha_mr, losses + 1, m.d_wav, m.mr, m.mr_bytes, stream))) return rc;  // train.py:293
   // d_logit += d(alpha_mr * MR)/d(wav) through the inverse STFT and |S| = mask * mix
   return svs_istft_bwd_mask(m.d_wav, mix_phase, mix, mk, c.t.d_logit, 1.0f, B, 2 * H, hop, W, stream);

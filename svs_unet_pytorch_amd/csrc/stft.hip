@@ -87,6 +87,8 @@ __device__ __forceinline__ int xpose_at(int wave, int k) { return wave * FftSize
 // ------------------------------------------------------------------------------------------------
 enum { SRC_SIGNAL = 0, SRC_ENVDIV = 1 };        // x[s] zero-padded | d_wav[s] / envelope (transpose of the inverse's tail)
 enum { SINK_MAGPHASE = 0, SINK_DMAG = 1 };
+// SINK_DMAG: whether the angle rows are staged after the transform in the waves' own buffers (no LDS plane of their own)
+__host__ __device__ constexpr bool dmag_late_angles(int n_fft) { return n_fft == 2048; }
 struct StftArgs {
   const float* y; long n_samples; int channels; int hop; int T;     // T frames per channel
   float* mag; SpecLayout lay;                                       // SINK_MAGPHASE
@@ -105,10 +107,14 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
   constexpr int BUF = FftSize<NFFT>::BUF, TW = FftSize<NFFT>::TW;
   float2* const fbuf = (float2*)smem;                       // [8][BUF]
   float2* const tw = fbuf + 8 * BUF;                        // [TW]
-  float* const angs = (float*)(tw + TW);                    // SINK_DMAG only: [513 * 17]
+  float* const angs = (float*)(tw + TW);                    // SINK_DMAG, N <= 1024 only: [513 * 17]
+  // SINK_DMAG at N = 2048: the eight buffers and the twiddles are 157,696 of the CU's 163,840 B, so the 1025 x 17 staged
+  // angles (69,700 B) have no room of their own.  They are loaded AFTER the transform instead, into the second plane of the
+  // transposed round (BUF / 2 above the first, as phase_mode 2 uses it), once every wave holds its spectra in registers.
+  constexpr bool LATE_ANGLES = SINK == SINK_DMAG && dmag_late_angles(NFFT);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = blockIdx.y, t0 = blockIdx.x * GROUP;
-  if (SINK == SINK_DMAG) {
+  if (SINK == SINK_DMAG && !LATE_ANGLES) {
     const int col = tid & (GROUP - 1), t = t0 + col;
     const long cbase = t < p.T ? p.lay.col(c, t) : 0;
     for (int k = tid >> 4; k < NBIN; k += 512 / GROUP)
@@ -167,6 +173,17 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
     B[r] = float2{0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)};
   }
   fft_wave_sync();                                          // every lane has read Z before the buffer is rewritten below
+  if (LATE_ANGLES) {
+    // rows in: 16 consecutive frames of a bin = one 64-byte run; thread (k, col) -> second plane of wave col >> 1, component
+    // col & 1, so that a wave reads the angles of its two frames back as one float2 (the banks are those of the rows-out read)
+    __syncthreads();                                        // every WAVE has read its Z: other waves' threads write into its buffer
+    float* const xa = (float*)fbuf;
+    const int col = tid & (GROUP - 1), t = t0 + col;
+    const long cbase = t < p.T ? p.lay.col(c, t) : 0;
+    for (int k = tid >> 4; k < NBIN; k += 512 / GROUP)
+      xa[2 * (xpose_at<NFFT>(col >> 1, k) + BUF / 2) + (col & 1)] = (k >= p.lay.first_bin && t < p.T) ? p.angle[cbase + (long)k * p.lay.seg] : 0.f;
+    __syncthreads();
+  }
   float vmax = 0.f;
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
@@ -191,7 +208,10 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
       const bool edge = (k == 0 || k == NFFT / 2);
       const float ck = edge ? 1.0f / NFFT : 2.0f / NFFT;
       // (the same one-instruction phasors as the inverse it is the transpose of)
-      const float ra = angs[k * SROW + 2 * wave] * 0.15915494309189535f, rb = angs[k * SROW + 2 * wave + 1] * 0.15915494309189535f;
+      float aa, ab;
+      if (LATE_ANGLES) { const float2 a2 = fbuf[xpose_at<NFFT>(wave, k) + BUF / 2]; aa = a2.x; ab = a2.y; }
+      else { aa = angs[k * SROW + 2 * wave]; ab = angs[k * SROW + 2 * wave + 1]; }
+      const float ra = aa * 0.15915494309189535f, rb = ab * 0.15915494309189535f;
       const float sa = __builtin_amdgcn_sinf(ra), ca = __builtin_amdgcn_cosf(ra), sb = __builtin_amdgcn_sinf(rb), cb = __builtin_amdgcn_cosf(rb);
       out = float2{ck * (A[r].x * ca + (edge ? 0.f : A[r].y * sa)), ck * (B[r].x * cb + (edge ? 0.f : B[r].y * sb))};
     }
@@ -583,7 +603,11 @@ static size_t fft_lds_bytes(int n_fft, int waves) {       // the waves' buffers 
   return (size_t)waves * buf * 8 + tw * 8;
 }
 // forward and two-frames-per-sample inverse, eight waves: 39,424 B (512), 79,872 B (1024: two blocks per CU), 157,696 B (2048)
-static size_t fwd_lds_bytes(int n_fft, bool dmag) { return fft_lds_bytes(n_fft, 8) + (dmag ? (size_t)(n_fft / 2 + 1) * SROW * 4 : 0); }
+// the transposed operator adds its staged-angle plane: 56,900 B (512) and 114,756 B (1024); at 2048 the angles go through the
+// buffers themselves (dmag_late_angles) and the block stays at 157,696 B
+static size_t fwd_lds_bytes(int n_fft, bool dmag) {
+  return fft_lds_bytes(n_fft, 8) + (dmag && !dmag_late_angles(n_fft) ? (size_t)(n_fft / 2 + 1) * SROW * 4 : 0);
+}
 template <class K>
 static int allow_lds(K kernel, size_t bytes) {
   SVS_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
@@ -765,23 +789,30 @@ extern "C" int svs_istft(const float* mag, const float* phase, int phase_is_angl
 
 // Transpose of the differentiable inverse of train.py:33-60 (`specific_istft`), fused with the mask's chain rule:
 //   d_logit[b, f, t] += alpha * dL/d|S|[b, f+1, t] * mix * mask * (1 - mask),   |S| = mask * mix (train.py:275,288)
-// d_wav: (B, hop * (T - 1)); angle / mix / mask / d_logit: (B, 1, 512, T) training tiles.  n_fft = 1024 only: training runs at
-// the config's window (ResidentSpectrograms' 512-row tiles, the multi-resolution objective's H == 512).
+// d_wav: (B, hop * (T - 1)); angle / mix / mask / d_logit: (B, 1, n_fft / 2, T) training tiles.  n_fft = 512, 1024 or 2048 and
+// any 0 < hop <= n_fft (the envelope division of SRC_ENVDIV walks however many frames cover a sample).
+template <int N>
+static int launch_istft_bwd(StftArgs& a, hipStream_t stream) {
+  const size_t lds = fwd_lds_bytes(N, true);
+  int rc = allow_lds(stft_fwd_kernel<N, SRC_ENVDIV, SINK_DMAG>, lds);
+  if (rc) return rc;
+  if ((rc = svs_fft_twiddles(N, stream, &a.twiddles))) return rc;
+  if (N != 1024 && (rc = svs_fft_hann(N, stream, &a.hann))) return rc;
+  dim3 grid((unsigned)((a.T + GROUP - 1) / GROUP), (unsigned)a.channels);
+  hipLaunchKernelGGL((stft_fwd_kernel<N, SRC_ENVDIV, SINK_DMAG>), grid, dim3(512), lds, stream, a);
+  SVS_CHECK_LAUNCH("istft_bwd");
+  return SVS_OK;
+}
 extern "C" int svs_istft_bwd_mask(const float* d_wav, const float* angle, const float* mix, const float* mask, float* d_logit,
                                   float alpha, int B, int n_fft, int hop, int frames, hipStream_t stream) {
   SVS_REQUIRE(d_wav && angle && mix && mask && d_logit && B > 0 && frames > 1 && hop > 0, "svs_istft_bwd_mask: bad arguments");
-  SVS_REQUIRE(n_fft == 1024, "svs_istft_bwd_mask: only n_fft=1024 is built, got %d", n_fft);
-  constexpr int NFFT = 1024, NBIN = NFFT / 2 + 1;
+  SVS_REQUIRE_NFFT("svs_istft_bwd_mask", n_fft);
+  SVS_REQUIRE(hop <= n_fft, "svs_istft_bwd_mask: hop %d > n_fft leaves samples that no frame covers", hop);
+  SVS_REQUIRE(B <= 65535, "svs_istft_bwd_mask: B = %d exceeds the grid's 65535 channels", B);
+  const int nbin = n_fft / 2 + 1;
   StftArgs a{};
   a.y = d_wav; a.n_samples = (long)hop * (frames - 1); a.channels = B; a.hop = hop; a.T = frames;
-  a.lay = SpecLayout{(long)(NBIN - 1) * frames, frames, NBIN - 1, 1, frames};
+  a.lay = SpecLayout{(long)(nbin - 1) * frames, frames, nbin - 1, 1, frames};
   a.angle = angle; a.mix = mix; a.mask = mask; a.d_logit = d_logit; a.alpha = alpha;
-  const size_t lds = fwd_lds_bytes(NFFT, true);
-  int rc = allow_lds(stft_fwd_kernel<NFFT, SRC_ENVDIV, SINK_DMAG>, lds);
-  if (rc) return rc;
-  if ((rc = svs_fft_twiddles(NFFT, stream, &a.twiddles))) return rc;
-  dim3 grid((unsigned)((frames + GROUP - 1) / GROUP), (unsigned)B);
-  hipLaunchKernelGGL((stft_fwd_kernel<NFFT, SRC_ENVDIV, SINK_DMAG>), grid, dim3(512), lds, stream, a);
-  SVS_CHECK_LAUNCH("istft_bwd");
-  return SVS_OK;
+  return n_fft == 512 ? launch_istft_bwd<512>(a, stream) : n_fft == 1024 ? launch_istft_bwd<1024>(a, stream) : launch_istft_bwd<2048>(a, stream);
 }

@@ -285,6 +285,7 @@ class UNet(nn.Module):
 
     def save(self, path):
         state = {"model_state_dict": self.state_dict(), "optim": self.optim.state_dict(), "dropout_step": self.dropout_step}
+        state.update(getattr(self, "stft_geometry", None) or {})    # train.py: {"win_size", "hop_size"} of the set it trains on
         for key in self.__dict__:
             if "loss_list" in key:
                 state[key] = getattr(self, key)
@@ -477,10 +478,11 @@ class UNet(nn.Module):
             self._ws[key] = ws
         return ws
 
-    def _fwd_losses(self, mix, voc, loss_scale, mix_phase, voc_phase, alpha_mr, ws):
+    def _fwd_losses(self, mix, voc, loss_scale, mix_phase, voc_phase, alpha_mr, ws, hop=None):
         """Forward + loss(es) + d(objective)/d(logit) left in the workspace.  Returns the L1 part as a device scalar; with
         phases and alpha_mr != 0 the multi-resolution STFT term of train.py:287-296 is part of the objective and its value
-        is kept in `self.last_mr_loss`."""
+        is kept in `self.last_mr_loss`.  The STFT window of that term is the tiles' own (n_fft = 2 H: 512, 1024 or 2048);
+        `hop` defaults to config.HOP_SIZE."""
         B, _, H, W = mix.shape
         L = lib()
         if mix_phase is None or not alpha_mr:
@@ -490,25 +492,28 @@ class UNet(nn.Module):
                                             B, H, W, float(loss_scale), None, ptr(loss), ptr(ws), ws.numel(), _lib.stream_ptr()),
                   "svs_unet_train_fwd_loss")
             return loss[0]
-        from .config import HOP_SIZE
+        if hop is None:
+            from .config import HOP_SIZE as hop
+        hop = int(hop)
         mix_phase, voc_phase = self._check_input(mix_phase), self._check_input(voc_phase)
         if mix_phase.shape != mix.shape or voc_phase.shape != mix.shape:
             raise ValueError("phase tensors must have the shape of the magnitude tiles")
-        mr_ws = self._mr_workspace(B, W, HOP_SIZE)
+        mr_ws = self._mr_workspace(B, W, hop)
         losses = torch.empty(2, dtype=torch.float32, device=mix.device)
         check(L.svs_unet_train_fwd_loss_mr(ptr(self._flat), ptr(self._bn_flat), ptr(self._nbt_flat), ptr(mix), ptr(voc), ptr(mix_phase),
-                                           ptr(voc_phase), ptr(self._drop), B, H, W, HOP_SIZE, float(loss_scale), float(alpha_mr), None,
+                                           ptr(voc_phase), ptr(self._drop), B, H, W, hop, float(loss_scale), float(alpha_mr), None,
                                            ptr(losses), ptr(ws), ws.numel(), ptr(mr_ws), mr_ws.numel(), _lib.stream_ptr()),
               "svs_unet_train_fwd_loss_mr")
         self.last_mr_loss = losses[1]
         return losses[0]
 
     @_on_model_device
-    def fwd_bwd(self, mix, voc, loss_scale=1.0, mix_phase=None, voc_phase=None, alpha_mr=0.0):
+    def fwd_bwd(self, mix, voc, loss_scale=1.0, mix_phase=None, voc_phase=None, alpha_mr=0.0, hop=None):
         """Fused training forward + loss + backward.  Objective: loss_scale * L1 terms (train.py:274-283) [+ alpha_mr *
         MR-STFT of the re-synthesised waveforms (train.py:287-296) when the phase tiles are given].  Gradients land in the
         flat gradient buffer; returns the unscaled L1 part as a device scalar (no host sync); the MR part, when
-        computed, is `self.last_mr_loss`."""
+        computed, is `self.last_mr_loss`.  `hop`: hop of the STFT the tiles came from (default config.HOP_SIZE); its window is
+        twice the tile height."""
         mix, voc = self._check_input(mix), self._check_input(voc)
         B, _, H, W = mix.shape
         ws = self._workspace("train", B, H, W)
@@ -524,7 +529,7 @@ class UNet(nn.Module):
                                                ws.numel(), _lib.stream_ptr()), "svs_unet_train_fwd_bwd")
             loss = loss[0]
         else:
-            loss = self._fwd_losses(mix, voc, loss_scale, mix_phase, voc_phase, alpha_mr, ws)
+            loss = self._fwd_losses(mix, voc, loss_scale, mix_phase, voc_phase, alpha_mr, ws, hop)
             check(lib().svs_unet_train_bwd_part(ptr(self._flat), ptr(target), ptr(mix), ptr(self._drop), B, H, W, 4, ptr(ws),
                                                 ws.numel(), _lib.stream_ptr()), "svs_unet_train_bwd_part")
         if tmp is not None:
@@ -533,7 +538,7 @@ class UNet(nn.Module):
         return loss
 
     @_on_model_device
-    def fwd_bwd_overlapped(self, mix, voc, loss_scale, grad_sync, mix_phase=None, voc_phase=None, alpha_mr=0.0):
+    def fwd_bwd_overlapped(self, mix, voc, loss_scale, grad_sync, mix_phase=None, voc_phase=None, alpha_mr=0.0, hop=None):
         """Same result as fwd_bwd, as five library calls so that the gradient exchange overlaps the backward:
         forward + loss; backward of the decoder half (its gradients occupy the tail of the flat buffer) followed
         at once by an asynchronous all-reduce of that tail; the conv6 block and its all-reduce; conv5 + conv4 and
@@ -547,7 +552,7 @@ class UNet(nn.Module):
         self._attach_grads()
         assert self._grads_clean, "overlapped exchange needs zero_grad() first (it overwrites the flat gradient buffer)"
         L = lib()
-        loss = self._fwd_losses(mix, voc, loss_scale, mix_phase, voc_phase, alpha_mr, ws)
+        loss = self._fwd_losses(mix, voc, loss_scale, mix_phase, voc_phase, alpha_mr, ws, hop)
         split = int(L.svs_unet_param_offset(24))           # first decoder tensor (deconv1.weight)
         c6 = int(L.svs_unet_param_offset(20))              # conv6.weight: the conv6 block is 13 of the encoder's 17.5 MB
         c4 = int(L.svs_unet_param_offset(12))              # conv4.weight: conv5 + conv4 are 4.1 MB, conv3..conv1 0.26 MB
@@ -570,18 +575,18 @@ class UNet(nn.Module):
         self._grads_clean = False
         return loss, handles
 
-    def train_step(self, mix, voc, loss_scale=1.0, grad_sync=None, mix_phase=None, voc_phase=None, alpha_mr=0.0):
+    def train_step(self, mix, voc, loss_scale=1.0, grad_sync=None, mix_phase=None, voc_phase=None, alpha_mr=0.0, hop=None):
         """zero_grad + fwd_bwd + (optional gradient all-reduce) + Adam: the whole of train.py:271-300
         (L1 terms).  `grad_sync` is the data-parallel hook (parallel.GradAllReduce): with `reduce_async` the
         exchange of the decoder half overlaps the encoder half's backward, otherwise `grad_sync(flat_grad)`
         runs after the backward."""
         self.optim.zero_grad()
         if grad_sync is not None and getattr(grad_sync, "overlap", False):
-            loss, handles = self.fwd_bwd_overlapped(mix, voc, loss_scale, grad_sync, mix_phase, voc_phase, alpha_mr)
+            loss, handles = self.fwd_bwd_overlapped(mix, voc, loss_scale, grad_sync, mix_phase, voc_phase, alpha_mr, hop)
             for h in handles:
                 h.wait()
         else:
-            loss = self.fwd_bwd(mix, voc, loss_scale, mix_phase, voc_phase, alpha_mr)
+            loss = self.fwd_bwd(mix, voc, loss_scale, mix_phase, voc_phase, alpha_mr, hop)
             if grad_sync is not None:
                 grad_sync(self._gflat)
         self.optim.step()

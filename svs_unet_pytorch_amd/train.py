@@ -3,7 +3,7 @@ reference's train.py (/root/reference/train.py:157-171, 65-143, 244-387), with t
 (train.py:265-300, L1 terms) running as one fused library call per step on each GPU.
 
     python -m svs_unet_pytorch_amd.train --train_folder spec/train --valid_folder spec/valid --label run1 \
-        --batch_size 64 --epoch 400 --val_interval 10 [--load_path CKPT/svs_run1.pth]
+        --batch_size 64 --epoch 400 --val_interval 10 [--load_path CKPT/svs_run1.pth] [--win_size 512|1024|2048] [--hop_size N]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m svs_unet_pytorch_amd.train ...
 
 What is kept: flags (--train_folder --load_path --label(required) --epoch --batch_size --valid_folder
@@ -21,6 +21,13 @@ SVS_OBJECTIVE=l1 drops the MR term (the BASELINE "L1-loss step"); it is also dro
 data set has no *_phase.npy files.  The logged totals are the same quantity as the reference's.  With WORLD_SIZE > 1 the batch is sharded over ranks and gradients are
 all-reduced over RCCL (parallel.py); rank 0 writes the files.  CKPT/ and LOG/ are created if missing (the
 reference assumes they exist).
+
+--win_size / --hop_size (the config's 1024 / 768 by default) name the STFT geometry of the folder that `data.py --direction
+to_spec --win_size W --hop_size H` wrote (data.py:24-25 lets both vary): tiles are (win_size / 2, INPUT_LEN), the network is
+fully convolutional, and the MR-STFT term re-synthesises its waveforms with that window and hop (its own three resolutions
+stay auraloss's).  Every file of the folder is checked against the window before anything is uploaded; checkpoints record
+`win_size` / `hop_size`, and resuming one under other flags is an error.  `separate.py --win_size W --hop_size H` takes the
+checkpoint.
 """
 from __future__ import annotations
 
@@ -32,15 +39,44 @@ import numpy as np
 import torch
 import torch.utils.data as Data
 
-from .config import INPUT_LEN, SAMPLES_PER_SONG
+from .config import HOP_SIZE, INPUT_LEN, SAMPLES_PER_SONG, WINDOW_SIZE
+from .data import WINDOW_SIZES            # the n_fft the transforms of csrc/stft.hip are built for
 from .model import ALPHA_L1, ALPHA_MR, UNet
 
 
-class SpectrogramDataset(Data.Dataset):
-    """train.py:65-143.  Returns (mix, voc, mix_phase, voc_phase), each float32 (1, 512, INPUT_LEN)."""
+def check_geometry(win_size, hop_size):
+    """The message for a --win_size / --hop_size pair that cannot be trained at, or None (data.py's own rule)."""
+    if win_size not in WINDOW_SIZES:
+        return (f"--win_size {win_size}: the STFT / iSTFT kernels are built for n_fft = {', '.join(map(str, WINDOW_SIZES))} "
+                f"(default {WINDOW_SIZE}, config.WINDOW_SIZE); --hop_size may be anything in 1..win_size")
+    if not 0 < hop_size <= win_size:
+        return f"--hop_size {hop_size}: must be in 1..{win_size} (a larger hop leaves samples that no frame covers)"
+    return None
 
-    def __init__(self, path, samples_per_song=SAMPLES_PER_SONG, with_phase=True):
+
+def checkpoint_geometry(checkpoint):
+    """(win_size, hop_size) a checkpoint was trained at; one written before the keys existed was trained at the config's."""
+    return int(checkpoint.get("win_size", WINDOW_SIZE)), int(checkpoint.get("hop_size", HOP_SIZE))
+
+
+def check_rows(path, rows, win_size):
+    """A spectrogram file of `rows` rows (DC row included) against the window: data.py writes win_size / 2 + 1 of them."""
+    if rows != win_size // 2 + 1:
+        fits = 2 * (rows - 1)
+        hint = f"--win_size {fits} would match it" if fits in WINDOW_SIZES else f"no built window ({', '.join(map(str, WINDOW_SIZES))}) matches it"
+        raise ValueError(f"{path}: {rows} rows, but --win_size {win_size} needs {win_size // 2 + 1} (n_fft / 2 + 1); {hint}")
+
+
+def _rows_of(path):
+    return int(np.load(path, mmap_mode="r").shape[0])          # (the header only: nothing of the array is read)
+
+
+class SpectrogramDataset(Data.Dataset):
+    """train.py:65-143.  Returns (mix, voc, mix_phase, voc_phase), each float32 (1, win_size / 2, INPUT_LEN)."""
+
+    def __init__(self, path, samples_per_song=SAMPLES_PER_SONG, with_phase=True, win_size=WINDOW_SIZE):
         self.path = path
+        self.win_size = int(win_size)
         self.with_phase = with_phase          # False: L1-only objective or a set without *_phase.npy -> empty phase tensors
         self.mixture_path = os.path.join(path, "mixture")
         self.vocal_path = os.path.join(path, "vocal")
@@ -49,6 +85,9 @@ class SpectrogramDataset(Data.Dataset):
             raise FileNotFoundError(f"Mixture folder not found: {self.mixture_path}")     # train.py:72-73
         names = sorted(f for f in os.listdir(self.mixture_path) if f.endswith("_spec.npy"))
         self.file_names = [f for f in names if os.path.exists(os.path.join(self.vocal_path, f))]
+        for f in self.file_names:                 # every song against the window, before anything is loaded or uploaded
+            for d in (self.mixture_path, self.vocal_path):
+                check_rows(os.path.join(d, f), _rows_of(os.path.join(d, f)), self.win_size)
         print(f"[{os.path.basename(path)}] {len(self.file_names)} songs x {self.samples_per_song} samples = {len(self)} items.")
 
     def __len__(self):
@@ -57,7 +96,9 @@ class SpectrogramDataset(Data.Dataset):
     def __getitem__(self, idx):
         name = self.file_names[idx % len(self.file_names)]
         pname = name.replace("_spec.npy", "_phase.npy")
-        mix = np.load(os.path.join(self.mixture_path, name))[1:, :]                      # drop the DC row (train.py:109-112)
+        mix = np.load(os.path.join(self.mixture_path, name))
+        check_rows(os.path.join(self.mixture_path, name), mix.shape[0], self.win_size)
+        mix = mix[1:, :]                                                                  # drop the DC row (train.py:109-112)
         voc = np.load(os.path.join(self.vocal_path, name))[1:, :]
         if self.with_phase:
             mix_phase = np.angle(np.load(os.path.join(self.mixture_path, pname))).astype(np.float32)[1:, :]
@@ -113,6 +154,10 @@ class ResidentSpectrograms:
         pname = lambda n: n.replace("_spec.npy", "_phase.npy")
         self.has_phase = with_phase and all(os.path.exists(os.path.join(d, pname(n))) for n in dataset.file_names
                                             for d in (dataset.mixture_path, dataset.vocal_path))
+        self.rows = dataset.win_size // 2
+        for name in dataset.file_names:          # (again here: the folder may have changed since the dataset listed it)
+            for d in (dataset.mixture_path, dataset.vocal_path):
+                check_rows(os.path.join(d, name), _rows_of(os.path.join(d, name)), dataset.win_size)
         for name in dataset.file_names:
             if self.has_phase:                       # unit phasors complex64 (513, T) -> rows 1.. (train.py:103-112)
                 ph_mix.append(np.ascontiguousarray(np.load(os.path.join(dataset.mixture_path, pname(name)))[1:, :], dtype=np.complex64).reshape(-1))
@@ -126,7 +171,6 @@ class ResidentSpectrograms:
             offsets.append(off)
             frames.append(mix.shape[1])
             off += mix.size
-        self.rows = 512
         empty = np.zeros(0, np.float32)
         self.mix = torch.from_numpy(np.concatenate(mix_parts) if mix_parts else empty).to(device)
         self.voc = torch.from_numpy(np.concatenate(voc_parts) if voc_parts else empty).to(device)
@@ -152,7 +196,7 @@ class ResidentSpectrograms:
         return songs, starts
 
     def crop(self, songs, starts, with_phase: bool = False):
-        """mix, voc [, mix_phase, voc_phase] (B, 1, 512, INPUT_LEN) on the device for the given songs / start frames; the
+        """mix, voc [, mix_phase, voc_phase] (B, 1, win_size / 2, INPUT_LEN) on the device for the given songs / start frames; the
         phase tiles are angles cut with the SAME start (train.py:121-127)."""
         from . import _lib
         B = len(songs)
@@ -187,14 +231,14 @@ def l1_terms(model, mix, voc):
     return model.crit(mask * mix, voc) + model.crit((1 - mask) * mix, torch.clamp(mix - voc, min=0.0))
 
 
-def mr_term(model, mix, voc, mix_phase, voc_phase):
-    """Eval-mode MR-STFT term of train.py:341-343 (no gradient): MR(specific_istft(mask*mix, mix_phase), specific_istft(voc, voc_phase))."""
+def mr_term(model, mix, voc, mix_phase, voc_phase, n_fft=WINDOW_SIZE, hop=HOP_SIZE):
+    """Eval-mode MR-STFT term of train.py:341-343 (no gradient): MR(specific_istft(mask*mix, mix_phase), specific_istft(voc, voc_phase)),
+    the waveforms re-synthesised with the window and hop the tiles were made with."""
     from . import _lib
-    from .config import HOP_SIZE, WINDOW_SIZE
     from .data import specific_istft
     mask = model(mix)
-    pred = specific_istft(mask * mix, mix_phase, WINDOW_SIZE, HOP_SIZE)
-    tgt = specific_istft(voc, voc_phase, WINDOW_SIZE, HOP_SIZE)
+    pred = specific_istft(mask * mix, mix_phase, n_fft, hop)
+    tgt = specific_istft(voc, voc_phase, n_fft, hop)
     B, L_ = pred.shape[0], pred.shape[-1]
     L = _lib.lib()
     ws = torch.empty(int(L.svs_mrstft_workspace_bytes(B, L_)), dtype=torch.uint8, device=mix.device)
@@ -213,7 +257,12 @@ def main(argv=None):
     parser.add_argument("--batch_size", type=int, default=2)
     parser.add_argument("--valid_folder", type=str, default="unet_spectrograms/valid")
     parser.add_argument("--val_interval", type=int, default=20)
+    parser.add_argument("--win_size", type=int, default=WINDOW_SIZE, help="STFT window the folders were written with (512, 1024 or 2048)")
+    parser.add_argument("--hop_size", type=int, default=HOP_SIZE, help="hop the folders were written with, 1..win_size")
     args = parser.parse_args(argv)
+    bad = check_geometry(args.win_size, args.hop_size)          # data.py:24-25 lets both vary; before any device is touched
+    if bad:
+        parser.error(bad)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -237,7 +286,16 @@ def main(argv=None):
         os.makedirs("LOG", exist_ok=True)
         os.makedirs("CKPT", exist_ok=True)
 
-    train_dataset = SpectrogramDataset(args.train_folder)
+    if os.path.exists(args.load_path):                                     # a checkpoint trained at another geometry: stop here
+        ck_geo = checkpoint_geometry(torch.load(args.load_path, map_location="cpu"))
+        if ck_geo != (args.win_size, args.hop_size):
+            raise SystemExit(f"train.py: {args.load_path} was trained at --win_size {ck_geo[0]} --hop_size {ck_geo[1]}, not at "
+                             f"--win_size {args.win_size} --hop_size {args.hop_size}: resume it with its own geometry")
+    try:                                                                   # and a folder written at another window
+        train_dataset = SpectrogramDataset(args.train_folder, win_size=args.win_size)
+        valid_dataset = SpectrogramDataset(args.valid_folder, win_size=args.win_size) if os.path.exists(args.valid_folder) else None
+    except ValueError as e:
+        raise SystemExit(f"train.py: {e}")
     sampler = train_loader = resident = None
     per_rank_batch = max(args.batch_size // world, 1)
     if os.environ.get("SVS_DATA_LOADER", "resident") == "resident":
@@ -247,8 +305,7 @@ def main(argv=None):
         train_loader = Data.DataLoader(train_dataset, batch_size=per_rank_batch, num_workers=8,
                                        shuffle=sampler is None, sampler=sampler, pin_memory=True)
     valid_loader = None
-    if os.path.exists(args.valid_folder):
-        valid_dataset = SpectrogramDataset(args.valid_folder)
+    if valid_dataset is not None:
         if len(valid_dataset) > 0:
             valid_loader = Data.DataLoader(valid_dataset, batch_size=max(args.batch_size // world, 1), num_workers=2,
                                            shuffle=False, pin_memory=True)
@@ -256,6 +313,8 @@ def main(argv=None):
         print(f"Warning: validation folder {args.valid_folder} not found, validation is skipped.")   # train.py:199-200
 
     model = UNet().to(device)
+    geometry = {"win_size": args.win_size, "hop_size": args.hop_size}
+    model.stft_geometry = geometry                                        # model.save (the best-validation checkpoint) records it too
     start_epoch = 0
     scheduler = None
     if os.path.exists(args.load_path):                                    # train.py:205-237
@@ -316,7 +375,7 @@ def main(argv=None):
             mix, voc = batch[0], batch[1]
             mph, vph = (batch[2], batch[3]) if full else (None, None)
             l1 = model.train_step(mix, voc, loss_scale=ALPHA_L1, grad_sync=grad_sync, mix_phase=mph, voc_phase=vph,
-                                  alpha_mr=alpha_mr)                                        # train.py:271-300
+                                  alpha_mr=alpha_mr, hop=args.hop_size)                     # train.py:271-300
             loss_sum += ALPHA_L1 * l1                                                       # no host sync per step
             if model.last_mr_loss is not None:
                 loss_sum += alpha_mr * model.last_mr_loss
@@ -334,7 +393,7 @@ def main(argv=None):
                     mix, voc = mix.to(device), voc.to(device)
                     val_sum += ALPHA_L1 * float(l1_terms(model, mix, voc))
                     if full and valid_dataset.with_phase:                  # train.py:341-346
-                        val_sum += alpha_mr * float(mr_term(model, mix, voc, mph.to(device), vph.to(device)))
+                        val_sum += alpha_mr * float(mr_term(model, mix, voc, mph.to(device), vph.to(device), args.win_size, args.hop_size))
             avg_val_loss = val_sum / len(valid_loader)
             log_buffer.append(f"Val {avg_val_loss}\n")
             print(f"\n[Epoch {ep + 1}] Train Loss: {avg_train_loss:.4e} | Val Loss: {avg_val_loss:.4e}")
@@ -354,7 +413,7 @@ def main(argv=None):
         if rank == 0:                                                      # train.py:369-382
             checkpoint = {"epoch": ep + 1, "model_state_dict": model.state_dict(), "optim": model.optim.state_dict(),
                           "scheduler": scheduler.state_dict() if scheduler is not None else None,
-                          "dropout_step": model.dropout_step}
+                          "dropout_step": model.dropout_step, **geometry}
             for key in model.__dict__:
                 if key.startswith("loss_list"):
                     checkpoint[key] = getattr(model, key)

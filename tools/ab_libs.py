@@ -3,6 +3,10 @@
 ONE device (devices differ by up to ~12%, so numbers from different gpurun calls cannot be compared).
 
     python tools/ab_libs.py tools/bin/libsvs_hip_A.so svs_unet_pytorch_amd/libsvs_hip.so [--batch 64]
+
+--full-step times instead the whole full-objective training pass (svs_unet_train_fwd_loss_mr + svs_unet_train_bwd_part: forward,
+L1 + MR-STFT losses, backward; no Adam) on 512 x 128 tiles at hop 768, alternating the two libraries round by round, and
+prints one JSON line.  Give it two builds of the SAME commit first: the B/A it prints for them is the spread of the harness.
 """
 import argparse
 import ctypes
@@ -21,7 +25,8 @@ DEC = ((512, 256), (512, 128), (256, 64), (128, 32), (64, 16))
 
 def load(path):
     h = ctypes.CDLL(os.path.abspath(path))
-    for name in ("svs_enc_block_fwd", "svs_dec_block_fwd", "svs_enc_block_bwd_weight"):
+    for name in ("svs_enc_block_fwd", "svs_dec_block_fwd", "svs_enc_block_bwd_weight", "svs_unet_train_fwd_loss_mr", "svs_unet_train_bwd_part",
+                 "svs_unet_train_workspace_bytes", "svs_unet_train_mr_workspace_bytes"):
         fn = getattr(h, name)
         fn.restype, fn.argtypes = _lib._SIGS[name]
     return h
@@ -38,15 +43,57 @@ def timeit(fn, reps=10):
     return e0.elapsed_time(e1) / reps
 
 
+def full_step(libs, B, rounds=7, reps=10):
+    """Best-of-`rounds` ms of the full-objective pass per library, the libraries taking turns inside every round."""
+    import json
+
+    from svs_unet_pytorch_amd import synth
+    from svs_unet_pytorch_amd.model import UNet
+    H, W, hop, dev = 512, 128, 768, "cuda"
+    model = UNet().to(dev).train()
+    mix_np, voc_np = synth.tiles(B, H, W, first_tile=800)
+    mix, voc = torch.from_numpy(mix_np).to(dev), torch.from_numpy(voc_np).to(dev)
+    mph, vph = ((torch.rand((B, 1, H, W), device=dev) * 2 - 1) * 3.14159 for _ in range(2))
+    drop = (torch.rand(B * (256 + 128 + 64 + 32 + 16), device=dev) > 0.5).float() * 2
+    grads, losses = torch.empty_like(model._flat), torch.empty(2, device=dev)
+    S = _lib.stream_ptr
+    runs, out = [], []
+    for Lb in libs:
+        ws = torch.empty(int(Lb.svs_unet_train_workspace_bytes(B, H, W)), dtype=torch.uint8, device=dev)
+        mr = torch.empty(int(Lb.svs_unet_train_mr_workspace_bytes(B, W, hop)), dtype=torch.uint8, device=dev)
+
+        def run(Lb=Lb, ws=ws, mr=mr):
+            rc = Lb.svs_unet_train_fwd_loss_mr(model._flat.data_ptr(), model._bn_flat.data_ptr(), model._nbt_flat.data_ptr(), mix.data_ptr(),
+                                               voc.data_ptr(), mph.data_ptr(), vph.data_ptr(), drop.data_ptr(), B, H, W, hop, 166.66, 1.0, None,
+                                               losses.data_ptr(), ws.data_ptr(), ws.numel(), mr.data_ptr(), mr.numel(), S())
+            rc = rc or Lb.svs_unet_train_bwd_part(model._flat.data_ptr(), grads.data_ptr(), mix.data_ptr(), drop.data_ptr(), B, H, W, 4,
+                                                  ws.data_ptr(), ws.numel(), S())
+            assert rc == 0, rc
+        runs.append(run)
+        run()
+        torch.cuda.synchronize()
+        out.append((grads.clone(), losses.clone()))
+    best = [1e9, 1e9]
+    for _ in range(rounds):
+        for i, r in enumerate(runs):
+            best[i] = min(best[i], timeit(r, reps))
+    print(json.dumps({"what": "full-objective fwd + losses + bwd, H=512 W=128 hop=768", "batch": B, "ms_A": round(best[0], 4),
+                      "ms_B": round(best[1], 4), "B_over_A": round(best[1] / best[0], 4),
+                      "grads_bitwise_equal": bool(torch.equal(out[0][0], out[1][0])), "losses_bitwise_equal": bool(torch.equal(out[0][1], out[1][1]))}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("lib_a")
     ap.add_argument("lib_b")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--wgrad", action="store_true")
+    ap.add_argument("--full-step", action="store_true")
     a = ap.parse_args()
     torch.zeros(1, device="cuda")
     libs = [load(a.lib_a), load(a.lib_b)]
+    if a.full_step:
+        return full_step(libs, a.batch)
     B, dev = a.batch, "cuda"
     hw = [(512, 128)]
     for _ in range(6):
