@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/svs_hip.h"
 
@@ -66,6 +67,24 @@ __device__ __forceinline__ float svs_wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+
+template <int N_, int I_ = 0, class F>
+__device__ __forceinline__ void svs_static_for(F&& f) {        // f(integral_constant<int, I>) for I = 0 .. N-1, unrolled
+  if constexpr (I_ < N_) {
+    f(std::integral_constant<int, I_>{});
+    svs_static_for<N_, I_ + 1>(f);
+  }
+}
+
+// x of lane R of the caller's quad of lanes (DPP quad_perm); every lane of the wave must be active
+template <int R>
+__device__ __forceinline__ float svs_quad_bcast(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), R * 0x55, 0xf, 0xf, true));
+}
+
+// 16-byte chunk `chunk` of the 64-byte LDS row `row` of a staged K-tile: XOR-swizzled so that the ds_read_b128 fragment reads of 16
+// consecutive rows are conflict-free
+__device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 3); }
 
 // the counter-based generator of svs_unet_pytorch_amd/synth.py
 __host__ __device__ __forceinline__ uint32_t svs_mix32(uint32_t x) {

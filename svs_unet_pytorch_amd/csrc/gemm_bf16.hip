@@ -15,8 +15,7 @@
 // 16-channel skip plane, 32 bytes per pixel each), so that conv1 / deconv5 write and conv2 reads whole HBM bursts instead of
 // 32 bytes of every 64.  Bound: HBM / launch at streaming batch sizes (bf16 MFMA peak ~2.5 PFLOP/s: 16x the fp32 rate).
 #include <string.h>
-#include <type_traits>
-
+#include "conv_geom.h"
 #include "unet_desc.h"
 
 typedef unsigned short u16;
@@ -36,16 +35,7 @@ struct ConvBf16Args {
   int ksplit; float* slab;         // fp32 partial sums [ksplit][B*Ho*Wo][N] when ksplit > 1
 };
 
-template <int N_, int I_ = 0, class F>
-__device__ __forceinline__ void bf_static_for(F&& f) {          // f(integral_constant<int, I>) for I = 0 .. N-1, unrolled
-  if constexpr (I_ < N_) {
-    f(std::integral_constant<int, I_>{});
-    bf_static_for<N_, I_ + 1>(f);
-  }
-}
-
-enum { BF_GATHER = 0, BF_PARITY = 1 };
-__device__ __forceinline__ int swz16(int row, int chunk) { return chunk ^ ((row >> 1) & 3); }
+enum { BF_GATHER = SVS_MODE_GATHER, BF_PARITY = SVS_MODE_PARITY };
 
 template <int MODE, int BM, int BN, int WM, int WN, int KB = 1>      // KB: K-tiles (32 channels of one tap each) per barrier
 __global__ __launch_bounds__(256) void conv_gemm_bf16_kernel(ConvBf16Args p) {
@@ -56,16 +46,9 @@ __global__ __launch_bounds__(256) void conv_gemm_bf16_kernel(ConvBf16Args p) {
   __shared__ __attribute__((aligned(16))) float Bs[2][KB][BN * 16];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = wave / WN, wn = wave % WN, lrow = lane & 15, q = lane >> 4;
-  int ph = 0, pw = 0, nth = 5, ntw = 5, Ha, Wa;
-  const u16* wp = p.wp;
-  if (MODE == BF_PARITY) {
-    const int par = blockIdx.z;
-    ph = par >> 1; pw = par & 1;
-    nth = 3 - ph; ntw = 3 - pw;
-    Ha = (p.Ho - ph + 1) >> 1; Wa = (p.Wo - pw + 1) >> 1;
-    const int poff = (par == 0) ? 0 : (par == 1) ? 9 : (par == 2) ? 15 : 21;
-    wp += (long)poff * p.N * p.C;
-  } else { Ha = p.Ho; Wa = p.Wo; }
+  const SvsConvClass cls = svs_conv_class<MODE>(blockIdx.z, p.Ho, p.Wo);
+  const int ph = cls.ph, pw = cls.pw, nth = cls.nth, ntw = cls.ntw, Ha = cls.Ha, Wa = cls.Wa;
+  const u16* const wp = p.wp + (long)cls.tap0 * p.N * p.C;
   const int ntaps = nth * ntw;
   const long M = (long)p.B * Ha * Wa;
   const int ntile_n = p.N / BN;
@@ -84,21 +67,10 @@ __global__ __launch_bounds__(256) void conv_gemm_bf16_kernel(ConvBf16Args p) {
     const int row = (t >> 2) + 64 * r;
     const long m = m0 + row;
     const bool ok = (row < BM) && (m < M);
-    const long mm = ok ? m : 0;
-    const unsigned um = (unsigned)mm, utmp = um / (unsigned)Wa;      // (M < 2^31, checked on the host: 32-bit divisions)
-    const int wq = (int)(um - utmp * (unsigned)Wa);
-    const unsigned ub = utmp / (unsigned)Ha;
-    const int hq = (int)(utmp - ub * (unsigned)Ha);
-    const long b = ub;
-    const int h0 = (MODE == BF_GATHER) ? 2 * hq : hq, w0 = (MODE == BF_GATHER) ? 2 * wq : wq;
-    a_voff[r] = ok ? (unsigned)((((b * p.H + h0) * p.W + w0) * p.ldx + chunk * 8) * 2) : OOB;
-    unsigned mask = 0;
-    for (int th = 0; th < nth; ++th)
-      for (int tw = 0; tw < ntw; ++tw) {
-        const int ih = (MODE == BF_GATHER) ? h0 - 2 + th : h0 + 1 - th, iw = (MODE == BF_GATHER) ? w0 - 2 + tw : w0 + 1 - tw;
-        if (ok && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) mask |= 1u << (th * ntw + tw);
-      }
-    a_mask[r] = mask;
+    const SvsConvRow g = svs_conv_row<false>(ok ? (unsigned)m : 0u, p.B, Ha, Wa);      // (M < 2^31, checked on the host)
+    const int h0 = svs_conv_anchor<MODE>(g.hq), w0 = svs_conv_anchor<MODE>(g.wq);
+    a_voff[r] = ok ? (unsigned)(((((long)g.b * p.H + h0) * p.W + w0) * p.ldx + chunk * 8) * 2) : OOB;
+    a_mask[r] = ok ? svs_tap_mask<MODE>(h0, w0, nth, ntw, p.H, p.W) : 0u;
   }
   unsigned b_voff[RB];
 #pragma unroll
@@ -106,13 +78,14 @@ __global__ __launch_bounds__(256) void conv_gemm_bf16_kernel(ConvBf16Args p) {
     const int row = (t >> 2) + 64 * r;
     b_voff[r] = (row < BN) ? (unsigned)(((long)(n0 + row) * Kw + chunk * 8) * 2) : OOB;
   }
-  const long shift_px = (MODE == BF_GATHER) ? (2L * p.W + 2) * p.ldx : (1L * p.W + 1) * p.ldx;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x - shift_px), 0, OOB, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x - svs_tap_base_shift<MODE>(p.W, p.ldx)), 0, OOB, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wp, 0, OOB, 0x00020000);
   // A "step" is KB consecutive K-tiles behind ONE barrier: a bf16 K-tile is only TM * TN MFMAs of 16 cycles per wave (128-256
   // cycles), far less than a barrier plus an LDS round trip (rocprofv3 at 216 tiles, one K-tile per barrier: MFMA-busy
   // 0.10-0.23, waves parked on waitcnt / barriers 0.41-0.63 of their cycles).  Two register sets of a whole step each: the
   // request for step s + 2 is issued when step s starts, so an operand has a full step to arrive before it goes to LDS.
+  // This is the PF = 2 schedule of gemm_pipeline.h with a step as the position, written out here: on svs_k_loop this kernel's
+  // 256x32 and 64x128 GATHER forms take 180 and 200 registers instead of 148 and 152 and lose their third wave per SIMD.
   f32x4 ra[2][KB][RA], rb[2][KB][RB];
   auto load_step = [&](int kt0, auto setc) __attribute__((always_inline)) {      // tap outer, channel chunk inner; past kt_end: zeros
     constexpr int set_ = decltype(setc)::value;
@@ -122,9 +95,9 @@ __global__ __launch_bounds__(256) void conv_gemm_bf16_kernel(ConvBf16Args p) {
       const bool live = kt < kt_end;                          // (block-uniform)
       const int ktc = live ? kt : kt_begin;
       const int tap = ktc / cpt, cc = ktc - tap * cpt;
-      const int th = (ntw == 5) ? tap / 5 : (ntw == 3) ? tap / 3 : tap >> 1;
+      const int th = svs_tap_row(tap, ntw);
       const int tw = tap - th * ntw;
-      const int pix = (MODE == BF_GATHER) ? th * p.W + tw : (2 - th) * p.W + (2 - tw);
+      const int pix = svs_tap_pix<MODE>(th, tw, p.W);
       const int soff_a = __builtin_amdgcn_readfirstlane((int)((pix * p.ldx + (cc << 5)) * 2));
       const int soff_b = __builtin_amdgcn_readfirstlane((int)(((long)tap * p.C + (cc << 5)) * 2));
 #pragma unroll
@@ -144,12 +117,12 @@ __global__ __launch_bounds__(256) void conv_gemm_bf16_kernel(ConvBf16Args p) {
 #pragma unroll
       for (int r = 0; r < RA; ++r) {
         const int row = (t >> 2) + 64 * r;
-        if (BM % 64 == 0 || row < BM) *(f32x4*)(&As[buf][u][row * 16 + swz16(row, chunk) * 4]) = ra[set_][u][r];
+        if (BM % 64 == 0 || row < BM) *(f32x4*)(&As[buf][u][row * 16 + swz(row, chunk) * 4]) = ra[set_][u][r];
       }
 #pragma unroll
       for (int r = 0; r < RB; ++r) {
         const int row = (t >> 2) + 64 * r;
-        if (BN % 64 == 0 || row < BN) *(f32x4*)(&Bs[buf][u][row * 16 + swz16(row, chunk) * 4]) = rb[set_][u][r];
+        if (BN % 64 == 0 || row < BN) *(f32x4*)(&Bs[buf][u][row * 16 + swz(row, chunk) * 4]) = rb[set_][u][r];
       }
     }
   };
@@ -164,7 +137,7 @@ __global__ __launch_bounds__(256) void conv_gemm_bf16_kernel(ConvBf16Args p) {
   if (nstep > 0) store_step(0, std::integral_constant<int, 0>{});
   __syncthreads();
   for (int s0 = 0; s0 < nstep; s0 += 2) {
-    bf_static_for<2>([&](auto dc) {
+    svs_static_for<2>([&](auto dc) {
       constexpr int d_ = decltype(dc)::value;
       const int st = s0 + d_;
       if (st < nstep) {                                       // (block-uniform)
@@ -176,12 +149,12 @@ __global__ __launch_bounds__(256) void conv_gemm_bf16_kernel(ConvBf16Args p) {
 #pragma unroll
           for (int i = 0; i < TM; ++i) {
             const int row = wm * (TM * 16) + i * 16 + lrow;
-            fa[i] = __builtin_bit_cast(bf16x8, *(const f32x4*)(&As[buf][u][row * 16 + swz16(row, q) * 4]));
+            fa[i] = __builtin_bit_cast(bf16x8, *(const f32x4*)(&As[buf][u][row * 16 + swz(row, q) * 4]));
           }
 #pragma unroll
           for (int j = 0; j < TN; ++j) {
             const int row = wn * (TN * 16) + j * 16 + lrow;
-            fb[j] = __builtin_bit_cast(bf16x8, *(const f32x4*)(&Bs[buf][u][row * 16 + swz16(row, q) * 4]));
+            fb[j] = __builtin_bit_cast(bf16x8, *(const f32x4*)(&Bs[buf][u][row * 16 + swz(row, q) * 4]));
           }
 #pragma unroll
           for (int i = 0; i < TM; ++i)
@@ -202,15 +175,10 @@ __global__ __launch_bounds__(256) void conv_gemm_bf16_kernel(ConvBf16Args p) {
   for (int i = 0; i < TM; ++i) {
     const long m = m0 + wm * (TM * 16) + i * 16 + lrow;
     if (m >= M) continue;
-    long opix;
-    if (MODE == BF_GATHER) opix = m;
-    else {
-      const unsigned um = (unsigned)m, utmp = um / (unsigned)Wa;
-      const int wq = (int)(um - utmp * (unsigned)Wa);
-      const unsigned ub = utmp / (unsigned)Ha;
-      const int hq = (int)(utmp - ub * (unsigned)Ha);
-      const long b = ub;
-      opix = (b * p.Ho + 2 * hq + ph) * p.Wo + 2 * wq + pw;
+    long opix = m;
+    if (MODE == BF_PARITY) {
+      const SvsConvRow g = svs_conv_row<false>((unsigned)m, p.B, Ha, Wa);
+      opix = svs_out_pixel<MODE>(g.b, g.hq, g.wq, ph, pw, p.Ho, p.Wo);
     }
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -227,8 +195,6 @@ __global__ __launch_bounds__(256) void conv_gemm_bf16_kernel(ConvBf16Args p) {
     }
   }
 }
-
-
 
 // ------------------------------------------------------------------------------------------------
 // LDS-window form of the PARITY mode for the shallow decoder layers (deconv4: 128 -> 32, deconv5: 64 -> 16 channels; 2/3 of
@@ -250,7 +216,6 @@ __global__ __launch_bounds__(256) void parity_window_bf16_kernel(ConvBf16Args p)
   constexpr int CQ = C / 8, CC = C / 32;
   constexpr int NST = (NPX * CQ + 255) / 256;
   constexpr unsigned OOB = 0x80000000u;
-  constexpr int POFF[4] = {0, 9, 15, 21};
   extern __shared__ __attribute__((aligned(16))) unsigned char pw_smem[];
   unsigned char* const win = pw_smem;                            // [NPX * LPB]
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -316,14 +281,14 @@ __global__ __launch_bounds__(256) void parity_window_bf16_kernel(ConvBf16Args p)
   auto fetch_w = [&](auto sc, auto setc) __attribute__((always_inline)) {         // global -> register set: weights of step sc
     constexpr int s_ = decltype(sc)::value;
     constexpr int set_ = decltype(setc)::value;
-    constexpr int par = s_ < 9 ? 0 : s_ < 15 ? 1 : s_ < 21 ? 2 : 3;
-    constexpr int tap = s_ - POFF[par];
+    constexpr int par = svs_step_class(s_);
+    constexpr int tap = s_ - SVS_CLASS_TAP0[par];
     constexpr int ntaps = (3 - (par >> 1)) * (3 - (par & 1));
 #pragma unroll
     for (int k = 0; k < NWL; ++k) {
       const int e = t + k * 256, n = e / CQ, cq = e - n * CQ;
       const unsigned vo = e < WCH ? (unsigned)((n * ntaps * C + cq * 8) * 2) : OOB;
-      wreg[set_][k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, (int)vo, (POFF[par] * N * C + tap * C) * 2, 0));
+      wreg[set_][k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, (int)vo, (SVS_CLASS_TAP0[par] * N * C + tap * C) * 2, 0));
     }
   };
   auto stash_w = [&](int buf, auto setc) __attribute__((always_inline)) {
@@ -336,8 +301,8 @@ __global__ __launch_bounds__(256) void parity_window_bf16_kernel(ConvBf16Args p)
   };
   auto step = [&](auto sc, f32x4 (&acc)[TM][TN], int wbuf) {
     constexpr int s_ = decltype(sc)::value;
-    constexpr int par = s_ < 9 ? 0 : s_ < 15 ? 1 : s_ < 21 ? 2 : 3;
-    constexpr int tap = s_ - POFF[par];
+    constexpr int par = svs_step_class(s_);
+    constexpr int tap = s_ - SVS_CLASS_TAP0[par];
     constexpr int ntw = 3 - (par & 1);
     constexpr int th = tap / ntw, tw = tap % ntw;
     constexpr int aoff = ((1 - th) * WW + (1 - tw)) * LPB;
@@ -385,9 +350,9 @@ __global__ __launch_bounds__(256) void parity_window_bf16_kernel(ConvBf16Args p)
   };
   f32x4 acc[TM][TN];
   using I0 = std::integral_constant<int, 0>;
-  if constexpr (WALL) bf_static_for<25>([&](auto sc) { fetch_w(sc, I0{}); stash_w(decltype(sc)::value, I0{}); });
+  if constexpr (WALL) svs_static_for<25>([&](auto sc) { fetch_w(sc, I0{}); stash_w(decltype(sc)::value, I0{}); });
   else {
-    bf_static_for<DEPTH>([&](auto sc) { fetch_w(sc, sc); });
+    svs_static_for<DEPTH>([&](auto sc) { fetch_w(sc, sc); });
     stash_w(0, I0{});
   }
   int gstep = 0;                               // taps done so far (all tiles): its parity is the weight buffer of the current tap
@@ -401,10 +366,10 @@ __global__ __launch_bounds__(256) void parity_window_bf16_kernel(ConvBf16Args p)
     commit_window(tile);
     if (PREFETCH && tile + (int)gridDim.x < ntiles) fetch_window(tile + gridDim.x);
     __syncthreads();
-    bf_static_for<25>([&](auto sc) {
+    svs_static_for<25>([&](auto sc) {
       constexpr int s_ = decltype(sc)::value;
-      constexpr int par = s_ < 9 ? 0 : s_ < 15 ? 1 : s_ < 21 ? 2 : 3;
-      if constexpr (s_ == POFF[par]) {
+      constexpr int par = svs_step_class(s_);
+      if constexpr (s_ == SVS_CLASS_TAP0[par]) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -412,7 +377,7 @@ __global__ __launch_bounds__(256) void parity_window_bf16_kernel(ConvBf16Args p)
       }
       if constexpr (!WALL) fetch_w(std::integral_constant<int, (s_ + DEPTH) % 25>{}, std::integral_constant<int, s_ % DEPTH>{});
       step(sc, acc, gstep & 1);
-      if constexpr (s_ == 24 || s_ + 1 == POFF[par < 3 ? par + 1 : 3]) store_class(par, acc);
+      if constexpr (s_ + 1 == SVS_CLASS_TAP0[par + 1]) store_class(par, acc);
       if constexpr (!WALL) {
         stash_w((gstep + 1) & 1, std::integral_constant<int, (s_ + 1) % DEPTH>{});   // the other buffer: its last readers passed the barrier that ended the previous tap
         __syncthreads();
@@ -606,7 +571,7 @@ __global__ __launch_bounds__(256) void conv2_window_bf16_kernel(Conv2WinArgs p) 
     // pixel fragment of output row 2*wave + i: lane (pixel lrow, q) reads channels half*8.. of tap 2s + t2
     const unsigned char* const pbase = &win[(((4 * wave) * 2) * PW + lrow) * 32 + half * 16];
     const unsigned char* const wbase = &wts[lrow * 64 + ((q ^ ((lrow >> 1) & 3)) * 16)];
-    bf_static_for<13>([&](auto sc) {
+    svs_static_for<13>([&](auto sc) {
       constexpr int s_ = decltype(sc)::value;
       constexpr int tap0 = 2 * s_, tap1 = (2 * s_ + 1 < 25) ? 2 * s_ + 1 : 24;     // (the 26th tap has zero weights: any finite data)
       constexpr int off0 = (((tap0 / 5) * 2 + ((tap0 % 5) & 1)) * PW + ((tap0 % 5) >> 1)) * 32;
@@ -709,7 +674,7 @@ __global__ __launch_bounds__(256) void conv3_window_bf16_kernel(Conv3WinArgs p) 
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    bf_static_for<25>([&](auto tc) {
+    svs_static_for<25>([&](auto tc) {
       constexpr int tap = decltype(tc)::value, kh = tap / 5, kw = tap % 5;
       bf16x8 fw[4], fp[2];
 #pragma unroll

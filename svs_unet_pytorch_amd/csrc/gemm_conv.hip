@@ -24,10 +24,11 @@
 #include <mutex>
 #include <type_traits>
 #include <vector>
-#include "common.h"
+#include "conv_geom.h"
+#include "gemm_pipeline.h"
 #include "mfma_split.h"
 
-enum { MODE_GATHER = 0, MODE_PARITY = 1 };
+enum { MODE_GATHER = SVS_MODE_GATHER, MODE_PARITY = SVS_MODE_PARITY };
 
 struct ConvGemmArgs {
   const float* x; long ldx;
@@ -66,7 +67,21 @@ struct ConvBal {
 };
 struct ConvNoBal {};
 
-__device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 3); }
+// One output value of a launch that writes y itself, shared by the address forms of conv_gemm_kernel's epilogue.  bias / scale /
+// shift [n]: the value's column in the call's arrays (read per value, under the test for the array) or in a lane's preloaded copy
+// of its columns; ssum / ssq: the lane's BatchNorm sums of that column.
+__device__ __forceinline__ void conv_put(const ConvGemmArgs& p, float v, float* dst, const float* bias, const float* scale, const float* shift,
+                                         int n, float& ssum, float& ssq) {
+  if (p.bias) v += bias[n];
+  if (p.scale) {
+    v = v * scale[n] + shift[n];
+    v = v > 0.f ? v : v * p.slope;
+  }
+  if (p.accumulate) v += *dst;
+  *dst = v;
+  ssum += v;
+  ssq += v * v;
+}
 
 // SKIP = true: rows are ordered (w, h, b) -- batch innermost -- instead of (b, h, w).  On the deep levels the images
 // are tiny (8x2 .. 32x8 anchors) and a third of the taps of an edge pixel fall into the zero padding; with the batch
@@ -125,19 +140,10 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
       upos = pos; ub0 = i * BM;
     }
   }
-  int ph = 0, pw = 0, nth = 5, ntw = 5;
-  int Ha, Wa;                      // rows / cols of the M grid
-  const float* wp = p.wp;
-  if (MODE == MODE_PARITY) {
-    const int par = bz;                     // classes outermost in dispatch order: all the long (9-tap) blocks start first
-    ph = par >> 1; pw = par & 1;
-    nth = 3 - ph; ntw = 3 - pw;
-    Ha = (p.Ho - ph + 1) >> 1; Wa = (p.Wo - pw + 1) >> 1;
-    const int poff = (par == 0) ? 0 : (par == 1) ? 9 : (par == 2) ? 15 : 21;
-    wp += (long)poff * p.N * p.C;
-  } else {
-    Ha = p.Ho; Wa = p.Wo;
-  }
+  const SvsConvClass cls = svs_conv_class<MODE>(bz, p.Ho, p.Wo);      // (classes outermost in dispatch order: all the long, 9-tap, blocks start first)
+  const int ph = cls.ph, pw = cls.pw, nth = cls.nth, ntw = cls.ntw;
+  const int Ha = cls.Ha, Wa = cls.Wa;                                // rows / cols of the M grid
+  const float* const wp = p.wp + (long)cls.tap0 * p.N * p.C;
   const int ntaps = nth * ntw;
   const long M = (long)p.B * Ha * Wa;
   const int ntile_n = p.N / BN;
@@ -175,17 +181,8 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
     }
     uwq = (int)((unsigned)upos / (unsigned)Ha);
     uhq = upos - uwq * Ha;
-    const int h0 = (MODE == MODE_GATHER) ? 2 * uhq : uhq, w0 = (MODE == MODE_GATHER) ? 2 * uwq : uwq;
-    unsigned wbits = 0;                           // taps tw inside the image's columns, then one copy per tap th inside its rows
-    for (int tw = 0; tw < ntw; ++tw) {
-      const int iw = (MODE == MODE_GATHER) ? w0 - 2 + tw : w0 + 1 - tw;
-      if ((unsigned)iw < (unsigned)p.W) wbits |= 1u << tw;
-    }
-    umask = 0;
-    for (int th = 0; th < nth; ++th) {
-      const int ih = (MODE == MODE_GATHER) ? h0 - 2 + th : h0 + 1 - th;
-      if ((unsigned)ih < (unsigned)p.H) umask |= wbits << (th * ntw);
-    }
+    const int h0 = svs_conv_anchor<MODE>(uhq), w0 = svs_conv_anchor<MODE>(uwq);
+    umask = svs_tap_mask<MODE>(h0, w0, nth, ntw, p.H, p.W);
     const unsigned base = (unsigned)((((long)h0 * p.W + w0) * p.ldx + chunk * 4) * 4);
     const unsigned per_image = (unsigned)(((long)p.H * p.W * p.ldx) * 4);
 #pragma unroll
@@ -200,31 +197,10 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
     const int row = (t >> 2) + 64 * r;
     const long m = m0 + row;
     const bool ok = (row < BM) && (m < M);
-    const long mm = ok ? m : 0;
-    int wq, hq; long b;
-    if (SKIP) {                                              // 32-bit: M < 2^31 follows from the host's 2 GiB view check
-      const unsigned pos = (unsigned)mm / (unsigned)p.B;
-      b = (long)((unsigned)mm - pos * (unsigned)p.B);
-      wq = (int)(pos / (unsigned)Ha);
-      hq = (int)(pos - (unsigned)wq * (unsigned)Ha);
-    } else {
-      const unsigned um = (unsigned)mm, utmp = um / (unsigned)Wa;
-      wq = (int)(um - utmp * (unsigned)Wa);
-      const unsigned ub = utmp / (unsigned)Ha;
-      hq = (int)(utmp - ub * (unsigned)Ha);
-      b = ub;
-    }
-    const int h0 = (MODE == MODE_GATHER) ? 2 * hq : hq;      // anchor pixel of the row
-    const int w0 = (MODE == MODE_GATHER) ? 2 * wq : wq;
-    a_voff[r] = ok ? (unsigned)((((b * p.H + h0) * p.W + w0) * p.ldx + chunk * 4) * 4) : OOB;
-    unsigned mask = 0;
-    for (int th = 0; th < nth; ++th)
-      for (int tw = 0; tw < ntw; ++tw) {
-        const int ih = (MODE == MODE_GATHER) ? h0 - 2 + th : h0 + 1 - th;
-        const int iw = (MODE == MODE_GATHER) ? w0 - 2 + tw : w0 + 1 - tw;
-        if (ok && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) mask |= 1u << (th * ntw + tw);
-      }
-    a_mask[r] = mask;
+    const SvsConvRow g = svs_conv_row<SKIP>(ok ? (unsigned)m : 0u, p.B, Ha, Wa);
+    const int h0 = svs_conv_anchor<MODE>(g.hq), w0 = svs_conv_anchor<MODE>(g.wq);      // anchor pixel of the row
+    a_voff[r] = ok ? (unsigned)(((((long)g.b * p.H + h0) * p.W + w0) * p.ldx + chunk * 4) * 4) : OOB;
+    a_mask[r] = ok ? svs_tap_mask<MODE>(h0, w0, nth, ntw, p.H, p.W) : 0u;
   }
   }
   if (SKIP) {
@@ -257,17 +233,15 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
     const int row = (t >> 2) + 64 * r;
     b_voff[r] = (row < BN) ? (unsigned)(((long)(n0 + row) * Kw + chunk * 4) * 4) : OOB;
   }
-  // base pointer shifted so that every per-tile scalar offset is >= 0: GATHER tap (th,tw) reads pixel
-  // anchor + (th-2, tw-2) = [anchor - (2,2)] + (th,tw); PARITY reads anchor + (1-th, 1-tw) = [anchor - (1,1)] + (2-th, 2-tw)
-  const long shift = (MODE == MODE_GATHER) ? (2L * p.W + 2) * p.ldx : (1L * p.W + 1) * p.ldx;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x - shift), 0, OOB, 0x00020000);
+  // (base pointer shifted so that every per-tile scalar offset is >= 0: conv_geom.h)
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x - svs_tap_base_shift<MODE>(p.W, p.ldx)), 0, OOB, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wp, 0, OOB, 0x00020000);
 
-  f32x4 ra[RA], rb[RB];
-  f32x4 ra2[PF == 2 ? RA : 1], rb2[PF == 2 ? RB : 1];       // PF = 2: a second register set (requests two K-tiles ahead)
+  f32x4 ra[PF][RA], rb[PF][RB];         // PF register sets (gemm_pipeline.h)
   // K-tile kt -> (tap, channel chunk), from block-uniform values only (plain scalar arithmetic: mutable loader
   // state captured by the lambdas below used to end up in scratch memory, with waterfall loops around the loads)
-  auto load_tile_to = [&](int kt, f32x4 (&ra)[RA], f32x4 (&rb)[RB]) __attribute__((always_inline)) {
+  auto load_tile = [&](int kt, auto setc) __attribute__((always_inline)) {
+    constexpr int set_ = decltype(setc)::value;
     int tap, cc;
     if (SKIP || !p.tap_inner) {            // tap outer, chunk inner
       if (p.cpt_shift >= 0) { tap = kt >> p.cpt_shift; cc = kt & (cpt - 1); }
@@ -276,35 +250,32 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
       cc = (ntaps == 25) ? kt / 25 : (ntaps == 9) ? kt / 9 : (ntaps == 6) ? kt / 6 : kt >> 2;
       tap = kt - cc * ntaps;
     }
-    const int th = (ntw == 5) ? tap / 5 : (ntw == 3) ? tap / 3 : tap >> 1;
+    const int th = svs_tap_row(tap, ntw);
     const int tw = tap - th * ntw;
-    const int pix = (MODE == MODE_GATHER) ? th * p.W + tw : (2 - th) * p.W + (2 - tw);
+    const int pix = svs_tap_pix<MODE>(th, tw, p.W);
     const int soff_a = __builtin_amdgcn_readfirstlane((int)((pix * p.ldx + (cc << 4)) * 4));
     const int soff_b = __builtin_amdgcn_readfirstlane((int)(((long)tap * p.C + (cc << 4)) * 4));
 #pragma unroll
     for (int r = 0; r < RA; ++r) {
       const unsigned vo = (UNI || ((a_mask[r] >> tap) & 1u)) ? a_voff[r] : OOB;       // (UNI: every tap visited is inside every row's mask)
-      ra[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)vo, soff_a, 0));
+      ra[set_][r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)vo, soff_a, 0));
     }
 #pragma unroll
     for (int r = 0; r < RB; ++r)
-      rb[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, (int)b_voff[r], soff_b, 0));
+      rb[set_][r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, (int)b_voff[r], soff_b, 0));
   };
-  auto load_tile = [&](int kt) __attribute__((always_inline)) { load_tile_to(kt, ra, rb); };
-  auto store_tile_from = [&](int buf, const f32x4 (&ra)[RA], const f32x4 (&rb)[RB]) __attribute__((always_inline)) {       // unconditional when the tile height is a multiple of 64 rows (no exec-mask branches)
+  auto store_tile = [&](int buf, auto setc) __attribute__((always_inline)) {       // unconditional when the tile height is a multiple of 64 rows (no exec-mask branches)
 #pragma unroll
     for (int r = 0; r < RA; ++r) {
       const int row = (t >> 2) + 64 * r;
-      if (BM % 64 == 0 || row < BM) *(f32x4*)(&As[buf][row * 16 + swz(row, chunk) * 4]) = ra[r];
+      if (BM % 64 == 0 || row < BM) *(f32x4*)(&As[buf][row * 16 + swz(row, chunk) * 4]) = ra[decltype(setc)::value][r];
     }
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
       const int row = (t >> 2) + 64 * r;
-      if (BN % 64 == 0 || row < BN) *(f32x4*)(&Bs[buf][row * 16 + swz(row, chunk) * 4]) = rb[r];
+      if (BN % 64 == 0 || row < BN) *(f32x4*)(&Bs[buf][row * 16 + swz(row, chunk) * 4]) = rb[decltype(setc)::value][r];
     }
   };
-
-  auto store_tile = [&](int buf) __attribute__((always_inline)) { store_tile_from(buf, ra, rb); };
   f32x4 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -351,78 +322,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][k], fb[j][k], acc[i][j], 0, 0, 0);
     }
   };
-  int kt_cur = first_valid(kt_begin);
-  if constexpr (PF == 2) {
-    // Two K-tiles in flight: the request for tile n + 2 goes out when tile n starts, so an operand has two tile times to arrive
-    // before it is written to LDS: one tile time -- 512 MFMA cycles on the 64x64 tile -- is less than an L2 / Infinity-Cache
-    // round trip under load (per layer at batch 64, one against two tiles ahead: deconv3 forward 130.7 -> 115.2 us, conv4
-    // backward-data 70.1 -> 63.3, the deep layers -1 ... -5 %).  Written out as two phases so that register set and LDS buffer are
-    // compile-time choices.  THREE tiles ahead (six phases) and a generic ring of PF sets with computed indices both measured
-    // ~5 % SLOWER on the whole train step (3.60 / 3.63 against 3.43 / 3.445 ms, same device): the loop body triples.
-    int kt_n1 = first_valid(kt_cur + 1);
-    if (kt_cur < kt_end) load_tile_to(kt_cur, ra, rb);
-    if (kt_n1 < kt_end) load_tile_to(kt_n1, ra2, rb2);
-    if (kt_cur < kt_end) store_tile_from(0, ra, rb);
-    __syncthreads();
-    while (kt_cur < kt_end) {
-      int kt_n2 = first_valid(kt_n1 + 1);                     // tile in LDS buffer 0; set 1 holds n1; set 0 is free
-      if (kt_n2 < kt_end) load_tile_to(kt_n2, ra, rb);
-      multiply(0);
-      if (kt_n1 < kt_end) store_tile_from(1, ra2, rb2);
-      __syncthreads();
-      kt_cur = kt_n1; kt_n1 = kt_n2;
-      if (kt_cur >= kt_end) break;
-      kt_n2 = first_valid(kt_n1 + 1);                         // tile in LDS buffer 1; set 0 holds n1; set 1 is free
-      if (kt_n2 < kt_end) load_tile_to(kt_n2, ra2, rb2);
-      multiply(1);
-      if (kt_n1 < kt_end) store_tile_from(0, ra, rb);
-      __syncthreads();
-      kt_cur = kt_n1; kt_n1 = kt_n2;
-    }
-  } else {
-  if (kt_cur < kt_end) {
-    load_tile(kt_cur);
-    store_tile(0);
-  }
-  __syncthreads();
-  for (int it = 0; kt_cur < kt_end; ++it) {
-    const int buf = it & 1;
-    const int kt_next = first_valid(kt_cur + 1);
-    const bool more = kt_next < kt_end;
-    if (more) load_tile(kt_next);
-    kt_cur = kt_next;
-    f32x4 fa[TM], fb[TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row = wm * (TM * 16) + i * 16 + lrow;
-      fa[i] = *(const f32x4*)(&As[buf][row * 16 + swz(row, q) * 4]);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int row = wn * (TN * 16) + j * 16 + lrow;
-      fb[j] = *(const f32x4*)(&Bs[buf][row * 16 + swz(row, q) * 4]);
-    }
-    if constexpr (SPLIT) {
-      SvsSplitA sa[TM];
-      SvsSplitB sb[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) sa[i] = svs_split_a(fa[i][0], fa[i][1], fa[i][2], fa[i][3]);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) sb[j] = svs_split_b(fb[j][0], fb[j][1], fb[j][2], fb[j][3]);
-      svs_mma_split<TM, TN>(acc, sa, sb);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][k], fb[j][k], acc[i][j], 0, 0, 0);
-    }
-    if (more) store_tile(buf ^ 1);
-    __syncthreads();
-  }
-  }
+  svs_k_loop<PF>(first_valid(kt_begin), kt_end, [&](int k) { return first_valid(k + 1); }, load_tile, store_tile, multiply);
 
   // ---- epilogue: C/D map of the 16x16 MFMA: col = lane & 15, row = 4*(lane>>4) + reg ------------
   const bool split = p.ksplit > 1;
@@ -436,8 +336,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
     // the lane's rows are images ub0 + wm * (TM * 16) + 4 q + 16 i + r of ONE output pixel: a base and a constant step, no divisions;
     // the per-column parameters once.  Values, stores and the order of the statistics' additions are the generic form's.
     const long HoWo = (long)p.Ho * p.Wo;
-    const long pix0 = ((MODE == MODE_GATHER) ? (long)uhq * p.Wo + uwq : (long)(2 * uhq + ph) * p.Wo + 2 * uwq + pw) +
-                      (long)(ub0 + wm * (TM * 16) + q * 4) * HoWo;
+    const long pix0 = svs_out_pixel<MODE>(0, uhq, uwq, ph, pw, p.Ho, p.Wo) + (long)(ub0 + wm * (TM * 16) + q * 4) * HoWo;
     const int ncol = n0 + wn * (TN * 16) + lrow;
     const long rstride = HoWo * (split ? (long)p.N : p.ldy);
     float* const out = split ? slab + pix0 * p.N + ncol : p.y + pix0 * p.ldy + ncol;
@@ -456,21 +355,8 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
         float* const row = out + (i * 16 + r) * rstride;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          float v = acc[i][j][r];
-          if (split) {
-            row[j * 16] = v;
-          } else {
-            if (p.bias) v += cb[j];
-            if (p.scale) {
-              v = v * csc[j] + csh[j];
-              v = v > 0.f ? v : v * p.slope;
-            }
-            float* dst = row + j * 16;
-            if (p.accumulate) v += *dst;
-            *dst = v;
-            ssum[j] += v;
-            ssq[j] += v * v;
-          }
+          if (split) row[j * 16] = acc[i][j][r];
+          else conv_put(p, acc[i][j][r], row + j * 16, cb, csc, csh, j, ssum[j], ssq[j]);
         }
       }
     }
@@ -481,42 +367,17 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p, std::con
     for (int r = 0; r < 4; ++r) {
       const long m = m0 + wm * (TM * 16) + i * 16 + q * 4 + r;
       if (m >= M) continue;
-      long opix;
-      if (SKIP) {
-        const unsigned pos = (unsigned)m / (unsigned)p.B;
-        const long b = (long)((unsigned)m - pos * (unsigned)p.B);
-        const int wq = (int)(pos / (unsigned)Ha);
-        const int hq = (int)(pos - (unsigned)wq * (unsigned)Ha);
-        opix = (MODE == MODE_GATHER) ? (b * p.Ho + hq) * p.Wo + wq : (b * p.Ho + 2 * hq + ph) * p.Wo + 2 * wq + pw;
-      } else if (MODE == MODE_GATHER) {
-        opix = m;
-      } else {                                     // (32-bit: M < 2^31, see the prologue; 64-bit divisions cost ~100 instructions each)
-        const unsigned um = (unsigned)m, utmp = um / (unsigned)Wa;
-        const int wq = (int)(um - utmp * (unsigned)Wa);
-        const unsigned ub = utmp / (unsigned)Ha;
-        const int hq = (int)(utmp - ub * (unsigned)Ha);
-        const long b = ub;
-        opix = (b * p.Ho + 2 * hq + ph) * p.Wo + 2 * wq + pw;
+      long opix = m;                                 // (b, h, w) rows in GATHER mode are the output pixels themselves
+      if (SKIP || MODE == MODE_PARITY) {
+        const SvsConvRow g = svs_conv_row<SKIP>((unsigned)m, p.B, Ha, Wa);
+        opix = svs_out_pixel<MODE>(g.b, g.hq, g.wq, ph, pw, p.Ho, p.Wo);
       }
       if constexpr (SKIP) { if (mark_rows && lrow == 0) bal.rowsplit[opix] = (unsigned char)nsplit; }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const int n = n0 + wn * (TN * 16) + j * 16 + lrow;
-        float v = acc[i][j][r];
-        if (split) {
-          slab[opix * p.N + n] = v;
-        } else {
-          if (p.bias) v += p.bias[n];
-          if (p.scale) {
-            v = v * p.scale[n] + p.shift[n];
-            v = v > 0.f ? v : v * p.slope;
-          }
-          float* dst = p.y + opix * p.ldy + n;
-          if (p.accumulate) v += *dst;
-          *dst = v;
-          ssum[j] += v;
-          ssq[j] += v * v;
-        }
+        if (split) slab[opix * p.N + n] = acc[i][j][r];
+        else conv_put(p, acc[i][j][r], p.y + opix * p.ldy + n, p.bias, p.scale, p.shift, n, ssum[j], ssq[j]);
       }
     }
   }
@@ -557,18 +418,9 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvGemmArgs p) {
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6;
   const int lrow = lane & 15, q = lane >> 4;
-  int ph = 0, pw = 0, nth = 5, ntw = 5, Ha, Wa;
-  const float* wp = p.wp;
-  if (MODE == MODE_PARITY) {
-    const int par = blockIdx.y;
-    ph = par >> 1; pw = par & 1;
-    nth = 3 - ph; ntw = 3 - pw;
-    Ha = (p.Ho - ph + 1) >> 1; Wa = (p.Wo - pw + 1) >> 1;
-    const int poff = (par == 0) ? 0 : (par == 1) ? 9 : (par == 2) ? 15 : 21;
-    wp += (long)poff * p.N * p.C;
-  } else {
-    Ha = p.Ho; Wa = p.Wo;
-  }
+  const SvsConvClass cls = svs_conv_class<MODE>(blockIdx.y, p.Ho, p.Wo);
+  const int ph = cls.ph, pw = cls.pw, nth = cls.nth, ntw = cls.ntw, Ha = cls.Ha, Wa = cls.Wa;
+  const float* const wp = p.wp + (long)cls.tap0 * p.N * p.C;
   const int ntaps = nth * ntw;
   const long M = (long)p.B * Ha * Wa;
   const long m0 = ((long)blockIdx.x * 4 + wave) * (TM * 16);
@@ -583,36 +435,22 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvGemmArgs p) {
   for (int i = 0; i < TM; ++i) {
     const long m = m0 + i * 16 + lrow;
     const bool ok = m < M;
-    const long mm = ok ? m : 0;
-    const unsigned um = (unsigned)mm, utmp = um / (unsigned)Wa;      // (M < 2^31: 32-bit divisions)
-    const int wq = (int)(um - utmp * (unsigned)Wa);
-    const unsigned ub = utmp / (unsigned)Ha;
-    const int hq = (int)(utmp - ub * (unsigned)Ha);
-    const long b = ub;
-    const int h0 = (MODE == MODE_GATHER) ? 2 * hq : hq;
-    const int w0 = (MODE == MODE_GATHER) ? 2 * wq : wq;
-    a_voff[i] = ok ? (unsigned)((((b * p.H + h0) * p.W + w0) * p.ldx + q * 4) * 4) : OOB;
-    unsigned mask = 0;
-    for (int th = 0; th < nth; ++th)
-      for (int tw = 0; tw < ntw; ++tw) {
-        const int ih = (MODE == MODE_GATHER) ? h0 - 2 + th : h0 + 1 - th;
-        const int iw = (MODE == MODE_GATHER) ? w0 - 2 + tw : w0 + 1 - tw;
-        if (ok && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) mask |= 1u << (th * ntw + tw);
-      }
-    a_mask[i] = mask;
+    const SvsConvRow g = svs_conv_row<false>(ok ? (unsigned)m : 0u, p.B, Ha, Wa);
+    const int h0 = svs_conv_anchor<MODE>(g.hq), w0 = svs_conv_anchor<MODE>(g.wq);
+    a_voff[i] = ok ? (unsigned)(((((long)g.b * p.H + h0) * p.W + w0) * p.ldx + q * 4) * 4) : OOB;
+    a_mask[i] = ok ? svs_tap_mask<MODE>(h0, w0, nth, ntw, p.H, p.W) : 0u;
   }
   unsigned b_voff[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) b_voff[j] = (unsigned)(((long)(j * 16 + lrow) * Kw + q * 4) * 4);
-  // base shifted so that every per-tile scalar offset is >= 0 (see conv_gemm_kernel for the tap geometry)
-  const long shift = (MODE == MODE_GATHER) ? (2L * p.W + 2) * p.ldx : (1L * p.W + 1) * p.ldx;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x - shift), 0, OOB, 0x00020000);
+  // (base shifted so that every per-tile scalar offset is >= 0: conv_geom.h)
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x - svs_tap_base_shift<MODE>(p.W, p.ldx)), 0, OOB, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wp, 0, OOB, 0x00020000);
 
   int l_th = 0, l_tw = 0, l_cc = 0;        // chunk outer, tap inner
   auto load_frags = [&](f32x4 (&fa)[TM], f32x4 (&fb)[TN]) {
     const int th = l_th, tw = l_tw, tap = th * ntw + tw;
-    const int pix = (MODE == MODE_GATHER) ? th * p.W + tw : (2 - th) * p.W + (2 - tw);
+    const int pix = svs_tap_pix<MODE>(th, tw, p.W);
     const int soff_a = (int)((pix * p.ldx + (l_cc << 4)) * 4);
     const int soff_b = (int)(((long)tap * p.C + (l_cc << 4)) * 4);
     if (++l_tw == ntw) { l_tw = 0; if (++l_th == nth) { l_th = 0; ++l_cc; } }
@@ -655,16 +493,10 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvGemmArgs p) {
     for (int r = 0; r < 4; ++r) {
       const long m = m0 + i * 16 + q * 4 + r;
       if (m >= M) continue;
-      long opix;
-      if (MODE == MODE_GATHER) {
-        opix = m;
-      } else {                                     // (32-bit: M < 2^31, see the prologue; 64-bit divisions cost ~100 instructions each)
-        const unsigned um = (unsigned)m, utmp = um / (unsigned)Wa;
-        const int wq = (int)(um - utmp * (unsigned)Wa);
-        const unsigned ub = utmp / (unsigned)Ha;
-        const int hq = (int)(utmp - ub * (unsigned)Ha);
-        const long b = ub;
-        opix = (b * p.Ho + 2 * hq + ph) * p.Wo + 2 * wq + pw;
+      long opix = m;
+      if (MODE == MODE_PARITY) {
+        const SvsConvRow g = svs_conv_row<false>((unsigned)m, p.B, Ha, Wa);
+        opix = svs_out_pixel<MODE>(g.b, g.hq, g.wq, ph, pw, p.Ho, p.Wo);
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
@@ -681,20 +513,6 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvGemmArgs p) {
       }
     }
   }
-}
-
-template <int N_, int I_ = 0, class F>
-__device__ __forceinline__ void svs_static_for(F&& f) {        // f(integral_constant<int, I>) for I = 0 .. N-1, unrolled
-  if constexpr (I_ < N_) {
-    f(std::integral_constant<int, I_>{});
-    svs_static_for<N_, I_ + 1>(f);
-  }
-}
-
-// x of lane R of the caller's quad of lanes (DPP quad_perm); every lane of the wave must be active
-template <int R>
-__device__ __forceinline__ float svs_quad_bcast(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), R * 0x55, 0xf, 0xf, true));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -721,7 +539,6 @@ void parity_window_kernel(ConvGemmArgs p) {      // (resident blocks per CU as b
   constexpr int CQ = CW / 4, CC = CW / 16;
   constexpr int NST = (NPX * CQ + 255) / 256;
   constexpr unsigned OOB = 0x80000000u;
-  constexpr int POFF[4] = {0, 9, 15, 21};
   __shared__ __attribute__((aligned(16))) float win[NPX * LP];
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6;
@@ -766,21 +583,21 @@ void parity_window_kernel(ConvGemmArgs p) {      // (resident blocks per CU as b
   f32x4 fb[2][CC][TN];
   auto load_b = [&](auto sc, int phase) {
     constexpr int s_ = decltype(sc)::value;
-    constexpr int par = s_ < 9 ? 0 : s_ < 15 ? 1 : s_ < 21 ? 2 : 3;
-    constexpr int tap = s_ - POFF[par];
+    constexpr int par = svs_step_class(s_);
+    constexpr int tap = s_ - SVS_CLASS_TAP0[par];
     constexpr int ntaps = (3 - (par >> 1)) * (3 - (par & 1));
-    // class weights start at POFF*N*C floats; row n of the class holds ntaps*C floats
+    // class weights start at SVS_CLASS_TAP0*N*C floats; row n of the class holds ntaps*C floats
 #pragma unroll
     for (int cc = 0; cc < CC; ++cc)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
         fb[s_ & 1][cc][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-            rw, (int)(b_voff[j] * ntaps + q * 16 + phase * (CW * 4)), (POFF[par] * (NT * 16) * C + tap * C + cc * 16) * 4, 0));
+            rw, (int)(b_voff[j] * ntaps + q * 16 + phase * (CW * 4)), (SVS_CLASS_TAP0[par] * (NT * 16) * C + tap * C + cc * 16) * 4, 0));
   };
   auto step = [&](auto sc, f32x4 (&acc)[TM][TN]) {
     constexpr int s_ = decltype(sc)::value;
-    constexpr int par = s_ < 9 ? 0 : s_ < 15 ? 1 : s_ < 21 ? 2 : 3;
-    constexpr int tap = s_ - POFF[par];
+    constexpr int par = svs_step_class(s_);
+    constexpr int tap = s_ - SVS_CLASS_TAP0[par];
     constexpr int ntw = 3 - (par & 1);
     constexpr int th = tap / ntw, tw = tap % ntw;
     constexpr int aoff = ((1 - th) * WW + (1 - tw)) * LP;
@@ -892,9 +709,9 @@ void parity_window_kernel(ConvGemmArgs p) {      // (resident blocks per CU as b
     load_b(std::integral_constant<int, 0>{}, 0);
     svs_static_for<25>([&](auto sc) {
       constexpr int s_ = decltype(sc)::value;
-      constexpr int par = s_ < 9 ? 0 : s_ < 15 ? 1 : s_ < 21 ? 2 : 3;
-      constexpr bool last = s_ == 24 || s_ + 1 == POFF[par < 3 ? par + 1 : 3];      // the class's last tap
-      if constexpr (s_ == POFF[par]) zero(acc);
+      constexpr int par = svs_step_class(s_);
+      constexpr bool last = s_ + 1 == SVS_CLASS_TAP0[par + 1];      // the class's last tap
+      if constexpr (s_ == SVS_CLASS_TAP0[par]) zero(acc);
       if constexpr (s_ + 1 < 25) load_b(std::integral_constant<int, (s_ + 1 < 25 ? s_ + 1 : 0)>{}, 0);
       if constexpr (last) pv = load_prev(par);                      // under this step's MFMAs
       __builtin_amdgcn_sched_barrier(0);
@@ -912,7 +729,7 @@ void parity_window_kernel(ConvGemmArgs p) {      // (resident blocks per CU as b
       load_b(std::integral_constant<int, 0>{}, phase);
       svs_static_for<25>([&](auto sc) {
         constexpr int s_ = decltype(sc)::value;
-        constexpr int par = s_ < 9 ? 0 : s_ < 15 ? 1 : s_ < 21 ? 2 : 3;
+        constexpr int par = svs_step_class(s_);
         if constexpr (s_ + 1 < 25) load_b(std::integral_constant<int, (s_ + 1 < 25 ? s_ + 1 : 0)>{}, phase);
         __builtin_amdgcn_sched_barrier(0);
         step(sc, acc[par]);
@@ -1148,7 +965,7 @@ __global__ __launch_bounds__(256) void gather_window_kernel(ConvGemmArgs p, int 
 enum ConvKind { CONV_GEMM, CONV_GATHER_WINDOW, CONV_PARITY_WINDOW, CONV_DIRECT };
 struct ConvPlan {
   int kind;
-  int cfg, BM, BN, WM, WN, pf;    // GEMM tile (cfg: the case of launch_conv_gemm_cfg), K-tiles requested ahead
+  int cfg, BM, BN, WM, WN;        // GEMM tile (cfg: the case of launch_conv_gemm_cfg)
   bool skip, split;               // tap skipping (batch-innermost rows), split-bf16 products (mfma_split.h)
   bool uni;                       // tap skipping with one pixel position per M-tile (UNI)
   long mtiles; int grid_y;        // M-tiles per parity class, parity classes
@@ -1220,11 +1037,13 @@ static void plan_gemm_tile(int mode, long Mmax, int N, int nkt_min, bool narrow,
   }
   if (svs_tune_on(SVS_TUNE_CONV_KSPLIT)) { int f = (int)svs_tune(SVS_TUNE_CONV_KSPLIT); if (f >= 1 && f <= nkt_min) ks = f; }
   pl.ksplit = ks;
-  // K-tiles requested ahead: two on every tile but 128x128 and 32x128 (same-device A/B at batch 64, train step: 3.530 -> 3.454 ms
-  // for the 64-row tiles, another -6 us for 128x64 / 256x32 / 256x16; eval forward 0.388 -> 0.379 ms at batch 16).  The 128x128
-  // and 32x128 tiles keep one ahead: at 164 registers a second set costs the 128x128 tile its third resident block.
-  pl.pf = (pl.cfg == 0 || pl.cfg == 4) ? 1 : 2;
 }
+
+// K-tiles requested ahead (PF of conv_gemm_kernel), a property of the tile: two on every tile but 128x128 and 32x128 (same-device
+// A/B at batch 64, train step: 3.530 -> 3.454 ms for the 64-row tiles, another -6 us for 128x64 / 256x32 / 256x16; eval forward
+// 0.388 -> 0.379 ms at batch 16).  The 128x128 and 32x128 tiles keep one ahead: at 164 registers a second set costs the 128x128
+// tile its third resident block.
+static constexpr int conv_gemm_pf(int BM, int BN) { return (BM == 128 && BN == 128) || BM == 32 ? 1 : 2; }
 
 // Host side of ConvBal (see the struct): per-position split counts for a tap-skipping launch.  Returns the number of slabs
 // (the largest split count), 0 = not applicable / not worth it -> uniform grid.  Purely a function of the shape, so the
@@ -1236,17 +1055,16 @@ static int plan_balance_search(int mode, int B, int H, int W, int C, int Ho, int
   int npos[4] = {0, 0, 0, 0}, nvk[4][64];
   long total = 0;
   for (int c = 0; c < ncls; ++c) {
-    const int ph = c >> 1, pw = c & 1;
-    const int Ha = (mode == MODE_PARITY) ? (Ho - ph + 1) / 2 : Ho, Wa = (mode == MODE_PARITY) ? (Wo - pw + 1) / 2 : Wo;
-    const int nth = (mode == MODE_PARITY) ? 3 - ph : 5, ntw = (mode == MODE_PARITY) ? 3 - pw : 5;
-    if (Ha * Wa > 64 || Ha * Wa < 1) return 0;
-    npos[c] = Ha * Wa;
-    for (int pos = 0; pos < npos[c]; ++pos) {                     // rows are ordered (w, h, b): pos = wq * Ha + hq
-      const int wq = pos / Ha, hq = pos - wq * Ha;
-      int vh = 0, vw = 0;
-      for (int th = 0; th < nth; ++th) { const int ih = (mode == MODE_GATHER) ? 2 * hq - 2 + th : hq + 1 - th; vh += (ih >= 0 && ih < H); }
-      for (int tw = 0; tw < ntw; ++tw) { const int iw = (mode == MODE_GATHER) ? 2 * wq - 2 + tw : wq + 1 - tw; vw += (iw >= 0 && iw < W); }
-      nvk[c][pos] = vh * vw * cpt;
+    const SvsConvClass g = (mode == MODE_PARITY) ? svs_conv_class<MODE_PARITY>(c, Ho, Wo) : svs_conv_class<MODE_GATHER>(c, Ho, Wo);
+    if (g.Ha * g.Wa > 64 || g.Ha * g.Wa < 1) return 0;
+    npos[c] = g.Ha * g.Wa;
+    for (int pos = 0; pos < npos[c]; ++pos) {                     // the kernel's own row decode and tap mask, for image 0 of the position
+      const SvsConvRow row = svs_conv_row<true>((unsigned)pos * (unsigned)B, B, g.Ha, g.Wa);
+      const unsigned mask =
+          (mode == MODE_PARITY)
+              ? svs_tap_mask<MODE_PARITY>(svs_conv_anchor<MODE_PARITY>(row.hq), svs_conv_anchor<MODE_PARITY>(row.wq), g.nth, g.ntw, H, W)
+              : svs_tap_mask<MODE_GATHER>(svs_conv_anchor<MODE_GATHER>(row.hq), svs_conv_anchor<MODE_GATHER>(row.wq), g.nth, g.ntw, H, W);
+      nvk[c][pos] = __builtin_popcount(mask) * cpt;
       total += (long)nvk[c][pos] * r * ntn;
     }
   }
@@ -1418,25 +1236,23 @@ static ConvPlan plan_conv_call(int mode, int B, int H, int W, int C, int Ho, int
   return p;
 }
 
-// one tile shape; the tap-skipping form exists for the tiles at least 64 wide, the two-ahead form for all but 128x128 and 32x128
+// one tile shape; the tap-skipping form exists for the tiles at least 64 wide
 template <int MODE, bool SPLIT, int BM, int BN, int WM, int WN>
 static void launch_conv_gemm_tile(const ConvGemmArgs& a, const ConvPlan& p, hipStream_t stream) {
-  constexpr int PF2 = (BM == 128 && BN == 128) || BM == 32 ? 1 : 2;
+  constexpr int PF = conv_gemm_pf(BM, BN);
   if constexpr (BN >= 64) {
     if constexpr (!SPLIT && !(BM == 128 && BN == 128)) {
       if (p.uni) {
-        hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, true, true, false, PF2>), p.grid, dim3(256), 0, stream, a, p.bal);
+        hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, true, true, false, PF>), p.grid, dim3(256), 0, stream, a, p.bal);
         return;
       }
     }
     if (p.skip) {
-      if (p.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, true, SPLIT, PF2>), p.grid, dim3(256), 0, stream, a, p.bal);
-      else hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, true, SPLIT, 1>), p.grid, dim3(256), 0, stream, a, p.bal);
+      hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, true, SPLIT, PF>), p.grid, dim3(256), 0, stream, a, p.bal);
       return;
     }
   }
-  if (p.pf == 2) hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, false, SPLIT, PF2>), p.grid, dim3(256), 0, stream, a, ConvNoBal{});
-  else hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, false, SPLIT, 1>), p.grid, dim3(256), 0, stream, a, ConvNoBal{});
+  hipLaunchKernelGGL((conv_gemm_kernel<MODE, BM, BN, WM, WN, false, false, SPLIT, PF>), p.grid, dim3(256), 0, stream, a, ConvNoBal{});
 }
 template <int MODE, bool SPLIT>
 static void launch_conv_gemm_cfg(const ConvGemmArgs& a, const ConvPlan& p, hipStream_t stream) {
@@ -1579,7 +1395,7 @@ int svs_conv_gemm_describe(int mode, int B, int H, int W, int C, int Ho, int Wo,
     case CONV_DIRECT: snprintf(buf, n, "conv_direct_kernel<%d, 4, %d>", mode, N / 16); break;
     default:
       snprintf(buf, n, "conv_gemm_kernel<%d, %d, %d, %d, %d, %s, %s, %s, %d>", mode, p.BM, p.BN, p.WM, p.WN, p.uni ? "true" : "false",
-               p.skip ? "true" : "false", p.split ? "true" : "false", p.pf);
+               p.skip ? "true" : "false", p.split ? "true" : "false", conv_gemm_pf(p.BM, p.BN));
   }
   return p.ksplit;
 }

@@ -15,6 +15,7 @@
 // Bound: MFMA; algorithmic FLOPs = 2 * Cs * 25*Cl * B*Hs*Ws.
 #include <stdlib.h>
 
+#include "gemm_pipeline.h"
 #include "internal.h"
 #include "mfma_split.h"
 
@@ -43,7 +44,7 @@ template <> __device__ __forceinline__ void store_vec<2>(float* p, const float (
 // the 16 pixels of a K-tile are the SAME position (i, j) of 16 images.  A tap that falls into the zero padding at
 // that position does so for the whole tile; a K-tile none of whose N-tile taps is inside the image is skipped
 // outright (about a third of the tiles on the 8x2 level).  The per-tile pixel decode also becomes scalar.
-template <int BM, int BN, int WM, int WN, bool SKIP = false, bool SPLIT = false, int PF = 1>     // SPLIT: mfma_split.h (optional mode); PF: K-tiles requested ahead
+template <int BM, int BN, int WM, int WN, bool SKIP, bool SPLIT, int PF>     // SPLIT: mfma_split.h (optional mode); PF: K-tiles requested ahead
 __global__ __launch_bounds__(256) void wgrad_gemm_kernel(WgradArgs p) {
   constexpr int TM = BM / WM / 16;
   constexpr int TN = BN / WN / 16;
@@ -161,8 +162,7 @@ __global__ __launch_bounds__(256) void wgrad_gemm_kernel(WgradArgs p) {
     }
     return (int)p_end;
   };
-  f32x4 ra[RA], rb[RB];
-  f32x4 ra2[PF == 2 ? RA : 1], rb2[PF == 2 ? RB : 1];       // PF = 2: a second register set (requests two K-tiles ahead)
+  f32x4 ra[PF][RA], rb[PF][RB];         // PF register sets (gemm_pipeline.h)
   auto load_tile_skip = [&](int pk, f32x4 (&ra)[RA], f32x4 (&rb)[RB]) __attribute__((always_inline)) {
     int i, j, b0;
     position(pk, i, j, b0);
@@ -198,13 +198,14 @@ __global__ __launch_bounds__(256) void wgrad_gemm_kernel(WgradArgs p) {
     }
     advance();
   };
-  auto store_tile = [&](int buf, const f32x4 (&ra)[RA], const f32x4 (&rb)[RB]) __attribute__((always_inline)) {
+  auto store_tile = [&](int buf, auto setc) __attribute__((always_inline)) {
+    constexpr int set_ = decltype(setc)::value;
 #pragma unroll
     for (int r = 0; r < RA; ++r)
-      if (aok[r]) *(f32x4*)(&As[buf][ak[r] * LDA + ac[r] * 4]) = ra[r];
+      if (aok[r]) *(f32x4*)(&As[buf][ak[r] * LDA + ac[r] * 4]) = ra[set_][r];
 #pragma unroll
     for (int r = 0; r < RB; ++r)
-      if (t + 256 * r < 16 * CB) *(f32x4*)(&Bs[buf][bk[r] * LDB + bc[r] * 4]) = rb[r];
+      if (t + 256 * r < 16 * CB) *(f32x4*)(&Bs[buf][bk[r] * LDB + bc[r] * 4]) = rb[set_][r];
   };
 
   f32x4 acc[TM][TN];
@@ -247,47 +248,12 @@ __global__ __launch_bounds__(256) void wgrad_gemm_kernel(WgradArgs p) {
     }
     }
   };
-  auto fetch = [&](int pkx, f32x4 (&xa)[RA], f32x4 (&xb)[RB]) __attribute__((always_inline)) { if (SKIP) load_tile_skip(pkx, xa, xb); else load_tile(pkx, xa, xb); };
-  int pk = first_valid((int)p_begin);
-  if constexpr (PF == 2) {
-    // two K-tiles in flight (see conv_gemm_kernel): the request for tile n + 2 goes out when tile n starts
-    int pk1 = first_valid(pk + 16);
-    if (pk < (int)p_end) fetch(pk, ra, rb);
-    if (pk1 < (int)p_end) fetch(pk1, ra2, rb2);
-    if (pk < (int)p_end) store_tile(0, ra, rb);
-    __syncthreads();
-    while (pk < (int)p_end) {
-      int pk2 = first_valid(pk1 + 16);
-      if (pk2 < (int)p_end) fetch(pk2, ra, rb);
-      multiply(0);
-      if (pk1 < (int)p_end) store_tile(1, ra2, rb2);
-      __syncthreads();
-      pk = pk1; pk1 = pk2;
-      if (pk >= (int)p_end) break;
-      pk2 = first_valid(pk1 + 16);
-      if (pk2 < (int)p_end) fetch(pk2, ra2, rb2);
-      multiply(1);
-      if (pk1 < (int)p_end) store_tile(0, ra, rb);
-      __syncthreads();
-      pk = pk1; pk1 = pk2;
-    }
-  } else {
-    if (pk < (int)p_end) {
-      fetch(pk, ra, rb);
-      store_tile(0, ra, rb);
-    }
-    __syncthreads();
-    for (int it = 0; pk < (int)p_end; ++it) {
-      const int buf = it & 1;
-      const int pkn = first_valid(pk + 16);
-      const bool more = pkn < (int)p_end;
-      if (more) fetch(pkn, ra, rb);
-      pk = pkn;
-      multiply(buf);
-      if (more) store_tile(buf ^ 1, ra, rb);
-      __syncthreads();
-    }
-  }
+  auto fetch = [&](int pk, auto setc) __attribute__((always_inline)) {
+    constexpr int set_ = decltype(setc)::value;
+    if (SKIP) load_tile_skip(pk, ra[set_], rb[set_]);
+    else load_tile(pk, ra[set_], rb[set_]);
+  };
+  svs_k_loop<PF>(first_valid((int)p_begin), (int)p_end, [&](int pk) { return first_valid(pk + 16); }, fetch, store_tile, multiply);
 
   // C/D map of the 16x16 MFMA (col = lane & 15, row = 4*(lane>>4) + reg) through the interleaving above:
   // tile (i, j), reg r holds row TM*(4q+r) + i, column TN*lrow + j -> the TN columns of a lane are adjacent
@@ -508,10 +474,14 @@ static WgWinPlan plan_wgrad_window(int B, int Hs, int Ws, int Cs, int Cl) {
 
 // One call's launch, decided once for svs_wgrad_gemm_run and svs_wgrad_gemm_describe: the window kernel, or the GEMM where the
 // window is not planned or its per-image views need 64-bit offsets
+// K-tiles requested ahead (PF of wgrad_gemm_kernel), a property of the tile and its form: two by the tap-skipping 128x128 and
+// 64x128 tiles (same-device A/B at batch 64: train step 3.465 -> 3.447 ms), one everywhere else
+static constexpr int wgrad_gemm_pf(int BM, bool skip) { return skip && BM != 32 ? 2 : 1; }
+
 struct WgradPlan {
   WgWinPlan win;                  // win.use: wgrad_window_kernel<win.MT>
   WgradTile tile;                 // else wgrad_gemm_kernel<BM, BN, WM, WN, skip, split, pf>
-  int WM, WN, pf;
+  int WM, WN;
   bool skip, split;
   dim3 grid;
   int nslab;                      // slabs the reduction sums
@@ -533,9 +503,6 @@ static WgradPlan plan_wgrad_call(int B, int Hs, int Ws, int Cs, int Cl, long lds
   const bool can_skip = B >= 16 && (B & (B - 1)) == 0 && (Ws & (Ws - 1)) == 0 && (long)B * Hs * Ws * lds * 4 < (1L << 31);
   const long f = svs_tune(SVS_TUNE_WGRAD_SKIP);
   p.skip = f == 0 ? false : f == 2 ? can_skip : can_skip && Ws <= 8;
-  // K-tiles requested ahead by the tap-skipping 128x128 and 64x128 tiles: two (same-device A/B at batch 64: train step 3.465 ->
-  // 3.447 ms)
-  p.pf = p.skip && p.tile.cfg <= 1 ? 2 : 1;
   p.split = svs_tune(SVS_TUNE_MFMA_SPLIT) > 0;      // optional mode: mfma_split.h
   p.grid = dim3((unsigned)(Cs / p.tile.BM), (unsigned)((25 * Cl + p.tile.BN - 1) / p.tile.BN), (unsigned)p.tile.ksplit);
   p.nslab = p.tile.ksplit;
@@ -568,10 +535,8 @@ static int wgrad_reduce_run(const float* slabs, int nslab, int Cs, int Cl, float
 
 template <bool SPLIT, int BM, int WM, int WN>
 static void launch_wgrad_tile(const WgradArgs& a, const WgradPlan& p, hipStream_t stream) {
-  constexpr int PF2 = BM == 32 ? 1 : 2;      // (the two-ahead variant exists for the 128x128 and 64x128 tiles)
-  if (!p.skip) hipLaunchKernelGGL((wgrad_gemm_kernel<BM, 128, WM, WN, false, SPLIT>), p.grid, dim3(256), 0, stream, a);
-  else if (p.pf == 2) hipLaunchKernelGGL((wgrad_gemm_kernel<BM, 128, WM, WN, true, SPLIT, PF2>), p.grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((wgrad_gemm_kernel<BM, 128, WM, WN, true, SPLIT>), p.grid, dim3(256), 0, stream, a);
+  if (p.skip) hipLaunchKernelGGL((wgrad_gemm_kernel<BM, 128, WM, WN, true, SPLIT, wgrad_gemm_pf(BM, true)>), p.grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((wgrad_gemm_kernel<BM, 128, WM, WN, false, SPLIT, wgrad_gemm_pf(BM, false)>), p.grid, dim3(256), 0, stream, a);
 }
 template <bool SPLIT>
 static void launch_wgrad_gemm(const WgradArgs& a, const WgradPlan& p, hipStream_t stream) {
@@ -624,6 +589,6 @@ int svs_wgrad_gemm_describe(int B, int Hs, int Ws, int Cs, int Cl, char* buf, si
   const WgradPlan p = plan_wgrad_call(B, Hs, Ws, Cs, Cl, Cs, 2 * Hs, 2 * Ws, Cl);
   if (p.win.use) snprintf(buf, n, "wgrad_window_kernel<%d>", p.win.MT);
   else snprintf(buf, n, "wgrad_gemm_kernel<%d, %d, %d, %d, %s, %s, %d>", p.tile.BM, p.tile.BN, p.WM, p.WN, p.skip ? "true" : "false",
-                p.split ? "true" : "false", p.pf);
+                p.split ? "true" : "false", wgrad_gemm_pf(p.tile.BM, p.skip));
   return p.nslab;
 }

@@ -349,6 +349,38 @@ def test_described_plans_name_built_kernels_and_fit_the_workspace(lib, tune, tmp
                 assert ws >= need, (where, ws, need)
 
 
+def test_each_gemm_tile_is_built_with_one_prefetch_depth(lib, tmp_path):
+    """PF (K-tiles requested ahead) is the last template argument of conv_gemm_kernel and wgrad_gemm_kernel and a compile-time
+    property of the tile: conv_gemm_pf(BM, BN) in gemm_conv.hip, wgrad_gemm_pf(BM, skip) in gemm_wgrad.hip, mirrored below.  Every
+    tile of the built library occurs with exactly that PF and no other (symbol names only: a form the launchers cannot reach is
+    compile time and code-object size for nothing)."""
+    import importlib.util
+    import re
+    spec = importlib.util.spec_from_file_location("check_isa", os.path.join(ROOT, "tools", "check_isa.py"))
+    isa = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(isa)
+    mangled = []
+    for co in isa.device_code_objects(_lib.LIB_PATH, str(tmp_path)):
+        syms = subprocess.run([f"{isa.LLVM}/llvm-objdump", "-t", co], capture_output=True, text=True, check=True).stdout
+        mangled += [ln.split()[-1] for ln in syms.splitlines() if " F .text" in ln]
+    demangled = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.splitlines()
+    args = lambda d: [a.strip() for a in re.search(r"<(.*)>", d.split("(")[0]).group(1).split(",")]
+    conv, wgrad = {}, {}                          # tile -> the PF values it is built with
+    for d in demangled:
+        if "conv_gemm_kernel<" in d:              # <MODE, BM, BN, WM, WN, UNI, SKIP, SPLIT, PF>
+            a = args(d)
+            conv.setdefault((int(a[1]), int(a[2]), int(a[3]), int(a[4])), set()).add(int(a[8]))
+        elif "wgrad_gemm_kernel<" in d:           # <BM, BN, WM, WN, SKIP, SPLIT, PF>: the tap-skipping form of a tile is a tile of its own
+            a = args(d)
+            wgrad.setdefault((int(a[0]), int(a[1]), int(a[2]), int(a[3]), a[4] == "true"), set()).add(int(a[6]))
+    assert set(conv) == {(128, 128, 2, 2), (128, 64, 2, 2), (256, 32, 4, 1), (256, 16, 4, 1), (32, 128, 1, 4), (64, 64, 2, 2), (64, 128, 2, 2)}
+    assert set(wgrad) == {(bm, 128, wm, 4 // wm, skip) for bm, wm in ((128, 2), (64, 1), (32, 1)) for skip in (False, True)}
+    for (bm, bn, _, _), pfs in conv.items():
+        assert pfs == {1 if (bm, bn) == (128, 128) or bm == 32 else 2}, (bm, bn, pfs)
+    for (bm, _, _, _, skip), pfs in wgrad.items():
+        assert pfs == {2 if skip and bm != 32 else 1}, (bm, skip, pfs)
+
+
 def test_bench_gpus_n_launches_child_ranks(tmp_path):
     """`python bench.py --gpus N` with no launcher around it starts N child ranks itself (before any GPU call), forwards rank 0's
     one JSON line and fails when a rank fails.  The ranks here are a stub script (SVS_BENCH_WORKER) that checks the rendezvous
