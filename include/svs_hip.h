@@ -348,6 +348,19 @@ int svs_istft_groups_n(int n_fft, int hop, int frames, int channels);
  * frames it walks for them (16 frames per round; 8 for n_fft = 2048 with hop < 1024, whose blocks have four waves) and the
  * dynamic LDS of a block in bytes.  hop >= n_fft / 2 is the two-frames-per-sample kernel (15 hops, one round). */
 int svs_istft_plan_n(int n_fft, int hop, int* hops_per_block, int* rounds, size_t* lds_bytes);
+/* Both stems of a mask from ONE launch (inference.py:100-107 computes either `mag * mask` or `mag * (1 - mask)`; the scorer
+ * forms the other stem as mix - vocal_est, evaluate.py:50-51): arguments as svs_istft_tiles_n without `invert`, the mask required.
+ *   y[0 .. ) (channels, hop * (frames - 1)) = istft(mag * mask * phase), and the same shape stem_stride floats higher
+ *   = istft(mag * (1 - mask) * phase); stem_stride >= channels * hop * (frames - 1).  phase_mode 1 or 3.  Magnitude, mask and
+ *   phase are read once; each stem goes through transforms of its own, so a mask of all ones leaves stem 1 exactly zero.
+ *   absmax_partial (optional): [2][channels][svs_istft_stems_groups_n(...)] maxima of |y|, stem-major.
+ * svs_istft_stems_groups_n / svs_istft_stems_plan_n: blocks per channel and the launch plan, as the two queries above (the
+ *   overlap-add accumulator of hop < n_fft / 2 holds 12 B per position here, so a block may own fewer hops). */
+int svs_istft_stems_n(const float* mag, int64_t chan_stride, int seg, int rows, int first_bin, const float* mask,
+                      const float* phase, int phase_mode, int channels, int n_fft, int hop, int frames, float* y,
+                      int64_t stem_stride, float* absmax_partial, hipStream_t stream);
+int svs_istft_stems_groups_n(int n_fft, int hop, int frames, int channels);
+int svs_istft_stems_plan_n(int n_fft, int hop, int* hops_per_block, int* rounds, size_t* lds_bytes);
 /* Host-only: the periodic Hann window the forward transform multiplies by (librosa.stft's default window, data.py:79,100):
  * out[m] = sin^2(pi m / n_fft) for m = 0 .. n_fft / 2 (n_fft / 2 + 1 floats; w[n_fft - m] = w[m]), rounded from double. */
 int svs_hann_table(int n_fft, float* out);

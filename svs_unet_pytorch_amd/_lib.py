@@ -92,6 +92,9 @@ _SIGS = {
     "svs_stft_groups_n": (I, [I, I]),
     "svs_istft_groups_n": (I, [I, I, I, I]),
     "svs_istft_plan_n": (I, [I, I, P, P, P]),
+    "svs_istft_stems_n": (I, [P, L, I, I, I, P, P, I, I, I, I, I, P, L, P, P]),
+    "svs_istft_stems_groups_n": (I, [I, I, I, I]),
+    "svs_istft_stems_plan_n": (I, [I, I, P, P, P]),
     "svs_hann_table": (I, [I, P]),
     "svs_transpose_c64": (I, [P, P, I, I, P]),
     "svs_istft_bwd_mask": (I, [P, P, P, P, P, F, I, I, I, I, P]),

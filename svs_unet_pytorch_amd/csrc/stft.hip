@@ -276,7 +276,8 @@ struct IstftArgs {
   const float* phase; int phase_mode;             // 1 frame-major phasors [c][t][513] float2, 3 angles in layout `lay`
   int channels, T, hop;
   float* y; long n_out;                           // (channels, hop * (T - 1))
-  float* absmax_partial;
+  long stem_stride;                               // STEMS: stem 1 (mag * (1 - mask)) is written this many floats after stem 0 (mag * mask)
+  float* absmax_partial;                          // [channel][group]; STEMS: [stem][channel][group]
   const float2* twiddles;                         // svs_fft_twiddles(N)
 };
 
@@ -290,8 +291,20 @@ struct IstftArgs {
 // (Measured alternatives, 240 s stereo: one block per CU with per-element divisions 0.29 ms; persistent blocks with register
 // prefetch of the next group, 239 VGPRs, one block per CU 0.165 ms.)
 // N = 2048: 157,696 B of LDS, one block per CU (and its 256 VGPRs); N = 512: 39,424 B.
-template <int NFFT, int PMODE>                              // phase_mode as a template argument: only its registers exist
-__global__ __launch_bounds__(512, NFFT == 2048 ? 1 : 2) void istft_kernel(IstftArgs p, int ngroups) {
+//
+// STEMS (svs_istft_stems_n): both stems of a mask from ONE launch, y = istft(mag * mask * phase) and, stem_stride floats higher,
+// istft(mag * (1 - mask) * phase).  The block stages magnitude, mask and phasors once and forms both spectra of its two frames;
+// the spectra of the second stem wait in registers while the first stem is transformed and written, then go through the same
+// buffers.  Same frames per block, same LDS, same transform count as two single-stem launches; half the loads, half the
+// staging and one launch.  Each stem is transformed on its own (two frames of ONE stem per transform, as above): a transform
+// of vocal + i accompaniment of one frame would leak rounding noise of either stem into the other (the imaginary part of a
+// transform of a Hermitian spectrum is ~1e-7 of it, not 0), and a stem whose mask is 0 everywhere must come out as exact zeros.
+// The second staged plane (BUF / 2 elements up) holds the second stem's magnitudes (PMODE 1) or the angles (PMODE 3, where the
+// second stem's magnitudes follow through the first plane in a second staging step).  The waiting spectra cost 4 NR VGPRs:
+// N = 1024 is held to 128 (four waves per SIMD = the two blocks per CU of the single-stem kernel; the compiler's own choice
+// was 132 and one block), N = 2048 spills 9-11 of its 256 to scratch.
+template <int NFFT, int PMODE, int STEMS = 0>               // phase_mode as a template argument: only its registers exist
+__global__ __launch_bounds__(512, NFFT == 2048 ? 1 : (STEMS && NFFT == 1024 ? 4 : 2)) void istft_kernel(IstftArgs p, int ngroups) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NBIN = NFFT / 2 + 1, NR = NFFT / 128 + 1;
   constexpr int BUF = FftSize<NFFT>::BUF, NW = 8, NF = 2 * NW;
@@ -310,7 +323,7 @@ __global__ __launch_bounds__(512, NFFT == 2048 ? 1 : 2) void istft_kernel(IstftA
   const __amdgpu_buffer_rsrc_t rph = __builtin_amdgcn_make_buffer_rsrc((void*)p.phase, 0, OOB, 0x00020000);
   const bool has_mask = p.mask != nullptr;
   // ---- loads first (in flight while the twiddles are built): this thread's frame column, and this wave's phasors
-  float sm[NIT], sa[PMODE == 3 ? NIT : 1];
+  float sm[NIT], sa[PMODE == 3 ? NIT : 1], sm2[STEMS ? NIT : 1];
   {
     const int tf = t0 - 1 + (tid & (NF - 1));               // a thread keeps its frame: one tile division per thread
     const bool tok = tf >= 0 && tf < p.T;
@@ -321,7 +334,11 @@ __global__ __launch_bounds__(512, NFFT == 2048 ? 1 : 2) void istft_kernel(IstftA
       const bool ok = tok && k < NBIN && k >= p.lay.first_bin;
       const unsigned off = ok ? (cbase + (unsigned)(k * p.lay.seg)) * 4u : OOB;
       float m = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rmag, (int)off, 0, 0));
-      if (has_mask) {
+      if (STEMS) {
+        const float mk = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rmask, (int)off, 0, 0));
+        sm2[STEMS ? it : 0] = m * (1.f - mk);
+        m *= mk;
+      } else if (has_mask) {
         const float mk = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rmask, (int)off, 0, 0));
         m *= p.invert ? 1.f - mk : mk;
       }
@@ -353,15 +370,18 @@ __global__ __launch_bounds__(512, NFFT == 2048 ? 1 : 2) void istft_kernel(IstftA
       const int w = f >> 1, at = 2 * (w * BUF + k + w) + (f & 1);
       raw[at] = sm[it];
       if (PMODE == 3) raw[at + BUF] = sa[PMODE == 3 ? it : 0];       // BUF floats = half a buffer higher
+      else if (STEMS) raw[at + BUF] = sm2[STEMS ? it : 0];
     }
   }
   __syncthreads();
   // spectra of this wave's two frames into registers (imaginary parts of DC / Nyquist dropped, as irfft does)
   float2 Sa[NR], Sb[NR];
+  float2 Ua[STEMS ? NR : 1], Ub[STEMS ? NR : 1];            // STEMS: the second stem's (PMODE 3: its phasors until its magnitudes arrive)
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
     const int k = lane + 64 * r;
     Sa[r] = Sb[r] = float2{0.f, 0.f};
+    if (STEMS) Ua[STEMS ? r : 0] = Ub[STEMS ? r : 0] = float2{0.f, 0.f};
     if (k > NFFT / 2) continue;
     const float2 m = buf[k + wave];
     float2 qa = pa[PMODE == 1 ? r : 0], qb = pb[PMODE == 1 ? r : 0];
@@ -376,24 +396,52 @@ __global__ __launch_bounds__(512, NFFT == 2048 ? 1 : 2) void istft_kernel(IstftA
     const bool edge = (k == 0 || k == NFFT / 2);
     Sa[r] = float2{m.x * qa.x, edge ? 0.f : m.x * qa.y};
     Sb[r] = float2{m.y * qb.x, edge ? 0.f : m.y * qb.y};
+    if (STEMS && PMODE == 1) {
+      const float2 m2 = buf[k + wave + BUF / 2];
+      Ua[STEMS ? r : 0] = float2{m2.x * qa.x, edge ? 0.f : m2.x * qa.y};
+      Ub[STEMS ? r : 0] = float2{m2.y * qb.x, edge ? 0.f : m2.y * qb.y};
+    } else if (STEMS) {
+      Ua[STEMS ? r : 0] = qa;
+      Ub[STEMS ? r : 0] = qb;
+    }
+  }
+  if constexpr (STEMS != 0 && PMODE == 3) {                 // the angles took the second plane: the second stem's magnitudes follow
+    __syncthreads();                                        // every wave has read its staged values: other waves' threads refill its buffer
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int k = (tid >> 4) + (512 / NF) * it, f = tid & (NF - 1);
+      if (k < NBIN) raw[2 * ((f >> 1) * BUF + k + (f >> 1)) + (f & 1)] = sm2[STEMS ? it : 0];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int k = lane + 64 * r;
+      if (k > NFFT / 2) continue;
+      const float2 m2 = buf[k + wave], qa = Ua[STEMS ? r : 0], qb = Ub[STEMS ? r : 0];
+      const bool edge = (k == 0 || k == NFFT / 2);
+      Ua[STEMS ? r : 0] = float2{m2.x * qa.x, edge ? 0.f : m2.x * qa.y};
+      Ub[STEMS ? r : 0] = float2{m2.y * qb.x, edge ? 0.f : m2.y * qb.y};
+    }
   }
   // conj(Z) with Z = Sa + i Sb (Hermitian-extended): the forward transform of conj(Z) is conj(ifft(Z)) = a - i b
-  fft_wave_sync();                                          // every lane has read its staged values before the buffer is refilled
+  auto transform = [&](const auto& A, const auto& B) __attribute__((always_inline)) {
+    fft_wave_sync();                                        // every lane has read its staged values before the buffer is refilled
 #pragma unroll
-  for (int r = 0; r < NR; ++r) {
-    const int k = lane + 64 * r;
-    if (k > NFFT / 2) continue;
-    buf[fft_pad(k)] = float2{Sa[r].x - Sb[r].y, -(Sa[r].y + Sb[r].x)};
-    if (k > 0 && k < NFFT / 2) buf[fft_pad(NFFT - k)] = float2{Sa[r].x + Sb[r].y, -(Sb[r].x - Sa[r].y)};
-  }
-  fft_wave<NFFT>(buf, tw, lane);
+    for (int r = 0; r < NR; ++r) {
+      const int k = lane + 64 * r;
+      if (k > NFFT / 2) continue;
+      buf[fft_pad(k)] = float2{A[r].x - B[r].y, -(A[r].y + B[r].x)};
+      if (k > 0 && k < NFFT / 2) buf[fft_pad(NFFT - k)] = float2{A[r].x + B[r].y, -(B[r].x - A[r].y)};
+    }
+    fft_wave<NFFT>(buf, tw, lane);
+  };
+  transform(Sa, Sb);
   __syncthreads();
   // ---- output: sample rel = hop * (f - 1) + m of local frame f; at most frames f_hi (m < hop) and f_hi - 1 (m + hop < n_fft)
-  float vmax = 0.f;
-  {
+  float vmax = 0.f, vmax2 = 0.f;
+  auto write_hops = [&](float* const yc, float& vmax) __attribute__((always_inline)) {
     // A thread keeps its position m inside the hop and walks the 15 hops: the two window values (and, away from the ends of
     // the signal, the envelope) are computed once per thread, and which frames exist is uniform across the block per hop.
-    float* const yc = p.y + (long)c * p.n_out + ((long)p.hop * t0 - NFFT / 2);
     const long ilo = NFFT / 2 - (long)p.hop * t0, ihi = p.n_out + ilo;       // valid e: ilo <= e < ihi
     auto emit = [&](int m, int fh_lo, int fh_hi) __attribute__((always_inline)) {
       const bool two = m + p.hop < NFFT;                    // frame fh - 1 still covers this position
@@ -426,17 +474,25 @@ __global__ __launch_bounds__(512, NFFT == 2048 ? 1 : 2) void istft_kernel(IstftA
         for (int m = 512 + tid; m < p.hop; m += 512) emit(m, 1, IGROUP);
       }
     }
+  };
+  float* const yc0 = p.y + (long)c * p.n_out + ((long)p.hop * t0 - NFFT / 2);
+  write_hops(yc0, vmax);
+  if constexpr (STEMS != 0) {
+    __syncthreads();                                        // every thread has read the first stem's frames before the buffers are refilled
+    transform(Ua, Ub);
+    __syncthreads();
+    write_hops(yc0 + p.stem_stride, vmax2);
   }
-  if (p.absmax_partial) {                                   // partial[c][group]: max |y| of this block
+  if (p.absmax_partial) {                                   // partial[c][group]: max |y| of this block (STEMS: [stem][c][group])
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o, 64));
+    for (int o = 32; o > 0; o >>= 1) { vmax = fmaxf(vmax, __shfl_xor(vmax, o, 64)); if (STEMS) vmax2 = fmaxf(vmax2, __shfl_xor(vmax2, o, 64)); }
     __syncthreads();
-    if (lane == 0) raw[wave] = vmax;
+    if (lane == 0) { raw[wave] = vmax; if (STEMS) raw[NW + wave] = vmax2; }
     __syncthreads();
-    if (tid == 0) {
-      float m = raw[0];
-      for (int w = 1; w < NW; ++w) m = fmaxf(m, raw[w]);
-      p.absmax_partial[g] = m;
+    if (tid <= STEMS) {
+      float m = raw[NW * tid];
+      for (int w = 1; w < NW; ++w) m = fmaxf(m, raw[NW * tid + w]);
+      p.absmax_partial[(long)tid * gridDim.x + g] = m;
     }
   }
 }
@@ -449,7 +505,10 @@ __global__ __launch_bounds__(512, NFFT == 2048 ? 1 : 2) void istft_kernel(IstftA
 // two-frames-per-sample kernel (one block per CU, divisions per position and round); that one keeps hop >= n_fft / 2.
 // NW waves per block (NF = 2 NW frames per round): 8, except N = 2048, where eight buffers and the twiddles fill 157,696 of the
 // CU's 163,840 B and leave no room for the accumulator -- four waves (88,064 B) leave 75,776 B (istft_plan below).
-template <int NFFT, int NW, int PMODE>
+// STEMS: both stems, as in istft_kernel -- one staging per round, the second stem's spectra wait in registers while the first
+// stem's frames are transformed and accumulated, then take the same buffers.  The accumulator gains one float per position
+// (sum of the second stem's windowed samples; the squared-window sum is shared): 12 B per position (istft_stems_plan).
+template <int NFFT, int NW, int PMODE, int STEMS = 0>
 __global__ __launch_bounds__(64 * NW) void istft_general_kernel(IstftArgs p, int ngroups, int G, int rounds) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NBIN = NFFT / 2 + 1, NR = NFFT / 128 + 1, NT = 64 * NW;
@@ -462,6 +521,7 @@ __global__ __launch_bounds__(64 * NW) void istft_general_kernel(IstftArgs p, int
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = blockIdx.x, c = g / ngroups, t0 = (g - c * ngroups) * G;      // padded samples [hop * t0, hop * (t0 + G))
   const int seg_len = G * p.hop, halo = (NFFT - 1) / p.hop;
+  float* const acc2 = (float*)(acc + seg_len);              // STEMS: [G * hop] sum of the second stem's windowed samples
   float2* const buf = fbuf + wave * BUF;
   constexpr unsigned OOB = 0x80000000u;
   const __amdgpu_buffer_rsrc_t rmag = __builtin_amdgcn_make_buffer_rsrc((void*)p.mag, 0, OOB, 0x00020000);
@@ -469,7 +529,7 @@ __global__ __launch_bounds__(64 * NW) void istft_general_kernel(IstftArgs p, int
   const __amdgpu_buffer_rsrc_t rph = __builtin_amdgcn_make_buffer_rsrc((void*)p.phase, 0, OOB, 0x00020000);
   const bool has_mask = p.mask != nullptr;
   fft_load_twiddles<NFFT>(tw, p.twiddles, tid, NT);
-  for (int i = tid; i < seg_len; i += NT) acc[i] = float2{0.f, 0.f};
+  for (int i = tid; i < seg_len; i += NT) { acc[i] = float2{0.f, 0.f}; if (STEMS) acc2[i] = 0.f; }
   for (int r = 0; r < rounds; ++r) {
     const int tb = t0 - halo + NF * r;                      // first frame of this round
     __syncthreads();                                        // the previous round's buffers have been consumed (and, r = 0: twiddles)
@@ -484,11 +544,15 @@ __global__ __launch_bounds__(64 * NW) void istft_general_kernel(IstftArgs p, int
         const bool ok = tok && k >= p.lay.first_bin;
         const unsigned off = ok ? (cbase + (unsigned)(k * p.lay.seg)) * 4u : OOB;
         float m = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rmag, (int)off, 0, 0));
-        if (has_mask) {
+        const int f = tid & (NF - 1), w = f >> 1, at = 2 * (w * BUF + k + w) + (f & 1);
+        if (STEMS) {
+          const float mk = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rmask, (int)off, 0, 0));
+          if (PMODE == 1) raw[at + BUF] = m * (1.f - mk);
+          m *= mk;
+        } else if (has_mask) {
           const float mk = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rmask, (int)off, 0, 0));
           m *= p.invert ? 1.f - mk : mk;
         }
-        const int f = tid & (NF - 1), w = f >> 1, at = 2 * (w * BUF + k + w) + (f & 1);
         raw[at] = m;
         if (PMODE == 3) raw[at + BUF] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rph, (int)off, 0, 0));
       }
@@ -497,10 +561,12 @@ __global__ __launch_bounds__(64 * NW) void istft_general_kernel(IstftArgs p, int
     // ---- spectra of this wave's two frames, Hermitian-extended conj(Sa + i Sb), one transform
     const int ta = tb + 2 * wave;
     float2 Sa[NR], Sb[NR];
+    float2 Ua[STEMS ? NR : 1], Ub[STEMS ? NR : 1];          // STEMS: the second stem's (PMODE 3: its phasors until its magnitudes arrive)
 #pragma unroll
     for (int q = 0; q < NR; ++q) {
       const int k = lane + 64 * q;
       Sa[q] = Sb[q] = float2{0.f, 0.f};
+      if (STEMS) Ua[STEMS ? q : 0] = Ub[STEMS ? q : 0] = float2{0.f, 0.f};
       if (k > NFFT / 2) continue;
       const float2 m = buf[k + wave];
       float2 qa, qb;
@@ -522,57 +588,111 @@ __global__ __launch_bounds__(64 * NW) void istft_general_kernel(IstftArgs p, int
       const bool edge = (k == 0 || k == NFFT / 2);
       Sa[q] = float2{m.x * qa.x, edge ? 0.f : m.x * qa.y};
       Sb[q] = float2{m.y * qb.x, edge ? 0.f : m.y * qb.y};
-    }
-    fft_wave_sync();                                        // every lane has read its staged values before the buffer is refilled
-#pragma unroll
-    for (int q = 0; q < NR; ++q) {
-      const int k = lane + 64 * q;
-      if (k > NFFT / 2) continue;
-      buf[fft_pad(k)] = float2{Sa[q].x - Sb[q].y, -(Sa[q].y + Sb[q].x)};
-      if (k > 0 && k < NFFT / 2) buf[fft_pad(NFFT - k)] = float2{Sa[q].x + Sb[q].y, -(Sb[q].x - Sa[q].y)};
-    }
-    fft_wave<NFFT>(buf, tw, lane);
-    __syncthreads();
-    // ---- accumulate: position i (padded sample hop * t0 + i) takes every frame of this round that covers it, ascending
-    for (int i = tid; i < seg_len; i += NT) {
-      const int q = p.hop * t0 + i;
-      int lo = q - (NFFT - 1);
-      lo = lo <= 0 ? 0 : (int)((unsigned)(lo + p.hop - 1) / (unsigned)p.hop);
-      int hi = (int)((unsigned)q / (unsigned)p.hop);
-      if (hi > p.T - 1) hi = p.T - 1;
-      if (lo < tb) lo = tb;
-      if (hi > tb + NF - 1) hi = tb + NF - 1;
-      float2 a = acc[i];
-      for (int t = lo; t <= hi; ++t) {
-        const int f = t - tb, m = q - t * p.hop;
-        const float2 z = fbuf[(f >> 1) * BUF + fft_pad(m)];
-        const float w = hann_fast<NFFT>(m);
-        a.x += ((f & 1) ? -z.y : z.x) * (w * (1.0f / NFFT));
-        a.y += w * w;
+      if (STEMS && PMODE == 1) {
+        const float2 m2 = buf[k + wave + BUF / 2];
+        Ua[STEMS ? q : 0] = float2{m2.x * qa.x, edge ? 0.f : m2.x * qa.y};
+        Ub[STEMS ? q : 0] = float2{m2.y * qb.x, edge ? 0.f : m2.y * qb.y};
+      } else if (STEMS) {
+        Ua[STEMS ? q : 0] = qa;
+        Ub[STEMS ? q : 0] = qb;
       }
-      acc[i] = a;
+    }
+    if constexpr (STEMS != 0 && PMODE == 3) {
+      // the angles took the second plane: the second stem's magnitudes follow through the first (loaded again: this kernel keeps
+      // no staged value in registers, and the lines are in L2 from a moment ago)
+      __syncthreads();                                      // every wave has read its staged values: other waves' threads refill its buffer
+      const int tf = tb + (tid & (NF - 1));
+      const bool tok = tf >= 0 && tf < p.T;
+      const unsigned cbase = tok ? (unsigned)p.lay.col(c, tf) : 0u;
+      for (int it = 0; it < NIT; ++it) {
+        const int k = tid / NF + (NT / NF) * it;
+        if (k >= NBIN) continue;
+        const bool ok = tok && k >= p.lay.first_bin;
+        const unsigned off = ok ? (cbase + (unsigned)(k * p.lay.seg)) * 4u : OOB;
+        const float m = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rmag, (int)off, 0, 0));
+        const float mk = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rmask, (int)off, 0, 0));
+        const int f = tid & (NF - 1), w = f >> 1;
+        raw[2 * (w * BUF + k + w) + (f & 1)] = m * (1.f - mk);
+      }
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < NR; ++q) {
+        const int k = lane + 64 * q;
+        if (k > NFFT / 2) continue;
+        const float2 m2 = buf[k + wave], qa = Ua[STEMS ? q : 0], qb = Ub[STEMS ? q : 0];
+        const bool edge = (k == 0 || k == NFFT / 2);
+        Ua[STEMS ? q : 0] = float2{m2.x * qa.x, edge ? 0.f : m2.x * qa.y};
+        Ub[STEMS ? q : 0] = float2{m2.y * qb.x, edge ? 0.f : m2.y * qb.y};
+      }
+    }
+    auto transform = [&](const auto& A, const auto& B) __attribute__((always_inline)) {
+      fft_wave_sync();                                      // every lane has read its staged values before the buffer is refilled
+#pragma unroll
+      for (int q = 0; q < NR; ++q) {
+        const int k = lane + 64 * q;
+        if (k > NFFT / 2) continue;
+        buf[fft_pad(k)] = float2{A[q].x - B[q].y, -(A[q].y + B[q].x)};
+        if (k > 0 && k < NFFT / 2) buf[fft_pad(NFFT - k)] = float2{A[q].x + B[q].y, -(B[q].x - A[q].y)};
+      }
+      fft_wave<NFFT>(buf, tw, lane);
+    };
+    // ---- accumulate: position i (padded sample hop * t0 + i) takes every frame of this round that covers it, ascending
+    auto accumulate = [&](const bool second) __attribute__((always_inline)) {
+      for (int i = tid; i < seg_len; i += NT) {
+        const int q = p.hop * t0 + i;
+        int lo = q - (NFFT - 1);
+        lo = lo <= 0 ? 0 : (int)((unsigned)(lo + p.hop - 1) / (unsigned)p.hop);
+        int hi = (int)((unsigned)q / (unsigned)p.hop);
+        if (hi > p.T - 1) hi = p.T - 1;
+        if (lo < tb) lo = tb;
+        if (hi > tb + NF - 1) hi = tb + NF - 1;
+        float2 a = second ? float2{acc2[i], 0.f} : acc[i];
+        for (int t = lo; t <= hi; ++t) {
+          const int f = t - tb, m = q - t * p.hop;
+          const float2 z = fbuf[(f >> 1) * BUF + fft_pad(m)];
+          const float w = hann_fast<NFFT>(m);
+          a.x += ((f & 1) ? -z.y : z.x) * (w * (1.0f / NFFT));
+          if (!second) a.y += w * w;
+        }
+        if (second) acc2[i] = a.x; else acc[i] = a;
+      }
+    };
+    transform(Sa, Sb);
+    __syncthreads();
+    accumulate(false);
+    if constexpr (STEMS != 0) {
+      __syncthreads();                                      // every thread has read the first stem's frames before the buffers are refilled
+      transform(Ua, Ub);
+      __syncthreads();
+      accumulate(true);
     }
   }
   // ---- divide by the window envelope, store, |.|max
-  float vmax = 0.f;
+  float vmax = 0.f, vmax2 = 0.f;
   for (int i = tid; i < seg_len; i += NT) {
     const long e = (long)p.hop * t0 + i - NFFT / 2;
     if (e < 0 || e >= p.n_out) continue;
     const float2 a = acc[i];
-    const float v = a.y > 1.1754944e-38f ? a.x * __builtin_amdgcn_rcpf(a.y) : a.x;
+    const bool div = a.y > 1.1754944e-38f;
+    const float v = div ? a.x * __builtin_amdgcn_rcpf(a.y) : a.x;
     p.y[(long)c * p.n_out + e] = v;
     vmax = fmaxf(vmax, fabsf(v));
+    if (STEMS) {
+      const float b = acc2[i], v2 = div ? b * __builtin_amdgcn_rcpf(a.y) : b;
+      p.y[p.stem_stride + (long)c * p.n_out + e] = v2;
+      vmax2 = fmaxf(vmax2, fabsf(v2));
+    }
   }
-  if (p.absmax_partial) {
+  if (p.absmax_partial) {                                   // (STEMS: [stem][c][group])
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o, 64));
+    for (int o = 32; o > 0; o >>= 1) { vmax = fmaxf(vmax, __shfl_xor(vmax, o, 64)); if (STEMS) vmax2 = fmaxf(vmax2, __shfl_xor(vmax2, o, 64)); }
     __syncthreads();
-    if (lane == 0) raw[wave] = vmax;
+    if (lane == 0) { raw[wave] = vmax; if (STEMS) raw[NW + wave] = vmax2; }
     __syncthreads();
-    if (tid == 0) {
-      float m = raw[0];
-      for (int w = 1; w < NW; ++w) m = fmaxf(m, raw[w]);
-      p.absmax_partial[g] = m;
+    if (tid <= STEMS) {
+      float m = raw[NW * tid];
+      for (int w = 1; w < NW; ++w) m = fmaxf(m, raw[NW * tid + w]);
+      p.absmax_partial[(long)tid * gridDim.x + g] = m;
     }
   }
 }
@@ -761,6 +881,89 @@ extern "C" int svs_istft_tiles(const float* mag, int64_t chan_stride, int seg, i
   return svs_istft_tiles_n(mag, chan_stride, seg, rows, first_bin, mask, invert, phase, phase_mode, channels, n_fft, hop, frames, y,
                            absmax_partial, stream);
 }
+
+// ---- both stems of a mask from one launch (STEMS kernels)
+// The two-frames-per-sample kernel keeps its plan (the second stem goes through the same buffers).  The general kernel's
+// accumulator is 12 B per position instead of 8: where G hops of it no longer fit beside the buffers (n_fft 1024, hop 500 .. 511:
+// 14 hops x 12 B x hop > 83,968 B) the block owns as many hops as fit; the rounds still cover G + halo frames.
+static constexpr size_t LDS_PER_CU = 163840;
+static IstftPlan istft_stems_plan(int n_fft, int hop) {
+  IstftPlan pl = istft_plan(n_fft, hop);
+  if (!pl.general) return pl;
+  const size_t fft = fft_lds_bytes(n_fft, pl.waves);
+  const int nf = 2 * pl.waves, halo = (n_fft - 1) / hop, fit = (int)((LDS_PER_CU - fft) / ((size_t)hop * 12));
+  if (pl.G > fit) { pl.G = fit; pl.rounds = (pl.G + halo + nf - 1) / nf; }
+  pl.lds = fft + (size_t)pl.G * hop * 12;
+  return pl;
+}
+static int istft_stems_groups_per_channel(int n_fft, int hop, int frames) {
+  const long span = (long)istft_stems_plan(n_fft, hop).G * hop;
+  return (int)((n_fft + (long)hop * (frames - 1) + span - 1) / span);
+}
+// blocks per channel of svs_istft_stems_n = absmax partials per channel and stem (layout [stem][channel][group])
+extern "C" int svs_istft_stems_groups_n(int n_fft, int hop, int frames, int channels) {
+  (void)channels;
+  SVS_REQUIRE_NFFT("svs_istft_stems_groups_n", n_fft);
+  SVS_REQUIRE(hop > 0 && hop <= n_fft && frames > 0, "svs_istft_stems_groups_n: need 0 < hop <= n_fft and frames > 0 (hop=%d frames=%d)", hop, frames);
+  return istft_stems_groups_per_channel(n_fft, hop, frames);
+}
+extern "C" int svs_istft_stems_plan_n(int n_fft, int hop, int* hops_per_block, int* rounds, size_t* lds_bytes) {
+  SVS_REQUIRE_NFFT("svs_istft_stems_plan_n", n_fft);
+  SVS_REQUIRE(hop > 0 && hop <= n_fft, "svs_istft_stems_plan_n: hop %d is not in 1..n_fft (a larger hop leaves samples that no frame covers)", hop);
+  const IstftPlan pl = istft_stems_plan(n_fft, hop);
+  if (hops_per_block) *hops_per_block = pl.G;
+  if (rounds) *rounds = pl.rounds;
+  if (lds_bytes) *lds_bytes = pl.lds;
+  return SVS_OK;
+}
+
+template <int N, int NW>
+static int launch_istft_stems(IstftArgs& a, const IstftPlan& pl, int ngroups, hipStream_t stream) {
+  int rc = svs_fft_twiddles(N, stream, &a.twiddles);
+  if (rc) return rc;
+  const dim3 grid((unsigned)((long)ngroups * a.channels));
+  if (pl.general) {
+    if ((rc = a.phase_mode == 1 ? allow_lds(istft_general_kernel<N, NW, 1, 1>, pl.lds) : allow_lds(istft_general_kernel<N, NW, 3, 1>, pl.lds))) return rc;
+    if (a.phase_mode == 1) hipLaunchKernelGGL((istft_general_kernel<N, NW, 1, 1>), grid, dim3(64 * NW), pl.lds, stream, a, ngroups, pl.G, pl.rounds);
+    else hipLaunchKernelGGL((istft_general_kernel<N, NW, 3, 1>), grid, dim3(64 * NW), pl.lds, stream, a, ngroups, pl.G, pl.rounds);
+    SVS_CHECK_LAUNCH("istft_general (stems)");
+    return SVS_OK;
+  }
+  if ((rc = a.phase_mode == 1 ? allow_lds(istft_kernel<N, 1, 1>, pl.lds) : allow_lds(istft_kernel<N, 3, 1>, pl.lds))) return rc;
+  if (a.phase_mode == 1) hipLaunchKernelGGL((istft_kernel<N, 1, 1>), grid, dim3(512), pl.lds, stream, a, ngroups);
+  else hipLaunchKernelGGL((istft_kernel<N, 3, 1>), grid, dim3(512), pl.lds, stream, a, ngroups);
+  SVS_CHECK_LAUNCH("istft (stems)");
+  return SVS_OK;
+}
+
+extern "C" int svs_istft_stems_n(const float* mag, int64_t chan_stride, int seg, int rows, int first_bin, const float* mask,
+                                 const float* phase, int phase_mode, int channels, int n_fft, int hop, int frames, float* y,
+                                 int64_t stem_stride, float* absmax_partial, hipStream_t stream) {
+  SVS_REQUIRE(mask, "svs_istft_stems: the mask is required (stem 0 is mag * mask, stem 1 mag * (1 - mask))");
+  SVS_REQUIRE(mag && phase && y && channels > 0, "svs_istft_stems: bad arguments (null pointer or channels < 1)");
+  SVS_REQUIRE_NFFT("svs_istft_stems_n", n_fft);
+  SVS_REQUIRE(hop > 0 && hop <= n_fft, "svs_istft_stems: hop %d is not in 1..n_fft (a larger hop leaves samples that no frame covers)", hop);
+  SVS_REQUIRE(frames > 1, "svs_istft_stems: need >= 2 frames, got %d", frames);
+  SVS_REQUIRE(phase_mode == 1 || phase_mode == 3, "svs_istft_stems: phase_mode must be 1 (frame-major phasors) or 3 (angles)");
+  const long nbin = n_fft / 2 + 1;
+  SVS_REQUIRE((long)channels * (chan_stride > (long)frames * nbin ? chan_stride : (long)frames * nbin) * 8 < (1L << 31),
+              "svs_istft_stems: a spectrogram view of more than 2 GiB needs 64-bit offsets; split the channels");
+  const long n_out = (long)hop * (frames - 1);
+  SVS_REQUIRE(stem_stride >= n_out * channels, "svs_istft_stems: stem_stride %lld is below the %lld samples of one stem (hop * (frames - 1) * channels)",
+              (long long)stem_stride, (long long)(n_out * channels));
+  int rc = check_layout("svs_istft_stems", n_fft, seg, rows, first_bin, frames, frames);
+  if (rc) return rc;
+  IstftArgs a{};
+  a.mag = mag; a.lay = SpecLayout{chan_stride, seg, rows, first_bin, frames};
+  a.mask = mask; a.phase = phase; a.phase_mode = phase_mode;
+  a.channels = channels; a.T = frames; a.hop = hop; a.y = y; a.n_out = n_out; a.stem_stride = stem_stride;
+  a.absmax_partial = absmax_partial;
+  const IstftPlan pl = istft_stems_plan(n_fft, hop);
+  const int ngroups = istft_stems_groups_per_channel(n_fft, hop, frames);
+  return n_fft == 512 ? launch_istft_stems<512, 8>(a, pl, ngroups, stream)
+       : n_fft == 1024 ? launch_istft_stems<1024, 8>(a, pl, ngroups, stream) : launch_istft_stems<2048, 4>(a, pl, ngroups, stream);
+}
+
 extern "C" size_t svs_istft_workspace_bytes(int n_fft, int hop, int frames) {
   (void)hop;
   return (size_t)frames * (n_fft / 2 + 1) * 8 + 256;           // frame-major copy of f-major phasors

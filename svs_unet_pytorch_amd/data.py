@@ -151,6 +151,33 @@ def istft_from_tiles(tiles: torch.Tensor, mask, phase_fm: torch.Tensor, frames: 
     return y
 
 
+def istft_stems_from_tiles(tiles: torch.Tensor, mask: torch.Tensor, phase_fm: torch.Tensor, frames: int, n_fft: int = WINDOW_SIZE,
+                           hop: int = HOP_SIZE, peak: float | None = None):
+    """Both stems of a mask from ONE launch (svs_istft_stems_n): tiles, mask and phasors as istft_from_tiles ->
+    (2, channels, hop*(T-1)) samples, [0] from tiles * mask (the vocal, inference.py:100-103) and [1] from tiles * (1 - mask) (the
+    accompaniment, inference.py:104-107).  peak: every stem and channel is normalised on its own (data.py:162-164)."""
+    _check_window(n_fft, hop)
+    if mask is None:
+        raise ValueError("istft_stems_from_tiles: the mask is required (both stems come from it)")
+    L = _lib.lib()
+    C, n_tiles, _, rows, seg = tiles.shape
+    ph = torch.view_as_real(phase_fm.contiguous()).contiguous()
+    n_out = hop * max(frames - 1, 0)
+    y = torch.empty((2, C, n_out), dtype=torch.float32, device=tiles.device)
+    groups = int(L.svs_istft_stems_groups_n(n_fft, hop, max(frames, 1), C))
+    part = torch.empty((2, C, groups), dtype=torch.float32, device=tiles.device) if peak is not None else None
+    _lib.check(L.svs_istft_stems_n(tiles.data_ptr(), n_tiles * rows * seg, seg, rows, 1, mask.data_ptr(), ph.data_ptr(), 1, C, n_fft, hop,
+                                   frames, y.data_ptr(), C * n_out, None if part is None else part.data_ptr(), _lib.stream_ptr()),
+               "svs_istft_stems_n")
+    if peak is not None:
+        pk = torch.empty((2, C), dtype=torch.float32, device=tiles.device)
+        for s in range(2):
+            for c in range(C):
+                _lib.check(L.svs_max(part[s, c].data_ptr(), groups, pk[s, c:].data_ptr(), _lib.stream_ptr()), "svs_max")
+                _lib.check(L.svs_scale_by_inv(y[s, c].data_ptr(), n_out, pk[s, c:].data_ptr(), float(peak), _lib.stream_ptr()), "svs_scale_by_inv")
+    return y
+
+
 # ------------------------------------------------------------------------------------------------
 # host-side file glue (not on the accelerated path)
 # ------------------------------------------------------------------------------------------------

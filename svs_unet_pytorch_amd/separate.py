@@ -7,12 +7,14 @@ evaluate.py accepts it beside the source's stems.
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src song.wav --tar out.wav
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src wav_folder --tar out_folder \
         [--vocal_solo 0|1] [--precision bf16] [--subtype PCM_16|PCM_32|FLOAT] [--no_keep_length] \
-        [--win_size 512|1024|2048] [--hop_size N]
+        [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder]
 
 A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
 default) is what the reference's data.py writes (data.py:166).  --win_size / --hop_size (the config's 1024 / 768 by default;
 data.py:24-25 takes the same two flags) are the window and hop of the two transforms, for a checkpoint trained at another
-geometry.  The reference has no such command: it goes through
+geometry.  --tar_accomp also writes the accompaniment (a file, or a folder with the names of --tar when --src is a folder) from
+the same pass: one STFT, one set of network forwards and one two-stem inverse STFT (svs_istft_stems_n), --tar then holding the
+vocal; it excludes --vocal_solo 0.  The reference has no such command: it goes through
 data.py to_spec, inference.py and data.py to_wave with .npy files in between.
 """
 from __future__ import annotations
@@ -40,11 +42,15 @@ def main(argv=None):
     parser.add_argument("--no_keep_length", action="store_true", help="do not cut / pad the output to the source's frame count")
     parser.add_argument("--win_size", type=int, default=WINDOW_SIZE, help="window of the STFT / inverse STFT (512, 1024 or 2048)")
     parser.add_argument("--hop_size", type=int, default=HOP_SIZE, help="hop of the two transforms, 1..win_size")
+    parser.add_argument("--tar_accomp", type=str, default=None,
+                        help="also write the accompaniment here, from the same pass (a wav file, or a folder when --src is one); --tar holds the vocal")
     args = parser.parse_args(argv)
     if args.win_size not in WINDOW_SIZES:
         parser.error(f"--win_size {args.win_size}: the STFT / iSTFT kernels are built for n_fft = {', '.join(map(str, WINDOW_SIZES))}")
     if not 0 < args.hop_size <= args.win_size:
         parser.error(f"--hop_size {args.hop_size}: must be in 1..{args.win_size} (a larger hop leaves samples that no frame covers)")
+    if args.tar_accomp is not None and not args.vocal_solo:
+        parser.error("--tar_accomp writes the vocal to --tar and the accompaniment to --tar_accomp: it cannot be combined with --vocal_solo 0")
 
     if not torch.cuda.is_available():
         print("separate.py needs a ROCm device (hand-written gfx950 kernels, no CPU path).")
@@ -62,15 +68,18 @@ def main(argv=None):
 
     if os.path.isdir(args.src):
         os.makedirs(args.tar, exist_ok=True)
-        jobs = [(os.path.join(args.src, f), os.path.join(args.tar, f)) for f in sorted(os.listdir(args.src)) if f.endswith(".wav")]
+        if args.tar_accomp is not None:
+            os.makedirs(args.tar_accomp, exist_ok=True)
+        jobs = [(os.path.join(args.src, f), os.path.join(args.tar, f), None if args.tar_accomp is None else os.path.join(args.tar_accomp, f))
+                for f in sorted(os.listdir(args.src)) if f.endswith(".wav")]
     else:
-        jobs = [(args.src, args.tar)]
+        jobs = [(args.src, args.tar, args.tar_accomp)]
     print(f"Found {len(jobs)} files, separating...")
-    for src, dst in jobs:
+    for src, dst, dst_accomp in jobs:
         frames, channels = separate_to_wav(model, src, dst, vocal_solo=bool(args.vocal_solo), precision=args.precision,
                                            subtype=args.subtype, keep_length=not args.no_keep_length, n_fft=args.win_size,
-                                           hop=args.hop_size)
-        print(f"{dst}: {frames} frames x {channels}")
+                                           hop=args.hop_size, dst_accomp_path=dst_accomp)
+        print(f"{dst}: {frames} frames x {channels}" + ("" if dst_accomp is None else f"; {dst_accomp}: the same"))
     print("Separation finished!")
 
 

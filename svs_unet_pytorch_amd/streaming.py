@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .config import HOP_SIZE, INPUT_LEN, SAMPLE_RATE, WINDOW_SIZE
-from .data import istft_from_tiles, stft_to_tiles
+from .data import istft_from_tiles, istft_stems_from_tiles, stft_to_tiles
 
 
 @torch.no_grad()
@@ -47,8 +47,11 @@ def separate_spectrogram_device(model, mag: torch.Tensor, seg_len: int = INPUT_L
 @torch.no_grad()
 def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
                       peak: float | None = 0.9, max_batch: int = 256, precision: str | None = None, sr_in: int | None = None,
-                      sr_out: int | None = None):
+                      sr_out: int | None = None, both_stems: bool = False):
     """float32 samples (n,) or (channels, n) on the GPU -> separated samples (hop*(T-1),) or (channels, hop*(T-1)).
+    both_stems: return (2, ...) stacked [vocal, accompaniment] -- what vocal_solo=True and vocal_solo=False return -- from ONE
+    forward transform, one set of network forwards and one inverse launch (data.istft_stems_from_tiles); vocal_solo is
+    ignored then.  sr_out and peak apply to every stem and channel on its own, as below.
     sr_in: the rate of y if it is not config.SAMPLE_RATE yet (a file's 44,100 Hz): every channel is first resampled to
     SAMPLE_RATE on the device (resample.resample_poly_gpu, no downmix); None: y is at the network rate already.
     sr_out: the rate to return (a file's 44,100 Hz): the separated channels are resampled from SAMPLE_RATE on the device and
@@ -80,16 +83,23 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     finally:                                                     # a failing forward must not leave the model in another mode
         model.eval_precision = was_precision
         model.train(was_training)
-    out = istft_from_tiles(tiles, mask, phase, T, invert=not vocal_solo, n_fft=n_fft, hop=hop, peak=None if sr_out is not None else peak)
+    if both_stems:                                               # (2 * C, n): the stems are further channels to everything below
+        out = istft_stems_from_tiles(tiles, mask, phase, T, n_fft=n_fft, hop=hop, peak=None if sr_out is not None else peak)
+        out = out.view(2 * C, out.shape[2])
+    else:
+        out = istft_from_tiles(tiles, mask, phase, T, invert=not vocal_solo, n_fft=n_fft, hop=hop, peak=None if sr_out is not None else peak)
     if sr_out is not None:
         from .resample import resample_poly_gpu
         out = resample_poly_gpu(out, int(sr_out), SAMPLE_RATE)
         if peak is not None:                                     # data.py:162-164 at the rate that is returned
             ws = torch.empty(4096, dtype=torch.uint8, device=out.device)
-            pk = torch.empty(C, dtype=torch.float32, device=out.device)
-            for c in range(C):
+            pk = torch.empty(out.shape[0], dtype=torch.float32, device=out.device)
+            for c in range(out.shape[0]):
                 _lib.check(L.svs_absmax(out[c].data_ptr(), out.shape[1], pk[c:].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "svs_absmax")
                 _lib.check(L.svs_scale_by_inv(out[c].data_ptr(), out.shape[1], pk[c:].data_ptr(), float(peak), _lib.stream_ptr()), "svs_scale_by_inv")
+    if both_stems:
+        out = out.view(2, C, out.shape[1])
+        return out[:, 0] if squeeze else out
     return out[0] if squeeze else out
 
 
@@ -114,7 +124,8 @@ def separated_frames(n_source: int, sr: int, hop: int = HOP_SIZE):
 
 @torch.no_grad()
 def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = True, precision: str | None = None,
-                    subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE):
+                    subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
+                    dst_accomp_path: str | None = None):
     """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
     the PCM is copied as the file stores it, resample.resample_poly_gpu (no downmix) brings every channel to SAMPLE_RATE,
     separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
@@ -122,7 +133,9 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     "FLOAT") and interleaves; only those samples return to the host.  keep_length: the frames are cut or zero-padded to the
     source's frame count (kept_length), so the file lines up sample for sample with the source's stems.  n_fft / hop: the
     window and hop of the two transforms (data.WINDOW_SIZES; the network is fully convolutional, so a checkpoint trained at
-    another geometry runs on the n_fft / 2 rows of that window).  Returns the (frames, channels) written."""
+    another geometry runs on the n_fft / 2 rows of that window).  dst_accomp_path: also write the accompaniment there, from the
+    same pass (separate_waveform(both_stems=True)): dst_path then holds the vocal whatever vocal_solo says, and each file is
+    encoded with its own common gain at peak 0.9.  Returns the (frames, channels) written (per file)."""
     from fractions import Fraction
 
     import numpy as np
@@ -143,11 +156,13 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     fr = Fraction(SAMPLE_RATE, int(rate))
     y = resample_poly_gpu(pcm, fr.numerator, fr.denominator, channels=channels, downmix=False)
     y = y[None] if y.dim() == 1 else y                            # (channels, n) at the network rate
-    sep = separate_waveform(model, y, vocal_solo=vocal_solo, n_fft=n_fft, hop=hop, peak=None, precision=precision)
-    enc = resample_encode_gpu(sep, fr.denominator, fr.numerator, fmt=subtype, peak=0.9, common_gain=True)
-    if keep_length:
-        keep, pad = kept_length(enc.shape[0], n_source)
-        enc = torch.nn.functional.pad(enc[:keep], (0, 0, 0, pad))
-    out = enc.cpu().numpy()
-    wavfile.write(dst_path, int(rate), out[:, 0] if channels == 1 else out)
+    sep = separate_waveform(model, y, vocal_solo=vocal_solo, n_fft=n_fft, hop=hop, peak=None, precision=precision,
+                            both_stems=dst_accomp_path is not None)
+    for stem, path in ((sep, dst_path),) if dst_accomp_path is None else ((sep[0], dst_path), (sep[1], dst_accomp_path)):
+        enc = resample_encode_gpu(stem, fr.denominator, fr.numerator, fmt=subtype, peak=0.9, common_gain=True)
+        if keep_length:
+            keep, pad = kept_length(enc.shape[0], n_source)
+            enc = torch.nn.functional.pad(enc[:keep], (0, 0, 0, pad))
+        out = enc.cpu().numpy()
+        wavfile.write(path, int(rate), out[:, 0] if channels == 1 else out)
     return out.shape
