@@ -192,6 +192,11 @@ int svs_bn_bwd(const float* dy, int64_t lddy, const float* raw, int64_t ldr, int
 size_t svs_l1_mask_loss_workspace_bytes(int64_t n);
 int svs_l1_mask_loss_fwd_bwd(const float* mask, const float* mix, const float* voc, int64_t n, float loss_scale,
                              float* d_logit, float* loss, void* ws, size_t ws_bytes, hipStream_t stream);
+/* The same loss with no gradient -- the eval-mode value of train.py:329-338: three read streams, no d_logit store.  Same
+ * blocks, summation order and workspace (svs_l1_mask_loss_workspace_bytes), so *loss is bit for bit what
+ * svs_l1_mask_loss_fwd_bwd writes for the same inputs. */
+int svs_l1_mask_loss_fwd(const float* mask, const float* mix, const float* voc, int64_t n, float* loss, void* ws,
+                         size_t ws_bytes, hipStream_t stream);
 
 /* torch.optim.Adam(lr, betas, eps), no weight decay / amsgrad (model.py:116), over flat buffers.
  * g is multiplied by grad_scale first (1/world for data-parallel mean). step is 1-based.  The hyper-parameters
@@ -269,6 +274,25 @@ int svs_unet_train_fwd_loss_mr(const float* params, float* bn_buffers, int64_t* 
                                const float* voc, const float* mix_phase, const float* voc_phase, const float* drop, int B, int H,
                                int W, int hop, float alpha_l1, float alpha_mr, float* mask, float* losses, void* ws, size_t ws_bytes,
                                void* mr_ws, size_t mr_ws_bytes, hipStream_t stream);
+/* One batch of the validation loop, train.py:317-363 -- the reference's eval-mode objective (train.py:329-346) with no
+ * gradient, from the blob of svs_unet_prepare_eval (the fp32 network): svs_unet_forward_eval, svs_l1_mask_loss_fwd into
+ * losses[0] and, when BOTH phase pointers are given, the two svs_istft_tiles_n calls of svs_unet_train_fwd_loss_mr (mix with
+ * the mask fused on load and mix_phase; voc with voc_phase) and svs_mrstft_loss_fwd_bwd(d_x = NULL) into losses[1]; both
+ * unscaled.  Both phase pointers NULL: the L1 part only, losses[1] = 0, any H and W the eval forward takes (hop is ignored;
+ * hop = 0 in the workspace query sizes that form).  With phases the early errors of svs_unet_train_fwd_loss_mr apply before
+ * the first launch: H = 256 / 512 / 1024, 0 < hop <= 2 H, W >= 2, hop * (W - 1) > 2048.  One phase pointer alone is an error.
+ *   mask (nullable): receives the mask, bit for bit svs_unet_forward_eval's.
+ *   acc (nullable, 3 doubles on the device): one last one-thread kernel adds, in double, each product rounded before its sum,
+ *     acc[0] += alpha_l1 * losses[0]; acc[0] += alpha_mr * losses[1]; acc[1] += losses[0]; acc[2] += losses[1]
+ *     -- the host loop `val_sum += ALPHA_L1 * float(l1); val_sum += alpha_mr * float(mr)` bit for bit, with no host sync per
+ *     batch (the alphas are doubles for that reason).  The caller zeroes acc before a pass and reads it once after it.
+ * Parameters, BatchNorm buffers and num_batches_tracked are not arguments and are never touched; every launch is on `stream`
+ * (no side stream); re-entrant like the eval forward.  The workspace holds the eval forward's, the mask, the loss partials and,
+ * for hop > 0, two waveforms of B * hop * (W - 1) floats and the MR-STFT workspace -- no gradient buffers. */
+size_t svs_unet_eval_loss_workspace_bytes(int B, int H, int W, int hop);
+int svs_unet_eval_loss(const void* prepared, const float* mix, const float* voc, const float* mix_phase, const float* voc_phase,
+                       int B, int H, int W, int hop, double alpha_l1, double alpha_mr, float* mask /*nullable*/,
+                       float* losses /*[2]*/, double* acc /*[3], nullable*/, void* ws, size_t ws_bytes, hipStream_t stream);
 /* training = 0: the workspace of svs_unet_forward_eval, 1: of the svs_unet_train_* calls, 2: of svs_unet_forward_eval_bf16
  * (names "cat1" .. "cat5" and "c6" only; see below what they hold). */
 int64_t svs_unet_ws_offset(const char* name, int B, int H, int W, int training);  /* bytes, <0 unknown */

@@ -57,6 +57,7 @@ _SIGS = {
     "svs_bn_bwd": (I, [P, L, P, L, L, I, L, P, P, P, P, F, P, P, P, P, P, Z, P]),
     "svs_l1_mask_loss_workspace_bytes": (Z, [L]),
     "svs_l1_mask_loss_fwd_bwd": (I, [P, P, P, L, F, P, P, P, Z, P]),
+    "svs_l1_mask_loss_fwd": (I, [P, P, P, L, P, P, Z, P]),
     "svs_adam_step": (I, [P, P, P, P, L, D, D, D, D, I, F, P]),
     "svs_apply_mask": (I, [P, P, P, L, I, P]),
     "svs_unet_param_offset": (L, [I]),
@@ -78,6 +79,8 @@ _SIGS = {
     "svs_unet_train_bwd_sync": (I, [P]),
     "svs_unet_train_mr_workspace_bytes": (Z, [I, I, I]),
     "svs_unet_train_fwd_loss_mr": (I, [P, P, P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, Z, P, Z, P]),
+    "svs_unet_eval_loss_workspace_bytes": (Z, [I, I, I, I]),
+    "svs_unet_eval_loss": (I, [P, P, P, P, P, I, I, I, I, D, D, P, P, P, P, Z, P]),
     "svs_unet_ws_offset": (L, [C.c_char_p, I, I, I, I]),
     "svs_stft_frames": (I, [L, I]),
     "svs_stft_fwd": (I, [P, L, I, I, P, P, P]),

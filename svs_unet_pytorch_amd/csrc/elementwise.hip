@@ -588,6 +588,66 @@ extern "C" int svs_l1_mask_loss_fwd_bwd(const float* mask, const float* mix, con
   return SVS_OK;
 }
 
+// The value of l1_mask_loss_kernel alone (validation, train.py:329-338): three float4 read streams, no write stream.  Same
+// blocks, same grid-stride order, same per-element expressions and the same block_sum, so partial[] -- and with it the loss
+// sum_partials_kernel folds -- is bit for bit what l1_mask_loss_kernel leaves for the same inputs.
+__global__ __launch_bounds__(256) void l1_mask_value_kernel(const float* __restrict__ mask, const float* __restrict__ mix,
+                                                            const float* __restrict__ voc, long n, float* __restrict__ partial) {
+  __shared__ float sh[4];
+  float s = 0.f;
+  auto one = [&](float m, float x, float v) __attribute__((always_inline)) {
+    const float d1 = m * x - v;
+    const float ta = fmaxf(x - v, 0.f);
+    const float d2 = (1.f - m) * x - ta;
+    s += fabsf(d1) + fabsf(d2);
+  };
+  const long n4 = n >> 2;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const f32x4 m = ((const f32x4*)mask)[i], x = ((const f32x4*)mix)[i], v = ((const f32x4*)voc)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) one(m[k], x[k], v[k]);
+  }
+  for (long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) one(mask[i], mix[i], voc[i]);
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+extern "C" int svs_l1_mask_loss_fwd(const float* mask, const float* mix, const float* voc, int64_t n, float* loss, void* ws,
+                                    size_t ws_bytes, hipStream_t stream) {
+  SVS_REQUIRE(mask && mix && voc && loss && n > 0, "svs_l1_mask_loss_fwd: null pointer");
+  SVS_REQUIRE(svs_aligned16(mask) && svs_aligned16(mix) && svs_aligned16(voc), "svs_l1_mask_loss_fwd: pointers must be 16-byte aligned");
+  if (!ws || ws_bytes < SCALAR_BLOCKS * sizeof(float)) { svs_set_error("svs_l1_mask_loss_fwd: workspace too small"); return SVS_ERR_WORKSPACE; }
+  int nb = (int)((n + 255) / 256);
+  if (nb > SCALAR_BLOCKS) nb = SCALAR_BLOCKS;
+  hipLaunchKernelGGL(l1_mask_value_kernel, dim3(nb), dim3(256), 0, stream, mask, mix, voc, (long)n, (float*)ws);
+  SVS_CHECK_LAUNCH("l1_mask_value");
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, stream, (const float*)ws, nb, 1.0 / (double)n, loss);
+  SVS_CHECK_LAUNCH("sum_partials");
+  return SVS_OK;
+}
+
+// Running totals of a validation pass (train.py:339,346,348): acc[0] += alpha_l1 * l1, then += alpha_mr * mr; acc[1] += l1;
+// acc[2] += mr -- in double, each product rounded before it is added (no fused multiply-add), which is what the host loop
+// `val_sum += ALPHA_L1 * float(l1); val_sum += alpha_mr * float(mr)` computes on the same per-batch values.
+__global__ void eval_loss_acc_kernel(const float* __restrict__ losses, double alpha_l1, double alpha_mr, double* __restrict__ acc) {
+#pragma clang fp contract(off)
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const double l1 = (double)losses[0], mr = (double)losses[1];
+  double total = acc[0];
+  const double p1 = alpha_l1 * l1;
+  total = total + p1;
+  const double p2 = alpha_mr * mr;
+  total = total + p2;
+  acc[0] = total;
+  acc[1] = acc[1] + l1;
+  acc[2] = acc[2] + mr;
+}
+int svs_eval_loss_acc_run(const float* losses, double alpha_l1, double alpha_mr, double* acc, hipStream_t stream) {
+  hipLaunchKernelGGL(eval_loss_acc_kernel, dim3(1), dim3(64), 0, stream, losses, alpha_l1, alpha_mr, acc);
+  SVS_CHECK_LAUNCH("eval_loss_acc");
+  return SVS_OK;
+}
+
 // d_logit = d_mask * mask * (1 - mask)    (autograd path: the loss was built by the caller in torch)
 __global__ __launch_bounds__(256) void sigmoid_bwd_kernel(const float* __restrict__ mask, const float* __restrict__ dmask,
                                                           long n, float* __restrict__ d_logit) {

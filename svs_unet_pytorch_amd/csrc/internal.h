@@ -39,6 +39,8 @@ size_t svs_wgrad_c1_workspace(int B, int Hs, int Ws, int Cs);
 
 int svs_channel_sum_run(const float* x, long ldx, long P, int C, float* out, void* ws, size_t ws_bytes, hipStream_t stream);
 int svs_sum_run(const float* x, long n, float* out, void* ws, size_t ws_bytes, hipStream_t stream);
+// acc[0] += alpha_l1 * losses[0], then += alpha_mr * losses[1]; acc[1] += losses[0]; acc[2] += losses[1] (double, unfused)
+int svs_eval_loss_acc_run(const float* losses, double alpha_l1, double alpha_mr, double* acc, hipStream_t stream);
 int svs_sigmoid_bwd_run(const float* mask, const float* dmask, long n, float* d_logit, hipStream_t stream);
 
 // out[g][i] = sum over the g-th chunk of `per` consecutive slabs of slab[z][i]   (i < n, g < groups)

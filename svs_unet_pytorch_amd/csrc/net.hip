@@ -287,6 +287,68 @@ extern "C" int svs_unet_forward_eval(const void* prepared, const float* mix, flo
                             "svs_unet_forward_eval", level1_plane(g));
 }
 
+// The reference's eval-mode objective (train.py:317-363, the loss of train.py:329-346) with no gradient: one eval forward, the
+// value-only L1 kernel and -- when the phase tiles are given -- the two inverse STFTs and the MR-STFT loss exactly as
+// svs_unet_train_fwd_loss_mr issues them, minus d_x.  Everything on the caller's stream; parameters and BatchNorm buffers are
+// never seen (only the prepared blob is).  hop == 0 in the workspace query: the L1 part alone.
+struct EvalLossWs { void* eval; size_t eval_bytes; float* mask; float* partial; float* wav_pred; float* wav_tgt; void* mr; size_t mr_bytes; size_t total; };
+static EvalLossWs eval_loss_layout(const Geo& g, int W, int hop, void* ws) {
+  EvalLossWs m{};
+  Arena a{(char*)ws, 0};
+  m.eval_bytes = eval_layout(g, nullptr).total;
+  m.eval = a.take<char>(m.eval_bytes);
+  m.mask = a.take<float>((size_t)g.P[0]);
+  m.partial = a.take<float>(svs_l1_mask_loss_workspace_bytes(g.P[0]) / sizeof(float));
+  if (hop > 0) {
+    const size_t L = (size_t)hop * (W - 1);
+    m.wav_pred = a.take<float>((size_t)g.B * L);
+    m.wav_tgt = a.take<float>((size_t)g.B * L);
+    m.mr_bytes = svs_mrstft_workspace_bytes(g.B, (int64_t)L);
+    m.mr = a.take<float>(m.mr_bytes / sizeof(float) + 64);
+  }
+  m.total = a.used;
+  return m;
+}
+extern "C" size_t svs_unet_eval_loss_workspace_bytes(int B, int H, int W, int hop) {
+  Geo g;
+  if (hop < 0 || (hop > 0 && W < 2) || make_geo(B, H, W, g)) return 0;
+  return eval_loss_layout(g, W, hop, nullptr).total;
+}
+extern "C" int svs_unet_eval_loss(const void* prepared, const float* mix, const float* voc, const float* mix_phase,
+                                  const float* voc_phase, int B, int H, int W, int hop, double alpha_l1, double alpha_mr, float* mask,
+                                  float* losses, double* acc, void* ws, size_t ws_bytes, hipStream_t stream) {
+  Geo g;
+  int rc = make_geo(B, H, W, g);
+  if (rc) return rc;
+  SVS_REQUIRE(prepared && mix && voc && losses && svs_aligned16(mix) && svs_aligned16(voc) && (!mask || svs_aligned16(mask)),
+              "svs_unet_eval_loss: bad pointers");
+  SVS_REQUIRE(!mix_phase == !voc_phase, "svs_unet_eval_loss: give both phase tiles (full objective) or neither (L1 part only)");
+  const bool full = mix_phase != nullptr;
+  if (full) {                                // the early errors of svs_unet_train_fwd_loss_mr
+    SVS_REQUIRE(H == 256 || H == 512 || H == 1024, "svs_unet_eval_loss: with phases needs H = n_fft / 2 = 256, 512 or 1024 (n_fft 512, 1024 or "
+                "2048: the sizes the inverse STFT is built for), got H = %d", H);
+    SVS_REQUIRE(W >= 2 && hop > 0 && hop <= 2 * H, "svs_unet_eval_loss: needs W >= 2 and 0 < hop <= n_fft = %d (W = %d, hop = %d)", 2 * H, W, hop);
+    SVS_REQUIRE((long)hop * (W - 1) > 2048, "svs_unet_eval_loss: W = %d frames at hop = %d give waveforms of hop * (W - 1) = %ld samples; the "
+                "multi-resolution STFT loss needs more than 2048", W, hop, (long)hop * (W - 1));
+    SVS_REQUIRE(svs_aligned16(mix_phase) && svs_aligned16(voc_phase), "svs_unet_eval_loss: bad pointers");
+  }
+  const EvalLossWs m = eval_loss_layout(g, W, full ? hop : 0, ws);
+  if (!ws || ws_bytes < m.total || !svs_aligned16(ws)) { svs_set_error("svs_unet_eval_loss: workspace too small (%zu < %zu)", ws_bytes, m.total); return SVS_ERR_WORKSPACE; }
+  float* mk = mask ? mask : m.mask;
+  if ((rc = svs_unet_forward_eval(prepared, mix, mk, B, H, W, m.eval, m.eval_bytes, stream))) return rc;
+  if ((rc = svs_l1_mask_loss_fwd(mk, mix, voc, g.P[0], losses, m.partial, svs_l1_mask_loss_workspace_bytes(g.P[0]), stream))) return rc;   // train.py:329-338
+  if (full) {
+    const int64_t cs = (int64_t)H * W;
+    const long L = (long)hop * (W - 1);
+    if ((rc = svs_istft_tiles_n(mix, cs, W, H, 1, mk, 0, mix_phase, 3, B, 2 * H, hop, W, m.wav_pred, nullptr, stream))) return rc;      // train.py:341
+    if ((rc = svs_istft_tiles_n(voc, cs, W, H, 1, nullptr, 0, voc_phase, 3, B, 2 * H, hop, W, m.wav_tgt, nullptr, stream))) return rc;  // train.py:342
+    if ((rc = svs_mrstft_loss_fwd_bwd(m.wav_pred, m.wav_tgt, B, L, 0.f, losses + 1, nullptr, m.mr, m.mr_bytes, stream))) return rc;      // train.py:343
+  } else {
+    SVS_HIP(hipMemsetAsync(losses + 1, 0, sizeof(float), stream));
+  }
+  return acc ? svs_eval_loss_acc_run(losses, alpha_l1, alpha_mr, acc, stream) : SVS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // training
 // ---------------------------------------------------------------------------------------------

@@ -323,12 +323,14 @@ class UNet(nn.Module):
             mix = mix.float()
         return mix.contiguous()
 
-    def _workspace(self, kind, B, H, W):
-        key = (kind, B, H, W)
+    def _workspace(self, kind, B, H, W, hop=0):
+        """`hop` belongs to the "eval_loss" kind alone (0: its L1-only form)."""
+        key = (kind, B, H, W) if kind != "eval_loss" else (kind, B, H, W, hop)
         ws = self._ws.get(key)
         if ws is None:
             fn = {"eval": lib().svs_unet_eval_workspace_bytes, "eval_bf16": lib().svs_unet_eval_bf16_workspace_bytes,
-                  "train": lib().svs_unet_train_workspace_bytes}[kind]
+                  "train": lib().svs_unet_train_workspace_bytes,
+                  "eval_loss": lambda b, h, w: lib().svs_unet_eval_loss_workspace_bytes(b, h, w, hop)}[kind]
             nbytes = int(fn(B, H, W))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self._flat.device)
             if len(self._ws) > 8:
@@ -351,8 +353,8 @@ class UNet(nn.Module):
     # ==============================================================================
     #   forward / backward
     # ==============================================================================
-    def _eval_forward(self, mix):
-        B, _, H, W = mix.shape
+    def _ensure_prepared(self):
+        """Re-folds the eval blob when -- and only when -- `_eval_key()` has changed; returns the key."""
         # everything that can change the folded weights: in-place edits of any parameter / BatchNorm buffer (each
         # parameter has its own version counter: p.data is re-pointed at the flat buffer), and `_param_epoch`, which
         # every path that updates them through raw pointers bumps (training forwards, Adam, broadcasts, re-flattening)
@@ -363,6 +365,11 @@ class UNet(nn.Module):
             check(lib().svs_unet_prepare_eval(ptr(self._flat), ptr(self._bn_flat), ptr(self._prepared), _lib.stream_ptr()),
                   "svs_unet_prepare_eval")
             self._prepared_key = key
+        return key
+
+    def _eval_forward(self, mix):
+        B, _, H, W = mix.shape
+        key = self._ensure_prepared()
         mask = torch.empty_like(mix)
         if self.eval_precision == "bf16":
             if self._prepared_bf16 is None or self._prepared_bf16_key != key:
@@ -469,6 +476,43 @@ class UNet(nn.Module):
         if torch.is_grad_enabled():
             return _TrainForward.apply(self._anchor, mix, self)
         return self._train_forward(mix)
+
+    @_on_model_device
+    def eval_losses(self, mix, voc, mix_phase=None, voc_phase=None, hop=None, alpha_l1=ALPHA_L1, alpha_mr=ALPHA_MR, acc=None):
+        """The eval-mode objective of one validation batch (train.py:329-346) as ONE library call, `svs_unet_eval_loss`:
+        returns the (2,) device tensor [L1 part, MR-STFT part], both unscaled; with no phase tiles the L1 part only and
+        losses[1] == 0.  `hop`: hop of the STFT the tiles came from (default config.HOP_SIZE); its window is twice the tile
+        height.  `acc` (optional): a float64 device tensor of 3 elements that the call adds to on the device --
+        acc[0] += alpha_l1 * l1, then += alpha_mr * mr; acc[1] += l1; acc[2] += mr -- so a whole pass needs one read-back.
+
+        Always the fp32 network, whatever `eval_precision` says (the bf16 network is an inference path).  Eval arithmetic
+        whatever `self.training` is, which it leaves as it found it: running statistics folded, no dropout, and neither
+        parameters nor BatchNorm buffers are written.  The folded blob is the one `forward` uses in eval mode, re-folded only
+        when parameters or buffers have changed.  No host sync."""
+        mix, voc = self._check_input(mix), self._check_input(voc)
+        if voc.shape != mix.shape:
+            raise ValueError(f"mix {tuple(mix.shape)} and voc {tuple(voc.shape)} differ")
+        B, _, H, W = mix.shape
+        if (mix_phase is None) != (voc_phase is None):
+            raise ValueError("give both phase tiles or neither")
+        if mix_phase is not None:
+            if hop is None:
+                from .config import HOP_SIZE as hop
+            hop = int(hop)
+            mix_phase, voc_phase = self._check_input(mix_phase), self._check_input(voc_phase)
+            if mix_phase.shape != mix.shape or voc_phase.shape != mix.shape:
+                raise ValueError("phase tensors must have the shape of the magnitude tiles")
+        else:
+            hop = 0
+        if acc is not None and (acc.dtype != torch.float64 or acc.numel() != 3 or acc.device != mix.device or not acc.is_contiguous()):
+            raise ValueError("acc must be a contiguous float64 tensor of 3 elements on the model's device")
+        self._ensure_prepared()
+        ws = self._workspace("eval_loss", B, H, W, hop)
+        losses = torch.empty(2, dtype=torch.float32, device=mix.device)
+        check(lib().svs_unet_eval_loss(ptr(self._prepared), ptr(mix), ptr(voc), ptr(mix_phase), ptr(voc_phase), B, H, W, hop,
+                                       float(alpha_l1), float(alpha_mr), None, ptr(losses), ptr(acc), ptr(ws), ws.numel(),
+                                       _lib.stream_ptr()), "svs_unet_eval_loss")
+        return losses
 
     def _mr_workspace(self, B, W, hop):
         key = ("mr", B, W, hop)

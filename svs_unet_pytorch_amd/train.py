@@ -22,6 +22,12 @@ data set has no *_phase.npy files.  The logged totals are the same quantity as t
 all-reduced over RCCL (parallel.py); rank 0 writes the files.  CKPT/ and LOG/ are created if missing (the
 reference assumes they exist).
 
+Validation (train.py:317-363) runs from HBM too under the default SVS_DATA_LOADER=resident: the validation folder is a second
+`ResidentSpectrograms` and `validation_pass` makes one `UNet.eval_losses` call (svs_unet_eval_loss) per batch, summing on the
+device; the pass ends in one read-back and logs the same `Val` value, the mean of per-batch totals.  Any other SVS_DATA_LOADER
+keeps the reference's host loop (a 2-worker DataLoader, `l1_terms` / `mr_term`).  `python -m svs_unet_pytorch_amd.validate`
+runs the pass on a checkpoint without training.
+
 --win_size / --hop_size (the config's 1024 / 768 by default) name the STFT geometry of the folder that `data.py --direction
 to_spec --win_size W --hop_size H` wrote (data.py:24-25 lets both vary): tiles are (win_size / 2, INPUT_LEN), the network is
 fully convolutional, and the MR-STFT term re-synthesises its waveforms with that window and hop (its own three resolutions
@@ -198,16 +204,30 @@ class ResidentSpectrograms:
     def crop(self, songs, starts, with_phase: bool = False):
         """mix, voc [, mix_phase, voc_phase] (B, 1, win_size / 2, INPUT_LEN) on the device for the given songs / start frames; the
         phase tiles are angles cut with the SAME start (train.py:121-127)."""
+        return self.crop_table(self.upload_table(songs, starts), 0, len(songs), with_phase)
+
+    def upload_table(self, songs, starts):
+        """The (song, start) table of any number of items -- a batch or a whole pass -- as one (2, N) int32 device tensor:
+        one host-to-device copy."""
+        return torch.tensor([songs, starts], dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+
+    def crop_table(self, table, lo, hi, with_phase: bool = False):
+        """`crop` for items lo..hi-1 of an uploaded table: `svs_crop_tiles` reads its songs and starts through pointers, so a
+        batch of a pass is a slice of the pass's table and costs no copy of its own."""
         from . import _lib
-        B = len(songs)
-        idx = torch.tensor([songs, starts], dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+        B = hi - lo
+        if not (0 <= lo < hi <= table.shape[1]) or table.dtype != torch.int32 or table.shape[0] != 2 or not table.is_contiguous():
+            raise ValueError(f"items {lo}..{hi} of a table of shape {tuple(table.shape)}")
+        if with_phase and self.mix_ang is None:
+            raise ValueError("phase tiles asked of a set without *_phase.npy files")
+        songs, starts = table[0, lo:hi], table[1, lo:hi]
         out = []
         pairs = [(self.mix, self.voc)] + ([(self.mix_ang, self.voc_ang)] if with_phase else [])
         for a_src, b_src in pairs:
             a = torch.empty((B, 1, self.rows, INPUT_LEN), dtype=torch.float32, device=self.device)
             b = torch.empty_like(a)
             _lib.check(_lib.lib().svs_crop_tiles(a_src.data_ptr(), b_src.data_ptr(), self.offsets.data_ptr(), self.frames.data_ptr(),
-                                                 idx[0].data_ptr(), idx[1].data_ptr(), B, self.rows, INPUT_LEN, a.data_ptr(), b.data_ptr(),
+                                                 songs.data_ptr(), starts.data_ptr(), B, self.rows, INPUT_LEN, a.data_ptr(), b.data_ptr(),
                                                  _lib.stream_ptr()), "svs_crop_tiles")
             out += [a, b]
         return tuple(out)
@@ -246,6 +266,35 @@ def mr_term(model, mix, voc, mix_phase, voc_phase, n_fft=WINDOW_SIZE, hop=HOP_SI
     _lib.check(L.svs_mrstft_loss_fwd_bwd(pred.data_ptr(), tgt.data_ptr(), B, L_, 0.0, out.data_ptr(), None, ws.data_ptr(), ws.numel(),
                                          _lib.stream_ptr()), "svs_mrstft_loss_fwd_bwd")
     return out[0]
+
+
+def validation_plan(resident, batch_size, rng=random):
+    """Host half of a validation pass: (songs, starts, [(lo, hi), ...]).  Items in dataset order, as DataLoader(shuffle=False)
+    hands them out (item idx -> song idx % n_songs), starts drawn with `ResidentSpectrograms.draw`, batches of `batch_size`
+    with a short last one."""
+    n = len(resident)
+    songs, starts = resident.draw(range(n), rng)
+    return songs, starts, [(lo, min(lo + batch_size, n)) for lo in range(0, n, batch_size)]
+
+
+def validation_pass(model, resident, batch_size, with_phase, win_size, hop_size, rng=random):
+    """The validation loop of train.py:317-363 from the HBM-resident set: the pass's (song, start) table goes up in one copy,
+    each batch is one `svs_crop_tiles` per tile pair and one `UNet.eval_losses(..., acc=acc)`; nothing inside reads from the
+    device.  Returns (acc, n_batches): acc is the device double[3] of [sum of ALPHA_L1 * l1 + ALPHA_MR * mr, sum of l1, sum of
+    mr] over the batches -- the caller's single `acc.cpu()` ends the pass, and acc[0] / n_batches is the logged value (the
+    reference's mean of per-batch totals).  with_phase False: the L1 part only."""
+    if resident.rows != win_size // 2:
+        raise ValueError(f"the resident set has {resident.rows}-row tiles, --win_size {win_size} needs {win_size // 2}")
+    songs, starts, bounds = validation_plan(resident, batch_size, rng)
+    acc = torch.zeros(3, dtype=torch.float64, device=resident.device)
+    if not bounds:
+        return acc, 0
+    table = resident.upload_table(songs, starts)
+    for lo, hi in bounds:
+        tiles = resident.crop_table(table, lo, hi, with_phase=with_phase)
+        mph, vph = (tiles[2], tiles[3]) if with_phase else (None, None)
+        model.eval_losses(tiles[0], tiles[1], mph, vph, hop=hop_size, acc=acc)
+    return acc, len(bounds)
 
 
 def main(argv=None):
@@ -305,8 +354,9 @@ def main(argv=None):
         train_loader = Data.DataLoader(train_dataset, batch_size=per_rank_batch, num_workers=8,
                                        shuffle=sampler is None, sampler=sampler, pin_memory=True)
     valid_loader = None
-    if valid_dataset is not None:
-        if len(valid_dataset) > 0:
+    valid_on_device = resident is not None and valid_dataset is not None and len(valid_dataset) > 0   # made resident below, once
+    if valid_dataset is not None:                                                                     # the objective is known
+        if len(valid_dataset) > 0 and not valid_on_device:
             valid_loader = Data.DataLoader(valid_dataset, batch_size=max(args.batch_size // world, 1), num_workers=2,
                                            shuffle=False, pin_memory=True)
     else:
@@ -342,10 +392,13 @@ def main(argv=None):
     # the CPU-side datasets load phase files only when the objective needs them (and they exist): the L1-only fallback
     # holds for the validation loop and the SVS_DATA_LOADER=cpu path too, not just for the resident loader
     train_dataset.with_phase = full
-    if valid_loader is not None:
+    valid_resident = None
+    if valid_loader is not None or valid_on_device:
         valid_dataset.with_phase = full and valid_dataset.has_phase_files()
         if full and not valid_dataset.with_phase:
             print("Warning: the validation set has no *_phase.npy files -- its loss is the L1 part only.")
+        if valid_on_device:                                               # a second resident set (a few hundred MB); no DataLoader
+            valid_resident = ResidentSpectrograms(valid_dataset, device, with_phase=valid_dataset.with_phase)
     alpha_mr = ALPHA_MR if full else 0.0
     print(f"Objective: {ALPHA_L1} * L1" + (f" + {ALPHA_MR} * MR-STFT (train.py:296)" if full else " (L1 terms only)"))
 
@@ -385,16 +438,22 @@ def main(argv=None):
         if world > 1:                                                      # one set of running statistics for validation / checkpoints
             from .parallel import average_bn_buffers
             average_bn_buffers(model)
-        if valid_loader and (ep + 1) % args.val_interval == 0:             # train.py:317-363
+        if (valid_loader or valid_resident is not None) and (ep + 1) % args.val_interval == 0:             # train.py:317-363
             model.eval()
-            val_sum = 0.0
-            with torch.no_grad():
-                for mix, voc, mph, vph in valid_loader:
-                    mix, voc = mix.to(device), voc.to(device)
-                    val_sum += ALPHA_L1 * float(l1_terms(model, mix, voc))
-                    if full and valid_dataset.with_phase:                  # train.py:341-346
-                        val_sum += alpha_mr * float(mr_term(model, mix, voc, mph.to(device), vph.to(device), args.win_size, args.hop_size))
-            avg_val_loss = val_sum / len(valid_loader)
+            if valid_resident is not None:                                 # on the device: one library call per batch, one read-back
+                with torch.no_grad():
+                    acc, n_val = validation_pass(model, valid_resident, max(args.batch_size // world, 1),
+                                                 valid_dataset.with_phase and valid_resident.has_phase, args.win_size, args.hop_size)
+                avg_val_loss = float(acc.cpu()[0]) / n_val
+            else:                                                          # SVS_DATA_LOADER != resident: the reference's host loop
+                val_sum = 0.0
+                with torch.no_grad():
+                    for mix, voc, mph, vph in valid_loader:
+                        mix, voc = mix.to(device), voc.to(device)
+                        val_sum += ALPHA_L1 * float(l1_terms(model, mix, voc))
+                        if full and valid_dataset.with_phase:              # train.py:341-346
+                            val_sum += alpha_mr * float(mr_term(model, mix, voc, mph.to(device), vph.to(device), args.win_size, args.hop_size))
+                avg_val_loss = val_sum / len(valid_loader)
             log_buffer.append(f"Val {avg_val_loss}\n")
             print(f"\n[Epoch {ep + 1}] Train Loss: {avg_train_loss:.4e} | Val Loss: {avg_val_loss:.4e}")
             if avg_val_loss < best_val_loss and rank == 0:
