@@ -24,6 +24,23 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ u16 to_bf16(float v) { return __builtin_bit_cast(u16, (__bf16)v); }
 __device__ __forceinline__ float from_bf16(u16 v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
 
+// The epilogue of every kernel whose D tile is [channel][pixel] (weights = FIRST MFMA operand): the four accumulators of a lane
+// are four consecutive channels of one pixel.  acc + shift -> LeakyReLU (slope 0: ReLU) -> four bf16 as they lie in memory ...
+__device__ __forceinline__ uint2 act_bf16x4(f32x4 acc, f32x4 sh, float slope) {
+  float v[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { const float u = acc[r] + sh[r]; v[r] = u > 0.f ? u : u * slope; }
+  return make_uint2((unsigned)to_bf16(v[0]) | ((unsigned)to_bf16(v[1]) << 16), (unsigned)to_bf16(v[2]) | ((unsigned)to_bf16(v[3]) << 16));
+}
+// ... and one 8-byte store of them
+__device__ __forceinline__ void store_act_bf16x4(u16* dst, f32x4 acc, f32x4 sh, float slope) { *(uint2*)dst = act_bf16x4(acc, sh, slope); }
+
+// Tile `tile` of a persistent kernel's walk over B x tiles_h x tiles_w tiles of th x tw pixels: image and first pixel
+struct TileAt { long b; int h0, w0; };
+__device__ __forceinline__ TileAt tile_at(int tile, int tiles_h, int tiles_w, int th, int tw) {
+  return {tile / (tiles_w * tiles_h), ((tile / tiles_w) % tiles_h) * th, (tile % tiles_w) * tw};
+}
+
 struct ConvBf16Args {
   const u16* x; long ldx;          // bf16 NHWC view, ld in elements
   int B, H, W, C;                  // C % 32 == 0
@@ -184,14 +201,7 @@ __global__ __launch_bounds__(256) void conv_gemm_bf16_kernel(ConvBf16Args p) {
     for (int j = 0; j < TN; ++j) {
       const int n = n0 + wn * (TN * 16) + j * 16 + q * 4;
       if (split) { *(f32x4*)(slab + opix * p.N + n) = acc[i][j]; continue; }
-      const f32x4 sh = *(const f32x4*)(p.shift + n);
-      float v[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { const float u = acc[i][j][r] + sh[r]; v[r] = u > 0.f ? u : u * p.slope; }
-      uint2 o;
-      o.x = (unsigned)to_bf16(v[0]) | ((unsigned)to_bf16(v[1]) << 16);
-      o.y = (unsigned)to_bf16(v[2]) | ((unsigned)to_bf16(v[3]) << 16);
-      *(uint2*)(p.y + opix * p.ldy + n) = o;
+      store_act_bf16x4(p.y + opix * p.ldy + n, acc[i][j], *(const f32x4*)(p.shift + n), p.slope);
     }
   }
 }
@@ -225,30 +235,26 @@ __global__ __launch_bounds__(256) void parity_window_bf16_kernel(ConvBf16Args p)
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.wp, 0, OOB, 0x00020000);
   // persistent blocks: a block walks tiles blockIdx.x, + gridDim.x, ... so that resident weights (WALL) are fetched once per
   // block instead of once per tile (51 KB per 128 anchors was most of the L2 traffic)
-  int th0 = 0, tw0 = 0;
-  long b = 0;
+  TileAt cur{};
   // The window of the NEXT tile is requested (global -> registers) before the current tile's taps run and written to LDS
   // after them: with one tile in flight per block the ~2 us of load latency were as long as the tile's MFMAs.
   f32x4 stage[NST];
   auto fetch_window = [&](int tile) __attribute__((always_inline)) {
-    const int ftw0 = (tile % tiles_w) * TW, fth0 = ((tile / tiles_w) % tiles_h) * TH;
-    const long fb_ = tile / (tiles_w * tiles_h);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + fb_ * p.H * p.W * p.ldx), 0, OOB, 0x00020000);
+    const TileAt f = tile_at(tile, tiles_h, tiles_w, TH, TW);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + f.b * p.H * p.W * p.ldx), 0, OOB, 0x00020000);
 #pragma unroll
     for (int k = 0; k < NST; ++k) {
       const int e = t + k * 256;
       const int cq = e % CQ, px = e / CQ;
       const int lw = px % WW, lh = px / WW;
-      const int ih = fth0 - 1 + lh, iw = ftw0 - 1 + lw;
+      const int ih = f.h0 - 1 + lh, iw = f.w0 - 1 + lw;
       const bool ok = px < NPX && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
       const unsigned vo = ok ? (unsigned)(((ih * p.W + iw) * (int)p.ldx + cq * 8) * 2) : OOB;
       stage[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)vo, 0, 0));
     }
   };
   auto commit_window = [&](int tile) __attribute__((always_inline)) {           // registers -> LDS; this tile becomes the current one
-    tw0 = (tile % tiles_w) * TW;
-    th0 = ((tile / tiles_w) % tiles_h) * TH;
-    b = tile / (tiles_w * tiles_h);
+    cur = tile_at(tile, tiles_h, tiles_w, TH, TW);
 #pragma unroll
     for (int k = 0; k < NST; ++k) {
       const int e = t + k * 256;
@@ -323,7 +329,7 @@ __global__ __launch_bounds__(256) void parity_window_bf16_kernel(ConvBf16Args p)
   // The weights are the FIRST MFMA operand, so the D tile is [channel][pixel]: column lrow = anchor (th0 + 2 wave + i, tw0 + lrow),
   // rows q*4 + r = output channels (+16 j) -- four consecutive channels per lane, one 8-byte store (2-byte stores of one
   // channel per lane were most of the kernel's time: deconv5 134 -> us at 216 tiles)
-  float shv[TN][4];
+  f32x4 shv[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -332,20 +338,12 @@ __global__ __launch_bounds__(256) void parity_window_bf16_kernel(ConvBf16Args p)
     const int ph = par >> 1, pw = par & 1;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
-      const int a = th0 + RPT * (2 * wave + i) + lrow / TW, oh = 2 * a + ph;
-      const int c = tw0 + lrow % TW, ow = 2 * c + pw;
+      const int a = cur.h0 + RPT * (2 * wave + i) + lrow / TW, oh = 2 * a + ph;
+      const int c = cur.w0 + lrow % TW, ow = 2 * c + pw;
       if (a >= p.H || oh >= p.Ho || c >= p.W || ow >= p.Wo) continue;
-      u16* const dst = p.y + ((b * p.Ho + oh) * p.Wo + ow) * p.ldy + q * 4;
+      u16* const dst = p.y + ((cur.b * p.Ho + oh) * p.Wo + ow) * p.ldy + q * 4;
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { const float u = acc[i][j][r] + shv[j][r]; v[r] = u > 0.f ? u : u * p.slope; }
-        uint2 o;
-        o.x = (unsigned)to_bf16(v[0]) | ((unsigned)to_bf16(v[1]) << 16);
-        o.y = (unsigned)to_bf16(v[2]) | ((unsigned)to_bf16(v[3]) << 16);
-        *(uint2*)(dst + j * 16) = o;
-      }
+      for (int j = 0; j < TN; ++j) store_act_bf16x4(dst + j * 16, acc[i][j], shv[j], p.slope);
     }
   };
   f32x4 acc[TM][TN];
@@ -398,10 +396,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_bf16_kernel(const float* 
     const int n = (int)(e - pix * N);
     f32x4 s = *(const f32x4*)(slab + e);
     for (int z = 1; z < ksplit; ++z) s += *(const f32x4*)(slab + z * stride + e);
-    u16 o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { float v = s[k] + shift[n + k]; v = v > 0.f ? v : v * slope; o[k] = to_bf16(v); }
-    *(uint2*)(y + pix * ldy + n) = make_uint2((unsigned)o[0] | ((unsigned)o[1] << 16), (unsigned)o[2] | ((unsigned)o[3] << 16));
+    store_act_bf16x4(y + pix * ldy + n, s, (f32x4){shift[n], shift[n + 1], shift[n + 2], shift[n + 3]}, slope);
   }
 }
 
@@ -434,12 +429,11 @@ __global__ __launch_bounds__(256) void conv1_mfma_bf16_kernel(Conv1Args p) {
   }
   float stage[NST];
   auto fetch_window = [&](int tile) __attribute__((always_inline)) {
-    const int fow0 = (tile % tiles_w) * TW, foh0 = ((tile / tiles_w) % tiles_h) * TH;
-    const int fb_ = tile / (tiles_w * tiles_h);
-    const int soff = __builtin_amdgcn_readfirstlane((int)((((long)fb_ * p.H + 2 * foh0) * p.W + 2 * fow0) * 4));
+    const TileAt f = tile_at(tile, tiles_h, tiles_w, TH, TW);
+    const int soff = __builtin_amdgcn_readfirstlane((int)(((f.b * p.H + 2 * f.h0) * p.W + 2 * f.w0) * 4));
 #pragma unroll
     for (int k = 0; k < NST; ++k) {
-      const bool ok = (unsigned)(2 * foh0 - 2 + s_wr[k]) < (unsigned)p.H && (unsigned)(2 * fow0 - 2 + s_wc[k]) < (unsigned)p.W;
+      const bool ok = (unsigned)(2 * f.h0 - 2 + s_wr[k]) < (unsigned)p.H && (unsigned)(2 * f.w0 - 2 + s_wc[k]) < (unsigned)p.W;
       stage[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (int)(ok ? s_rel[k] : OOB), soff, 0));
     }
   };
@@ -450,8 +444,7 @@ __global__ __launch_bounds__(256) void conv1_mfma_bf16_kernel(Conv1Args p) {
   const f32x4 sh = *(const f32x4*)(p.shift + q * 4);
   if ((int)blockIdx.x < ntiles) fetch_window(blockIdx.x);
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int ow0 = (tile % tiles_w) * TW, oh0 = ((tile / tiles_w) % tiles_h) * TH;
-    const long b = tile / (tiles_w * tiles_h);
+    const TileAt o = tile_at(tile, tiles_h, tiles_w, TH, TW);
     __syncthreads();                                                               // the previous tile's readers are done
 #pragma unroll
     for (int k = 0; k < NST; ++k) {
@@ -478,15 +471,9 @@ __global__ __launch_bounds__(256) void conv1_mfma_bf16_kernel(Conv1Args p) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw, __builtin_bit_cast(bf16x8, (uint4){lo[0], lo[1], lo[2], lo[3]}), acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw, __builtin_bit_cast(bf16x8, (uint4){hi[0], hi[1], hi[2], hi[3]}), acc, 0, 0, 0);
-      const int oh = oh0 + ohl, ow = ow0 + owl;
+      const int oh = o.h0 + ohl, ow = o.w0 + owl;
       if (oh >= p.Ho || ow >= p.Wo) continue;
-      float v[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { const float u = acc[r] + sh[r]; v[r] = u > 0.f ? u : u * p.slope; }
-      uint2 o;
-      o.x = (unsigned)to_bf16(v[0]) | ((unsigned)to_bf16(v[1]) << 16);
-      o.y = (unsigned)to_bf16(v[2]) | ((unsigned)to_bf16(v[3]) << 16);
-      *(uint2*)(p.y + ((b * p.Ho + oh) * p.Wo + ow) * p.ldy + q * 4) = o;
+      store_act_bf16x4(p.y + ((o.b * p.Ho + oh) * p.Wo + ow) * p.ldy + q * 4, acc, sh, p.slope);
     }
   }
 }
@@ -499,220 +486,137 @@ __global__ void conv1_pack_kernel(const float* __restrict__ w, const float* __re
 }
 
 // ------------------------------------------------------------------------------------------------
-// conv2 (model.py:53-57: 16 -> 32 channels, 5x5, stride 2) as an LDS-window kernel.  In the GEMM form each input element
-// travels 25/4 times through L2 and a K-tile is one tap of 32 channels, half of them the zero-weighted decoder half of the
-// interleaved level-1 buffer: 185 us at 216 tiles for 57 us of HBM traffic.  Here a block owns 8 x 16 OUTPUT pixels,
-// stages their (2*8+3) x (2*16+3) input window (the 16 skip channels only) once, split by column parity so that the 16
-// pixels of an operand fragment -- stride 2 in the image -- are consecutive 32-byte LDS slots (conflict-free ds_read_b128),
-// and walks 13 K-steps of two taps x 16 channels.  The 26 KB of weights stay in LDS while the block walks its tiles
-// (persistent blocks).  Operand roles are swapped (weights = first MFMA operand): the four accumulator registers of a
-// lane are then four consecutive CHANNELS of one pixel, which leave as one 8-byte store.
+// conv2 (model.py:53-57: 16 -> 32 channels) and conv3 (32 -> 64), 5x5, stride 2, as ONE LDS-window kernel, C = 16 / 32 input
+// and N = 2C output channels.  In the GEMM form every input element travels 25/4 times through L2 / LDS (conv3: 4.6x the
+// algorithmic HBM bytes by the counters, 89 us at 216 tiles), and conv2's K-tile is one tap of 32 channels, half of them the
+// zero-weighted decoder half of an interleaved level 1: 185 us at 216 tiles for 57 us of HBM traffic.  Here a block owns 8 x 16
+// OUTPUT pixels and stages their (2*8+3) x (2*16+3) input window ONCE (conv2: the 16 skip channels only), even / odd columns
+// in separate planes, so that the 16 pixels of an operand fragment -- stride 2 in the image -- are adjacent LDS slots
+// (conflict-free ds_read_b128: 32-byte slots for C = 16, an 80-byte pixel pitch for C = 32).  A K-step is 32 values of k:
+// two taps x 16 channels (13 steps, the 26th tap has zero weights) or one tap x 32 channels (25 steps).  ALL weights stay in
+// LDS for the block's whole life as [step][n][64 bytes], the 16-byte pieces XOR-swizzled by the row (26 KB / 100 KB), and
+// every step is 2 pixel rows x N / 16 channel tiles of MFMAs per wave with both fragments at base + compile-time offset: no
+// barrier and no global access inside a tile.  Operand roles are swapped (weights = first MFMA operand): the four accumulator
+// registers of a lane are then four consecutive CHANNELS of one pixel, which leave as one 8-byte store.  Persistent blocks,
+// the next tile's window in flight (registers) during the current tile's MFMAs.
 // ------------------------------------------------------------------------------------------------
-struct Conv2WinArgs {
-  const u16* x; long ldx; int B, H, W;       // skip half of level 1 (16 channels at x, pixel pitch ldx)
-  const u16* wk;                             // [13 steps][32 n][32 k = (tap parity, channel)] bf16, scale folded
+struct GatherWinArgs {
+  const u16* x; long ldx; int B, H, W;       // C channels at x, pixel pitch ldx (conv2: the skip plane of level 1)
+  const u16* wk;                             // [steps][N][32 k = (tap of the step, channel)] bf16, scale folded: gather_window_pack_kernel
   const float* shift; float slope;
-  u16* y; long ldy; int Ho, Wo;              // 32 channels at y
+  u16* y; long ldy; int Ho, Wo;              // N channels at y
 };
-__global__ __launch_bounds__(256) void conv2_window_bf16_kernel(Conv2WinArgs p) {
+constexpr int gw_steps(int C) { return (25 + 32 / C - 1) / (32 / C); }          // K-steps of 32 / C taps
+constexpr int gw_pitch(int C) { return C == 16 ? 32 : 2 * C + 16; }             // LDS bytes per staged pixel
+constexpr int gw_lds(int C) { return 19 * 2 * 18 * gw_pitch(C) + gw_steps(C) * 2 * C * 64; }      // window + weights: 48512 / 157120 bytes
+// grid cap = resident blocks per CU x 256 CUs: three by LDS for C = 16 (and by registers: at most 168 per lane), one for C = 32
+constexpr int gw_max_blocks(int C) { return C == 16 ? 768 : 256; }
+template <int C>
+__global__ __launch_bounds__(256) void gather_window_bf16_kernel(GatherWinArgs p) {
+  constexpr int N = 2 * C, TPS = 32 / C, NS = gw_steps(C), CQ = C / 8, TNJ = N / 16, LPB = gw_pitch(C);
   constexpr int TH = 8, TW = 16, WR = 2 * TH + 3, WC = 2 * TW + 3, PW = TW + 2;     // window rows / columns; slots per parity plane
-  constexpr int NCH = WR * WC * 2, NST = (NCH + 255) / 256;                         // 16-byte pieces of the window
-  constexpr int NWP = 13 * 32 * 4, NWL = (NWP + 255) / 256;                         // 16-byte pieces of the weights
-  __shared__ __attribute__((aligned(16))) unsigned char win[WR * 2 * PW * 32];
-  __shared__ __attribute__((aligned(16))) unsigned char wts[13 * 32 * 64];
+  constexpr int NCH = WR * WC * CQ, NST = (NCH + 255) / 256;                        // 16-byte pieces of the window
+  constexpr int NWP = NS * N * 4, NWL = (NWP + 255) / 256;                          // 16-byte pieces of the weights
+  constexpr int WIN_BYTES = WR * 2 * PW * LPB;
+  static_assert(WIN_BYTES + NS * N * 64 == gw_lds(C) && WIN_BYTES % 16 == 0, "LDS size");
+  extern __shared__ __attribute__((aligned(16))) unsigned char gw_smem[];
+  unsigned char* const win = gw_smem;
+  unsigned char* const wts = gw_smem + WIN_BYTES;                                   // [step][n][64 bytes], piece ^ ((n >> 1) & 3)
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, lrow = lane & 15, q = lane >> 4;
   const int tiles_w = (p.Wo + TW - 1) / TW, tiles_h = (p.Ho + TH - 1) / TH;
   const int ntiles = p.B * tiles_h * tiles_w;
+  // weights: row n of step s, piece swizzled by n.  Unrolled, so that a thread's 7 / 25 loads are in flight together: as a rolled loop
+  // every block began with that many load round trips in turn (conv3 51.1 -> 44.5 us at 216 tiles)
 #pragma unroll
-  for (int k = 0; k < NWL; ++k) {                                                  // weights: row n of step s, piece swizzled by n
+  for (int k = 0; k < NWL; ++k) {
     const int e = t + k * 256;
     if (e < NWP) {
-      const int piece = e & 3, n = (e >> 2) & 31, s_ = e >> 7;
-      *(uint4*)(&wts[(s_ * 32 + n) * 64 + ((piece ^ ((n >> 1) & 3)) * 16)]) = *(const uint4*)(p.wk + (long)e * 8);
+      const int piece = e & 3, n = (e >> 2) % N, s_ = e / (4 * N);
+      *(uint4*)(wts + (s_ * N + n) * 64 + ((piece ^ ((n >> 1) & 3)) * 16)) = *(const uint4*)(p.wk + (long)e * 8);
     }
   }
-  const int t2 = q >> 1, half = q & 1;
-  float sh[2][4];
+  const int tsel = q / CQ, cq = q % CQ;                                             // lane (pixel lrow, q): channels 8 cq.. of tap TPS s + tsel
+  f32x4 sh[TNJ];
 #pragma unroll
-  for (int j = 0; j < 2; ++j)
+  for (int j = 0; j < TNJ; ++j)
 #pragma unroll
     for (int r = 0; r < 4; ++r) sh[j][r] = p.shift[j * 16 + q * 4 + r];
   uint4 stage[NST];
   auto fetch_window = [&](int tile) __attribute__((always_inline)) {              // global -> registers (in flight during the previous tile's MFMAs)
-    const int fow0 = (tile % tiles_w) * TW, foh0 = ((tile / tiles_w) % tiles_h) * TH;
-    const u16* const xb = p.x + (long)(tile / (tiles_w * tiles_h)) * p.H * p.W * p.ldx;
+    const TileAt f = tile_at(tile, tiles_h, tiles_w, TH, TW);
+    const u16* const xb = p.x + f.b * p.H * p.W * p.ldx;
 #pragma unroll
     for (int k = 0; k < NST; ++k) {
-      const int e = t + k * 256, hf = e & 1, px = e >> 1;
+      const int e = t + k * 256, c8 = e % CQ, px = e / CQ;
       const int wr = px / WC, wc = px - wr * WC;
-      const int ih = 2 * foh0 - 2 + wr, iw = 2 * fow0 - 2 + wc;
+      const int ih = 2 * f.h0 - 2 + wr, iw = 2 * f.w0 - 2 + wc;
       stage[k] = make_uint4(0u, 0u, 0u, 0u);
-      if (e < NCH && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) stage[k] = *(const uint4*)(xb + ((long)ih * p.W + iw) * p.ldx + hf * 8);
+      if (e < NCH && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) stage[k] = *(const uint4*)(xb + ((long)ih * p.W + iw) * p.ldx + c8 * 8);
     }
   };
   if ((int)blockIdx.x < ntiles) fetch_window(blockIdx.x);
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int ow0 = (tile % tiles_w) * TW, oh0 = ((tile / tiles_w) % tiles_h) * TH;
-    const long b = tile / (tiles_w * tiles_h);
-    __syncthreads();                                                               // the previous tile's readers are done
-#pragma unroll
-    for (int k = 0; k < NST; ++k) {
-      const int e = t + k * 256, hf = e & 1, px = e >> 1;
-      const int wr = px / WC, wc = px - wr * WC;
-      if (e < NCH) *(uint4*)(&win[((wr * 2 + (wc & 1)) * PW + (wc >> 1)) * 32 + hf * 16]) = stage[k];
-    }
-    if (tile + (int)gridDim.x < ntiles) fetch_window(tile + gridDim.x);
-    __syncthreads();
-    f32x4 acc[2][2];                                                               // [pixel row i][channel tile j]
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // pixel fragment of output row 2*wave + i: lane (pixel lrow, q) reads channels half*8.. of tap 2s + t2
-    const unsigned char* const pbase = &win[(((4 * wave) * 2) * PW + lrow) * 32 + half * 16];
-    const unsigned char* const wbase = &wts[lrow * 64 + ((q ^ ((lrow >> 1) & 3)) * 16)];
-    svs_static_for<13>([&](auto sc) {
-      constexpr int s_ = decltype(sc)::value;
-      constexpr int tap0 = 2 * s_, tap1 = (2 * s_ + 1 < 25) ? 2 * s_ + 1 : 24;     // (the 26th tap has zero weights: any finite data)
-      constexpr int off0 = (((tap0 / 5) * 2 + ((tap0 % 5) & 1)) * PW + ((tap0 % 5) >> 1)) * 32;
-      constexpr int off1 = (((tap1 / 5) * 2 + ((tap1 % 5) & 1)) * PW + ((tap1 % 5) >> 1)) * 32;
-      const int off = t2 ? off1 : off0;
-      bf16x8 fw[2], fp[2];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) fw[j] = __builtin_bit_cast(bf16x8, *(const f32x4*)(wbase + (s_ * 32 + j * 16) * 64));
-#pragma unroll
-      for (int i = 0; i < 2; ++i) fp[i] = __builtin_bit_cast(bf16x8, *(const f32x4*)(pbase + off + i * (4 * PW * 32)));
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fp[i], acc[i][j], 0, 0, 0);
-    });
-    // D map: column lrow = pixel, rows q*4 + r = channels (+16 j): 4 consecutive channels per lane -> one 8-byte store
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int oh = oh0 + 2 * wave + i, ow = ow0 + lrow;
-      if (oh >= p.Ho || ow >= p.Wo) continue;
-      u16* const dst = p.y + ((b * p.Ho + oh) * p.Wo + ow) * p.ldy + q * 4;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { const float u = acc[i][j][r] + sh[j][r]; v[r] = u > 0.f ? u : u * p.slope; }
-        uint2 o;
-        o.x = (unsigned)to_bf16(v[0]) | ((unsigned)to_bf16(v[1]) << 16);
-        o.y = (unsigned)to_bf16(v[2]) | ((unsigned)to_bf16(v[3]) << 16);
-        *(uint2*)(dst + j * 16) = o;
-      }
-    }
-  }
-}
-// conv3 (32 -> 64 channels, stride-2 gather) in the same LDS-window form.  In the GEMM form every input pixel goes through L2 /
-// LDS 6.25 times (4.6x the algorithmic HBM bytes by the counters, 89 us at 216 tiles); here a block owns 8 x 16 output pixels,
-// stages their 19 x 35 input window ONCE (even / odd columns in separate planes so that the 16 pixels of a fragment, two input
-// columns apart, are adjacent slots; 80-byte pixel pitch: conflict-free ds_read_b128), keeps ALL 25 x 64 x 32 weights in LDS for
-// its whole life (100 KB, 16-byte pieces XOR-swizzled by the row; gather-packed bf16 weights [n][tap][c] as the GEMM has them),
-// and every tap is eight MFMAs per wave (2 pixel rows x 4 channel tiles, K = the tap's 32 channels) with both fragments at
-// base + compile-time offset: no barrier and no global access inside a tile.  157 KB of LDS: one persistent block per CU, the next
-// tile's window in flight (registers) during the current tile's MFMAs.
-struct Conv3WinArgs {
-  const u16* x; long ldx; int B, H, W;       // 32 channels at x
-  const u16* wg;                             // [64][25][32] bf16, BatchNorm scale folded in
-  const float* shift; float slope;
-  u16* y; long ldy; int Ho, Wo;              // 64 channels at y
-};
-#define CONV3_WIN_LDS (19 * 2 * 18 * 80 + 25 * 64 * 64)
-__global__ __launch_bounds__(256) void conv3_window_bf16_kernel(Conv3WinArgs p) {
-  constexpr int TH = 8, TW = 16, WR = 2 * TH + 3, WC = 2 * TW + 3, PW = TW + 2, LPB = 80;
-  constexpr int NCH = WR * WC * 4, NST = (NCH + 255) / 256;                       // 16-byte pieces of the window
-  constexpr int WIN_BYTES = WR * 2 * PW * LPB;
-  static_assert(WIN_BYTES + 25 * 64 * 64 == CONV3_WIN_LDS, "LDS size");
-  extern __shared__ __attribute__((aligned(16))) unsigned char c3_smem[];
-  unsigned char* const win = c3_smem;
-  unsigned char* const wts = c3_smem + WIN_BYTES;                                 // [tap][n][64 bytes], piece ^ ((n >> 1) & 3)
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, lrow = lane & 15, q = lane >> 4;
-  const int tiles_w = (p.Wo + TW - 1) / TW, tiles_h = (p.Ho + TH - 1) / TH;
-  const int ntiles = p.B * tiles_h * tiles_w;
-  for (int e = t; e < 25 * 64 * 4; e += 256) {                                    // global [n][tap][4 pieces]: contiguous
-    const int piece = e & 3, tap = (e >> 2) % 25, n = e / 100;
-    *(uint4*)(wts + (tap * 64 + n) * 64 + ((piece ^ ((n >> 1) & 3)) * 16)) = *(const uint4*)(p.wg + (long)e * 8);
-  }
-  float sh[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sh[j][r] = p.shift[j * 16 + q * 4 + r];
-  uint4 stage[NST];
-  auto fetch_window = [&](int tile) __attribute__((always_inline)) {
-    const int fow0 = (tile % tiles_w) * TW, foh0 = ((tile / tiles_w) % tiles_h) * TH;
-    const u16* const xb = p.x + (long)(tile / (tiles_w * tiles_h)) * p.H * p.W * p.ldx;
-#pragma unroll
-    for (int k = 0; k < NST; ++k) {
-      const int e = t + k * 256, c4 = e & 3, px = e >> 2;
-      const int wr = px / WC, wc = px - wr * WC;
-      const int ih = 2 * foh0 - 2 + wr, iw = 2 * fow0 - 2 + wc;
-      stage[k] = make_uint4(0u, 0u, 0u, 0u);
-      if (e < NCH && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) stage[k] = *(const uint4*)(xb + ((long)ih * p.W + iw) * p.ldx + c4 * 8);
-    }
-  };
-  if ((int)blockIdx.x < ntiles) fetch_window(blockIdx.x);
-  const unsigned char* const pbase = win + ((8 * wave) * PW + lrow) * LPB + q * 16;       // window row 4 wave (+ 2 i + kh), plane 0, slot lrow
+  // pixel fragment of output row 2 wave + i: window row 4 wave (+ 2 i + kh), plane 0, slot lrow
+  const unsigned char* const pbase = win + ((8 * wave) * PW + lrow) * LPB + cq * 16;
   const unsigned char* const wbase = wts + lrow * 64 + ((q ^ ((lrow >> 1) & 3)) * 16);
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int ow0 = (tile % tiles_w) * TW, oh0 = ((tile / tiles_w) % tiles_h) * TH;
-    const long b = tile / (tiles_w * tiles_h);
+    const TileAt o = tile_at(tile, tiles_h, tiles_w, TH, TW);
     __syncthreads();                                                               // the previous tile's readers are done (first tile: the weights are staged)
 #pragma unroll
     for (int k = 0; k < NST; ++k) {
-      const int e = t + k * 256, c4 = e & 3, px = e >> 2;
+      const int e = t + k * 256, c8 = e % CQ, px = e / CQ;
       const int wr = px / WC, wc = px - wr * WC;
-      if (e < NCH) *(uint4*)(win + ((wr * 2 + (wc & 1)) * PW + (wc >> 1)) * LPB + c4 * 16) = stage[k];
+      if (e < NCH) *(uint4*)(win + ((wr * 2 + (wc & 1)) * PW + (wc >> 1)) * LPB + c8 * 16) = stage[k];
     }
     if (tile + (int)gridDim.x < ntiles) fetch_window(tile + gridDim.x);
     __syncthreads();
-    f32x4 acc[2][4];
+    f32x4 acc[2][TNJ];                                                             // [pixel row i][channel tile j]
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    svs_static_for<25>([&](auto tc) {
-      constexpr int tap = decltype(tc)::value, kh = tap / 5, kw = tap % 5;
-      bf16x8 fw[4], fp[2];
+      for (int j = 0; j < TNJ; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    svs_static_for<NS>([&](auto sc) {
+      constexpr int s_ = decltype(sc)::value;
+      constexpr int tap0 = TPS * s_, tap1 = (tap0 + 1 < 25) ? tap0 + 1 : 24;       // (the 26th tap has zero weights: any finite data)
+      constexpr int off0 = (((tap0 / 5) * 2 + ((tap0 % 5) & 1)) * PW + ((tap0 % 5) >> 1)) * LPB;
+      constexpr int off1 = (((tap1 / 5) * 2 + ((tap1 % 5) & 1)) * PW + ((tap1 % 5) >> 1)) * LPB;
+      const int off = (TPS == 2 && tsel) ? off1 : off0;
+      bf16x8 fw[TNJ], fp[2];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) fw[j] = __builtin_bit_cast(bf16x8, *(const f32x4*)(wbase + (tap * 64 + j * 16) * 64));
+      for (int j = 0; j < TNJ; ++j) fw[j] = __builtin_bit_cast(bf16x8, *(const f32x4*)(wbase + (s_ * N + j * 16) * 64));
 #pragma unroll
-      for (int i = 0; i < 2; ++i) fp[i] = __builtin_bit_cast(bf16x8, *(const f32x4*)(pbase + (((2 * i + kh) * 2 + (kw & 1)) * PW + (kw >> 1)) * LPB));
+      for (int i = 0; i < 2; ++i) fp[i] = __builtin_bit_cast(bf16x8, *(const f32x4*)(pbase + off + i * (4 * PW * LPB)));
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fp[i], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < TNJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fp[i], acc[i][j], 0, 0, 0);
     });
     // D map: column lrow = pixel, rows q*4 + r = channels (+16 j): 4 consecutive channels per lane -> one 8-byte store
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int oh = oh0 + 2 * wave + i, ow = ow0 + lrow;
+      const int oh = o.h0 + 2 * wave + i, ow = o.w0 + lrow;
       if (oh >= p.Ho || ow >= p.Wo) continue;
-      u16* const dst = p.y + ((b * p.Ho + oh) * p.Wo + ow) * p.ldy + q * 4;
+      u16* const dst = p.y + ((o.b * p.Ho + oh) * p.Wo + ow) * p.ldy + q * 4;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { const float u = acc[i][j][r] + sh[j][r]; v[r] = u > 0.f ? u : u * p.slope; }
-        uint2 o;
-        o.x = (unsigned)to_bf16(v[0]) | ((unsigned)to_bf16(v[1]) << 16);
-        o.y = (unsigned)to_bf16(v[2]) | ((unsigned)to_bf16(v[3]) << 16);
-        *(uint2*)(dst + j * 16) = o;
-      }
+      for (int j = 0; j < TNJ; ++j) store_act_bf16x4(dst + j * 16, acc[i][j], sh[j], p.slope);
     }
   }
 }
-
-// wk[s][n][k]: k = t2*16 + c holds scale[n] * W[n][tap = 2s + t2][c] (zero for the 26th tap), from the gather-packed fp32 weights [n][25][16]
-__global__ void conv2_pack_kernel(const float* __restrict__ wp, const float* __restrict__ scale, u16* __restrict__ wk) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 13 * 32 * 32) return;
-  const int k = i & 31, n = (i >> 5) & 31, s_ = i >> 10;
-  const int tap = 2 * s_ + (k >> 4), c = k & 15;
-  wk[i] = tap < 25 ? to_bf16(wp[(n * 25 + tap) * 16 + c] * scale[n]) : (u16)0;
+// wk[s][n][k]: k = t2 * C + c holds scale[n] * W[n][tap = (32 / C) s + t2][c] (zero past the 25th tap), from the gather-packed fp32
+// weights [n][25][C]
+__global__ void gather_window_pack_kernel(const float* __restrict__ wp, const float* __restrict__ scale, u16* __restrict__ wk, int C) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, N = 2 * C;
+  if (i >= gw_steps(C) * N * 32) return;
+  const int k = i & 31, n = (i >> 5) % N, s_ = i / (32 * N);
+  const int tap = (32 / C) * s_ + k / C, c = k % C;
+  wk[i] = tap < 25 ? to_bf16(wp[(n * 25 + tap) * C + c] * scale[n]) : (u16)0;
+}
+template <int C>
+static int launch_gather_window_bf16(const GatherWinArgs& a, hipStream_t stream) {
+  const long tiles = (long)a.B * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);
+  SVS_HIP(hipFuncSetAttribute((const void*)gather_window_bf16_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, gw_lds(C)));
+  hipLaunchKernelGGL(gather_window_bf16_kernel<C>, dim3((unsigned)(tiles < gw_max_blocks(C) ? tiles : gw_max_blocks(C))), dim3(256), gw_lds(C), stream, a);
+  SVS_CHECK_LAUNCH("gather_window_bf16");
+  return SVS_OK;
 }
 
 // deconv6 + sigmoid (model.py:109,198-200): 32 bf16 channels -> 1 fp32 channel, on the MFMA.  One output channel is no GEMM
@@ -758,19 +662,17 @@ __global__ __launch_bounds__(256) void deconv6_mfma_bf16_kernel(Deconv6Args p) {
   }
   uint4 stage[NST];
   auto fetch_window = [&](int tile) __attribute__((always_inline)) {
-    const int ftw0 = (tile % tiles_w) * TW, fth0 = ((tile / tiles_w) % tiles_h) * TH;
-    const int fb_ = tile / (tiles_w * tiles_h);
-    const int soff = __builtin_amdgcn_readfirstlane((int)((((long)fb_ * p.H + fth0) * p.W + ftw0) * p.ldx * 2));
+    const TileAt f = tile_at(tile, tiles_h, tiles_w, TH, TW);
+    const int soff = __builtin_amdgcn_readfirstlane((int)(((f.b * p.H + f.h0) * p.W + f.w0) * p.ldx * 2));
 #pragma unroll
     for (int k = 0; k < NST; ++k) {
-      const bool ok = (unsigned)(fth0 - 1 + s_lh[k]) < (unsigned)p.H && (unsigned)(ftw0 - 1 + s_lw[k]) < (unsigned)p.W;
+      const bool ok = (unsigned)(f.h0 - 1 + s_lh[k]) < (unsigned)p.H && (unsigned)(f.w0 - 1 + s_lw[k]) < (unsigned)p.W;
       stage[k] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(ok ? s_rel[k] : OOB), soff, 0));
     }
   };
   if ((int)blockIdx.x < ntiles) fetch_window(blockIdx.x);
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int tw0 = (tile % tiles_w) * TW, th0 = ((tile / tiles_w) % tiles_h) * TH;
-    const long b = tile / (tiles_w * tiles_h);
+    const TileAt o = tile_at(tile, tiles_h, tiles_w, TH, TW);
     __syncthreads();                                               // the previous tile's readers are done
 #pragma unroll
     for (int k = 0; k < NST; ++k)
@@ -800,8 +702,8 @@ __global__ __launch_bounds__(256) void deconv6_mfma_bf16_kernel(Deconv6Args p) {
       v = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, a3), 0x11C, 0xF, 0x8, false));   // row_shr:12 -> lanes 12..15
       v = 1.f / (1.f + __expf(-(v + bias)));
       const int par = lrow & 3, an = q * 4 + (lrow >> 2);
-      const int oh = 2 * (th0 + ah) + (par >> 1), ow = 2 * (tw0 + an) + (par & 1);
-      if (th0 + ah < p.H && tw0 + an < p.W && oh < p.Ho && ow < p.Wo) p.y[(b * p.Ho + oh) * p.Wo + ow] = v;
+      const int oh = 2 * (o.h0 + ah) + (par >> 1), ow = 2 * (o.w0 + an) + (par & 1);
+      if (o.h0 + ah < p.H && o.w0 + an < p.W && oh < p.Ho && ow < p.Wo) p.y[(o.b * p.Ho + oh) * p.Wo + ow] = v;
     }
   }
 }
@@ -819,14 +721,12 @@ __global__ void deconv6_pack_kernel(const float* __restrict__ w, u16* __restrict
 }
 
 // packed fp32 weights (gather [n][25][c] or parity [class][n][taps][c]) times the folded BatchNorm scale of output channel n
-// -> bf16.  cpad > c: the channels are placed at [cpad - c, cpad) of a cpad-wide K row and the rest is zero (conv2 reads the
-// interleaved 32-channel level 1 with zero weights on the decoder half).
+// -> bf16, same layout
 __global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict__ wp, const float* __restrict__ scale, u16* __restrict__ out,
-                                                        int N, int C, int cpad, int parity) {
-  const long total = (long)N * cpad * 25;
+                                                        int N, int C, int parity) {
+  const long total = (long)N * C * 25;
   for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long)gridDim.x * 256) {
-    const int c = (int)(o % cpad);
-    const long r = o / cpad;                                  // (class, n, tap) flattened as in the fp32 packing
+    const long r = o / C;                                     // (class, n, tap) flattened as in the fp32 packing
     int n;
     if (!parity) n = (int)(r / 25);
     else {
@@ -835,8 +735,7 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict_
       if (rr >= 9 * NC) { rr -= 9 * NC; ntaps = 6; if (rr >= 6 * NC) { rr -= 6 * NC; if (rr >= 6 * NC) { rr -= 6 * NC; ntaps = 4; } } }
       n = (int)(rr / ntaps);
     }
-    const int cs = c - (cpad - C);
-    out[o] = cs >= 0 ? to_bf16(wp[r * C + cs] * scale[n]) : (u16)0;
+    out[o] = to_bf16(wp[o] * scale[n]);
   }
 }
 
@@ -845,10 +744,14 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict_
 // (whenever its tiles fill the chip), else the GEMM.  The GEMM tile and its K-split are planned for every layer: SVS_CONV_WINDOW=0
 // selects that form at any launch, so the workspace is sized for it.
 enum { BF16_GEMM, BF16_WINDOW };
+// The kernels a plan can name, stated once: plan_bf16, the launches and svs_conv_bf16_describe all expand these two lists.
+// conv_gemm_bf16_kernel<MODE, BM, BN, WM, WN, KB> by plan cfg (two K-tiles per barrier where the tile is 64 or 128 columns wide) ...
+#define BF16_GEMM_TILES(X) X(0, 128, 128, 2, 2, 2) X(1, 128, 64, 2, 2, 2) X(2, 256, 32, 4, 1, 1) X(3, 256, 16, 4, 1, 1) X(4, 64, 128, 2, 2, 2)
+// ... and parity_window_bf16_kernel<C, TN, TW> by input channels (deconv4, deconv5, deconv3)
+#define BF16_WINDOW_SHAPES(X) X(128, 2, 16) X(64, 1, 16) X(256, 4, 8)
 struct Bf16Plan {
   int kind;
-  int wC, wTN, wTW;               // parity_window_bf16_kernel<C, TN, TW>
-  size_t lds;                     // its dynamic LDS
+  int wC;                         // BF16_WINDOW: the shape of BF16_WINDOW_SHAPES with this C
   int BM, BN, cfg, ksplit, grid_y; long mtiles;
   dim3 grid;
   size_t slab_bytes;              // the GEMM form's split-K slabs
@@ -863,16 +766,15 @@ static Bf16Plan plan_bf16(int mode, int B, int H, int W, int C, int Ho, int Wo, 
   Bf16Plan pl{};
   const long Mmax = mode == BF_GATHER ? (long)B * Ho * Wo : (long)B * ((Ho + 1) / 2) * ((Wo + 1) / 2);
   const int nkt = (mode == BF_GATHER ? 25 : 4) * (C / 32);
-  if (N % 128 == 0) { pl.cfg = Mmax >= 4096 ? 0 : 4; pl.BM = Mmax >= 4096 ? 128 : 64; pl.BN = 128; }
-  else if (N == 64) { pl.cfg = 1; pl.BM = 128; pl.BN = 64; }
-  else if (N == 32) { pl.cfg = 2; pl.BM = 256; pl.BN = 32; }
-  else { pl.cfg = 3; pl.BM = 256; pl.BN = 16; }
+  pl.cfg = N % 128 == 0 ? (Mmax >= 4096 ? 0 : 4) : N == 64 ? 1 : N == 32 ? 2 : 3;
   if (svs_tune_on(SVS_TUNE_BF16_CFG)) {                       // sweeps: 0 128x128, 1 128x64, 4 64x128 (where N allows)
     const int c = (int)svs_tune(SVS_TUNE_BF16_CFG);
-    if (c == 0 && N % 128 == 0) { pl.cfg = 0; pl.BM = 128; pl.BN = 128; }
-    if (c == 1 && N % 64 == 0) { pl.cfg = 1; pl.BM = 128; pl.BN = 64; }
-    if (c == 4 && N % 128 == 0) { pl.cfg = 4; pl.BM = 64; pl.BN = 128; }
+    if ((c == 0 || c == 4) && N % 128 == 0) pl.cfg = c;
+    if (c == 1 && N % 64 == 0) pl.cfg = 1;
   }
+#define X(cfg_, BM_, BN_, WM_, WN_, KB_) if (pl.cfg == cfg_) { pl.BM = BM_; pl.BN = BN_; }
+  BF16_GEMM_TILES(X)
+#undef X
   pl.mtiles = (Mmax + pl.BM - 1) / pl.BM;
   pl.grid_y = mode == BF_PARITY ? 4 : 1;
   const long blocks = pl.mtiles * (N / pl.BN) * pl.grid_y;
@@ -892,7 +794,7 @@ static Bf16Plan plan_bf16(int mode, int B, int H, int W, int C, int Ho, int Wo, 
   // deconv4 / deconv5 on 8 x 16 tiles, persistent: two blocks per CU
   const long wtiles = (long)B * ((H + 7) / 8) * ((W + 15) / 16);
   if (((C == 128 && N == 32) || (C == 64 && N == 16)) && H >= 8 && W >= 16 && wtiles >= 128) {
-    pl.kind = BF16_WINDOW; pl.wC = C; pl.wTN = N / 16; pl.wTW = 16;
+    pl.kind = BF16_WINDOW; pl.wC = C;
     pl.grid = dim3((unsigned)(wtiles < 512 ? wtiles : 512));
   }
   // deconv3 (256 -> 64 channels on 32 x 8 anchors): the same kernel on 16 x 8 tiles.  In the GEMM form 1 GB goes from L2 to LDS
@@ -900,10 +802,9 @@ static Bf16Plan plan_bf16(int mode, int B, int H, int W, int C, int Ho, int Wo, 
   // 106 us; here the window is staged once and only the weights (819 KB per tile) stream.
   const long wtiles8 = (long)B * ((H + 15) / 16) * ((W + 7) / 8);
   if (C == 256 && N == 64 && W <= 8 && wtiles8 >= 128) {
-    pl.kind = BF16_WINDOW; pl.wC = 256; pl.wTN = 4; pl.wTW = 8;
+    pl.kind = BF16_WINDOW; pl.wC = C;
     pl.grid = dim3((unsigned)(wtiles8 < 256 ? wtiles8 : 256));
   }
-  if (pl.kind == BF16_WINDOW) pl.lds = pw_lds(pl.wC, N, pl.wTW);
   return pl;
 }
 // (ldx = C: the stride enters the plan only through a 2 GiB guard, which conv_bf16_run's own limit on the view implies)
@@ -912,32 +813,32 @@ static size_t bf16_layer_ws(int mode, int B, int H, int W, int C, int Ho, int Wo
 }
 template <int C, int TN, int TW>
 static int launch_window_bf16(const ConvBf16Args& a, const Bf16Plan& pl, hipStream_t stream) {
-  SVS_HIP(hipFuncSetAttribute((const void*)parity_window_bf16_kernel<C, TN, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
-  hipLaunchKernelGGL((parity_window_bf16_kernel<C, TN, TW>), pl.grid, dim3(256), pl.lds, stream, a);
+  const size_t lds = pw_lds(C, TN * 16, TW);
+  SVS_HIP(hipFuncSetAttribute((const void*)parity_window_bf16_kernel<C, TN, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((parity_window_bf16_kernel<C, TN, TW>), pl.grid, dim3(256), lds, stream, a);
+  SVS_CHECK_LAUNCH("parity_window_bf16");
   return SVS_OK;
 }
 // svs_describe_plan kinds 3 / 4: the kernel plan_bf16 picks, named as rocprofv3 prints it, and its K-split (host arithmetic only)
 int svs_conv_bf16_describe(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, char* buf, size_t n) {
-  static const int TILE[5][5] = {{128, 128, 2, 2, 2}, {128, 64, 2, 2, 2}, {256, 32, 4, 1, 1}, {256, 16, 4, 1, 1}, {64, 128, 2, 2, 2}};   // launch_gemm_bf16's cases
   if (B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || C % 32 || !(N == 16 || N == 32 || N == 64 || (N > 0 && N % 128 == 0))) {
     svs_set_error("svs_describe_plan: no bf16 layer has B=%d %dx%d C=%d -> %dx%d N=%d", B, H, W, C, Ho, Wo, N);
     return SVS_ERR_INVALID;
   }
   const Bf16Plan pl = plan_bf16(mode, B, H, W, C, Ho, Wo, N, C);
-  if (pl.kind == BF16_WINDOW) { snprintf(buf, n, "parity_window_bf16_kernel<%d, %d, %d>", pl.wC, pl.wTN, pl.wTW); return 1; }
-  const int* t = TILE[pl.cfg];
-  snprintf(buf, n, "conv_gemm_bf16_kernel<%d, %d, %d, %d, %d, %d>", mode, t[0], t[1], t[2], t[3], t[4]);
+#define X(C_, TN_, TW_) if (pl.kind == BF16_WINDOW && pl.wC == C_) { snprintf(buf, n, "parity_window_bf16_kernel<%d, %d, %d>", C_, TN_, TW_); return 1; }
+  BF16_WINDOW_SHAPES(X)
+#undef X
+#define X(cfg_, BM_, BN_, WM_, WN_, KB_) if (pl.cfg == cfg_) snprintf(buf, n, "conv_gemm_bf16_kernel<%d, %d, %d, %d, %d, %d>", mode, BM_, BN_, WM_, WN_, KB_);
+  BF16_GEMM_TILES(X)
+#undef X
   return pl.ksplit;
 }
 template <int MODE>
 static void launch_gemm_bf16(const ConvBf16Args& a, const Bf16Plan& pl, hipStream_t stream) {
-  switch (pl.cfg) {        // two K-tiles per barrier where the tile is 64 or 128 columns wide
-    case 0: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE, 128, 128, 2, 2, 2>), pl.grid, dim3(256), 0, stream, a); break;
-    case 1: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE, 128, 64, 2, 2, 2>), pl.grid, dim3(256), 0, stream, a); break;
-    case 2: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE, 256, 32, 4, 1, 1>), pl.grid, dim3(256), 0, stream, a); break;
-    case 3: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE, 256, 16, 4, 1, 1>), pl.grid, dim3(256), 0, stream, a); break;
-    default: hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE, 64, 128, 2, 2, 2>), pl.grid, dim3(256), 0, stream, a); break;
-  }
+#define X(cfg_, BM_, BN_, WM_, WN_, KB_) if (pl.cfg == cfg_) hipLaunchKernelGGL((conv_gemm_bf16_kernel<MODE, BM_, BN_, WM_, WN_, KB_>), pl.grid, dim3(256), 0, stream, a);
+  BF16_GEMM_TILES(X)
+#undef X
 }
 static int conv_bf16_run(int mode, const u16* x, long ldx, int B, int H, int W, int C, const u16* wp, const float* shift, float slope,
                          u16* y, long ldy, int Ho, int Wo, int N, void* ws, size_t ws_bytes, hipStream_t stream) {
@@ -947,12 +848,9 @@ static int conv_bf16_run(int mode, const u16* x, long ldx, int B, int H, int W, 
   ConvBf16Args a{x, ldx, B, H, W, C, wp, shift, slope, y, ldy, Ho, Wo, N, pl.ksplit, nullptr};
   if (pl.kind == BF16_WINDOW) {
     a.ksplit = 1;
-    int rc = pl.wC == 128 ? launch_window_bf16<128, 2, 16>(a, pl, stream)
-           : pl.wC == 64  ? launch_window_bf16<64, 1, 16>(a, pl, stream)
-                          : launch_window_bf16<256, 4, 8>(a, pl, stream);
-    if (rc) return rc;
-    SVS_CHECK_LAUNCH("parity_window_bf16");
-    return SVS_OK;
+#define X(C_, TN_, TW_) if (pl.wC == C_) return launch_window_bf16<C_, TN_, TW_>(a, pl, stream);
+    BF16_WINDOW_SHAPES(X)
+#undef X
   }
   if (pl.ksplit > 1) {
     if (!ws || ws_bytes < pl.slab_bytes) { svs_set_error("conv_bf16: workspace too small (%zu < %zu)", ws_bytes, pl.slab_bytes); return SVS_ERR_WORKSPACE; }
@@ -972,13 +870,13 @@ static int conv_bf16_run(int mode, const u16* x, long ldx, int B, int H, int W, 
 }
 
 // ---- whole network (described in unet_desc.h) ------------------------------------------------------
-struct Bf16Prepared { long w[12], shift[11], w1, w2k, w6, bias6, total; };          // byte offsets into the prepared blob
+struct Bf16Prepared { long w[12], shift[11], w1, wk[2], w6, bias6, total; };        // byte offsets into the prepared blob
 static Bf16Prepared bf16_prepared_layout() {
   Bf16Prepared L{};
   Arena a{};
   L.w1 = a.skip(16 * 32 * 2);                                  // conv1: bf16 [16 n][32 taps (25 used)], scale folded
-  for (int l = 2; l <= 10; ++l) L.w[l] = a.skip(param_numel(4 * l) * 2);    // conv3..deconv5 (conv2 has its own form: w2k)
-  L.w2k = a.skip(13 * 32 * 32 * 2);                            // conv2, window kernel: bf16 [13 steps][32 n][2 taps x 16 channels]
+  for (int k = 0; k < 2; ++k) L.wk[k] = a.skip(gw_steps(16 << k) * (32 << k) * 32 * 2);      // conv2, conv3 (window kernel): bf16 [steps][N][32 k]
+  for (int l = 3; l <= 10; ++l) L.w[l] = a.skip(param_numel(4 * l) * 2);    // conv4..deconv5
   L.w6 = a.skip(9 * 16 * 32 * 2);                              // deconv6: bf16 [9 positions][16 columns (4 parities used)][32 channels]
   for (int l = 0; l < 11; ++l) L.shift[l] = a.skip(bn_channels(l) * 4);
   L.bias6 = a.skip(4);
@@ -996,13 +894,17 @@ extern "C" int svs_unet_prepare_eval_bf16(const void* prepared_f32, void* prepar
   const float* blob = (const float*)prepared_f32;
   hipLaunchKernelGGL(conv1_pack_kernel, dim3(2), dim3(256), 0, stream, blob + F.wp[0], blob + F.scale[0], (u16*)(out + L.w1));
   SVS_CHECK_LAUNCH("conv1_pack");
-  for (int l = 2; l <= 10; ++l) {
+  for (int k = 0; k < 2; ++k) {                                // conv2, conv3 = layers 1, 2
+    const int C = 16 << k;
+    hipLaunchKernelGGL(gather_window_pack_kernel, dim3((gw_steps(C) * 2 * C * 32 + 255) / 256), dim3(256), 0, stream, blob + F.wp[1 + k],
+                       blob + F.scale[1 + k], (u16*)(out + L.wk[k]), C);
+    SVS_CHECK_LAUNCH("gather_window_pack");
+  }
+  for (int l = 3; l <= 10; ++l) {
     const Layer& D = LAYERS[l];
-    hipLaunchKernelGGL(pack_bf16_kernel, dim3(512), dim3(256), 0, stream, blob + F.wp[l], blob + F.scale[l], (u16*)(out + L.w[l]), D.N, D.C, D.C, (int)D.up);
+    hipLaunchKernelGGL(pack_bf16_kernel, dim3(512), dim3(256), 0, stream, blob + F.wp[l], blob + F.scale[l], (u16*)(out + L.w[l]), D.N, D.C, (int)D.up);
     SVS_CHECK_LAUNCH("pack_bf16");
   }
-  hipLaunchKernelGGL(conv2_pack_kernel, dim3(52), dim3(256), 0, stream, blob + F.wp[1], blob + F.scale[1], (u16*)(out + L.w2k));
-  SVS_CHECK_LAUNCH("conv2_pack");
   hipLaunchKernelGGL(deconv6_pack_kernel, dim3(18), dim3(256), 0, stream, blob + F.wp[11], (u16*)(out + L.w6));
   SVS_CHECK_LAUNCH("deconv6_pack");
   SVS_HIP(hipMemcpyAsync(out + L.bias6, blob + F.bias6, 4, hipMemcpyDeviceToDevice, stream));
@@ -1054,29 +956,21 @@ extern "C" int svs_unet_forward_eval_bf16(const void* prepared_bf16, const float
   auto SH = [&](int l) { return (const float*)(blob + L.shift[l]); };
   // encoder (model.py:176-181): conv_k writes the skip half of level k and reads the skip half of level k - 1 (cat_half: levels
   // 2..5 interleaved, level 1 planar -- interleaved, each producer wrote, and conv2 read, 32 bytes of every 64, i.e. half of every
-  // HBM burst: conv1 72 us for 170 MB at 216 tiles).  conv1 and conv2 have kernels of their own (1 and 16 input channels)
-  const HalfView<u16> skip1 = cat_half(e.cat, g, 1, 1), skip2 = cat_half(e.cat, g, 2, 1);
+  // HBM burst: conv1 72 us for 170 MB at 216 tiles).  conv1 has a kernel of its own (1 input channel), conv2 and conv3 the
+  // LDS-window kernel, conv4 .. conv6 the GEMM
+  const HalfView<u16> skip1 = cat_half(e.cat, g, 1, 1);
   {
     Conv1Args c{mix, B, H, W, (const u16*)(blob + L.w1), SH(0), 0.2f, skip1.p, skip1.ld, g.h[1], g.w[1]};
     const long tiles = (long)B * ((g.h[1] + 15) / 16) * ((g.w[1] + 31) / 32);
     hipLaunchKernelGGL(conv1_mfma_bf16_kernel, dim3((unsigned)(tiles < 2048 ? tiles : 2048)), dim3(256), 0, stream, c);      // persistent: 8 blocks per CU
     SVS_CHECK_LAUNCH("conv1_mfma_bf16");
   }
-  {
-    Conv2WinArgs c{skip1.p, skip1.ld, B, g.h[1], g.w[1], (const u16*)(blob + L.w2k), SH(1), 0.2f, skip2.p, skip2.ld, g.h[2], g.w[2]};
-    const long tiles = (long)B * ((g.h[2] + 7) / 8) * ((g.w[2] + 15) / 16);
-    hipLaunchKernelGGL(conv2_window_bf16_kernel, dim3((unsigned)(tiles < 768 ? tiles : 768)), dim3(256), 0, stream, c);
-    SVS_CHECK_LAUNCH("conv2_window_bf16");
-  }
-  for (int k = 3; k <= 6; ++k) {
+  for (int k = 2; k <= 6; ++k) {
     const HalfView<u16> xi = cat_half(e.cat, g, k - 1, 1);
     const HalfView<u16> yo = k == 6 ? HalfView<u16>{e.c6, CH[6]} : cat_half(e.cat, g, k, 1);
-    if (k == 3) {                                                       // LDS-window form
-      Conv3WinArgs c{xi.p, xi.ld, B, g.h[2], g.w[2], (const u16*)(blob + L.w[2]), SH(2), 0.2f, yo.p, yo.ld, g.h[3], g.w[3]};
-      const long tiles = (long)B * ((g.h[3] + 7) / 8) * ((g.w[3] + 15) / 16);
-      SVS_HIP(hipFuncSetAttribute((const void*)conv3_window_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CONV3_WIN_LDS));
-      hipLaunchKernelGGL(conv3_window_bf16_kernel, dim3((unsigned)(tiles < 256 ? tiles : 256)), dim3(256), CONV3_WIN_LDS, stream, c);
-      SVS_CHECK_LAUNCH("conv3_window_bf16");
+    if (k <= 3) {                                                       // LDS-window form
+      const GatherWinArgs c{xi.p, xi.ld, B, g.h[k - 1], g.w[k - 1], (const u16*)(blob + L.wk[k - 2]), SH(k - 1), 0.2f, yo.p, yo.ld, g.h[k], g.w[k]};
+      if ((rc = k == 2 ? launch_gather_window_bf16<16>(c, stream) : launch_gather_window_bf16<32>(c, stream))) return rc;
       continue;
     }
     if ((rc = conv_bf16_run(BF_GATHER, xi.p, xi.ld, B, g.h[k - 1], g.w[k - 1], CH[k - 1], (const u16*)(blob + L.w[k - 1]), SH(k - 1), 0.2f, yo.p, yo.ld,

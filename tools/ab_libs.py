@@ -7,6 +7,7 @@ ONE device (devices differ by up to ~12%, so numbers from different gpurun calls
 --full-step times instead the whole full-objective training pass (svs_unet_train_fwd_loss_mr + svs_unet_train_bwd_part: forward,
 L1 + MR-STFT losses, backward; no Adam) on 512 x 128 tiles at hop 768, alternating the two libraries round by round, and
 prints one JSON line.  Give it two builds of the SAME commit first: the B/A it prints for them is the spread of the harness.
+--eval-bf16 [--hw H W] does the same for the bf16 eval forward (svs_unet_forward_eval_bf16) and compares every layer's output bitwise.
 """
 import argparse
 import ctypes
@@ -26,7 +27,9 @@ DEC = ((512, 256), (512, 128), (256, 64), (128, 32), (64, 16))
 def load(path):
     h = ctypes.CDLL(os.path.abspath(path))
     for name in ("svs_enc_block_fwd", "svs_dec_block_fwd", "svs_enc_block_bwd_weight", "svs_unet_train_fwd_loss_mr", "svs_unet_train_bwd_part",
-                 "svs_unet_train_workspace_bytes", "svs_unet_train_mr_workspace_bytes"):
+                 "svs_unet_train_workspace_bytes", "svs_unet_train_mr_workspace_bytes", "svs_unet_prepared_bytes", "svs_unet_prepare_eval",
+                 "svs_unet_prepared_bf16_bytes", "svs_unet_prepare_eval_bf16", "svs_unet_eval_bf16_workspace_bytes",
+                 "svs_unet_forward_eval_bf16", "svs_unet_ws_offset"):
         fn = getattr(h, name)
         fn.restype, fn.argtypes = _lib._SIGS[name]
     return h
@@ -82,6 +85,53 @@ def full_step(libs, B, rounds=7, reps=10):
                       "grads_bitwise_equal": bool(torch.equal(out[0][0], out[1][0])), "losses_bitwise_equal": bool(torch.equal(out[0][1], out[1][1]))}))
 
 
+def eval_bf16(libs, B, H, W, rounds=7, reps=10):
+    """Best-of-`rounds` ms of svs_unet_forward_eval_bf16 per library, the libraries taking turns inside every round.  Each library
+    prepares the closed-form checkpoint itself and runs on the same seeded input into a sentinel-filled workspace; the workspace
+    from its start to the end of c6 (every layer's bf16 output) and the mask are compared bitwise."""
+    import json
+
+    import numpy as np
+
+    from svs_unet_pytorch_amd import synth
+    from svs_unet_pytorch_amd.model import UNet
+    dev = "cuda"
+    model = UNet()
+    model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.closed_form_state().items()})
+    model.to(dev).eval()
+    mix = torch.rand((B, 1, H, W), device=dev, generator=torch.Generator(dev).manual_seed(0))
+    h6, w6 = H, W
+    for _ in range(6):
+        h6, w6 = (h6 + 1) // 2, (w6 + 1) // 2
+    S = _lib.stream_ptr
+    runs, out = [], []
+    for Lb in libs:
+        f32 = torch.empty(int(Lb.svs_unet_prepared_bytes()), dtype=torch.uint8, device=dev)
+        blob = torch.empty(int(Lb.svs_unet_prepared_bf16_bytes()), dtype=torch.uint8, device=dev)
+        rc = Lb.svs_unet_prepare_eval(model._flat.data_ptr(), model._bn_flat.data_ptr(), f32.data_ptr(), S())
+        rc = rc or Lb.svs_unet_prepare_eval_bf16(f32.data_ptr(), blob.data_ptr(), S())
+        assert rc == 0, rc
+        nbytes = int(Lb.svs_unet_eval_bf16_workspace_bytes(B, H, W))
+        ws = torch.full((nbytes // 2,), 0x7FC1, dtype=torch.int16, device=dev)          # a bf16 NaN no kernel computes
+        mask = torch.full_like(mix, float("nan"))
+        span = Lb.svs_unet_ws_offset(b"c6", B, H, W, 2) + 2 * B * h6 * w6 * CH[6]
+
+        def run(Lb=Lb, blob=blob, ws=ws, mask=mask, nbytes=nbytes):
+            rc = Lb.svs_unet_forward_eval_bf16(blob.data_ptr(), mix.data_ptr(), mask.data_ptr(), B, H, W, ws.data_ptr(), nbytes, S())
+            assert rc == 0, rc
+        runs.append(run)
+        run()
+        torch.cuda.synchronize()
+        out.append((ws[:span // 2].clone(), mask.clone()))
+    best = [1e9, 1e9]
+    for _ in range(rounds):
+        for i, r in enumerate(runs):
+            best[i] = min(best[i], timeit(r, reps))
+    print(json.dumps({"what": f"bf16 eval forward, H={H} W={W}", "batch": B, "ms_A": round(best[0], 4), "ms_B": round(best[1], 4),
+                      "B_over_A": round(best[1] / best[0], 4), "workspace_bitwise_equal": bool(torch.equal(out[0][0], out[1][0])),
+                      "mask_bitwise_equal": bool(torch.equal(out[0][1], out[1][1]))}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("lib_a")
@@ -89,11 +139,15 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--wgrad", action="store_true")
     ap.add_argument("--full-step", action="store_true")
+    ap.add_argument("--eval-bf16", action="store_true")
+    ap.add_argument("--hw", type=int, nargs=2, default=(512, 128), metavar=("H", "W"), help="tile size of --eval-bf16")
     a = ap.parse_args()
     torch.zeros(1, device="cuda")
     libs = [load(a.lib_a), load(a.lib_b)]
     if a.full_step:
         return full_step(libs, a.batch)
+    if a.eval_bf16:
+        return eval_bf16(libs, a.batch, *a.hw)
     B, dev = a.batch, "cuda"
     hw = [(512, 128)]
     for _ in range(6):
