@@ -501,6 +501,36 @@ int svs_resample_encode(const float* x, int channels, int64_t n_in, int64_t ld_i
                         const float* gain /* [channels] device, nullable */, int out_fmt /* SVS_PCM_* */,
                         void* out /* svs_resample_out_len(n_in, up, down) x channels, interleaved */, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Overlapped tiles with cross-faded masks (csrc/overlap.hip).  inference.py:72-120 cuts a spectrogram into disjoint seg-frame
+ * tiles, so the frames at a tile's edges see zero padding in place of their neighbours; here overlapped tile j of a channel
+ * covers frames [j * tile_hop, j * tile_hop + seg), each goes through the network alone, and the masks are cross-faded back.
+ * Rules, checked before any launch: all sizes positive; seg % 4 == 0, tile_hop % 4 == 0, seg % tile_hop == 0 and
+ * seg / tile_hop <= 8; n_tiles * seg < 2^31 (a frame index is an int; every other index is 64-bit); channel strides at least
+ * n_tiles * rows * seg and multiples of 4 floats; pointers non-null (except mix) and 16-byte aligned.  tile_hop == seg is legal: both kernels are then copies, bit for bit.
+ * svs_overlap_count is host-only (inference.py:72-120's n_tiles disjoint tiles -> overlapped tiles that cover them):
+ *   (n_tiles - 1) * (seg / tile_hop) + 1, the last overlapped tile being the last disjoint tile; -1 + error on bad arguments. */
+int svs_overlap_count(int n_tiles, int seg, int tile_hop);
+/* inference.py:72-120 with overlap, the way in.  tiles: the standard tile addressing of svs_stft_tiles,
+ *   (channel c, row r, frame t) = tiles[c*chan_stride + ((t/seg)*rows + r)*seg + t%seg],   t < n_tiles*seg.
+ * out: (channels * n_ov, rows, seg) contiguous, n_ov = svs_overlap_count; overlapped tile j of a channel = frames
+ * [j*tile_hop, j*tile_hop + seg).  A streaming copy: one thread moves 4 frames of one row as one 16-byte load and store. */
+int svs_overlap_tiles(const float* tiles, int64_t chan_stride, int channels, int n_tiles, int rows, int seg, int tile_hop,
+                      float* out, hipStream_t stream);
+/* inference.py:72-120 with overlap, the way out.  masks: (channels * n_ov, rows, seg), the network's output for
+ * svs_overlap_tiles' tiles.  For every frame t of every channel and row
+ *   b(t) = sum_j w[t - j*tile_hop] * masks[j][t - j*tile_hop] / sum_j w[t - j*tile_hop]   over the j with 0 <= t - j*tile_hop < seg,
+ *   w[i] = sin^2(pi * (i + 0.5) / seg)  (strictly positive; for tile_hop = seg/2 the interior weights sum to 1),
+ * summed in ascending j in fp32 (num = fmaf(w, m, num); den += w; one division).  w is computed in double and rounded once.
+ * A frame that exactly one tile covers takes that tile's mask value unchanged (no multiply, no divide).
+ * mix == NULL: out = b (invert != 0: 1 - b).  mix given (same addressing as out, with mix_chan_stride): out = mix * b or
+ * mix * (1 - b), with svs_apply_mask's expressions (inference.py:100-107).
+ * out: standard tile addressing with out_chan_stride, so it can be handed to svs_istft_tiles_n / svs_istft_stems_n as `mask`
+ * unchanged.  No atomics; bitwise reproducible.  The first call of a process for a seg that cross-fades (tile_hop < seg
+ * and n_tiles > 1) uploads w (seg floats, kept per device) and must run outside a stream capture. */
+int svs_overlap_blend(const float* masks, int channels, int n_tiles, int rows, int seg, int tile_hop, const float* mix,
+                      int64_t mix_chan_stride, int invert, float* out, int64_t out_chan_stride, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(HERE, "libsvs_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "svs_hip.h")
 
+# the one handle lib() returns.  tools/ab_libs.py --separate swaps it between two builds bound with _SIGS; nothing in the package may
+# keep a copy of the handle (call lib() each time), and whatever a library prepared (a model's weights) stays with that library
 _lib = None
 
 P = C.c_void_p
@@ -122,6 +124,9 @@ _SIGS = {
     "svs_resample_peaks_workspace_bytes": (Z, [L, I, I, I, I]),
     "svs_resample_peaks": (I, [P, I, L, L, P, I, I, I, P, P, Z, P]),
     "svs_resample_encode": (I, [P, I, L, L, P, I, I, I, P, I, P, P]),
+    "svs_overlap_count": (I, [I, I, I]),
+    "svs_overlap_tiles": (I, [P, L, I, I, I, I, I, P, P]),
+    "svs_overlap_blend": (I, [P, I, I, I, I, I, P, L, I, P, L, P]),
 }
 
 

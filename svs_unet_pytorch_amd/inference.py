@@ -2,7 +2,7 @@
 (/root/reference/inference.py:29-34, 56-127), with the per-tile loop replaced by ONE batched forward.
 
     python -m svs_unet_pytorch_amd.inference --model_path CKPT/svs_x.pth --mixture_folder spec/mixture \
-        --tar spec/pred [--vocal_solo 0|1]
+        --tar spec/pred [--vocal_solo 0|1] [--tile_hop 128|64|32]
 
 Per file: load (513, T) -> drop the DC row (inference.py:68) -> cut into T//INPUT_LEN + 1 segments of
 INPUT_LEN frames, skipping an empty last one and right-zero-padding a short one (inference.py:75-92)
@@ -24,6 +24,7 @@ import torch
 from . import _lib
 from .config import INPUT_LEN
 from .model import UNet
+from .overlap import blend_masks, check_tile_hop, overlap_tiles
 
 
 def segment_plan(n_frames: int, seg_len: int = INPUT_LEN):
@@ -38,8 +39,15 @@ def segment_plan(n_frames: int, seg_len: int = INPUT_LEN):
 
 
 @torch.no_grad()
-def separate(model: UNet, mix_spec, seg_len: int = INPUT_LEN, vocal_solo: bool = True, max_batch: int = 256):
-    """(F+1, T) mixture magnitude (numpy or tensor) -> (F+1, T) float32 numpy array."""
+def separate(model: UNet, mix_spec, seg_len: int = INPUT_LEN, vocal_solo: bool = True, max_batch: int = 256,
+             tile_hop: int | None = None):
+    """(F+1, T) mixture magnitude (numpy or tensor) -> (F+1, T) float32 numpy array.
+    tile_hop: None (the default) or seg_len = disjoint seg_len-frame tiles, whatever seg_len is; below seg_len: overlapped tiles every
+    tile_hop frames with cross-faded masks (overlap.py)."""
+    if tile_hop is None:
+        tile_hop = seg_len
+    if tile_hop != seg_len:
+        check_tile_hop(tile_hop, seg_len)
     dev = model._flat.device
     spec = torch.as_tensor(np.asarray(mix_spec)).to(torch.float32)
     crop = spec[1:, :]
@@ -54,11 +62,18 @@ def separate(model: UNet, mix_spec, seg_len: int = INPUT_LEN, vocal_solo: bool =
     out = torch.empty_like(tiles)
     was_training = model.training
     model.eval()
-    for s in range(0, n, max_batch):
-        t = tiles[s:s + max_batch]
-        mask = model(t)
-        _lib.check(_lib.lib().svs_apply_mask(t.data_ptr(), mask.data_ptr(), out[s:s + max_batch].data_ptr(), t.numel(),
-                                             0 if vocal_solo else 1, _lib.stream_ptr()), "svs_apply_mask")
+    if tile_hop != seg_len:                        # overlapped tiles -> masks -> out = mix * cross-faded mask, one launch
+        ov = overlap_tiles(tiles.view(1, n, 1, F_, seg_len), tile_hop)
+        masks = torch.empty_like(ov)
+        for s in range(0, ov.shape[0], max_batch):
+            masks[s:s + max_batch] = model(ov[s:s + max_batch])
+        blend_masks(masks, n, tile_hop, mix=tiles.view(1, n, 1, F_, seg_len), invert=not vocal_solo, out=out.view(1, n, 1, F_, seg_len))
+    else:
+        for s in range(0, n, max_batch):
+            t = tiles[s:s + max_batch]
+            mask = model(t)
+            _lib.check(_lib.lib().svs_apply_mask(t.data_ptr(), mask.data_ptr(), out[s:s + max_batch].data_ptr(), t.numel(),
+                                                 0 if vocal_solo else 1, _lib.stream_ptr()), "svs_apply_mask")
     model.train(was_training)
     full = out[:, 0].permute(1, 0, 2).reshape(F_, n * seg_len)[:, :T].cpu()
     return torch.cat([torch.zeros((1, T), dtype=torch.float32), full], dim=0).numpy()
@@ -70,7 +85,13 @@ def main(argv=None):
     parser.add_argument("--tar", type=str, required=True)
     parser.add_argument("--mixture_folder", type=str, required=True)
     parser.add_argument("--vocal_solo", type=int, default=1, help="1: keep the vocal, 0: remove it")
+    parser.add_argument("--tile_hop", type=int, default=INPUT_LEN,
+                        help=f"frames between tiles: {INPUT_LEN} = disjoint tiles as the reference cuts them; 64 or 32 = overlapped tiles with cross-faded masks")
     args = parser.parse_args(argv)
+    try:
+        check_tile_hop(args.tile_hop, INPUT_LEN)
+    except ValueError as e:
+        parser.error(f"--tile_hop: {e}")
 
     os.makedirs(args.tar, exist_ok=True)
     if not torch.cuda.is_available():
@@ -93,7 +114,7 @@ def main(argv=None):
     print(f"Found {len(files)} files, separating...")
     for name in files:
         mix = np.load(os.path.join(args.mixture_folder, name))
-        pred = separate(model, mix, INPUT_LEN, bool(args.vocal_solo))
+        pred = separate(model, mix, INPUT_LEN, bool(args.vocal_solo), tile_hop=args.tile_hop)
         if pred is not None:
             np.save(os.path.join(args.tar, name), pred)
     print("Separation finished!")

@@ -7,14 +7,16 @@ evaluate.py accepts it beside the source's stems.
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src song.wav --tar out.wav
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src wav_folder --tar out_folder \
         [--vocal_solo 0|1] [--precision bf16] [--subtype PCM_16|PCM_32|FLOAT] [--no_keep_length] \
-        [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder]
+        [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder] [--tile_hop 128|64|32]
 
 A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
 default) is what the reference's data.py writes (data.py:166).  --win_size / --hop_size (the config's 1024 / 768 by default;
 data.py:24-25 takes the same two flags) are the window and hop of the two transforms, for a checkpoint trained at another
 geometry.  --tar_accomp also writes the accompaniment (a file, or a folder with the names of --tar when --src is a folder) from
 the same pass: one STFT, one set of network forwards and one two-stem inverse STFT (svs_istft_stems_n), --tar then holding the
-vocal; it excludes --vocal_solo 0.  The reference has no such command: it goes through
+vocal; it excludes --vocal_solo 0.  --tile_hop (128 by default: disjoint 128-frame tiles, inference.py:72-120) below 128 runs the
+network on overlapped tiles that start every 64 or 32 frames and cross-fades their masks (overlap.py), at 2x / 4x the network
+forwards: no frame's mask then comes from a tile's zero-padded edge alone.  The reference has no such command: it goes through
 data.py to_spec, inference.py and data.py to_wave with .npy files in between.
 """
 from __future__ import annotations
@@ -25,9 +27,10 @@ import sys
 
 import torch
 
-from .config import HOP_SIZE, WINDOW_SIZE
+from .config import HOP_SIZE, INPUT_LEN, WINDOW_SIZE
 from .data import WINDOW_SIZES
 from .model import UNet
+from .overlap import check_tile_hop
 from .streaming import separate_to_wav
 
 
@@ -44,7 +47,13 @@ def main(argv=None):
     parser.add_argument("--hop_size", type=int, default=HOP_SIZE, help="hop of the two transforms, 1..win_size")
     parser.add_argument("--tar_accomp", type=str, default=None,
                         help="also write the accompaniment here, from the same pass (a wav file, or a folder when --src is one); --tar holds the vocal")
+    parser.add_argument("--tile_hop", type=int, default=INPUT_LEN,
+                        help=f"frames between tiles: {INPUT_LEN} = disjoint tiles as the reference cuts them; 64 or 32 = overlapped tiles with cross-faded masks")
     args = parser.parse_args(argv)
+    try:
+        check_tile_hop(args.tile_hop, INPUT_LEN)
+    except ValueError as e:
+        parser.error(f"--tile_hop: {e}")
     if args.win_size not in WINDOW_SIZES:
         parser.error(f"--win_size {args.win_size}: the STFT / iSTFT kernels are built for n_fft = {', '.join(map(str, WINDOW_SIZES))}")
     if not 0 < args.hop_size <= args.win_size:
@@ -78,7 +87,7 @@ def main(argv=None):
     for src, dst, dst_accomp in jobs:
         frames, channels = separate_to_wav(model, src, dst, vocal_solo=bool(args.vocal_solo), precision=args.precision,
                                            subtype=args.subtype, keep_length=not args.no_keep_length, n_fft=args.win_size,
-                                           hop=args.hop_size, dst_accomp_path=dst_accomp)
+                                           hop=args.hop_size, dst_accomp_path=dst_accomp, tile_hop=args.tile_hop)
         print(f"{dst}: {frames} frames x {channels}" + ("" if dst_accomp is None else f"; {dst_accomp}: the same"))
     print("Separation finished!")
 

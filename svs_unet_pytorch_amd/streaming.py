@@ -16,11 +16,19 @@ import torch
 from . import _lib
 from .config import HOP_SIZE, INPUT_LEN, SAMPLE_RATE, WINDOW_SIZE
 from .data import istft_from_tiles, istft_stems_from_tiles, stft_to_tiles
+from .overlap import blend_masks, check_tile_hop, overlap_tiles
 
 
 @torch.no_grad()
-def separate_spectrogram_device(model, mag: torch.Tensor, seg_len: int = INPUT_LEN, vocal_solo: bool = True, max_batch: int = 256):
-    """(F+1, T) magnitude on the GPU -> (F+1, T) separated magnitude on the GPU (inference.py:65-127 semantics)."""
+def separate_spectrogram_device(model, mag: torch.Tensor, seg_len: int = INPUT_LEN, vocal_solo: bool = True, max_batch: int = 256,
+                                tile_hop: int | None = None):
+    """(F+1, T) magnitude on the GPU -> (F+1, T) separated magnitude on the GPU (inference.py:65-127 semantics).
+    tile_hop: None (the default) or seg_len = disjoint seg_len-frame tiles, whatever seg_len is; below seg_len: overlapped tiles every
+    tile_hop frames with cross-faded masks (overlap.py)."""
+    if tile_hop is None:
+        tile_hop = seg_len
+    if tile_hop != seg_len:
+        check_tile_hop(tile_hop, seg_len)
     crop = mag[1:, :]
     F_, T = crop.shape
     n = T // seg_len + 1
@@ -34,11 +42,18 @@ def separate_spectrogram_device(model, mag: torch.Tensor, seg_len: int = INPUT_L
     out = torch.empty_like(tiles)
     was_training = model.training
     model.eval()
-    for s in range(0, n, max_batch):
-        t = tiles[s:s + max_batch]
-        mask = model(t)
-        _lib.check(_lib.lib().svs_apply_mask(t.data_ptr(), mask.data_ptr(), out[s:s + max_batch].data_ptr(), t.numel(),
-                                             0 if vocal_solo else 1, _lib.stream_ptr()), "svs_apply_mask")
+    if tile_hop != seg_len:                        # overlapped tiles -> masks -> out = mix * cross-faded mask, one launch
+        ov = overlap_tiles(tiles.view(1, n, 1, F_, seg_len), tile_hop)
+        masks = torch.empty_like(ov)
+        for s in range(0, ov.shape[0], max_batch):
+            masks[s:s + max_batch] = model(ov[s:s + max_batch])
+        blend_masks(masks, n, tile_hop, mix=tiles.view(1, n, 1, F_, seg_len), invert=not vocal_solo, out=out.view(1, n, 1, F_, seg_len))
+    else:
+        for s in range(0, n, max_batch):
+            t = tiles[s:s + max_batch]
+            mask = model(t)
+            _lib.check(_lib.lib().svs_apply_mask(t.data_ptr(), mask.data_ptr(), out[s:s + max_batch].data_ptr(), t.numel(),
+                                                 0 if vocal_solo else 1, _lib.stream_ptr()), "svs_apply_mask")
     model.train(was_training)
     full = out[:, 0].permute(1, 0, 2).reshape(F_, n * seg_len)[:, :T]
     return torch.cat([torch.zeros((1, T), dtype=torch.float32, device=mag.device), full], dim=0)
@@ -47,7 +62,7 @@ def separate_spectrogram_device(model, mag: torch.Tensor, seg_len: int = INPUT_L
 @torch.no_grad()
 def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
                       peak: float | None = 0.9, max_batch: int = 256, precision: str | None = None, sr_in: int | None = None,
-                      sr_out: int | None = None, both_stems: bool = False):
+                      sr_out: int | None = None, both_stems: bool = False, tile_hop: int = INPUT_LEN):
     """float32 samples (n,) or (channels, n) on the GPU -> separated samples (hop*(T-1),) or (channels, hop*(T-1)).
     both_stems: return (2, ...) stacked [vocal, accompaniment] -- what vocal_solo=True and vocal_solo=False return -- from ONE
     forward transform, one set of network forwards and one inverse launch (data.istft_stems_from_tiles); vocal_solo is
@@ -59,7 +74,13 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     network rate, as always.
     All channels go through ONE forward transform (which writes network tiles and frame-major phasors directly), one
     batched network forward per `max_batch` tiles and ONE inverse transform (which applies the mask on load and
-    overlap-adds in LDS); the only other passes are the two per-channel normalisations."""
+    overlap-adds in LDS); the only other passes are the two per-channel normalisations.
+    tile_hop: INPUT_LEN (the default) separates disjoint tiles as the reference does (inference.py:72-120).  A smaller hop (64,
+    32: a multiple of 4 that divides INPUT_LEN, at least INPUT_LEN / 8) cuts overlapped tiles out of the transform's tiles
+    (overlap.overlap_tiles), runs the network over all of them, and cross-fades their masks into the one mask the inverse
+    transform reads (overlap.blend_masks): two more launches, INPUT_LEN / tile_hop times the network forwards."""
+    if tile_hop != INPUT_LEN:
+        check_tile_hop(tile_hop, INPUT_LEN)
     squeeze = y.dim() == 1
     if squeeze:
         y = y[None]
@@ -72,6 +93,8 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     for c in range(C):                                           # divide by the channel's maximum magnitude (data.py:84-85,105)
         _lib.check(L.svs_scale_by_inv(tiles[c].data_ptr(), tiles[c].numel(), norm[c:].data_ptr(), 1.0, _lib.stream_ptr()), "svs_scale_by_inv")
     flat = tiles.view(C * n_tiles, 1, tiles.shape[3], tiles.shape[4])
+    if tile_hop != INPUT_LEN:
+        flat = overlap_tiles(tiles, tile_hop)                    # (C * n_ov, 1, rows, INPUT_LEN)
     mask = torch.empty_like(flat)
     was_training, was_precision = model.training, model.eval_precision
     try:
@@ -83,6 +106,8 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     finally:                                                     # a failing forward must not leave the model in another mode
         model.eval_precision = was_precision
         model.train(was_training)
+    if tile_hop != INPUT_LEN:
+        mask = blend_masks(mask, n_tiles, tile_hop)              # back to one mask value per frame, in the layout of `tiles`
     if both_stems:                                               # (2 * C, n): the stems are further channels to everything below
         out = istft_stems_from_tiles(tiles, mask, phase, T, n_fft=n_fft, hop=hop, peak=None if sr_out is not None else peak)
         out = out.view(2 * C, out.shape[2])
@@ -125,7 +150,7 @@ def separated_frames(n_source: int, sr: int, hop: int = HOP_SIZE):
 @torch.no_grad()
 def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = True, precision: str | None = None,
                     subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
-                    dst_accomp_path: str | None = None):
+                    dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN):
     """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
     the PCM is copied as the file stores it, resample.resample_poly_gpu (no downmix) brings every channel to SAMPLE_RATE,
     separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
@@ -135,7 +160,8 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     window and hop of the two transforms (data.WINDOW_SIZES; the network is fully convolutional, so a checkpoint trained at
     another geometry runs on the n_fft / 2 rows of that window).  dst_accomp_path: also write the accompaniment there, from the
     same pass (separate_waveform(both_stems=True)): dst_path then holds the vocal whatever vocal_solo says, and each file is
-    encoded with its own common gain at peak 0.9.  Returns the (frames, channels) written (per file)."""
+    encoded with its own common gain at peak 0.9.  tile_hop: separate_waveform's (overlapped tiles with cross-faded masks when it
+    is below INPUT_LEN).  Returns the (frames, channels) written (per file)."""
     from fractions import Fraction
 
     import numpy as np
@@ -157,7 +183,7 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     y = resample_poly_gpu(pcm, fr.numerator, fr.denominator, channels=channels, downmix=False)
     y = y[None] if y.dim() == 1 else y                            # (channels, n) at the network rate
     sep = separate_waveform(model, y, vocal_solo=vocal_solo, n_fft=n_fft, hop=hop, peak=None, precision=precision,
-                            both_stems=dst_accomp_path is not None)
+                            both_stems=dst_accomp_path is not None, tile_hop=tile_hop)
     for stem, path in ((sep, dst_path),) if dst_accomp_path is None else ((sep[0], dst_path), (sep[1], dst_accomp_path)):
         enc = resample_encode_gpu(stem, fr.denominator, fr.numerator, fmt=subtype, peak=0.9, common_gain=True)
         if keep_length:

@@ -8,6 +8,8 @@ ONE device (devices differ by up to ~12%, so numbers from different gpurun calls
 L1 + MR-STFT losses, backward; no Adam) on 512 x 128 tiles at hop 768, alternating the two libraries round by round, and
 prints one JSON line.  Give it two builds of the SAME commit first: the B/A it prints for them is the spread of the harness.
 --eval-bf16 [--hw H W] does the same for the bf16 eval forward (svs_unet_forward_eval_bf16) and compares every layer's output bitwise.
+--separate does the same for tools/stream_bench.py's case (streaming.separate_waveform on 240 s of stereo, default arguments, so
+disjoint tiles), in fp32 and bf16, one JSON line each, and compares the separated samples bitwise.
 """
 import argparse
 import ctypes
@@ -132,6 +134,45 @@ def eval_bf16(libs, B, H, W, rounds=7, reps=10):
                       "mask_bitwise_equal": bool(torch.equal(out[0][1], out[1][1]))}))
 
 
+def separate(paths, seconds=240.0, rate=44100, rounds=7, reps=5):
+    """Best-of-`rounds` ms of separate_waveform per library, the libraries taking turns inside every round: the package's
+    handle (_lib._lib) is swapped between two fully bound ones, and each library has a model of its own (the same checkpoint), so
+    that the weights it prepared stay its own."""
+    import json
+
+    import numpy as np
+
+    from svs_unet_pytorch_amd import synth
+    from svs_unet_pytorch_amd.model import UNet
+    from svs_unet_pytorch_amd.streaming import separate_waveform
+    handles = []
+    for path in paths:
+        h = ctypes.CDLL(os.path.abspath(path))
+        for name, (res, args) in _lib._SIGS.items():
+            if hasattr(h, name):                                     # (an older build lacks the entry points added since)
+                fn = getattr(h, name)
+                fn.restype, fn.argtypes = res, args
+        handles.append(h)
+    n = int(seconds * rate)
+    y = torch.from_numpy(np.stack([synth.audio(n, 20), synth.audio(n, 21)])).to("cuda")
+    for precision in ("fp32", "bf16"):
+        models, out = [], []
+        for h in handles:
+            _lib._lib = h
+            model = UNet()
+            model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.closed_form_state().items()})
+            models.append(model.to("cuda").eval())
+            out.append(separate_waveform(models[-1], y, precision=precision).clone())
+        best = [1e9, 1e9]
+        for _ in range(rounds):
+            for i, h in enumerate(handles):
+                _lib._lib = h
+                best[i] = min(best[i], timeit(lambda: separate_waveform(models[i], y, precision=precision), reps))
+        print(json.dumps({"what": f"separate_waveform, {seconds:.0f} s stereo, disjoint tiles (tile_hop 128)", "precision": precision,
+                          "ms_A": round(best[0], 4), "ms_B": round(best[1], 4), "B_over_A": round(best[1] / best[0], 4),
+                          "samples_bitwise_equal": bool(torch.equal(out[0], out[1]))}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("lib_a")
@@ -140,9 +181,12 @@ def main():
     ap.add_argument("--wgrad", action="store_true")
     ap.add_argument("--full-step", action="store_true")
     ap.add_argument("--eval-bf16", action="store_true")
+    ap.add_argument("--separate", action="store_true")
     ap.add_argument("--hw", type=int, nargs=2, default=(512, 128), metavar=("H", "W"), help="tile size of --eval-bf16")
     a = ap.parse_args()
     torch.zeros(1, device="cuda")
+    if a.separate:
+        return separate([a.lib_a, a.lib_b])
     libs = [load(a.lib_a), load(a.lib_b)]
     if a.full_step:
         return full_step(libs, a.batch)
