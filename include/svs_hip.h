@@ -385,6 +385,19 @@ int svs_istft_stems_n(const float* mag, int64_t chan_stride, int seg, int rows, 
                       int64_t stem_stride, float* absmax_partial, hipStream_t stream);
 int svs_istft_stems_groups_n(int n_fft, int hop, int frames, int channels);
 int svs_istft_stems_plan_n(int n_fft, int hop, int* hops_per_block, int* rounds, size_t* lds_bytes);
+/* The analysis half of a phase-refinement iteration (Griffin-Lim; MISI of Gunawan and Sen for two stems that must add up to a
+ * mixture): the forward transform of svs_stft_tiles_n that writes ONLY the frame-major unit phasors of phase_mode 1 -- no
+ * magnitudes, no tile padding, no maxima -- which svs_istft_tiles_n reads back as its `phase`.  The reference writes
+ * `mag * mask * phase of the mixture` through librosa.istft (inference.py:100-107, data.py:159) and has no such step.
+ *   x (stems, channels, n_samples), stem s at x + s * stem_stride; stems 1 or 2.
+ *   mix (channels, n_samples) or NULL.  Given (stems == 2 only), stem s is transformed as x_s + 0.5 * (mix - x_0 - x_1), formed
+ *   on load from the three streams; NULL: every stem is transformed as it is.
+ *   phase (stems, channels, T, n_fft / 2 + 1, 2) (re, im), T = svs_stft_frames(n_samples, hop), stem s at
+ *   phase + s * phase_stem_stride floats (even, at least one stem's size); exactly 1 + 0i where a bin is exactly zero.
+ * n_fft = 512, 1024 or 2048, 0 < hop <= n_fft, every view below 2 GiB: anything else is SVS_ERR_INVALID with its own message,
+ * before any launch.  16-byte loads when n_samples, hop and stem_stride are multiples of 4 and x and mix are 16-byte aligned. */
+int svs_stft_rephase_n(const float* x, int64_t stem_stride, int stems, const float* mix, int64_t n_samples, int channels,
+                       int n_fft, int hop, float* phase, int64_t phase_stem_stride, hipStream_t stream);
 /* Host-only: the periodic Hann window the forward transform multiplies by (librosa.stft's default window, data.py:79,100):
  * out[m] = sin^2(pi m / n_fft) for m = 0 .. n_fft / 2 (n_fft / 2 + 1 floats; w[n_fft - m] = w[m]), rounded from double. */
 int svs_hann_table(int n_fft, float* out);

@@ -100,6 +100,7 @@ _SIGS = {
     "svs_istft_stems_n": (I, [P, L, I, I, I, P, P, I, I, I, I, I, P, L, P, P]),
     "svs_istft_stems_groups_n": (I, [I, I, I, I]),
     "svs_istft_stems_plan_n": (I, [I, I, P, P, P]),
+    "svs_stft_rephase_n": (I, [P, L, I, P, L, I, I, I, P, L, P]),
     "svs_hann_table": (I, [I, P]),
     "svs_transpose_c64": (I, [P, P, I, I, P]),
     "svs_istft_bwd_mask": (I, [P, P, P, P, P, F, I, I, I, I, P]),

@@ -85,8 +85,12 @@ __device__ __forceinline__ int xpose_at(int wave, int k) { return wave * FftSize
 // ------------------------------------------------------------------------------------------------
 // forward: frames of a real signal -> bins
 // ------------------------------------------------------------------------------------------------
-enum { SRC_SIGNAL = 0, SRC_ENVDIV = 1 };        // x[s] zero-padded | d_wav[s] / envelope (transpose of the inverse's tail)
-enum { SINK_MAGPHASE = 0, SINK_DMAG = 1 };
+// x[s] zero-padded | d_wav[s] / envelope (transpose of the inverse's tail) | stem s of two plus half of what the stems fail to add
+// up to, x_s + 0.5 (mix - x_0 - x_1), formed on load (MISI's re-analysis input)
+enum { SRC_SIGNAL = 0, SRC_ENVDIV = 1, SRC_MISI = 2 };
+// SINK_PHASOR: only the frame-major unit phasors of phase_mode 1, [s][c][t][N / 2 + 1] (re, im), straight from registers: no
+// magnitudes, no transposed LDS round, no tile padding, no |.|max (svs_stft_rephase_n)
+enum { SINK_MAGPHASE = 0, SINK_DMAG = 1, SINK_PHASOR = 2 };
 // SINK_DMAG: whether the angle rows are staged after the transform in the waves' own buffers (no LDS plane of their own)
 __host__ __device__ constexpr bool dmag_late_angles(int n_fft) { return n_fft == 2048; }
 struct StftArgs {
@@ -98,6 +102,9 @@ struct StftArgs {
   const float* angle; const float* mix; const float* mask; float* d_logit; float alpha;
   const float2* twiddles;                                           // svs_fft_twiddles(N): the device-wide table
   const float* hann;                                                // svs_fft_hann(N), N != 1024
+  // SINK_PHASOR: y is (stems, channels, n_samples) with stem_stride floats between the stems, and stem s writes its phasors at
+  // phase + s * phase_stem_stride floats; SRC_MISI: msig is the mixture (channels, n_samples)
+  const float* msig; long stem_stride; long phase_stem_stride;
 };
 
 template <int NFFT, int SRC, int SINK>
@@ -113,7 +120,8 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
   // transposed round (BUF / 2 above the first, as phase_mode 2 uses it), once every wave holds its spectra in registers.
   constexpr bool LATE_ANGLES = SINK == SINK_DMAG && dmag_late_angles(NFFT);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c = blockIdx.y, t0 = blockIdx.x * GROUP;
+  const int stem = SINK == SINK_PHASOR ? (int)blockIdx.y / p.channels : 0;    // SINK_PHASOR: blockIdx.y = stem * channels + channel
+  const int c = (int)blockIdx.y - stem * p.channels, t0 = blockIdx.x * GROUP;
   if (SINK == SINK_DMAG && !LATE_ANGLES) {
     const int col = tid & (GROUP - 1), t = t0 + col;
     const long cbase = t < p.T ? p.lay.col(c, t) : 0;
@@ -124,8 +132,14 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
   const int ta = t0 + 2 * wave, tb = ta + 1;
   // ---- frames ta, tb -> z = a + i b (windowed); 4 consecutive samples per lane and step.  The loads are issued first and
   // stay in flight while the twiddle table is built.
-  const float* ysig = p.y + (long)c * p.n_samples;
-  const bool vec_ok = ((p.n_samples | p.hop) & 3) == 0 && ((uintptr_t)p.y & 15u) == 0;
+  // SRC_MISI reads three streams, stem 0 (ysig), stem 1 and the mixture, and keeps its own stem's sample plus half the residual;
+  // SRC_SIGNAL under SINK_PHASOR reads stem `stem` alone
+  constexpr bool misi = SRC == SRC_MISI;
+  const float* ysig = p.y + (long)c * p.n_samples + (SINK == SINK_PHASOR && !misi ? (long)stem * p.stem_stride : 0);
+  const float* const ysig1 = misi ? ysig + p.stem_stride : ysig;
+  const float* const ymix = misi ? p.msig + (long)c * p.n_samples : ysig;
+  const bool vec_ok = ((p.n_samples | p.hop) & 3) == 0 && ((uintptr_t)p.y & 15u) == 0 &&
+                      (SINK != SINK_PHASOR || ((p.stem_stride & 3) == 0 && ((uintptr_t)p.msig & 15u) == 0));
   float v[NFFT / 256][2][4];
 #pragma unroll
   for (int r = 0; r < NFFT / 256; ++r) {
@@ -136,7 +150,21 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
       const long q0 = (long)t * p.hop + m0, s0 = q0 - NFFT / 2;
       if (t < p.T && vec_ok && s0 >= 0 && s0 + 3 < p.n_samples) {
         const f32x4 x = *(const f32x4*)(ysig + s0);
-        v[r][h][0] = x[0]; v[r][h][1] = x[1]; v[r][h][2] = x[2]; v[r][h][3] = x[3];
+        if (misi) {
+          const f32x4 x1 = *(const f32x4*)(ysig1 + s0), xm = *(const f32x4*)(ymix + s0);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[r][h][j] = (stem ? x1[j] : x[j]) + 0.5f * (xm[j] - x[j] - x1[j]);
+        } else {
+          v[r][h][0] = x[0]; v[r][h][1] = x[1]; v[r][h][2] = x[2]; v[r][h][3] = x[3];
+        }
+      } else if (misi) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const long s = s0 + j;
+          const bool ok = t < p.T && s >= 0 && s < p.n_samples;
+          const float x0 = ok ? ysig[s] : 0.f, x1 = ok ? ysig1[s] : 0.f, xm = ok ? ymix[s] : 0.f;
+          v[r][h][j] = (stem ? x1 : x0) + 0.5f * (xm - x0 - x1);
+        }
       } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) { const long s = s0 + j; v[r][h][j] = (t < p.T && s >= 0 && s < p.n_samples) ? ysig[s] : 0.f; }
@@ -171,6 +199,21 @@ __global__ __launch_bounds__(512) void stft_fwd_kernel(StftArgs p) {
     const float2 zk = buf[fft_pad(k)], zn = buf[fft_pad((NFFT - k) & (NFFT - 1))];
     A[r] = float2{0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)};
     B[r] = float2{0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)};
+  }
+  if constexpr (SINK == SINK_PHASOR) {
+    // the wave's two frames straight from registers: per r, 64 lanes x 8 B contiguous.  The arithmetic is phase_mode 1's below
+    // (v_sqrt_f32 / v_rcp_f32, exactly 1 + 0i where the bin is exactly zero); nothing goes back through LDS, so no barrier follows
+    float2* const ph = (float2*)(p.phase + (long)stem * p.phase_stem_stride) + (long)c * p.T * NBIN;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int k = lane + 64 * r;
+      if (k > NFFT / 2) continue;
+      const float ma = __builtin_amdgcn_sqrtf(A[r].x * A[r].x + A[r].y * A[r].y), mb = __builtin_amdgcn_sqrtf(B[r].x * B[r].x + B[r].y * B[r].y);
+      const float ia = __builtin_amdgcn_rcpf(ma), ib = __builtin_amdgcn_rcpf(mb);
+      if (ta < p.T) ph[(long)ta * NBIN + k] = ma == 0.f ? float2{1.f, 0.f} : float2{A[r].x * ia, A[r].y * ia};
+      if (tb < p.T) ph[(long)tb * NBIN + k] = mb == 0.f ? float2{1.f, 0.f} : float2{B[r].x * ib, B[r].y * ib};
+    }
+    return;
   }
   fft_wave_sync();                                          // every lane has read Z before the buffer is rewritten below
   if (LATE_ANGLES) {
@@ -783,6 +826,52 @@ extern "C" int svs_stft_groups(int frames_alloc) { return (frames_alloc + GROUP 
 extern "C" int svs_stft_groups_n(int n_fft, int frames_alloc) {
   SVS_REQUIRE_NFFT("svs_stft_groups_n", n_fft);
   return svs_stft_groups(frames_alloc);
+}
+
+// ---- re-phasing forward transform: the analysis half of a Griffin-Lim (SRC_SIGNAL) / MISI (SRC_MISI) iteration, SINK_PHASOR
+template <int N>
+static int launch_stft_rephase(StftArgs& a, int stems, hipStream_t stream) {
+  int rc = svs_fft_twiddles(N, stream, &a.twiddles);
+  if (rc) return rc;
+  if (N != 1024 && (rc = svs_fft_hann(N, stream, &a.hann))) return rc;
+  const size_t lds = fft_lds_bytes(N, 8);                 // the eight wave buffers and the twiddle table: the forward kernel's own
+  if ((rc = a.msig ? allow_lds(stft_fwd_kernel<N, SRC_MISI, SINK_PHASOR>, lds) : allow_lds(stft_fwd_kernel<N, SRC_SIGNAL, SINK_PHASOR>, lds))) return rc;
+  dim3 grid((unsigned)((a.T + GROUP - 1) / GROUP), (unsigned)(a.channels * stems));
+  if (a.msig) hipLaunchKernelGGL((stft_fwd_kernel<N, SRC_MISI, SINK_PHASOR>), grid, dim3(512), lds, stream, a);
+  else hipLaunchKernelGGL((stft_fwd_kernel<N, SRC_SIGNAL, SINK_PHASOR>), grid, dim3(512), lds, stream, a);
+  SVS_CHECK_LAUNCH("stft_rephase");
+  return SVS_OK;
+}
+
+extern "C" int svs_stft_rephase_n(const float* x, int64_t stem_stride, int stems, const float* mix, int64_t n_samples, int channels,
+                                  int n_fft, int hop, float* phase, int64_t phase_stem_stride, hipStream_t stream) {
+  SVS_REQUIRE(n_samples > 0 && channels > 0, "svs_stft_rephase_n: n_samples and channels must be positive (n_samples=%lld channels=%d)",
+              (long long)n_samples, channels);
+  SVS_REQUIRE(stems == 1 || stems == 2, "svs_stft_rephase_n: stems must be 1 or 2, got %d", stems);
+  SVS_REQUIRE(!mix || stems == 2, "svs_stft_rephase_n: a mixture needs stems == 2 (x_s + (mix - x_0 - x_1) / 2), got stems = %d", stems);
+  SVS_REQUIRE_NFFT("svs_stft_rephase_n", n_fft);
+  SVS_REQUIRE(hop > 0 && hop <= n_fft, "svs_stft_rephase_n: hop %d is not in 1..n_fft (a larger hop leaves samples that no frame covers)", hop);
+  SVS_REQUIRE((long)channels * stems <= 65535, "svs_stft_rephase_n: channels * stems = %ld exceeds the grid's 65535", (long)channels * stems);
+  const long T = 1 + n_samples / hop, nbin = n_fft / 2 + 1;
+  const long x_one = (long)channels * n_samples, ph_one = (long)channels * T * nbin * 2;        // floats of one stem
+  SVS_REQUIRE(stems == 1 || (stem_stride >= x_one && phase_stem_stride >= ph_one),
+              "svs_stft_rephase_n: stem_stride %lld / phase_stem_stride %lld are below one stem's %lld samples / %lld phase floats",
+              (long long)stem_stride, (long long)phase_stem_stride, (long long)x_one, (long long)ph_one);
+  SVS_REQUIRE(stems == 1 || (phase_stem_stride & 1) == 0, "svs_stft_rephase_n: phase_stem_stride %lld must be even (whole (re, im) pairs)",
+              (long long)phase_stem_stride);
+  const long x_view = (stems - 1) * (long)stem_stride + x_one, ph_view = (stems - 1) * (long)phase_stem_stride + ph_one;
+  SVS_REQUIRE(x_view * 4 < (1L << 31) && ph_view * 4 < (1L << 31),
+              "svs_stft_rephase_n: a view of 2 GiB or more (signals %lld B, phasors %lld B); split the channels",
+              (long long)(x_view * 4), (long long)(ph_view * 4));
+  SVS_REQUIRE(x && phase, "svs_stft_rephase_n: null pointer (x or phase)");
+  SVS_REQUIRE((((uintptr_t)phase) & 7u) == 0 && (((uintptr_t)x | (uintptr_t)mix) & 3u) == 0,
+              "svs_stft_rephase_n: phase must be 8-byte aligned, x and mix 4-byte aligned");
+  StftArgs a{};
+  a.y = x; a.n_samples = n_samples; a.channels = channels; a.hop = hop; a.T = (int)T;
+  a.msig = mix; a.stem_stride = stems == 2 ? (long)stem_stride : 0; a.phase = phase; a.phase_mode = 1;
+  a.phase_stem_stride = stems == 2 ? (long)phase_stem_stride : 0;
+  return n_fft == 512 ? launch_stft_rephase<512>(a, stems, stream)
+       : n_fft == 1024 ? launch_stft_rephase<1024>(a, stems, stream) : launch_stft_rephase<2048>(a, stems, stream);
 }
 
 extern "C" int svs_stft_fwd(const float* y, int64_t n_samples, int n_fft, int hop, float* mag, float* phase, hipStream_t stream) {

@@ -7,7 +7,7 @@ evaluate.py accepts it beside the source's stems.
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src song.wav --tar out.wav
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src wav_folder --tar out_folder \
         [--vocal_solo 0|1] [--precision bf16] [--subtype PCM_16|PCM_32|FLOAT] [--no_keep_length] \
-        [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder] [--tile_hop 128|64|32]
+        [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder] [--tile_hop 128|64|32] [--phase_iters N]
 
 A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
 default) is what the reference's data.py writes (data.py:166).  --win_size / --hop_size (the config's 1024 / 768 by default;
@@ -16,7 +16,10 @@ geometry.  --tar_accomp also writes the accompaniment (a file, or a folder with 
 the same pass: one STFT, one set of network forwards and one two-stem inverse STFT (svs_istft_stems_n), --tar then holding the
 vocal; it excludes --vocal_solo 0.  --tile_hop (128 by default: disjoint 128-frame tiles, inference.py:72-120) below 128 runs the
 network on overlapped tiles that start every 64 or 32 frames and cross-fades their masks (overlap.py), at 2x / 4x the network
-forwards: no frame's mask then comes from a tile's zero-padded edge alone.  The reference has no such command: it goes through
+forwards: no frame's mask then comes from a tile's zero-padded edge alone.  --phase_iters N (0 by default: the masked magnitude
+carries the mixture's phase, as the reference writes it) refines the phase before the last inverse transform (rephase.py): N
+Griffin-Lim updates of the written stem, or, with --tar_accomp, N MISI updates of both stems, which also share out what the two fail
+to add up to.  The reference has no such command: it goes through
 data.py to_spec, inference.py and data.py to_wave with .npy files in between.
 """
 from __future__ import annotations
@@ -49,7 +52,11 @@ def main(argv=None):
                         help="also write the accompaniment here, from the same pass (a wav file, or a folder when --src is one); --tar holds the vocal")
     parser.add_argument("--tile_hop", type=int, default=INPUT_LEN,
                         help=f"frames between tiles: {INPUT_LEN} = disjoint tiles as the reference cuts them; 64 or 32 = overlapped tiles with cross-faded masks")
+    parser.add_argument("--phase_iters", type=int, default=0,
+                        help="phase-refinement updates before the last inverse STFT: 0 = the mixture's phase; N > 0 = N Griffin-Lim updates (MISI with --tar_accomp)")
     args = parser.parse_args(argv)
+    if args.phase_iters < 0:
+        parser.error(f"--phase_iters {args.phase_iters}: must be 0 (the mixture's phase) or a positive number of updates")
     try:
         check_tile_hop(args.tile_hop, INPUT_LEN)
     except ValueError as e:
@@ -87,7 +94,8 @@ def main(argv=None):
     for src, dst, dst_accomp in jobs:
         frames, channels = separate_to_wav(model, src, dst, vocal_solo=bool(args.vocal_solo), precision=args.precision,
                                            subtype=args.subtype, keep_length=not args.no_keep_length, n_fft=args.win_size,
-                                           hop=args.hop_size, dst_accomp_path=dst_accomp, tile_hop=args.tile_hop)
+                                           hop=args.hop_size, dst_accomp_path=dst_accomp, tile_hop=args.tile_hop,
+                                           phase_iters=args.phase_iters)
         print(f"{dst}: {frames} frames x {channels}" + ("" if dst_accomp is None else f"; {dst_accomp}: the same"))
     print("Separation finished!")
 

@@ -17,6 +17,7 @@ from . import _lib
 from .config import HOP_SIZE, INPUT_LEN, SAMPLE_RATE, WINDOW_SIZE
 from .data import istft_from_tiles, istft_stems_from_tiles, stft_to_tiles
 from .overlap import blend_masks, check_tile_hop, overlap_tiles
+from .rephase import check_phase_iters, refine_phase
 
 
 @torch.no_grad()
@@ -62,7 +63,7 @@ def separate_spectrogram_device(model, mag: torch.Tensor, seg_len: int = INPUT_L
 @torch.no_grad()
 def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
                       peak: float | None = 0.9, max_batch: int = 256, precision: str | None = None, sr_in: int | None = None,
-                      sr_out: int | None = None, both_stems: bool = False, tile_hop: int = INPUT_LEN):
+                      sr_out: int | None = None, both_stems: bool = False, tile_hop: int = INPUT_LEN, phase_iters: int = 0):
     """float32 samples (n,) or (channels, n) on the GPU -> separated samples (hop*(T-1),) or (channels, hop*(T-1)).
     both_stems: return (2, ...) stacked [vocal, accompaniment] -- what vocal_solo=True and vocal_solo=False return -- from ONE
     forward transform, one set of network forwards and one inverse launch (data.istft_stems_from_tiles); vocal_solo is
@@ -78,9 +79,14 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     tile_hop: INPUT_LEN (the default) separates disjoint tiles as the reference does (inference.py:72-120).  A smaller hop (64,
     32: a multiple of 4 that divides INPUT_LEN, at least INPUT_LEN / 8) cuts overlapped tiles out of the transform's tiles
     (overlap.overlap_tiles), runs the network over all of them, and cross-fades their masks into the one mask the inverse
-    transform reads (overlap.blend_masks): two more launches, INPUT_LEN / tile_hop times the network forwards."""
+    transform reads (overlap.blend_masks): two more launches, INPUT_LEN / tile_hop times the network forwards.
+    phase_iters: 0 (the default) writes the masked magnitude with the mixture's phase, as the reference does.  N > 0 refines the phase
+    between the mask and the last inverse (rephase.refine_phase): N Griffin-Lim updates on the requested stem, or, with both_stems,
+    N MISI updates that also hand each stem half of what the two fail to add up to; the stems then come from two single-stem
+    inverse launches, each with its own phase."""
     if tile_hop != INPUT_LEN:
         check_tile_hop(tile_hop, INPUT_LEN)
+    phase_iters = check_phase_iters(phase_iters)
     squeeze = y.dim() == 1
     if squeeze:
         y = y[None]
@@ -108,10 +114,20 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
         model.train(was_training)
     if tile_hop != INPUT_LEN:
         mask = blend_masks(mask, n_tiles, tile_hop)              # back to one mask value per frame, in the layout of `tiles`
-    if both_stems:                                               # (2 * C, n): the stems are further channels to everything below
+    if phase_iters and both_stems:                               # MISI: each stem ends with its own phase, so two single-stem inverses
+        ymix = y[:, :hop * (T - 1)].float().clone(memory_format=torch.contiguous_format)
+        for c in range(C):                                       # the mixture at the scale of the tiles: one pass per call, not per iteration
+            _lib.check(L.svs_scale_by_inv(ymix[c].data_ptr(), ymix.shape[1], norm[c:].data_ptr(), 1.0, _lib.stream_ptr()), "svs_scale_by_inv")
+        refined = refine_phase(tiles, mask, phase, T, phase_iters, stems=2, mix=ymix, n_fft=n_fft, hop=hop)
+        out = torch.stack([istft_from_tiles(tiles, mask, refined[s], T, invert=bool(s), n_fft=n_fft, hop=hop,
+                                            peak=None if sr_out is not None else peak) for s in range(2)])
+        out = out.view(2 * C, out.shape[2])
+    elif both_stems:                                             # (2 * C, n): the stems are further channels to everything below
         out = istft_stems_from_tiles(tiles, mask, phase, T, n_fft=n_fft, hop=hop, peak=None if sr_out is not None else peak)
         out = out.view(2 * C, out.shape[2])
     else:
+        if phase_iters:                                          # Griffin-Lim on the requested stem
+            phase = refine_phase(tiles, mask, phase, T, phase_iters, stems=1, invert=not vocal_solo, n_fft=n_fft, hop=hop)[0]
         out = istft_from_tiles(tiles, mask, phase, T, invert=not vocal_solo, n_fft=n_fft, hop=hop, peak=None if sr_out is not None else peak)
     if sr_out is not None:
         from .resample import resample_poly_gpu
@@ -150,7 +166,7 @@ def separated_frames(n_source: int, sr: int, hop: int = HOP_SIZE):
 @torch.no_grad()
 def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = True, precision: str | None = None,
                     subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
-                    dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN):
+                    dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN, phase_iters: int = 0):
     """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
     the PCM is copied as the file stores it, resample.resample_poly_gpu (no downmix) brings every channel to SAMPLE_RATE,
     separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
@@ -161,7 +177,8 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     another geometry runs on the n_fft / 2 rows of that window).  dst_accomp_path: also write the accompaniment there, from the
     same pass (separate_waveform(both_stems=True)): dst_path then holds the vocal whatever vocal_solo says, and each file is
     encoded with its own common gain at peak 0.9.  tile_hop: separate_waveform's (overlapped tiles with cross-faded masks when it
-    is below INPUT_LEN).  Returns the (frames, channels) written (per file)."""
+    is below INPUT_LEN).  phase_iters: separate_waveform's (Griffin-Lim updates of the written stem's phase, MISI updates with
+    dst_accomp_path).  Returns the (frames, channels) written (per file)."""
     from fractions import Fraction
 
     import numpy as np
@@ -183,7 +200,7 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     y = resample_poly_gpu(pcm, fr.numerator, fr.denominator, channels=channels, downmix=False)
     y = y[None] if y.dim() == 1 else y                            # (channels, n) at the network rate
     sep = separate_waveform(model, y, vocal_solo=vocal_solo, n_fft=n_fft, hop=hop, peak=None, precision=precision,
-                            both_stems=dst_accomp_path is not None, tile_hop=tile_hop)
+                            both_stems=dst_accomp_path is not None, tile_hop=tile_hop, phase_iters=phase_iters)
     for stem, path in ((sep, dst_path),) if dst_accomp_path is None else ((sep[0], dst_path), (sep[1], dst_accomp_path)):
         enc = resample_encode_gpu(stem, fr.denominator, fr.numerator, fmt=subtype, peak=0.9, common_gain=True)
         if keep_length:
