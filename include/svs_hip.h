@@ -544,6 +544,49 @@ int svs_overlap_tiles(const float* tiles, int64_t chan_stride, int channels, int
 int svs_overlap_blend(const float* masks, int channels, int n_tiles, int rows, int seg, int tile_hop, const float* mix,
                       int64_t mix_chan_stride, int invert, float* out, int64_t out_chan_stride, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Multichannel Wiener filter with EM updates of a local Gaussian model (csrc/wiener.hip; Duong, Vincent and Gribonval; the
+ * post-filter of Open-Unmix).  The reference writes `mag * mask * phase of the mixture` (inference.py:100-107, data.py:159) and
+ * has no such step.  Two sources (0 vocal, 1 accompaniment), `channels` 1 or 2, bins (t, f) with f over the tiles' rows (the
+ * DC bin is absent from the tiles and stays zero in every stem).  With x_c = scale[c] * mag_c * P_c the mixture, one update is
+ *     v_j[t,f] = mean_c |y_jc|^2                                   R_j[f] = sum_t y_j y_j^H / (eps + sum_t v_j[t,f])
+ *     Cxx[t,f] = sum_j v_j R_j + reg * I                           y_j = v_j R_j Cxx^-1 x
+ * from y_0c = scale[c] mag_c mask_c P_c and y_1c = scale[c] mag_c (1 - mask_c) P_c.  All arithmetic is fp64 (identical channels make
+ * Cxx = s 11^T + reg I, whose inverse cancels in fp32); loads and stores per bin are fp32.  Open-Unmix's constants are
+ * eps = 1e-10 and, for a mixture whose maximum is 1, reg = 1e-7.
+ *   mag, mask: the standard tile addressing of svs_stft_tiles with first_bin = 1,
+ *     (channel c, row r, frame t) = base[c * chan_stride + ((t / seg) * rows + r) * seg + t % seg],  t < ceil(frames / seg) * seg.
+ *   phase: frame-major unit phasors (channels, frames, rows + 1, 2) (re, im), phase_mode 1 of svs_stft_tiles.
+ *   scale: [channels] floats on the device (norm_c / max_c' norm_c': both channels on one scale, |x| <= 1).
+ *   v: (2, ...) float32, stem j at v + j * v_stem_stride in the tile addressing of ONE channel; zero in the padded frames.
+ *   R: (2, rows, 4) doubles (R00, R11, Re R01, Im R01); one channel: R00, the rest zero.
+ * Rules, each checked before any launch with its own message: channels 1 or 2; rows a positive multiple of 64; seg a positive
+ * multiple of 4; frames >= 1; strides at least one channel's / stem's size and multiples of 4 floats; pointers non-null, 16-byte
+ * aligned for mag, mask, v and the stems' magnitudes, 8-byte aligned for phasors, R and the workspace; every view below 2 GiB;
+ * reg > 0, eps >= 0; the workspace size.
+ * svs_wiener_workspace_bytes: bytes of svs_wiener_model's workspace (0 for invalid arguments).
+ * svs_wiener_model: ONE update of the model.  v_prev == R_prev == NULL: the posterior is the masked magnitudes with the
+ *   mixture's phase (the first update; mask required).  Given: the posterior is W(v_prev, R_prev) x, formed on the fly (mask is
+ *   not read; no y is ever stored between passes).  v may be v_prev and R may be R_prev: a block reads its bins before it writes
+ *   them, and R is written by a second launch.  The sums over t run over the real frames only, in fp64, per block of 32 frames
+ *   into the workspace and from there in a fixed order (ascending within 16 consecutive runs of blocks, then the runs in
+ *   ascending order): no atomics, bitwise reproducible. */
+size_t svs_wiener_workspace_bytes(int channels, int rows, int seg, int frames);
+int svs_wiener_model(const float* mag, int64_t chan_stride, int seg, int rows, const float* mask, const float* phase,
+                     const float* scale, int channels, int frames, const float* v_prev, int64_t v_prev_stem_stride,
+                     const double* R_prev, double eps, double reg, float* v, int64_t v_stem_stride, double* R, void* ws,
+                     size_t ws_bytes, hipStream_t stream);
+/* svs_wiener_stems: y_j = W_j(v, R) x as magnitude tiles (addressing of mag with out_chan_stride) and frame-major unit phasors
+ *   (channels, frames, rows + 1, 2), which svs_istft_tiles_n(mask = NULL, phase_mode 1) reads unchanged.  stem 0 or 1: that stem
+ *   alone, written at out_mag / out_phase (the stem strides are not read; nothing of the other stem is stored); stem 2: stem j
+ *   at out_mag + j * out_mag_stem_stride and out_phase + j * out_phase_stem_stride (even).  The phasor is exactly 1 + 0i where y
+ *   is exactly zero (or its magnitude rounds to a float32 zero) and in the DC bin; the magnitude is exactly zero in the padded frames of the last tile.  The stems are on the
+ *   common scale of x, so the stereo balance of the mixture is kept. */
+int svs_wiener_stems(const float* mag, int64_t chan_stride, int seg, int rows, const float* phase, const float* scale,
+                     int channels, int frames, const float* v, int64_t v_stem_stride, const double* R, double reg, int stem,
+                     float* out_mag, int64_t out_chan_stride, int64_t out_mag_stem_stride, float* out_phase,
+                     int64_t out_phase_stem_stride, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

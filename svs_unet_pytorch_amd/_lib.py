@@ -128,6 +128,9 @@ _SIGS = {
     "svs_overlap_count": (I, [I, I, I]),
     "svs_overlap_tiles": (I, [P, L, I, I, I, I, I, P, P]),
     "svs_overlap_blend": (I, [P, I, I, I, I, I, P, L, I, P, L, P]),
+    "svs_wiener_workspace_bytes": (Z, [I, I, I, I]),
+    "svs_wiener_model": (I, [P, L, I, I, P, P, P, I, I, P, L, P, D, D, P, L, P, P, Z, P]),
+    "svs_wiener_stems": (I, [P, L, I, I, P, P, I, I, P, L, P, D, I, P, L, L, P, L, P]),
 }
 
 

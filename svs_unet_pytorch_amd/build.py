@@ -41,8 +41,9 @@ def _stale(target, deps):
 # vectoriser turns complex multiplies into v_pk_mul_f32 / v_pk_fma_f32 with op_sel swizzles, and on gfx950 a packed-fp32
 # instruction whose op_sel takes the HIGH half of a source for the low result returns garbage while a bf16 MFMA
 # (v_mfma_f32_16x16x32_bf16) of any other wave -- another stream, another process -- is executing on the CU
-# (reproduced with two-line kernels: DESIGN.md section 5).  No other source file produces that form.
-EXTRA_FLAGS = {"stft.hip": ["-fno-slp-vectorize"], "mrstft.hip": ["-fno-slp-vectorize"]}
+# (reproduced with two-line kernels: DESIGN.md section 5).  No other source file produces that form; wiener.hip's complex
+# arithmetic is fp64, but its fp32 loads and stores sit beside it, so it is built the same way.
+EXTRA_FLAGS = {"stft.hip": ["-fno-slp-vectorize"], "mrstft.hip": ["-fno-slp-vectorize"], "wiener.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src):

@@ -8,6 +8,7 @@ evaluate.py accepts it beside the source's stems.
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src wav_folder --tar out_folder \
         [--vocal_solo 0|1] [--precision bf16] [--subtype PCM_16|PCM_32|FLOAT] [--no_keep_length] \
         [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder] [--tile_hop 128|64|32] [--phase_iters N]
+        [--wiener_iters N]
 
 A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
 default) is what the reference's data.py writes (data.py:166).  --win_size / --hop_size (the config's 1024 / 768 by default;
@@ -19,7 +20,10 @@ network on overlapped tiles that start every 64 or 32 frames and cross-fades the
 forwards: no frame's mask then comes from a tile's zero-padded edge alone.  --phase_iters N (0 by default: the masked magnitude
 carries the mixture's phase, as the reference writes it) refines the phase before the last inverse transform (rephase.py): N
 Griffin-Lim updates of the written stem, or, with --tar_accomp, N MISI updates of both stems, which also share out what the two fail
-to add up to.  The reference has no such command: it goes through
+to add up to.  --wiener_iters N (0 by default; 1..8; files of one or two channels; not beside --phase_iters) runs the multichannel
+Wiener filter after the mask (wiener.py): N updates of a power per bin and a spatial covariance per frequency for each of the two
+sources, then each written stem re-filtered from the complex stereo mixture -- magnitudes and phases of its own, the mixture's
+stereo balance kept, and with --tar_accomp two files that add up to the mixture.  The reference has no such command: it goes through
 data.py to_spec, inference.py and data.py to_wave with .npy files in between.
 """
 from __future__ import annotations
@@ -35,6 +39,7 @@ from .data import WINDOW_SIZES
 from .model import UNet
 from .overlap import check_tile_hop
 from .streaming import separate_to_wav
+from .wiener import check_wiener_iters
 
 
 def main(argv=None):
@@ -54,7 +59,15 @@ def main(argv=None):
                         help=f"frames between tiles: {INPUT_LEN} = disjoint tiles as the reference cuts them; 64 or 32 = overlapped tiles with cross-faded masks")
     parser.add_argument("--phase_iters", type=int, default=0,
                         help="phase-refinement updates before the last inverse STFT: 0 = the mixture's phase; N > 0 = N Griffin-Lim updates (MISI with --tar_accomp)")
+    parser.add_argument("--wiener_iters", type=int, default=0,
+                        help="updates of the multichannel Wiener filter after the mask: 0 = none; 1..8 (one or two channels; not with --phase_iters)")
     args = parser.parse_args(argv)
+    try:
+        check_wiener_iters(args.wiener_iters)
+    except ValueError as e:
+        parser.error(f"--{e}")
+    if args.wiener_iters and args.phase_iters > 0:
+        parser.error("--wiener_iters and --phase_iters exclude each other: phase refinement on top of Wiener-filtered stems is out of scope")
     if args.phase_iters < 0:
         parser.error(f"--phase_iters {args.phase_iters}: must be 0 (the mixture's phase) or a positive number of updates")
     try:
@@ -95,7 +108,7 @@ def main(argv=None):
         frames, channels = separate_to_wav(model, src, dst, vocal_solo=bool(args.vocal_solo), precision=args.precision,
                                            subtype=args.subtype, keep_length=not args.no_keep_length, n_fft=args.win_size,
                                            hop=args.hop_size, dst_accomp_path=dst_accomp, tile_hop=args.tile_hop,
-                                           phase_iters=args.phase_iters)
+                                           phase_iters=args.phase_iters, wiener_iters=args.wiener_iters)
         print(f"{dst}: {frames} frames x {channels}" + ("" if dst_accomp is None else f"; {dst_accomp}: the same"))
     print("Separation finished!")
 

@@ -7,7 +7,9 @@ This is the composition of the reference's three CLI stages without the .npy rou
   inference.py      (inference.py:65-127) inference.separate's bookkeeping, kept on the device
   data.py to_wave   (data.py:151-166)     svs_istft + peak normalisation
 Channels of a stereo signal are separated independently (the reference itself downmixes to mono with
-librosa.load(mono=True), data.py:78; a stereo caller gets per-channel masks).
+librosa.load(mono=True), data.py:78; a stereo caller gets per-channel masks).  wiener_iters > 0 puts the multichannel Wiener filter
+(wiener.py) between the mask and the inverse transform: the channels' masked magnitudes then start one model of both channels, and
+the stems are re-filtered from the complex stereo mixture.
 """
 from __future__ import annotations
 
@@ -18,6 +20,7 @@ from .config import HOP_SIZE, INPUT_LEN, SAMPLE_RATE, WINDOW_SIZE
 from .data import istft_from_tiles, istft_stems_from_tiles, stft_to_tiles
 from .overlap import blend_masks, check_tile_hop, overlap_tiles
 from .rephase import check_phase_iters, refine_phase
+from .wiener import check_wiener_iters, wiener_filter
 
 
 @torch.no_grad()
@@ -63,7 +66,8 @@ def separate_spectrogram_device(model, mag: torch.Tensor, seg_len: int = INPUT_L
 @torch.no_grad()
 def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
                       peak: float | None = 0.9, max_batch: int = 256, precision: str | None = None, sr_in: int | None = None,
-                      sr_out: int | None = None, both_stems: bool = False, tile_hop: int = INPUT_LEN, phase_iters: int = 0):
+                      sr_out: int | None = None, both_stems: bool = False, tile_hop: int = INPUT_LEN, phase_iters: int = 0,
+                      wiener_iters: int = 0):
     """float32 samples (n,) or (channels, n) on the GPU -> separated samples (hop*(T-1),) or (channels, hop*(T-1)).
     both_stems: return (2, ...) stacked [vocal, accompaniment] -- what vocal_solo=True and vocal_solo=False return -- from ONE
     forward transform, one set of network forwards and one inverse launch (data.istft_stems_from_tiles); vocal_solo is
@@ -83,13 +87,28 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     phase_iters: 0 (the default) writes the masked magnitude with the mixture's phase, as the reference does.  N > 0 refines the phase
     between the mask and the last inverse (rephase.refine_phase): N Griffin-Lim updates on the requested stem, or, with both_stems,
     N MISI updates that also hand each stem half of what the two fail to add up to; the stems then come from two single-stem
-    inverse launches, each with its own phase."""
+    inverse launches, each with its own phase.
+    wiener_iters: 0 (the default) makes exactly the calls above.  N in 1..8 runs the multichannel Wiener filter after the mask (the
+    cross-faded one of tile_hop included; wiener.wiener_filter): N updates of a local Gaussian model of the two sources -- a power
+    per bin and a spatial covariance per frequency, over one or two channels -- then the stems re-filtered from the complex
+    mixture, each with magnitudes and phases of its own, and one inverse launch per requested stem (both_stems: two; else the one
+    vocal_solo names).  The stems are on ONE scale for both channels (each channel's maximum relative to the larger), so the
+    stereo balance of the mixture is kept and the two stems add up to the mixture but for the regulariser; peak and sr_out apply
+    afterwards as before.  One channel is the power-ratio Wiener filter.  More than two channels, and phase_iters > 0 beside
+    it (MISI on top of Wiener stems is not built), raise ValueError before any device work."""
     if tile_hop != INPUT_LEN:
         check_tile_hop(tile_hop, INPUT_LEN)
     phase_iters = check_phase_iters(phase_iters)
+    wiener_iters = check_wiener_iters(wiener_iters)
     squeeze = y.dim() == 1
     if squeeze:
         y = y[None]
+    if wiener_iters:
+        if phase_iters:
+            raise ValueError(f"wiener_iters {wiener_iters} with phase_iters {phase_iters}: phase refinement (Griffin-Lim / MISI) on top of Wiener-"
+                             "filtered stems is out of scope; use one of the two")
+        if y.shape[0] > 2:
+            raise ValueError(f"wiener_iters {wiener_iters} with {y.shape[0]} channels: the multichannel Wiener filter is built for 1 or 2 channels")
     if sr_in is not None and sr_in != SAMPLE_RATE:
         from .resample import resample_poly_gpu
         y = resample_poly_gpu(y.contiguous().float(), SAMPLE_RATE, sr_in)
@@ -114,7 +133,13 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
         model.train(was_training)
     if tile_hop != INPUT_LEN:
         mask = blend_masks(mask, n_tiles, tile_hop)              # back to one mask value per frame, in the layout of `tiles`
-    if phase_iters and both_stems:                               # MISI: each stem ends with its own phase, so two single-stem inverses
+    if wiener_iters:                                             # stems with magnitudes and phases of their own: one inverse per stem
+        want = (0, 1) if both_stems else ((0,) if vocal_solo else (1,))
+        smag, sphase = wiener_filter(tiles, mask.view(tiles.shape), phase, norm, T, wiener_iters, stems=want)
+        out = torch.stack([istft_from_tiles(smag[s], None, sphase[s], T, n_fft=n_fft, hop=hop, peak=None if sr_out is not None else peak)
+                           for s in range(len(want))])
+        out = out.view(len(want) * C, out.shape[2])
+    elif phase_iters and both_stems:                             # MISI: each stem ends with its own phase, so two single-stem inverses
         ymix = y[:, :hop * (T - 1)].float().clone(memory_format=torch.contiguous_format)
         for c in range(C):                                       # the mixture at the scale of the tiles: one pass per call, not per iteration
             _lib.check(L.svs_scale_by_inv(ymix[c].data_ptr(), ymix.shape[1], norm[c:].data_ptr(), 1.0, _lib.stream_ptr()), "svs_scale_by_inv")
@@ -166,7 +191,7 @@ def separated_frames(n_source: int, sr: int, hop: int = HOP_SIZE):
 @torch.no_grad()
 def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = True, precision: str | None = None,
                     subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
-                    dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN, phase_iters: int = 0):
+                    dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN, phase_iters: int = 0, wiener_iters: int = 0):
     """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
     the PCM is copied as the file stores it, resample.resample_poly_gpu (no downmix) brings every channel to SAMPLE_RATE,
     separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
@@ -178,7 +203,12 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     same pass (separate_waveform(both_stems=True)): dst_path then holds the vocal whatever vocal_solo says, and each file is
     encoded with its own common gain at peak 0.9.  tile_hop: separate_waveform's (overlapped tiles with cross-faded masks when it
     is below INPUT_LEN).  phase_iters: separate_waveform's (Griffin-Lim updates of the written stem's phase, MISI updates with
-    dst_accomp_path).  Returns the (frames, channels) written (per file)."""
+    dst_accomp_path).  wiener_iters: separate_waveform's (the multichannel Wiener filter after the mask, for files of one or two
+    channels; the written stems keep the mixture's stereo balance, one gain per file).  Returns the (frames, channels) written
+    (per file)."""
+    if check_wiener_iters(wiener_iters) and phase_iters:
+        raise ValueError(f"wiener_iters {wiener_iters} with phase_iters {phase_iters}: phase refinement (Griffin-Lim / MISI) on top of Wiener-filtered "
+                         "stems is out of scope; use one of the two")
     from fractions import Fraction
 
     import numpy as np
@@ -200,7 +230,7 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     y = resample_poly_gpu(pcm, fr.numerator, fr.denominator, channels=channels, downmix=False)
     y = y[None] if y.dim() == 1 else y                            # (channels, n) at the network rate
     sep = separate_waveform(model, y, vocal_solo=vocal_solo, n_fft=n_fft, hop=hop, peak=None, precision=precision,
-                            both_stems=dst_accomp_path is not None, tile_hop=tile_hop, phase_iters=phase_iters)
+                            both_stems=dst_accomp_path is not None, tile_hop=tile_hop, phase_iters=phase_iters, wiener_iters=wiener_iters)
     for stem, path in ((sep, dst_path),) if dst_accomp_path is None else ((sep[0], dst_path), (sep[1], dst_accomp_path)):
         enc = resample_encode_gpu(stem, fr.denominator, fr.numerator, fmt=subtype, peak=0.9, common_gain=True)
         if keep_length:
