@@ -407,6 +407,44 @@ def test_dec_block_bwd(B, H, W, C, N, Ho, Wo, report):
     assert report(f"dec_bwd_bias B{B} {H}x{W} C{C} N{N}", relerr(db, b.grad), 2e-5)
 
 
+@pytest.mark.parametrize("kind,B,H,W,C,N,layout", [("enc", 2, 33, 9, 32, 64, "interleaved"), ("enc", 1, 65, 34, 16, 32, "planar"),
+                                                   ("dec", 2, 9, 3, 64, 32, "interleaved")])
+def test_block_bwd_data_accumulates_into_a_half(kind, B, H, W, C, N, layout, report):
+    """accumulate = 1 into one half of a concat gradient, as the training step calls svs_enc_block_bwd_data for the skip half
+    of dcat: channels C .. 2C-1 of every pixel (lddx = 2C, levels 2..5) or the second of two dense planes (level 1), at odd
+    sizes.  The half holds what was there plus dx; the other half keeps its bits."""
+    x = rnd((B, C, H, W), 64).double().requires_grad_(True)
+    if kind == "enc":
+        w = rnd((N, C, 5, 5), 65, -0.1, 0.1).double()
+        y = F.conv2d(x, w, None, stride=2, padding=2)
+    else:
+        w = rnd((C, N, 5, 5), 65, -0.1, 0.1).double()
+        y = F.conv_transpose2d(x, w, None, stride=2, padding=2)        # Ho = 2H - 1, Wo = 2W - 1
+    Ho, Wo = y.shape[-2:]
+    dy = rnd(tuple(y.shape), 66)
+    y.backward(dy.double())
+    before = rnd((2, B, H, W, C) if layout == "planar" else (B, H, W, 2, C), 67)
+    both = before.to(DEV)
+    half = 1 if layout == "planar" else (slice(None),) * 3 + (1,)
+    ldd, offset = (C, B * H * W * C) if layout == "planar" else (2 * C, C)
+    dyd = nhwc(dy).to(DEV)
+    if kind == "enc":
+        wp = pack_parity(w.float())
+        ws = ws_tensor(L().svs_dec_block_workspace_bytes(B, Ho, Wo, N, H, W, C))
+        fn = L().svs_enc_block_bwd_data
+    else:
+        wp = pack_gather(w.float())
+        ws = ws_tensor(L().svs_enc_block_workspace_bytes(B, Ho, Wo, N, C))
+        fn = L().svs_dec_block_bwd_data
+    _lib.check(fn(dyd.data_ptr(), N, B, Ho, Wo, N, wp.data_ptr(), both.data_ptr() + 4 * offset, ldd, H, W, C, 1,
+                  ws.data_ptr(), ws.numel(), S()))
+    got = both.cpu()
+    other = 0 if layout == "planar" else (slice(None),) * 3 + (0,)
+    assert torch.equal(got[other], before[other]), "the other half was written"
+    want = before[half].double() + nhwc(x.grad)
+    assert report(f"{kind}_bwd_data accumulate {layout} B{B} {H}x{W} C{C} N{N}", relerr(got[half], want), 2e-5)
+
+
 @pytest.mark.parametrize("kind,B,H,W,C,N", [("enc", 16, 8, 4, 64, 128), ("enc", 32, 16, 16, 32, 128), ("dec", 16, 4, 2, 256, 128),
                                             ("dec", 16, 8, 8, 128, 64)])
 def test_wgrad_padding_skip(kind, B, H, W, C, N, report, tune):

@@ -278,8 +278,9 @@ def test_production_kernels_at_batch_32(report, tune):
         d = (named[n] - named_plain[n]).norm().item() / max(named_plain[n].norm().item(), 1e-12)
         # two fp32 evaluation orders of the same step: the first layers' gradients pass through all 22 BatchNorm /
         # conv backward stages and carry the rounding noise measured for the reference itself (its fp32 run deviates from
-        # its fp64 run by up to 3e-3 per tensor); observed here: up to 3.7e-3 on the encoder weights.  Every
-        # kernel involved is checked on its own against fp64 to 2e-5 in test_gpu_ops.py; an indexing error would show as O(1)
+        # its fp64 run by up to 3e-3 per tensor); observed here: up to 3.7e-3 on the encoder weights.  What
+        # this bound cannot see -- one stage of the step a few 1e-5 off -- is test_gpu_train_stages.py's to catch: every stage
+        # of a step, in the forms the step calls, against fp64 on its own inputs; an indexing error would show as O(1)
         assert report(f"B32 grad {n}: production vs plain kernels", d, 1e-2)
     st = uo.to_torch_state(synth.closed_form_state(trained_stats=False))
     opt = uo.new_adam_state(st)
