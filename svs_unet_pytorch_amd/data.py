@@ -52,6 +52,30 @@ def _check_window(n_fft: int, hop: int):
 # ------------------------------------------------------------------------------------------------
 # GPU signal path
 # ------------------------------------------------------------------------------------------------
+def phase_floats(phase: torch.Tensor) -> torch.Tensor:
+    """complex64 phasors -> the contiguous float32 (..., 2) tensor of the same values that the kernels read (a view if it can be)."""
+    return torch.view_as_real(phase.contiguous()).contiguous()
+
+
+def _scale_rows(rows, numer, *, partials=None, ws=None, maxima=None):
+    """Scale every row of the 2-D view `rows` (contiguous rows) by numer / its maximum, in place and row by row (data.py:84-85,
+    105, 162-164) -> the (n_rows,) float32 maxima on the device.  Row r's maximum is svs_max over partials[r], the per-block
+    partials a transform wrote; or svs_absmax over the row itself, with the workspace `ws`; or maxima[r], which the caller
+    holds already.  numer None only reduces (`rows` may then be None beside partials)."""
+    L = _lib.lib()
+    n_rows = (partials if rows is None else rows).shape[0]
+    if maxima is None:
+        maxima = torch.empty(n_rows, dtype=torch.float32, device=(partials if rows is None else rows).device)
+    for r in range(n_rows):
+        if partials is not None:
+            _lib.check(L.svs_max(partials[r].data_ptr(), partials.shape[1], maxima[r:].data_ptr(), _lib.stream_ptr()), "svs_max")
+        elif ws is not None:
+            _lib.check(L.svs_absmax(rows[r].data_ptr(), rows.shape[1], maxima[r:].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "svs_absmax")
+        if numer is not None:
+            _lib.check(L.svs_scale_by_inv(rows[r].data_ptr(), rows.shape[1], maxima[r:].data_ptr(), float(numer), _lib.stream_ptr()), "svs_scale_by_inv")
+    return maxima
+
+
 def stft_magphase(y: torch.Tensor, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE):
     """float32 (n,) on the GPU -> (mag float32 (n_fft/2+1,T), phase complex64 (n_fft/2+1,T)), both on the GPU."""
     _check_window(n_fft, hop)                  # (the buffers below are sized by n_fft before the library sees it)
@@ -76,7 +100,7 @@ def istft(mag: torch.Tensor, phase: torch.Tensor, n_fft: int = WINDOW_SIZE, hop:
     if nbin != n_fft // 2 + 1 or tuple(phase.shape) != (nbin, T):
         raise ValueError(f"istft: magnitude {tuple(mag.shape)} / phase {tuple(phase.shape)} are not ({n_fft // 2 + 1}, T) for n_fft = {n_fft}")
     is_angle = not torch.is_complex(phase)
-    ph = phase.contiguous().float() if is_angle else torch.view_as_real(phase.contiguous().to(torch.complex64)).contiguous()
+    ph = phase.contiguous().float() if is_angle else phase_floats(phase.to(torch.complex64))
     y = torch.empty(hop * max(T - 1, 0), dtype=torch.float32, device=mag.device)
     ws = torch.empty(int(L.svs_istft_workspace_bytes(n_fft, hop, T)) + 4096, dtype=torch.uint8, device=mag.device)
     if is_angle:
@@ -87,9 +111,7 @@ def istft(mag: torch.Tensor, phase: torch.Tensor, n_fft: int = WINDOW_SIZE, hop:
     _lib.check(L.svs_istft_tiles_n(mag.data_ptr(), nbin * T, T, nbin, 0, None, 0, src.data_ptr(), mode, 1, n_fft, hop, T, y.data_ptr(), None,
                                    _lib.stream_ptr()), "svs_istft_tiles_n")
     if peak is not None:
-        pk = torch.empty(1, dtype=torch.float32, device=mag.device)
-        _lib.check(L.svs_absmax(y.data_ptr(), y.numel(), pk.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "svs_absmax")
-        _lib.check(L.svs_scale_by_inv(y.data_ptr(), y.numel(), pk.data_ptr(), float(peak), _lib.stream_ptr()), "svs_scale_by_inv")
+        _scale_rows(y[None], peak, ws=ws)
     return y
 
 
@@ -123,10 +145,7 @@ def stft_to_tiles(y: torch.Tensor, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE
     part = torch.empty((C, groups), dtype=torch.float32, device=y.device)
     _lib.check(L.svs_stft_tiles_n(y.data_ptr(), n, C, n_fft, hop, tiles.data_ptr(), n_tiles * rows * seg, seg, rows, 1, n_tiles * seg,
                                   phase.data_ptr(), 1, part.data_ptr(), _lib.stream_ptr()), "svs_stft_tiles_n")
-    peak = torch.empty(C, dtype=torch.float32, device=y.device)
-    for c in range(C):
-        _lib.check(L.svs_max(part[c].data_ptr(), groups, peak[c:].data_ptr(), _lib.stream_ptr()), "svs_max")
-    return tiles, torch.view_as_complex(phase), peak, T
+    return tiles, torch.view_as_complex(phase), _scale_rows(None, None, partials=part), T
 
 
 def istft_from_tiles(tiles: torch.Tensor, mask, phase_fm: torch.Tensor, frames: int, invert: bool = False,
@@ -136,7 +155,7 @@ def istft_from_tiles(tiles: torch.Tensor, mask, phase_fm: torch.Tensor, frames: 
     _check_window(n_fft, hop)
     L = _lib.lib()
     C, n_tiles, _, rows, seg = tiles.shape
-    ph = torch.view_as_real(phase_fm.contiguous()).contiguous()
+    ph = phase_floats(phase_fm)
     y = torch.empty((C, hop * max(frames - 1, 0)), dtype=torch.float32, device=tiles.device)
     groups = int(L.svs_istft_groups_n(n_fft, hop, max(frames, 1), C))
     part = torch.empty((C, groups), dtype=torch.float32, device=tiles.device) if peak is not None else None
@@ -144,10 +163,7 @@ def istft_from_tiles(tiles: torch.Tensor, mask, phase_fm: torch.Tensor, frames: 
                                    1 if invert else 0, ph.data_ptr(), 1, C, n_fft, hop, frames, y.data_ptr(),
                                    None if part is None else part.data_ptr(), _lib.stream_ptr()), "svs_istft_tiles_n")
     if peak is not None:
-        pk = torch.empty(C, dtype=torch.float32, device=tiles.device)
-        for c in range(C):
-            _lib.check(L.svs_max(part[c].data_ptr(), groups, pk[c:].data_ptr(), _lib.stream_ptr()), "svs_max")
-            _lib.check(L.svs_scale_by_inv(y[c].data_ptr(), y.shape[1], pk[c:].data_ptr(), float(peak), _lib.stream_ptr()), "svs_scale_by_inv")
+        _scale_rows(y, peak, partials=part)
     return y
 
 
@@ -161,7 +177,7 @@ def istft_stems_from_tiles(tiles: torch.Tensor, mask: torch.Tensor, phase_fm: to
         raise ValueError("istft_stems_from_tiles: the mask is required (both stems come from it)")
     L = _lib.lib()
     C, n_tiles, _, rows, seg = tiles.shape
-    ph = torch.view_as_real(phase_fm.contiguous()).contiguous()
+    ph = phase_floats(phase_fm)
     n_out = hop * max(frames - 1, 0)
     y = torch.empty((2, C, n_out), dtype=torch.float32, device=tiles.device)
     groups = int(L.svs_istft_stems_groups_n(n_fft, hop, max(frames, 1), C))
@@ -170,11 +186,7 @@ def istft_stems_from_tiles(tiles: torch.Tensor, mask: torch.Tensor, phase_fm: to
                                    frames, y.data_ptr(), C * n_out, None if part is None else part.data_ptr(), _lib.stream_ptr()),
                "svs_istft_stems_n")
     if peak is not None:
-        pk = torch.empty((2, C), dtype=torch.float32, device=tiles.device)
-        for s in range(2):
-            for c in range(C):
-                _lib.check(L.svs_max(part[s, c].data_ptr(), groups, pk[s, c:].data_ptr(), _lib.stream_ptr()), "svs_max")
-                _lib.check(L.svs_scale_by_inv(y[s, c].data_ptr(), n_out, pk[s, c:].data_ptr(), float(peak), _lib.stream_ptr()), "svs_scale_by_inv")
+        _scale_rows(y.view(2 * C, n_out), peak, partials=part.view(2 * C, groups))
     return y
 
 
@@ -204,16 +216,22 @@ def load_wav_mono(path: str, sr: int, device=None):
     return np.ascontiguousarray(data, dtype=np.float32)
 
 
-def _load_wav_mono_device(path: str, sr: int, device) -> torch.Tensor:
+def read_pcm(path: str):
+    """wav file -> (rate, samples, channels) for the device kernels, which convert 16- and 32-bit PCM themselves: those stay as the
+    file stores them, everything else becomes float32 on the host.  samples: (frames,) or (frames, channels)."""
     from scipy.io import wavfile
-    from .resample import resample_poly_gpu
     rate, data = wavfile.read(path)
     if data.dtype.kind == "u":                                 # 8-bit files: offset binary, converted on the host
         data = (data.astype(np.float32) - 128.0) / 128.0
     elif data.dtype not in (np.int16, np.int32):               # float files (and int64, which wavfile never returns)
         data = data.astype(np.float32)
-    channels = data.shape[1] if data.ndim == 2 else 1
-    pcm = torch.from_numpy(np.ascontiguousarray(data)).to(device)
+    return rate, np.ascontiguousarray(data), data.shape[1] if data.ndim == 2 else 1
+
+
+def _load_wav_mono_device(path: str, sr: int, device) -> torch.Tensor:
+    from .resample import resample_poly_gpu
+    rate, data, channels = read_pcm(path)
+    pcm = torch.from_numpy(data).to(device)
     fr = Fraction(sr, rate)                                    # 1/1 (rate == sr): the call only converts and downmixes
     return resample_poly_gpu(pcm, fr.numerator, fr.denominator, channels=channels, downmix=True)
 
@@ -256,9 +274,7 @@ def to_spec(args, device):
             on_gpu = getattr(args, "resample", "cpu") == "gpu"
             y_mix = load_wav_mono(mix_path, args.sr, device if on_gpu else None)
             spec_mix, _ = stft_magphase(y_mix if on_gpu else torch.from_numpy(y_mix).to(device), args.win_size, args.hop_size)
-            norm = torch.empty(1, dtype=torch.float32, device=device)     # max magnitude, 0 -> 1 (data.py:84-85)
-            _lib.check(_lib.lib().svs_absmax(spec_mix.data_ptr(), spec_mix.numel(), norm.data_ptr(), ws.data_ptr(), ws.numel(),
-                                             _lib.stream_ptr()), "svs_absmax")
+            norm = _scale_rows(spec_mix.view(1, -1), None, ws=ws)          # max magnitude, 0 -> 1 (data.py:84-85)
             for wav_file, folder in TRACK_MAP.items():
                 track = os.path.join(song_path, wav_file)
                 if not os.path.exists(track):
@@ -271,8 +287,7 @@ def to_spec(args, device):
                     y = y[: len(y_mix)] if len(y) > len(y_mix) else np.pad(y, (0, len(y_mix) - len(y)))   # data.py:97-98
                     y = torch.from_numpy(y).to(device)
                 spec, phase = stft_magphase(y, args.win_size, args.hop_size)
-                _lib.check(_lib.lib().svs_scale_by_inv(spec.data_ptr(), spec.numel(), norm.data_ptr(), 1.0, _lib.stream_ptr()),
-                           "svs_scale_by_inv")
+                _scale_rows(spec.view(1, -1), 1.0, maxima=norm)
                 base = f"{num2str(audio_idx)}_{song}"
                 np.save(os.path.join(args.tar, folder, f"{base}_spec.npy"), spec.cpu().numpy())
                 np.save(os.path.join(args.tar, folder, f"{base}_phase.npy"), phase.cpu().numpy())

@@ -21,10 +21,9 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib
 from .config import INPUT_LEN
 from .model import UNet
-from .overlap import blend_masks, check_tile_hop, overlap_tiles
+from .overlap import check_tile_hop
 
 
 def segment_plan(n_frames: int, seg_len: int = INPUT_LEN):
@@ -41,42 +40,27 @@ def segment_plan(n_frames: int, seg_len: int = INPUT_LEN):
 @torch.no_grad()
 def separate(model: UNet, mix_spec, seg_len: int = INPUT_LEN, vocal_solo: bool = True, max_batch: int = 256,
              tile_hop: int | None = None):
-    """(F+1, T) mixture magnitude (numpy or tensor) -> (F+1, T) float32 numpy array.
-    tile_hop: None (the default) or seg_len = disjoint seg_len-frame tiles, whatever seg_len is; below seg_len: overlapped tiles every
-    tile_hop frames with cross-faded masks (overlap.py)."""
-    if tile_hop is None:
-        tile_hop = seg_len
-    if tile_hop != seg_len:
-        check_tile_hop(tile_hop, seg_len)
-    dev = model._flat.device
+    """(F+1, T) mixture magnitude (numpy or tensor) -> (F+1, T) float32 numpy array, or None for a spectrogram with no frames:
+    the host wrapper of streaming.separate_spectrogram_device, whose arguments these are."""
+    from .streaming import separate_spectrogram_device
     spec = torch.as_tensor(np.asarray(mix_spec)).to(torch.float32)
-    crop = spec[1:, :]
-    F_, T = crop.shape
-    plan = segment_plan(T, seg_len)
-    if not plan:
+    if spec.shape[1] == 0:
         return None
-    n = len(plan)
-    padded = torch.zeros((F_, n * seg_len), dtype=torch.float32)
-    padded[:, :T] = crop
-    tiles = padded.view(F_, n, seg_len).permute(1, 0, 2).contiguous().unsqueeze(1).to(dev)     # (n,1,F,L)
-    out = torch.empty_like(tiles)
-    was_training = model.training
-    model.eval()
-    if tile_hop != seg_len:                        # overlapped tiles -> masks -> out = mix * cross-faded mask, one launch
-        ov = overlap_tiles(tiles.view(1, n, 1, F_, seg_len), tile_hop)
-        masks = torch.empty_like(ov)
-        for s in range(0, ov.shape[0], max_batch):
-            masks[s:s + max_batch] = model(ov[s:s + max_batch])
-        blend_masks(masks, n, tile_hop, mix=tiles.view(1, n, 1, F_, seg_len), invert=not vocal_solo, out=out.view(1, n, 1, F_, seg_len))
-    else:
-        for s in range(0, n, max_batch):
-            t = tiles[s:s + max_batch]
-            mask = model(t)
-            _lib.check(_lib.lib().svs_apply_mask(t.data_ptr(), mask.data_ptr(), out[s:s + max_batch].data_ptr(), t.numel(),
-                                                 0 if vocal_solo else 1, _lib.stream_ptr()), "svs_apply_mask")
-    model.train(was_training)
-    full = out[:, 0].permute(1, 0, 2).reshape(F_, n * seg_len)[:, :T].cpu()
-    return torch.cat([torch.zeros((1, T), dtype=torch.float32), full], dim=0).numpy()
+    return separate_spectrogram_device(model, spec.to(model._flat.device), seg_len, vocal_solo, max_batch, tile_hop).cpu().numpy()
+
+
+def load_checkpoint_model(path: str, device):
+    """A UNet on `device` in eval mode with the checkpoint's model_state_dict; a checkpoint that does not load is reported and
+    ends the process with status 1 (inference.py:49-51)."""
+    model = UNet().to(device)
+    try:
+        checkpoint = torch.load(path, map_location=device)
+        if isinstance(checkpoint, dict) and "model_state_dict" in checkpoint:
+            model.load_state_dict(checkpoint["model_state_dict"])
+    except Exception as e:
+        print(f"Failed to load the model: {e}")
+        sys.exit(1)
+    return model.eval()
 
 
 def main(argv=None):
@@ -100,15 +84,7 @@ def main(argv=None):
     device = torch.device("cuda")
     print(f"Inference using device: {device}")
 
-    model = UNet().to(device)
-    try:
-        checkpoint = torch.load(args.model_path, map_location=device)
-        if isinstance(checkpoint, dict) and "model_state_dict" in checkpoint:
-            model.load_state_dict(checkpoint["model_state_dict"])
-    except Exception as e:      # inference.py:49-51
-        print(f"Failed to load the model: {e}")
-        sys.exit(1)
-    model.eval()
+    model = load_checkpoint_model(args.model_path, device)
 
     files = sorted(f for f in os.listdir(args.mixture_folder) if f.endswith("_spec.npy"))[:20]   # inference.py:58-59
     print(f"Found {len(files)} files, separating...")

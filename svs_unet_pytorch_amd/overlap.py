@@ -41,15 +41,22 @@ def overlap_count(n_tiles: int, seg: int, tile_hop: int) -> int:
     return n
 
 
+def check_tile_layout(who: str, tiles):
+    """(channels, n_tiles, rows, seg) of data.stft_to_tiles' layout; raises ValueError in the caller's name for anything else."""
+    import torch
+    if tiles.dim() != 5 or tiles.shape[2] != 1 or tiles.dtype != torch.float32 or not tiles.is_contiguous():
+        raise ValueError(f"{who}: expected contiguous float32 (channels, n_tiles, 1, rows, seg) tiles, got {tuple(tiles.shape)} {tiles.dtype}")
+    C, n_tiles, _, rows, seg = tiles.shape
+    return C, n_tiles, rows, seg
+
+
 def overlap_tiles(tiles, tile_hop: int):
     """(channels, n_tiles, 1, rows, seg) contiguous float32 tiles on the GPU (data.stft_to_tiles) -> (channels * n_ov, 1, rows, seg):
     overlapped tile j of a channel holds frames [j * tile_hop, j * tile_hop + seg).  One launch."""
     import torch
 
     from . import _lib
-    if tiles.dim() != 5 or tiles.shape[2] != 1 or tiles.dtype != torch.float32 or not tiles.is_contiguous():
-        raise ValueError(f"overlap_tiles: expected contiguous float32 (channels, n_tiles, 1, rows, seg) tiles, got {tuple(tiles.shape)} {tiles.dtype}")
-    C, n_tiles, _, rows, seg = tiles.shape
+    C, n_tiles, rows, seg = check_tile_layout("overlap_tiles", tiles)
     n_ov = overlap_count(n_tiles, seg, tile_hop)
     out = torch.empty((C * n_ov, 1, rows, seg), dtype=torch.float32, device=tiles.device)
     _lib.check(_lib.lib().svs_overlap_tiles(tiles.data_ptr(), n_tiles * rows * seg, C, n_tiles, rows, seg, int(tile_hop), out.data_ptr(),

@@ -76,7 +76,7 @@ def refine_phase(tiles, mask, phase, frames: int, iters: int, *, stems: int, inv
     import torch
 
     from . import _lib
-    from .data import _check_window
+    from .data import _check_window, phase_floats
     iters = check_phase_iters(iters)
     _check_stems(stems, mix)
     _check_window(n_fft, hop)
@@ -100,7 +100,7 @@ def refine_phase(tiles, mask, phase, frames: int, iters: int, *, stems: int, inv
         _lib.check(L.svs_istft_tiles_n(tiles.data_ptr(), n_tiles * rows * seg, seg, rows, 1, mask.data_ptr(), inv[s], phasors.data_ptr(), 1,
                                        C, n_fft, hop, frames, x[s].data_ptr(), None, _lib.stream_ptr()), "svs_istft_tiles_n")
 
-    first = torch.view_as_real(phase.contiguous()).contiguous()
+    first = phase_floats(phase)
     for s in range(stems):
         inverse(s, first)
     for it in range(iters):

@@ -36,10 +36,9 @@ import torch
 
 from .config import HOP_SIZE, INPUT_LEN, WINDOW_SIZE
 from .data import WINDOW_SIZES
-from .model import UNet
+from .inference import load_checkpoint_model
 from .overlap import check_tile_hop
-from .streaming import separate_to_wav
-from .wiener import check_wiener_iters
+from .streaming import check_refinement, separate_to_wav
 
 
 def main(argv=None):
@@ -62,14 +61,12 @@ def main(argv=None):
     parser.add_argument("--wiener_iters", type=int, default=0,
                         help="updates of the multichannel Wiener filter after the mask: 0 = none; 1..8 (one or two channels; not with --phase_iters)")
     args = parser.parse_args(argv)
-    try:
-        check_wiener_iters(args.wiener_iters)
-    except ValueError as e:
-        parser.error(f"--{e}")
-    if args.wiener_iters and args.phase_iters > 0:
-        parser.error("--wiener_iters and --phase_iters exclude each other: phase refinement on top of Wiener-filtered stems is out of scope")
     if args.phase_iters < 0:
         parser.error(f"--phase_iters {args.phase_iters}: must be 0 (the mixture's phase) or a positive number of updates")
+    try:
+        check_refinement(args.phase_iters, args.wiener_iters)
+    except ValueError as e:
+        parser.error(f"--{e}")
     try:
         check_tile_hop(args.tile_hop, INPUT_LEN)
     except ValueError as e:
@@ -85,15 +82,7 @@ def main(argv=None):
         print("separate.py needs a ROCm device (hand-written gfx950 kernels, no CPU path).")
         sys.exit(1)
     device = torch.device("cuda")
-    model = UNet().to(device)
-    try:                                                        # as inference.py loads it
-        checkpoint = torch.load(args.model_path, map_location=device)
-        if isinstance(checkpoint, dict) and "model_state_dict" in checkpoint:
-            model.load_state_dict(checkpoint["model_state_dict"])
-    except Exception as e:
-        print(f"Failed to load the model: {e}")
-        sys.exit(1)
-    model.eval()
+    model = load_checkpoint_model(args.model_path, device)
 
     if os.path.isdir(args.src):
         os.makedirs(args.tar, exist_ok=True)

@@ -40,9 +40,9 @@ def check_wiener_iters(wiener_iters: int) -> int:
 
 def _check_tiles(who, tiles, phase, frames):
     import torch
-    if tiles.dim() != 5 or tiles.shape[2] != 1 or tiles.dtype != torch.float32 or not tiles.is_contiguous():
-        raise ValueError(f"{who}: expected contiguous float32 (channels, n_tiles, 1, rows, seg) tiles, got {tuple(tiles.shape)} {tiles.dtype}")
-    C, n_tiles, _, rows, seg = tiles.shape
+
+    from .overlap import check_tile_layout
+    C, n_tiles, rows, seg = check_tile_layout(who, tiles)
     if C not in (1, 2):
         raise ValueError(f"{who}: {C} channels: the filter is built for 1 or 2")
     if n_tiles != -(-int(frames) // seg):
@@ -50,11 +50,6 @@ def _check_tiles(who, tiles, phase, frames):
     if tuple(phase.shape) != (C, frames, rows + 1) or phase.dtype != torch.complex64:
         raise ValueError(f"{who}: phase {tuple(phase.shape)} {phase.dtype} is not complex64 (channels, frames, rows + 1) = {(C, frames, rows + 1)}")
     return C, n_tiles, rows, seg
-
-
-def _phase_floats(phase):
-    import torch
-    return torch.view_as_real(phase.contiguous()).contiguous()
 
 
 def wiener_model(tiles, mask, phase, scale, frames: int, prev=None, eps: float = EPS, reg: float = REG, out=None):
@@ -66,6 +61,7 @@ def wiener_model(tiles, mask, phase, scale, frames: int, prev=None, eps: float =
     import torch
 
     from . import _lib
+    from .data import phase_floats
     C, n_tiles, rows, seg = _check_tiles("wiener_model", tiles, phase, frames)
     if prev is None and mask is None:
         raise ValueError("wiener_model: the first update needs the mask")
@@ -79,7 +75,7 @@ def wiener_model(tiles, mask, phase, scale, frames: int, prev=None, eps: float =
     L = _lib.lib()
     ws = torch.empty(int(L.svs_wiener_workspace_bytes(C, rows, seg, frames)), dtype=torch.uint8, device=tiles.device)
     v_prev, R_prev = (None, None) if prev is None else prev
-    _lib.check(L.svs_wiener_model(tiles.data_ptr(), one, seg, rows, _lib.ptr(mask), _phase_floats(phase).data_ptr(), scale.data_ptr(), C,
+    _lib.check(L.svs_wiener_model(tiles.data_ptr(), one, seg, rows, _lib.ptr(mask), phase_floats(phase).data_ptr(), scale.data_ptr(), C,
                                   frames, _lib.ptr(v_prev), one, _lib.ptr(R_prev), float(eps), float(reg), v.data_ptr(), one, R.data_ptr(),
                                   ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "svs_wiener_model")
     return v, R
@@ -93,6 +89,7 @@ def wiener_stems(tiles, phase, scale, frames: int, model, stems=(0, 1), reg: flo
     import torch
 
     from . import _lib
+    from .data import phase_floats
     C, n_tiles, rows, seg = _check_tiles("wiener_stems", tiles, phase, frames)
     stems = tuple(stems)
     if stems not in ((0,), (1,), (0, 1)):
@@ -102,7 +99,7 @@ def wiener_stems(tiles, phase, scale, frames: int, model, stems=(0, 1), reg: flo
     S = len(stems)
     mags = torch.empty((S, C, n_tiles, 1, rows, seg), dtype=torch.float32, device=tiles.device)
     ph = torch.empty((S, C, frames, rows + 1, 2), dtype=torch.float32, device=tiles.device)
-    _lib.check(_lib.lib().svs_wiener_stems(tiles.data_ptr(), one, seg, rows, _phase_floats(phase).data_ptr(), scale.data_ptr(), C, frames,
+    _lib.check(_lib.lib().svs_wiener_stems(tiles.data_ptr(), one, seg, rows, phase_floats(phase).data_ptr(), scale.data_ptr(), C, frames,
                                            v.data_ptr(), one, R.data_ptr(), float(reg), 2 if S == 2 else stems[0], mags.data_ptr(), one,
                                            C * one, ph.data_ptr(), C * frames * (rows + 1) * 2, _lib.stream_ptr()), "svs_wiener_stems")
     return mags, torch.view_as_complex(ph)

@@ -264,6 +264,50 @@ def test_default_is_disjoint_tiles_at_any_seg_len(seg_len):
     assert np.array_equal(inference.separate(model, mag_np, seg_len=seg_len, tile_hop=seg_len // 2), half.cpu().numpy())
 
 
+def test_remainder_batches_through_the_spectrogram_path():
+    """max_batch that does not divide the tiles: 128 rows, 300 frames at seg_len 64 are 5 tiles, batches of 2, 2 and 1.  Bit-equal
+    to the model on those three slices and ONE svs_apply_mask over all five, on the device and through the host wrapper.  (Nothing
+    is compared across max_batch values: the layers' plans, and with them the bits of the masks, depend on the batch size.)"""
+    from svs_unet_pytorch_amd import inference
+    from svs_unet_pytorch_amd.streaming import separate_spectrogram_device
+    model = random_model()
+    rows, T, seg_len, max_batch = 128, 300, 64, 2
+    mag_np = synth.uniform(17, (rows + 1) * T, offset=seg_len).reshape(rows + 1, T)
+    mag = torch.from_numpy(mag_np).to(DEV)
+    n = -(-T // seg_len)
+    assert n == 5
+    pad = np.zeros((rows, n * seg_len), np.float32)
+    pad[:, :T] = mag_np[1:]
+    tiles = torch.from_numpy(np.ascontiguousarray(pad.reshape(rows, n, seg_len).transpose(1, 0, 2))).to(DEV).unsqueeze(1)
+    with torch.no_grad():
+        batches = [model(tiles[s:s + max_batch]) for s in range(0, n, max_batch)]
+    assert [b.shape[0] for b in batches] == [2, 2, 1]
+    masks = torch.cat(batches)
+    for solo in (True, False):
+        want = torch.empty_like(tiles)
+        _lib.check(L().svs_apply_mask(tiles.data_ptr(), masks.data_ptr(), want.data_ptr(), tiles.numel(), 0 if solo else 1, S()), "svs_apply_mask")
+        want = want[:, 0].permute(1, 0, 2).reshape(rows, n * seg_len)[:, :T]
+        got = separate_spectrogram_device(model, mag, seg_len=seg_len, vocal_solo=solo, max_batch=max_batch)
+        assert got.shape == (rows + 1, T) and torch.all(got[0] == 0) and torch.equal(got[1:], want)
+        host = inference.separate(model, mag_np, seg_len=seg_len, vocal_solo=solo, max_batch=max_batch)
+        assert host.dtype == np.float32 and np.array_equal(host, got.cpu().numpy())
+    assert not model.training and model.eval_precision == "fp32"
+
+
+def test_remainder_batches_through_the_waveform_path():
+    """The same through separate_waveform: 10 overlapped tiles at tile_hop 64 in batches of 4, 4 and 2, bit-equal to the composition
+    with those batches, for one stem and for both."""
+    from svs_unet_pytorch_amd.streaming import separate_waveform
+    model, y = random_model(), stereo()
+    tiles, phase, T, masks, mask = compose(64, max_batch=4)
+    assert masks.shape[0] == 10
+    one = separate_waveform(model, y, n_fft=N_FFT, hop=HOP, peak=None, tile_hop=64, max_batch=4)
+    assert one.shape == (2, HOP * 300) and torch.equal(one, svs_data.istft_from_tiles(tiles, mask, phase, T, n_fft=N_FFT, hop=HOP))
+    both = separate_waveform(model, y, n_fft=N_FFT, hop=HOP, peak=None, both_stems=True, tile_hop=64, max_batch=4)
+    assert both.shape == (2, 2, HOP * 300) and torch.equal(both, svs_data.istft_stems_from_tiles(tiles, mask, phase, T, n_fft=N_FFT, hop=HOP))
+    assert not model.training and model.eval_precision == "fp32"
+
+
 def test_the_option_does_something():
     """(5) tile_hop = 64 changes the output, and leaves the mask of the song's first and last 64 frames bit for bit what disjoint
     tiles give: overlapped tile 0 is disjoint tile 0 and the last overlapped tile is the last disjoint one, and one tile covers

@@ -219,6 +219,39 @@ def test_default_tile_hop_is_the_tile_length():
         assert inspect.signature(fn).parameters["tile_hop"].default == INPUT_LEN == 128, fn.__name__
 
 
+def test_a_failing_forward_leaves_the_model_as_it_came():
+    """The network stage restores the caller's mode and precision in `finally`: a model in training mode at fp32 whose forward raises
+    is in training mode at fp32 afterwards, through separate_spectrogram_device and through its host wrapper inference.separate.
+    CPU tensors and disjoint tiles: the forward raises before any library call."""
+    import torch
+
+    from svs_unet_pytorch_amd import inference, streaming
+
+    class Stub:
+        def __init__(self):
+            self.training, self.eval_precision, self.calls = True, "fp32", 0
+            self._flat = torch.zeros(1)
+
+        def eval(self):
+            return self.train(False)
+
+        def train(self, mode=True):
+            self.training = mode
+            return self
+
+        def __call__(self, tiles):
+            self.calls += 1
+            assert not self.training and tiles.shape == (2, 1, 256, 128)
+            raise RuntimeError("the forward failed")
+
+    mag = torch.rand(257, 130)
+    for call in (lambda m: streaming.separate_spectrogram_device(m, mag), lambda m: inference.separate(m, mag.numpy())):
+        stub = Stub()
+        with pytest.raises(RuntimeError, match="the forward failed"):
+            call(stub)
+        assert stub.calls == 1 and stub.training is True and stub.eval_precision == "fp32"
+
+
 def test_python_check_names_the_rule():
     for hop in (128, 64, 32, 16):
         assert ov.check_tile_hop(hop, 128) == hop

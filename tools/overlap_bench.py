@@ -12,7 +12,6 @@ line."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -24,39 +23,7 @@ from svs_unet_pytorch_amd import _lib, synth  # noqa: E402
 from svs_unet_pytorch_amd import data as svs_data  # noqa: E402
 from svs_unet_pytorch_amd import overlap as ov  # noqa: E402
 from svs_unet_pytorch_amd.config import INPUT_LEN  # noqa: E402
-
-
-def stats(v):
-    return dict(median_ms=round(statistics.median(v), 5), min_ms=round(min(v), 5), max_ms=round(max(v), 5))
-
-
-def timed_pair(fa, fb, reps, warmup=5):
-    """Median and spread (ms) of fa and fb, alternating a / b inside every repetition."""
-    for _ in range(warmup):
-        fa()
-        fb()
-    torch.cuda.synchronize()
-    ta, tb = [], []
-    for i in range(reps):
-        first, second = (fa, fb) if i % 2 == 0 else (fb, fa)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record()
-        first()
-        ev[1].record()
-        second()
-        ev[2].record()
-        torch.cuda.synchronize()
-        t1, t2 = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
-        ta.append(t1 if i % 2 == 0 else t2)
-        tb.append(t2 if i % 2 == 0 else t1)
-    return stats(ta), stats(tb)
-
-
-def copy_of(nbytes):
-    """A torch device copy that moves `nbytes` in all: nbytes / 2 read and nbytes / 2 written."""
-    src = torch.rand(nbytes // 8, device="cuda")
-    dst = torch.empty_like(src)
-    return lambda: dst.copy_(src)
+from tools._benchlib import closed_form_model, copy_of, timed, timed_pair  # noqa: E402
 
 
 def kernel_rows(y, reps):
@@ -88,28 +55,14 @@ def kernel_rows(y, reps):
 
 
 def end_to_end_rows(y, reps):
-    from svs_unet_pytorch_amd.model import UNet
     from svs_unet_pytorch_amd.streaming import separate_waveform
-    model = UNet()
-    model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.closed_form_state().items()})
-    model.to("cuda").eval()
+    model = closed_form_model()
     frames = 1 + y.shape[1] // 768
     n_tiles = -(-frames // INPUT_LEN)
     for precision in ("fp32", "bf16"):
         base = None
         for tile_hop in (128, 64, 32):
-            for _ in range(2):
-                separate_waveform(model, y, precision=precision, tile_hop=tile_hop)
-            torch.cuda.synchronize()
-            t = []
-            for _ in range(reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                separate_waveform(model, y, precision=precision, tile_hop=tile_hop)
-                e1.record()
-                torch.cuda.synchronize()
-                t.append(e0.elapsed_time(e1))
-            s = stats(t)
+            s = timed(lambda: separate_waveform(model, y, precision=precision, tile_hop=tile_hop), reps)
             base = s["median_ms"] if base is None else base
             n_net = y.shape[0] * ov.overlap_count(n_tiles, INPUT_LEN, tile_hop)
             yield dict(kind="end_to_end", precision=precision, tile_hop=tile_hop, n_fft=1024, hop=768, channels=y.shape[0],

@@ -16,7 +16,6 @@ import datetime
 import itertools
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -26,38 +25,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from svs_unet_pytorch_amd import _lib, synth  # noqa: E402
 from svs_unet_pytorch_amd.config import INPUT_LEN  # noqa: E402
+from tools._benchlib import closed_form_model, timed, timed_pair  # noqa: E402
 
 WINDOWS = (512, 1024, 2048)
 
 
 def geometries():
     return [(n_fft, hop) for n_fft in WINDOWS for hop in (3 * n_fft // 4, n_fft // 4)]
-
-
-def stats(v):
-    return dict(median_ms=round(statistics.median(v), 5), min_ms=round(min(v), 5), max_ms=round(max(v), 5))
-
-
-def timed_pair(fa, fb, reps, warmup=5):
-    """Median and spread (ms) of fa and fb, alternating a / b inside every repetition."""
-    for _ in range(warmup):
-        fa()
-        fb()
-    torch.cuda.synchronize()
-    ta, tb = [], []
-    for i in range(reps):
-        first, second = (fa, fb) if i % 2 == 0 else (fb, fa)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record()
-        first()
-        ev[1].record()
-        second()
-        ev[2].record()
-        torch.cuda.synchronize()
-        t1, t2 = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
-        ta.append(t1 if i % 2 == 0 else t2)
-        tb.append(t2 if i % 2 == 0 else t1)
-    return stats(ta), stats(tb)
 
 
 def kernel_rows(y, reps):
@@ -97,27 +71,13 @@ def kernel_rows(y, reps):
 
 
 def end_to_end_rows(y, reps):
-    from svs_unet_pytorch_amd.model import UNet
     from svs_unet_pytorch_amd.streaming import separate_waveform
-    model = UNet()
-    model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.closed_form_state().items()})
-    model.to("cuda").eval()
+    model = closed_form_model()
     for (n_fft, hop), precision, both in itertools.product(geometries(), ("fp32", "bf16"), (False, True)):
         base = None
         for iters in (0, 2, 4):
             kw = dict(n_fft=n_fft, hop=hop, precision=precision, both_stems=both, phase_iters=iters)
-            for _ in range(2):
-                separate_waveform(model, y, **kw)
-            torch.cuda.synchronize()
-            t = []
-            for _ in range(reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                separate_waveform(model, y, **kw)
-                e1.record()
-                torch.cuda.synchronize()
-                t.append(e0.elapsed_time(e1))
-            s = stats(t)
+            s = timed(lambda: separate_waveform(model, y, **kw), reps)
             base = s["median_ms"] if base is None else base
             yield dict(kind="end_to_end", n_fft=n_fft, hop=hop, precision=precision, both_stems=both, phase_iters=iters, channels=y.shape[0],
                        samples_per_channel=y.shape[1], frames=1 + y.shape[1] // hop, separate_waveform=s,

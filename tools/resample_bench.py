@@ -111,12 +111,9 @@ def record(args, rate):
     rec["speedup_device_resident"] = rec["host_s"] / (rec["gpu_ms"] / 1e3)
     rec["speedup_from_host_memory"] = rec["host_h2d_s"] / (rec["gpu_h2d_ms"] / 1e3)
     if rate == 44100 and not args.no_separate:
-        from svs_unet_pytorch_amd import synth
-        from svs_unet_pytorch_amd.model import UNet
         from svs_unet_pytorch_amd.streaming import separate_waveform
-        model = UNet()
-        model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.closed_form_state().items()})
-        model.to(dev).eval()
+        from tools._benchlib import closed_form_model
+        model = closed_form_model(dev)
         planar = np.ascontiguousarray((pcm.astype(np.float32) / 32768.0).T)               # (2, n) float32 at the file rate
         planar_dev = torch.from_numpy(planar).to(dev)
 

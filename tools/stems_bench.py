@@ -11,7 +11,6 @@ import argparse
 import ctypes
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -22,29 +21,7 @@ sys.path.insert(0, ROOT)
 from svs_unet_pytorch_amd import _lib, synth  # noqa: E402
 from svs_unet_pytorch_amd import data as svs_data  # noqa: E402
 from svs_unet_pytorch_amd.config import SAMPLE_RATE  # noqa: E402
-
-
-def timed_pair(fa, fb, reps, warmup=5):
-    """Median and spread (ms) of fa and fb, alternating a / b inside every repetition."""
-    for _ in range(warmup):
-        fa()
-        fb()
-    torch.cuda.synchronize()
-    ta, tb = [], []
-    for i in range(reps):                                        # a b, b a, a b, ...: neither side always finds the other's cache lines
-        first, second = (fa, fb) if i % 2 == 0 else (fb, fa)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record()
-        first()
-        ev[1].record()
-        second()
-        ev[2].record()
-        torch.cuda.synchronize()
-        t1, t2 = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
-        ta.append(t1 if i % 2 == 0 else t2)
-        tb.append(t2 if i % 2 == 0 else t1)
-    q = lambda v: dict(median_ms=round(statistics.median(v), 5), min_ms=round(min(v), 5), max_ms=round(max(v), 5))  # noqa: E731
-    return q(ta), q(tb)
+from tools._benchlib import closed_form_model, timed_pair  # noqa: E402
 
 
 def kernel_rows(n, reps):
@@ -55,7 +32,7 @@ def kernel_rows(n, reps):
             tiles, phase, _, T = svs_data.stft_to_tiles(y, n_fft, hop, 128)
             C, n_tiles, _, rows, seg = tiles.shape
             mask = torch.rand_like(tiles)
-            ph = torch.view_as_real(phase.contiguous()).contiguous()
+            ph = svs_data.phase_floats(phase)
             n_out = hop * (T - 1)
             out2 = torch.empty((2, C, n_out), device="cuda")
             out1 = torch.empty((2, C, n_out), device="cuda")
@@ -83,11 +60,8 @@ def kernel_rows(n, reps):
 
 
 def end_to_end_rows(n, reps):
-    from svs_unet_pytorch_amd.model import UNet
     from svs_unet_pytorch_amd.streaming import separate_waveform
-    model = UNet()
-    model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.closed_form_state().items()})
-    model.to("cuda").eval()
+    model = closed_form_model()
     y = torch.from_numpy(np.stack([synth.audio(n, 20), synth.audio(n, 21)])).to("cuda")
     for precision in ("fp32", "bf16"):
         res = {}

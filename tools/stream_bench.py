@@ -15,8 +15,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from svs_unet_pytorch_amd import synth  # noqa: E402
-from svs_unet_pytorch_amd.model import UNet  # noqa: E402
 from svs_unet_pytorch_amd.streaming import separate_waveform  # noqa: E402
+from tools._benchlib import closed_form_model  # noqa: E402
 
 
 def main():
@@ -26,9 +26,7 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"))
     a = ap.parse_args()
     n = int(a.seconds * a.rate)
-    model = UNet()
-    model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.closed_form_state().items()})
-    model.to("cuda").eval()
+    model = closed_form_model()
     y = torch.from_numpy(np.stack([synth.audio(n, 20), synth.audio(n, 21)])).to("cuda")
     for _ in range(2):
         out = separate_waveform(model, y, precision=a.precision)

@@ -34,7 +34,8 @@ sys.path.insert(0, ROOT)
 from svs_unet_pytorch_amd import synth  # noqa: E402
 from svs_unet_pytorch_amd import train as svs_train  # noqa: E402
 from svs_unet_pytorch_amd.config import HOP_SIZE, INPUT_LEN, WINDOW_SIZE  # noqa: E402
-from svs_unet_pytorch_amd.model import ALPHA_L1, ALPHA_MR, UNet  # noqa: E402
+from svs_unet_pytorch_amd.model import ALPHA_L1, ALPHA_MR  # noqa: E402
+from tools._benchlib import closed_form_model  # noqa: E402
 
 
 def write_folder(root, songs, frames):
@@ -93,9 +94,7 @@ def main():
         write_folder(root, a.songs, a.frames)
         dataset = svs_train.SpectrogramDataset(root, samples_per_song=a.samples_per_song)
         loader = Data.DataLoader(dataset, batch_size=a.batch, num_workers=2, shuffle=False, pin_memory=True)
-        model = UNet()
-        model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth.closed_form_state().items()})
-        model.to(device).eval()
+        model = closed_form_model(device)
         upload_ms, resident = clocked(lambda: svs_train.ResidentSpectrograms(dataset, device))
         torch.cuda.synchronize()
         rng = random.Random(0)
