@@ -84,6 +84,26 @@ int svs_crop_tiles(const float* mix_songs, const float* voc_songs, const int64_t
 /* The phase half of the same items (train.py:103-112): angle = np.angle(unit phasor) = atan2(im, re) as float32; the
  * resident angle buffers are then cropped with svs_crop_tiles exactly like the magnitudes (same shared start). */
 int svs_phase_angle(const float* phasor /* n complex64 */, float* angle, int64_t n, hipStream_t stream);
+/* Remix and gain augmentation of the same items (csrc/augment.hip; Uhlich et al. 2017, Open-Unmix, Demucs -- the reference's
+ * SpectrogramDataset, train.py:86-143, always pairs a song's mixture with its own vocal).  Song storage, DC-row convention,
+ * seg % 4 == 0, 16-byte-aligned outputs and right zero-padding are those of svs_crop_tiles; mix_ang / voc_ang are the resident
+ * angles of svs_phase_angle, |angle| <= pi.  Item b, element (f, t); A = song_v[b] at column start_v[b] + t, B = song_a[b] at
+ * column start_a[b] + t, every value past a song's end 0 (independently for A and B):
+ *   song_a[b] >= 0 (remix):  z = g_v V_A cis(phi_vA) + g_a (M_B cis(phi_mB) - V_B cis(phi_vB))       g_v = gain_v[b], g_a = gain_a[b]
+ *                            mix = |z|, mix_phase = atan2(Im z, Re z), voc = g_v V_A, voc_phase = phi_vA (0 where padded)
+ *   song_a[b] <  0 (gain):   mix = g_v M_A, voc = g_v V_A (one fp32 multiply each), both angles copied; gain_a[b] is not used.
+ * Mixture and vocal of a song share one norm (data.py:84-85,105), so M cis(phi_m) - V cis(phi_v) is the accompaniment's STFT and
+ * z is, frame for frame, the STFT of the re-mixed waveform.  fp32 throughout, the device library's accurate sincosf / hypotf /
+ * atan2f.  mix_ang == voc_ang == NULL is the gain-only form: every item is a gain item, song_a / start_a are never read (they must
+ * still be non-null) and the phase outputs must be NULL.  mix_phase == voc_phase == NULL: the phase tiles are not written and no
+ * atan2f is computed; mix and voc are bit for bit those of the call with phase outputs.  One angle source or one phase output
+ * alone, phase outputs without angle sources, a null table and bad geometry are SVS_ERR_INVALID before any launch.  The kernel
+ * trusts its tables as svs_crop_tiles does: song indices in range, 0 <= start <= max(T - seg, 0) (augment.crop_remix checks
+ * them on the host).  One launch writes all the tiles.  mix, voc, mix_phase, voc_phase: (B, 1, F, seg). */
+int svs_crop_remix_tiles(const float* mix_songs, const float* voc_songs, const float* mix_ang, const float* voc_ang,
+                         const int64_t* offset, const int32_t* frames, const int32_t* song_v, const int32_t* start_v,
+                         const int32_t* song_a, const int32_t* start_a, const float* gain_v, const float* gain_a, int B, int F,
+                         int seg, float* mix, float* voc, float* mix_phase, float* voc_phase, hipStream_t stream);
 int svs_dropout_mask(float* out, int B, int C, int layer, uint32_t seed, int step, int rank, hipStream_t stream);
 /* The five decoder masks of one step in one launch: out = [B*256 | B*128 | B*64 | B*32 | B*16] floats, each block
  * bit-identical to svs_dropout_mask(layer = 0..4) -- the layout svs_unet_train_* take as `drop`. */

@@ -34,6 +34,12 @@ fully convolutional, and the MR-STFT term re-synthesises its waveforms with that
 stay auraloss's).  Every file of the folder is checked against the window before anything is uploaded; checkpoints record
 `win_size` / `hop_size`, and resuming one under other flags is an error.  `separate.py --win_size W --hop_size H` takes the
 checkpoint.
+
+--augment gain|remix (default none: the path above, unchanged) cuts augmented training tiles from the same resident set
+(augment.py, csrc/augment.hip; the reference has no augmentation): a random gain per source and, for remix, the vocal of one crop
+over the accompaniment of another, formed from the complex spectra so that it is the STFT of the re-mixed audio.  --gain_range,
+--remix_prob and --augment_seed set it; an epoch's table depends on (seed, epoch) only, goes up in one copy, and each step is one
+launch.  Validation is never augmented; the checkpoint format is unchanged.
 """
 from __future__ import annotations
 
@@ -126,6 +132,16 @@ class SpectrogramDataset(Data.Dataset):
     def has_phase_files(self):
         pname = lambda n: n.replace("_spec.npy", "_phase.npy")
         return all(os.path.exists(os.path.join(d, pname(n))) for n in self.file_names for d in (self.mixture_path, self.vocal_path))
+
+
+def folder_has_phase_files(path):
+    """SpectrogramDataset.has_phase_files from the listing alone (no file is opened): every paired song of `path` has its
+    *_phase.npy in mixture/ and vocal/.  A folder that is not there has none."""
+    mixture, vocal = os.path.join(path, "mixture"), os.path.join(path, "vocal")
+    if not os.path.isdir(mixture):
+        return False
+    names = [f for f in sorted(os.listdir(mixture)) if f.endswith("_spec.npy") and os.path.exists(os.path.join(vocal, f))]
+    return all(os.path.exists(os.path.join(d, n.replace("_spec.npy", "_phase.npy"))) for n in names for d in (mixture, vocal))
 
 
 def epoch_order(n, shuffle=True, rank=0, world=1, epoch=0):
@@ -240,6 +256,24 @@ class ResidentSpectrograms:
         for i in range(0, len(order), batch_size):
             yield self.crop(*self.draw(order[i:i + batch_size]), with_phase=with_phase)
 
+    def augmented_batches(self, batch_size, rank=0, world=1, epoch=0, with_phase: bool = False, aug=None):
+        """One epoch of `batches` with gain / remix augmentation (augment.py): the same permutation and sharding of the items, each
+        item's sources, starts and gains from `augment.draw_epoch` -- a function of (aug.seed, epoch), so every rank draws the same
+        table.  The rank's whole epoch goes up in ONE pinned copy (four int32 rows and two float32 rows of one buffer, as
+        `validation_pass` uploads its pass); a batch is a slice of it and one `svs_crop_remix_tiles` launch: no per-step
+        host-to-device copy, no read-back."""
+        from . import augment
+        if aug is None or aug.mode == "none":
+            raise ValueError("augmented_batches needs augmentation settings other than 'none' (`batches` is the plain path)")
+        order = epoch_order(len(self), True, rank, world, epoch)
+        if not order:
+            return
+        drawn = augment.draw_epoch(len(self), self.frames_host, INPUT_LEN, epoch, aug.seed, aug.gain_range,
+                                   aug.remix_prob if aug.mode == "remix" else 0.0)
+        table = augment.upload_table(self, drawn, order)
+        for lo in range(0, len(order), batch_size):
+            yield augment.crop_remix(self, table, lo, min(lo + batch_size, len(order)), with_phase)
+
     def num_batches(self, batch_size, world=1):
         per_rank = (len(self) + world - 1) // world
         return (per_rank + batch_size - 1) // batch_size
@@ -308,10 +342,33 @@ def main(argv=None):
     parser.add_argument("--val_interval", type=int, default=20)
     parser.add_argument("--win_size", type=int, default=WINDOW_SIZE, help="STFT window the folders were written with (512, 1024 or 2048)")
     parser.add_argument("--hop_size", type=int, default=HOP_SIZE, help="hop the folders were written with, 1..win_size")
+    from . import augment
+    parser.add_argument("--augment", choices=augment.MODES, default="none",
+                        help="training-set augmentation, cut on the device (augment.py): gain = a random gain per item; remix = a gain per "
+                             "source and, with --remix_prob, the accompaniment of another crop under the item's vocal (needs *_phase.npy); "
+                             "validation is never augmented")
+    parser.add_argument("--gain_range", type=float, nargs=2, metavar=("LO", "HI"), default=list(augment.GAIN_RANGE),
+                        help="gains are uniform in [LO, HI] (default: Open-Unmix's 0.25 1.25)")
+    parser.add_argument("--remix_prob", type=float, default=augment.REMIX_PROB,
+                        help="share of the items whose accompaniment comes from a random crop of a random song (default 0.5: a choice, not a tuned value)")
+    parser.add_argument("--augment_seed", type=int, default=0, help="the tables of an epoch depend on (this, epoch) only")
     args = parser.parse_args(argv)
     bad = check_geometry(args.win_size, args.hop_size)          # data.py:24-25 lets both vary; before any device is touched
     if bad:
         parser.error(bad)
+    aug = None
+    if args.augment != "none":                                  # `none` reaches nothing of augment.py beyond the flags' defaults
+        bad = augment.check_settings(args.augment, args.gain_range, args.remix_prob)
+        if bad:
+            parser.error(bad)
+        loader = os.environ.get("SVS_DATA_LOADER", "resident")
+        if loader != "resident":
+            parser.error(f"--augment {args.augment}: the augmentation is cut from the HBM-resident set, SVS_DATA_LOADER={loader} has none "
+                         "(unset it, or train with --augment none)")
+        if args.augment == "remix" and not folder_has_phase_files(args.train_folder):
+            raise SystemExit(f"train.py: --augment remix needs the *_phase.npy files of every song of {args.train_folder} (the accompaniment "
+                             "is mixture minus vocal as complex spectra); --augment gain works without them")
+        aug = augment.Augment(args.augment, (float(args.gain_range[0]), float(args.gain_range[1])), float(args.remix_prob), args.augment_seed)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -401,6 +458,8 @@ def main(argv=None):
             valid_resident = ResidentSpectrograms(valid_dataset, device, with_phase=valid_dataset.with_phase)
     alpha_mr = ALPHA_MR if full else 0.0
     print(f"Objective: {ALPHA_L1} * L1" + (f" + {ALPHA_MR} * MR-STFT (train.py:296)" if full else " (L1 terms only)"))
+    if aug is not None:
+        print(aug.describe())
 
     best_val_loss = 100.0
     log_buffer = []
@@ -419,7 +478,10 @@ def main(argv=None):
         loss_sum = torch.zeros((), device=device)
         if resident is not None:
             steps = resident.num_batches(per_rank_batch, world)
-            stream = resident.batches(per_rank_batch, True, rank, world, ep, with_phase=full)
+            if aug is None:
+                stream = resident.batches(per_rank_batch, True, rank, world, ep, with_phase=full)
+            else:
+                stream = resident.augmented_batches(per_rank_batch, rank, world, ep, with_phase=full, aug=aug)
         else:
             steps = len(train_loader)
             to_dev = lambda t: t.to(device, non_blocking=True)
