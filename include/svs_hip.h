@@ -483,6 +483,30 @@ size_t svs_bss_solve_batched_workspace_bytes(int64_t nbatch, int K, int flen, in
 int svs_bss_solve_batched(const double* corr, int64_t nbatch, int K, int flen, const int64_t* gram_off,
                           const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, void* ws, size_t ws_bytes,
                           hipStream_t stream);
+/* BSS-eval images (evaluate.py: bss_eval_images -- stereo stems): the two stages above at the sizes of a stereo two-source
+ * problem, through entry points and kernels of their own; the limits of the entry points above do not change. */
+#define SVS_BSS_IMG_MAX_SIGNALS 12
+#define SVS_BSS_IMG_MAX_PAIRS 64
+#define SVS_BSS_IMG_MAX_REFS 4
+/* svs_bss_corr_windows for up to SVS_BSS_IMG_MAX_SIGNALS signals and SVS_BSS_IMG_MAX_PAIRS pairs: the same windows, the same
+ * out[w*out_stride + off_q + k], fixed-order sums, no atomics, bitwise reproducible.  The pair table is copied to the head of
+ * the workspace (pairs: HOST array, read before the call returns).  The query is 0 for invalid arguments (a signal index
+ * >= SVS_BSS_IMG_MAX_SIGNALS included) and for a grid too wide for one launch. */
+size_t svs_bss_img_corr_windows_workspace_bytes(int64_t window, int64_t nwin, int npairs, const int* pairs);
+int svs_bss_img_corr_windows(const double* x, int64_t ld, int nsig, int64_t n, int64_t window, int64_t hop, int64_t nwin,
+                             const int* pairs, int npairs, double* out, int64_t out_stride, void* ws, size_t ws_bytes,
+                             hipStream_t stream);
+/* svs_bss_solve_batched for K <= SVS_BSS_IMG_MAX_REFS reference channels (order up to 2048), the same arguments and layout,
+ * with the diagonal tile of each step factored once per system, and with rank deficiency handled on the device: with
+ * thr = K*flen * 2^-52 * (largest diagonal entry of G), a pivot d with |d| <= thr marks a column that depends on the earlier
+ * ones (identical channels, a silent channel); it is skipped, and ynorm2 is the energy of the projection on the span of the
+ * remaining columns -- the same span.  skipped[s] (device int) = number of skipped columns of system s.  A pivot below -thr
+ * (or NaN) is a failure: status[s] = 1 + the index of the first one (ynorm2 of that system is then meaningless); the
+ * factorisation goes on without faulting and no other system's result changes. */
+size_t svs_bss_img_solve_batched_workspace_bytes(int64_t nbatch, int K, int flen, int nrhs);
+int svs_bss_img_solve_batched(const double* corr, int64_t nbatch, int K, int flen, const int64_t* gram_off,
+                              const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, int* skipped, void* ws,
+                              size_t ws_bytes, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Resampling to the network rate (csrc/resample.hip): the arithmetic half of librosa.load(path, sr=8192, mono=True),

@@ -51,6 +51,27 @@ __device__ __forceinline__ int pair_of_run(const CorrArgs& a, int run) {
   return p;
 }
 
+// One staged chunk of a run: acc[j] += sum_m X[m + k0 + j] Y[m], m < BSS_T, with the run's window of X in registers.
+__device__ __forceinline__ void corr_sweep(const double* X, const double* Y, int k0, double (&acc)[BSS_RUN]) {
+  double win[BSS_RUN];
+#pragma unroll
+  for (int j = 0; j < BSS_RUN; ++j) win[j] = X[pidx(k0 + j)];
+  for (int m = 0; m < BSS_T; m += BSS_RUN) {
+    // m, k0 multiples of 8: the next window and the 8 y samples are contiguous groups of the padded layout
+    const double* xn = X + (m + k0 + BSS_RUN) / 8 * 9;
+    const double* yn = Y + m / 8 * 9;
+    double nx[BSS_RUN], y[BSS_RUN];
+#pragma unroll
+    for (int j = 0; j < BSS_RUN; ++j) { nx[j] = xn[j]; y[j] = yn[j]; }
+#pragma unroll
+    for (int t = 0; t < BSS_RUN; ++t)
+#pragma unroll
+      for (int j = 0; j < BSS_RUN; ++j) acc[j] = fma(t + j < BSS_RUN ? win[t + j] : nx[t + j - BSS_RUN], y[t], acc[j]);
+#pragma unroll
+    for (int j = 0; j < BSS_RUN; ++j) win[j] = nx[j];
+  }
+}
+
 __global__ __launch_bounds__(BSS_THREADS) void bss_corr_kernel(CorrArgs a) {
   extern __shared__ __attribute__((aligned(16))) double sig[];      // [nsig][BSS_PADLEN]
   const int tid = threadIdx.x;
@@ -81,23 +102,7 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_corr_kernel(CorrArgs a) {
     }
     __syncthreads();
     if (active) {
-      double win[BSS_RUN];
-#pragma unroll
-      for (int j = 0; j < BSS_RUN; ++j) win[j] = X[pidx(k0 + j)];
-      for (int m = 0; m < BSS_T; m += BSS_RUN) {
-        // m, k0 multiples of 8: the next window and the 8 y samples are contiguous groups of the padded layout
-        const double* xn = X + (m + k0 + BSS_RUN) / 8 * 9;
-        const double* yn = Y + m / 8 * 9;
-        double nx[BSS_RUN], y[BSS_RUN];
-#pragma unroll
-        for (int j = 0; j < BSS_RUN; ++j) { nx[j] = xn[j]; y[j] = yn[j]; }
-#pragma unroll
-        for (int t = 0; t < BSS_RUN; ++t)
-#pragma unroll
-          for (int j = 0; j < BSS_RUN; ++j) acc[j] = fma(t + j < BSS_RUN ? win[t + j] : nx[t + j - BSS_RUN], y[t], acc[j]);
-#pragma unroll
-        for (int j = 0; j < BSS_RUN; ++j) win[j] = nx[j];
-      }
+      corr_sweep(X, Y, k0, acc);
     }
   }
   if (active) {
@@ -480,4 +485,346 @@ extern "C" int svs_bss_solve_batched(const double* corr, int64_t nbatch, int K, 
   // from pageable memory: the runtime has staged `tab` by the time the copy call returns
   SVS_HIP(hipMemcpyAsync((void*)a.tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream));
   return solve_launch(a, nbatch, stream);
+}
+
+// ---- BSS-eval images: stereo stems (evaluate.py: bss_eval_images) ------------------------------
+// The same two stages at the sizes a stereo two-source problem needs -- 10 signals, about 50 pairs, 4 reference channels
+// (order 2048) -- with entry points and kernels of their own; the ones above keep their limits.
+//   bss_img_corr_kernel     the sweep of bss_corr_kernel.  The pair table no longer fits the kernel arguments, so it lives in
+//                           device memory at the head of the workspace, one int4 per thread slot.  The host packs whole
+//                           pairs into groups of 256 slots (blockIdx.y) that touch at most SVS_BSS_MAX_SIGNALS signals, and a
+//                           block stages only its group's signals: the LDS stays at the 83 KB of the kernel above and two
+//                           blocks share a CU, whatever the number of signals.
+//   bss_img_reduce_kernel   the fixed-order sum over blocks, one thread per (slot, lag of its run).
+//   bss_img_diag_kernel     factors the diagonal tile (k,k) ONCE per system and step and writes the factor back;
+//   bss_img_panel_kernel    the panel blocks then only solve X L_kk^T = A against it (bss_panel_kernel's scheme, every block
+//                           factoring the tile for itself, measured 9 % slower at order 2048: DESIGN.md section 9).
+// Rank rule (img_factor_tile): stereo images make G singular as a rule (L == R, a silent channel).  With
+// thr = order * 2^-52 * max diag G (LAPACK dpstrf's tolerance), a pivot d <= thr with |d| <= thr marks a delayed channel that
+// depends on the earlier columns: its column of L and its y component are zero, so |y|^2 is the energy of the projection on
+// the span of the remaining columns -- the same span.  A pivot below -thr (or NaN) is a failure: status = 1 + its index; the
+// column is zeroed as well, so nothing faults.  skipped[s] counts the skipped columns of system s.
+
+namespace {
+
+struct ImgCorrArgs {
+  const double* x; long ld; long n;
+  const int4* slots;      // [ngroups * 256]: {x slot | y slot << 8 in the group's staging, k0, offset of lag k0 in a window's
+                          //                   output, lags of the run that exist (0: idle slot)}
+  const int* gsig;        // [ngroups * 8]: number of staged signals, then their rows
+  double* slab; double* out;
+  long hop, window, out_stride; int chunks, gx, ngroups;
+};
+
+__global__ __launch_bounds__(BSS_THREADS) void bss_img_corr_kernel(ImgCorrArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double sig[];      // [<= SVS_BSS_MAX_SIGNALS][BSS_PADLEN]
+  const int tid = threadIdx.x, g = blockIdx.y;
+  const int4 slot = a.slots[g * BSS_THREADS + tid];
+  const bool active = slot.w > 0;
+  const int k0 = slot.y;
+  const double* X = sig + (slot.x & 0xff) * BSS_PADLEN;
+  const double* Y = sig + (slot.x >> 8) * BSS_PADLEN;
+  const int nstage = a.gsig[g * 8];
+  const int w = blockIdx.x / a.gx, bx = blockIdx.x % a.gx;
+  const long base = (long)w * a.hop;
+  const long nw = a.n - base < a.window ? a.n - base : a.window;
+  double acc[BSS_RUN];
+#pragma unroll
+  for (int j = 0; j < BSS_RUN; ++j) acc[j] = 0.0;
+  for (int c = bx; c < a.chunks; c += a.gx) {
+    const long m0 = (long)c * BSS_T;
+    __syncthreads();
+    for (int s = 0; s < nstage; ++s) {
+      const double* src = a.x + (long)a.gsig[g * 8 + 1 + s] * a.ld + base;
+      for (int i = tid; i < BSS_STAGE; i += BSS_THREADS) {
+        const long gi = m0 + i;
+        sig[s * BSS_PADLEN + pidx(i)] = gi < nw ? src[gi] : 0.0;
+      }
+    }
+    __syncthreads();
+    if (active) {
+      corr_sweep(X, Y, k0, acc);
+    }
+  }
+  if (active) {
+    double* dst = a.slab + ((((long)w * a.gx + bx) * a.ngroups + g) * BSS_THREADS + tid) * BSS_RUN;
+#pragma unroll
+    for (int j = 0; j < BSS_RUN; ++j) dst[j] = acc[j];
+  }
+}
+
+// grid: nwin * ngroups * BSS_RUN blocks; thread l of a window is lag l % 8 of slot l / 8
+__global__ __launch_bounds__(BSS_THREADS) void bss_img_reduce_kernel(ImgCorrArgs a) {
+  const int per = a.ngroups * BSS_RUN;
+  const int w = blockIdx.x / per;
+  const int l = (blockIdx.x % per) * BSS_THREADS + threadIdx.x;
+  const int4 slot = a.slots[l / BSS_RUN];
+  const int j = l % BSS_RUN;
+  if (j >= slot.w) return;
+  const long stride = (long)a.ngroups * BSS_THREADS * BSS_RUN;
+  const double* slab = a.slab + (long)w * a.gx * stride;
+  double s = 0.0;
+  for (int b = 0; b < a.gx; ++b) s += slab[b * stride + l];
+  a.out[(long)w * a.out_stride + slot.z + j] = s;
+}
+
+struct ImgCorrPlan {
+  int ngroups = 0; long lags = 0;
+  std::vector<int> slots, gsig;      // the device table: slots (4 ints per slot), then gsig
+};
+
+bool img_pairs_valid(int npairs, const int* pairs) {
+  if (npairs < 1 || npairs > SVS_BSS_IMG_MAX_PAIRS || !pairs) return false;
+  for (int q = 0; q < npairs; ++q)
+    if (pairs[3 * q] < 0 || pairs[3 * q] >= SVS_BSS_IMG_MAX_SIGNALS || pairs[3 * q + 1] < 0 ||
+        pairs[3 * q + 1] >= SVS_BSS_IMG_MAX_SIGNALS || pairs[3 * q + 2] < 1 || pairs[3 * q + 2] > SVS_BSS_MAX_LAG)
+      return false;
+  return true;
+}
+
+// Packs whole pairs into groups of at most 256 runs and SVS_BSS_MAX_SIGNALS distinct signals: a group takes the first
+// pair that is left, then, while one fits, the pair that adds the fewest new signals (the first of those).  pairs valid.
+ImgCorrPlan img_corr_plan(int npairs, const int* pairs) {
+  ImgCorrPlan p;
+  std::vector<int> off(npairs);
+  for (int q = 0; q < npairs; ++q) { off[q] = (int)p.lags; p.lags += pairs[3 * q + 2]; }
+  std::vector<bool> done(npairs, false);
+  for (int left = npairs; left > 0;) {
+    int staged[SVS_BSS_MAX_SIGNALS], nstaged = 0, used = 0;
+    auto slot_of = [&](int s) { for (int i = 0; i < nstaged; ++i) if (staged[i] == s) return i; return -1; };
+    p.slots.resize((size_t)(p.ngroups + 1) * BSS_THREADS * 4, 0);
+    for (;;) {
+      int best = -1, best_new = 3;
+      for (int q = 0; q < npairs; ++q) {
+        if (done[q] || used + (pairs[3 * q + 2] + BSS_RUN - 1) / BSS_RUN > BSS_THREADS) continue;
+        const int a = pairs[3 * q], b = pairs[3 * q + 1];
+        const int add = (slot_of(a) < 0) + (b != a && slot_of(b) < 0);
+        if (nstaged + add <= SVS_BSS_MAX_SIGNALS && add < best_new) { best = q; best_new = add; }
+      }
+      if (best < 0) break;
+      const int a = pairs[3 * best], b = pairs[3 * best + 1], nl = pairs[3 * best + 2];
+      if (slot_of(a) < 0) staged[nstaged++] = a;
+      if (slot_of(b) < 0) staged[nstaged++] = b;
+      for (int k0 = 0; k0 < nl; k0 += BSS_RUN, ++used) {
+        int* s = &p.slots[((size_t)p.ngroups * BSS_THREADS + used) * 4];
+        s[0] = slot_of(a) | slot_of(b) << 8; s[1] = k0; s[2] = off[best] + k0; s[3] = std::min(BSS_RUN, nl - k0);
+      }
+      done[best] = true;
+      --left;
+    }
+    p.gsig.push_back(nstaged);
+    for (int i = 0; i < 7; ++i) p.gsig.push_back(i < nstaged ? staged[i] : 0);
+    ++p.ngroups;
+  }
+  return p;
+}
+
+size_t img_corr_table_bytes(int ngroups) {
+  return svs_align_up((size_t)ngroups * (BSS_THREADS * 4 + 8) * sizeof(int), 256);
+}
+
+long img_corr_blocks(long window, int ngroups, long nwin) {
+  const long chunks = (window + BSS_T - 1) / BSS_T;
+  return std::min<long>(chunks, std::max<long>(1, BSS_MAX_BLOCKS / (ngroups * nwin)));
+}
+
+// 0: the arguments are invalid or the grid is too wide for one launch
+size_t img_corr_ws_bytes(long window, long nwin, const ImgCorrPlan& p) {
+  if (window < 1 || nwin < 1 || (window + BSS_T - 1) / BSS_T >= (1L << 31)) return 0;
+  const long gx = img_corr_blocks(window, p.ngroups, nwin);
+  if (nwin > BSS_MAX_GRID / gx || nwin > BSS_MAX_GRID / (p.ngroups * BSS_RUN)) return 0;
+  return img_corr_table_bytes(p.ngroups) + (size_t)nwin * gx * p.ngroups * BSS_THREADS * BSS_RUN * sizeof(double);
+}
+
+// The rank rule on the 64 x 64 tile in L (lower part), all threads of the block; col0 is the tile's first column and kf the
+// order of G (the identity padding past it is never counted).  bad: first failing column of the tile or -1; nskip: skipped.
+__device__ __forceinline__ void img_factor_tile(double (*L)[NB + 1], double thr, int col0, int kf, int& bad, int& nskip) {
+  const int tid = threadIdx.x;
+  bad = -1; nskip = 0;
+  for (int c = 0; c < NB; ++c) {
+    __syncthreads();
+    const double d = L[c][c];
+    const bool ok = d > thr;                           // false for NaN
+    if (!ok && col0 + c < kf) {
+      if (fabs(d) <= thr) ++nskip;
+      else if (bad < 0) bad = c;
+    }
+    const double piv = ok ? sqrt(d) : 0.0;
+    __syncthreads();
+    if (tid == c) L[c][c] = piv;
+    else if (tid > c && tid < NB) L[tid][c] = ok ? L[tid][c] / piv : 0.0;
+    __syncthreads();
+    for (int e = tid; e < NB * NB; e += BSS_THREADS) {
+      const int r = e / NB, q = e % NB;
+      if (q > c && r >= q) L[r][q] -= L[r][c] * L[q][c];
+    }
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ double img_threshold(const SolveArgs& a, int s) {
+  double top = 0.0;
+  for (int i = 0; i < a.K; ++i) top = fmax(top, a.corr[gram_at(a, s, i * a.K + i)]);
+  return (double)(a.K * a.flen) * 0x1p-52 * top;
+}
+
+// Step k, one block per system: factor tile (k,k) in place.
+__global__ __launch_bounds__(BSS_THREADS) void bss_img_diag_kernel(SolveArgs a, int* skipped, int k) {
+  __shared__ double L[NB][NB + 1];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const long ld = a.np;
+  double* dk = a.M + s * a.mstride + (long)k * NB * ld + (long)k * NB;
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) L[e / NB][e % NB] = dk[(e / NB) * ld + e % NB];
+  int bad, nskip;
+  img_factor_tile(L, img_threshold(a, s), k * NB, a.K * a.flen, bad, nskip);
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) dk[(e / NB) * ld + e % NB] = L[e / NB][e % NB];
+  if (tid == 0) {
+    if (bad >= 0 && a.status[s] == 0) a.status[s] = k * NB + bad + 1;
+    skipped[s] = (k ? skipped[s] : 0) + nskip;         // one block per system and step, steps in stream order
+  }
+}
+
+// Step k: tile (i, k), i > k, becomes X with X L_kk^T = A against the factor bss_img_diag_kernel left in tile (k,k); a
+// skipped column (L_kk[c][c] == 0) of X is zero.  Block index: system, then tile row.
+__global__ __launch_bounds__(BSS_THREADS) void bss_img_panel_kernel(SolveArgs a, int k) {
+  __shared__ double L[NB][NB + 1];
+  __shared__ double A[NB][NB + 1];
+  const int nt = a.rows / NB - k - 1;
+  const int s = blockIdx.x / nt;
+  const int tid = threadIdx.x, i = k + 1 + blockIdx.x % nt;
+  const long ld = a.np;
+  double* M = a.M + s * a.mstride;
+  const double* dk = M + (long)k * NB * ld + (long)k * NB;
+  double* di = M + (long)i * NB * ld + (long)k * NB;
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) {
+    L[e / NB][e % NB] = dk[(e / NB) * ld + e % NB];
+    A[e / NB][e % NB] = di[(e / NB) * ld + e % NB];
+  }
+  __syncthreads();
+  for (int c = 0; c < NB; ++c) {
+    const double piv = L[c][c];
+    if (tid < NB) A[tid][c] = piv != 0.0 ? A[tid][c] / piv : 0.0;
+    __syncthreads();
+    for (int e = tid; e < NB * NB; e += BSS_THREADS) {
+      const int r = e / NB, q = e % NB;
+      if (q > c) A[r][q] -= A[r][c] * L[q][c];
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) di[(e / NB) * ld + e % NB] = A[e / NB][e % NB];
+}
+
+// expand; per step the diagonal, the panel and the update launch; the norms -- each over all nsys systems at once
+int img_solve_launch(const SolveArgs& a, int* skipped, long nsys, hipStream_t stream) {
+  const int tc = a.np / NB, tr = a.rows / NB;
+  const int per = svs_cdiv((long)a.rows * a.np, BSS_THREADS);
+  hipLaunchKernelGGL(bss_expand_kernel, dim3((unsigned)(nsys * per)), dim3(BSS_THREADS), 0, stream, a, per);
+  SVS_CHECK_LAUNCH("bss_expand");
+  for (int k = 0; k < tc; ++k) {
+    hipLaunchKernelGGL(bss_img_diag_kernel, dim3((unsigned)nsys), dim3(BSS_THREADS), 0, stream, a, skipped, k);
+    SVS_CHECK_LAUNCH("bss_img_diag");
+    hipLaunchKernelGGL(bss_img_panel_kernel, dim3((unsigned)(nsys * (tr - k - 1))), dim3(BSS_THREADS), 0, stream, a, k);
+    SVS_CHECK_LAUNCH("bss_img_panel");
+    if (k + 1 < tc) {
+      hipLaunchKernelGGL(bss_update_kernel, dim3((unsigned)(nsys * (tc - k - 1) * (tr - k - 1))), dim3(BSS_THREADS), 0,
+                         stream, a, k);
+      SVS_CHECK_LAUNCH("bss_update");
+    }
+  }
+  hipLaunchKernelGGL(bss_norm_kernel, dim3((unsigned)(nsys * a.nrhs)), dim3(BSS_THREADS), 0, stream, a);
+  SVS_CHECK_LAUNCH("bss_norm");
+  return SVS_OK;
+}
+
+bool img_solve_shape_valid(int K, int flen, int nrhs) {
+  return K >= 1 && K <= SVS_BSS_IMG_MAX_REFS && flen >= 1 && flen <= SVS_BSS_MAX_LAG && nrhs >= 1 && nrhs <= SVS_BSS_MAX_RHS;
+}
+
+}  // namespace
+
+extern "C" size_t svs_bss_img_corr_windows_workspace_bytes(int64_t window, int64_t nwin, int npairs, const int* pairs) {
+  if (!img_pairs_valid(npairs, pairs)) return 0;
+  return img_corr_ws_bytes(window, nwin, img_corr_plan(npairs, pairs));
+}
+
+extern "C" int svs_bss_img_corr_windows(const double* x, int64_t ld, int nsig, int64_t n, int64_t window, int64_t hop,
+                                        int64_t nwin, const int* pairs, int npairs, double* out, int64_t out_stride,
+                                        void* ws, size_t ws_bytes, hipStream_t stream) {
+  SVS_REQUIRE(x && out && pairs && n >= 1 && ld >= n && nsig >= 1 && nsig <= SVS_BSS_IMG_MAX_SIGNALS && npairs >= 1 &&
+              npairs <= SVS_BSS_IMG_MAX_PAIRS, "svs_bss_img_corr_windows: bad arguments");
+  for (int q = 0; q < npairs; ++q) {
+    const int px = pairs[3 * q], py = pairs[3 * q + 1], nl = pairs[3 * q + 2];
+    SVS_REQUIRE(px >= 0 && px < nsig && py >= 0 && py < nsig && nl >= 1 && nl <= SVS_BSS_MAX_LAG,
+                "svs_bss_img_corr_windows: pair %d = (%d, %d, %d) out of range", q, px, py, nl);
+  }
+  const ImgCorrPlan p = img_corr_plan(npairs, pairs);
+  SVS_REQUIRE(window >= 1 && hop >= 1 && nwin >= 1 && out_stride >= p.lags,
+              "svs_bss_img_corr_windows: window = %ld, hop = %ld, nwin = %ld, out_stride = %ld (>= %ld lags) out of range",
+              (long)window, (long)hop, (long)nwin, (long)out_stride, p.lags);
+  const size_t need = img_corr_ws_bytes(window, nwin, p);
+  SVS_REQUIRE(need > 0, "svs_bss_img_corr_windows: %ld windows of %ld samples do not fit one launch", (long)nwin,
+              (long)window);
+  if (!ws || ws_bytes < need) {
+    svs_set_error("svs_bss_img_corr_windows: workspace too small");
+    return SVS_ERR_WORKSPACE;
+  }
+  ImgCorrArgs a{};
+  a.x = x; a.ld = ld; a.n = n; a.out = out; a.hop = hop; a.window = window; a.out_stride = out_stride;
+  a.ngroups = p.ngroups;
+  a.chunks = (int)((window + BSS_T - 1) / BSS_T);
+  a.gx = (int)img_corr_blocks(window, p.ngroups, nwin);
+  a.slots = (const int4*)ws;
+  a.gsig = (const int*)ws + (size_t)p.ngroups * BSS_THREADS * 4;
+  a.slab = (double*)((char*)ws + img_corr_table_bytes(p.ngroups));
+  // from pageable memory: the runtime has staged the tables by the time the copy calls return
+  SVS_HIP(hipMemcpyAsync((void*)a.slots, p.slots.data(), p.slots.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+  SVS_HIP(hipMemcpyAsync((void*)a.gsig, p.gsig.data(), p.gsig.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+  const int lds = SVS_BSS_MAX_SIGNALS * BSS_PADLEN * (int)sizeof(double);
+  SVS_HIP(hipFuncSetAttribute((const void*)bss_img_corr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipLaunchKernelGGL(bss_img_corr_kernel, dim3((unsigned)(nwin * a.gx), p.ngroups), dim3(BSS_THREADS), lds, stream, a);
+  SVS_CHECK_LAUNCH("bss_img_corr");
+  hipLaunchKernelGGL(bss_img_reduce_kernel, dim3((unsigned)(nwin * p.ngroups * BSS_RUN)), dim3(BSS_THREADS), 0, stream, a);
+  SVS_CHECK_LAUNCH("bss_img_reduce");
+  return SVS_OK;
+}
+
+extern "C" size_t svs_bss_img_solve_batched_workspace_bytes(int64_t nbatch, int K, int flen, int nrhs) {
+  if (!img_solve_shape_valid(K, flen, nrhs) || nbatch < 1 || nbatch > solve_max_systems(K, flen, nrhs)) return 0;
+  int np, rows;
+  solve_dims(K, flen, nrhs, np, rows);
+  return solve_table_bytes(nbatch, K, nrhs) + (size_t)nbatch * rows * np * sizeof(double);
+}
+
+extern "C" int svs_bss_img_solve_batched(const double* corr, int64_t nbatch, int K, int flen, const int64_t* gram_off,
+                                         const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, int* skipped,
+                                         void* ws, size_t ws_bytes, hipStream_t stream) {
+  SVS_REQUIRE(corr && gram_off && rhs_off && ynorm2 && status && skipped && nbatch >= 1 && img_solve_shape_valid(K, flen, nrhs),
+              "svs_bss_img_solve_batched: bad arguments");
+  SVS_REQUIRE(nbatch <= solve_max_systems(K, flen, nrhs), "svs_bss_img_solve_batched: nbatch = %ld too large for one launch",
+              (long)nbatch);
+  const int ng = K * K, nr = K * nrhs;
+  std::vector<int64_t> tab((size_t)nbatch * (ng + nr));
+  for (long s = 0; s < nbatch; ++s) {
+    for (int q = 0; q < ng; ++q) {
+      SVS_REQUIRE(gram_off[s * ng + q] >= 0, "svs_bss_img_solve_batched: negative offset (system %ld)", s);
+      tab[s * (ng + nr) + q] = gram_off[s * ng + q];
+    }
+    for (int q = 0; q < nr; ++q) {
+      SVS_REQUIRE(rhs_off[s * nr + q] >= 0, "svs_bss_img_solve_batched: negative offset (system %ld)", s);
+      tab[s * (ng + nr) + ng + q] = rhs_off[s * nr + q];
+    }
+  }
+  if (!ws || ws_bytes < svs_bss_img_solve_batched_workspace_bytes(nbatch, K, flen, nrhs)) {
+    svs_set_error("svs_bss_img_solve_batched: workspace too small");
+    return SVS_ERR_WORKSPACE;
+  }
+  SolveArgs a{};
+  a.corr = corr; a.K = K; a.flen = flen; a.nrhs = nrhs; a.status = status; a.ynorm2 = ynorm2;
+  solve_dims(K, flen, nrhs, a.np, a.rows);
+  a.tab = (const int64_t*)ws;
+  a.M = (double*)((char*)ws + solve_table_bytes(nbatch, K, nrhs));
+  a.mstride = (long)a.rows * a.np;
+  // from pageable memory: the runtime has staged `tab` by the time the copy call returns
+  SVS_HIP(hipMemcpyAsync((void*)a.tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+  return img_solve_launch(a, skipped, nbatch, stream);
 }

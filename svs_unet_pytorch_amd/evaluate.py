@@ -36,6 +36,24 @@ s_true + e_spat = P_j e, e_interf = P_all e - P_j e and e_artif = e - P_all e; t
     SAR = 10 log10( |P_all e|^2 / (|e|^2 - |P_all e|^2) )
 exactly (_metrics_from_gram).  Only correlations are computed over the track: every R and D is a lagged correlation
 C_xy[k] = sum_m x[m+k] y[m], k >= 0 (R_ij[-k] = C_ji[k], D_i(e)[p] = C_{e s_i}[p]), and |e|^2 = C_ee[0].
+
+Stereo stems (`--stereo`): `bss_eval_images` / `bss_eval_images_framewise` restate mir_eval.separation.bss_eval_images (BSS-eval
+v3 images, the measure behind the SiSEC / MUSDB figures; PARITY UNPINNED as above) for sources of shape (nsampl, nchan).  Each
+channel e_c of an estimate is projected onto ALL channels of reference source j (P_j) and of all sources (P_all) delayed by
+0 .. F-1 samples, and with s_j the true image
+    e_spat = P_j e - s_j,   e_interf = P_all e - P_j e,   e_artif = e - P_all e       (sums below over samples and channels)
+    SDR = |s_j|^2 / |e - s_j|^2,  ISR = |s_j|^2 / |e_spat|^2,  SIR = |P_j e|^2 / |e_interf|^2,  SAR = |P_all e|^2 / |e_artif|^2.
+ISR, the image-to-spatial-distortion ratio, is the figure that reacts to a wrong stereo balance or to swapped channels.
+The Gram form of the images (_image_metrics_from_gram).  Per estimate a and source j, summed over channels c:
+    E_s = sum |s_jc|^2,  E_e = sum |e_c|^2,  X = sum <s_jc, e_c>,  P1 = sum |P_j e_c|^2,  Pa = sum |P_all e_c|^2
+    SDR = E_s / (E_e - 2 X + E_s)        |e - s|^2 expanded: only lag-0 terms, no projection
+    ISR = E_s / (P1 - 2 X + E_s)         |P_j e_c - s_jc|^2 = |P_j e_c|^2 - 2 <P_j e_c, s_jc> + |s_jc|^2, and s_jc (delay 0 of
+                                         channel c of source j) lies in the span P_j projects onto, so <P_j e_c, s_jc> = <e_c, s_jc>
+    SIR = P1 / (Pa - P1),   SAR = Pa / (E_e - Pa)            the spans are nested, as in the mono case
+with every P a |y|^2 of a system whose references are the nchan (P_j) or nsrc * nchan (P_all) reference channels: order up to
+4 * 512 = 2048 for a stereo two-source problem.  Such G are singular as a rule, not as an exception -- a centre-panned vocal
+has L == R, a hard-panned stem a silent channel -- so the device factorisation skips dependent columns (include/svs_hip.h,
+svs_bss_img_solve_batched): the projection onto the remaining columns is the projection onto the same span.
 """
 from __future__ import annotations
 
@@ -51,12 +69,13 @@ import numpy as np
 
 FILTER_LEN = 512
 METRICS = ("SDR", "SIR", "SAR", "NSDR")
+IMAGE_METRICS = ("SDR", "ISR", "SIR", "SAR", "NSDR")     # --stereo: ISR between SDR and SIR
 WS_BUDGET = 1 << 30          # default workspace bytes of one batch of framewise factorisations
 MAX_BATCH = 1024             # systems per batched factorisation (the kernels' grid limit is far above this)
 
 
-def load_mono_audio(path):
-    """wav -> (float64 mono waveform, sample rate); the file's own rate is kept (evaluate.py:15-23)."""
+def load_audio_channels(path):
+    """wav -> (float64 (n, nchan) waveform, sample rate): every channel kept (a mono file is nchan 1), the file's own rate."""
     from scipy.io import wavfile
     if not os.path.exists(path):
         raise FileNotFoundError(f"File not found: {path}")
@@ -67,9 +86,13 @@ def load_mono_audio(path):
         data = (data.astype(np.float64) - 128.0) / 128.0
     else:
         data = data.astype(np.float64)
-    if data.ndim == 2:
-        data = data.mean(axis=1)
-    return data, sr
+    return (data[:, np.newaxis] if data.ndim == 1 else data), sr
+
+
+def load_mono_audio(path):
+    """wav -> (float64 mono waveform, sample rate); the file's own rate is kept (evaluate.py:15-23)."""
+    data, sr = load_audio_channels(path)
+    return (data[:, 0] if data.shape[1] == 1 else data.mean(axis=1)), sr
 
 
 def _project(reference_sources, estimated_source, flen):
@@ -214,10 +237,10 @@ def compute_frame_metrics_for_track(mix_path, vocal_ref_path, vocal_est_path, wi
     return frames
 
 
-def frame_summary(frames):
+def frame_summary(frames, metrics=METRICS):
     """The NaN-ignoring median of each metric over a track's frames and the number of valid frames (SDR not NaN)."""
     out = {}
-    for k in METRICS:
+    for k in metrics:
         v = np.asarray(frames[k], dtype=np.float64)
         v = v[~np.isnan(v)]
         out[k] = float(np.median(v)) if v.size else float("nan")
@@ -496,8 +519,377 @@ def _vocal_metrics_gpu(mix, vocal_ref, vocal_est, window, hop, compute_permutati
     return _frames(sdr, sir, sar, sdr_mix, hop)
 
 
+# ---- stereo: BSS-eval images ------------------------------------------------------------------
+
+def _project_images(reference_channels, estimated_channels, flen):
+    """_project for images: every row of estimated_channels (nchan, nsampl) projected onto all rows of reference_channels
+    (R, nsampl) delayed by 0 .. flen-1 samples; (nchan, nsampl + flen - 1)."""
+    from scipy.linalg import toeplitz
+    from scipy.signal import fftconvolve
+    nref, nsampl = reference_channels.shape
+    nchan = estimated_channels.shape[0]
+    refs = np.hstack((reference_channels, np.zeros((nref, flen - 1))))
+    est = np.hstack((estimated_channels, np.zeros((nchan, flen - 1))))
+    n_fft = int(2 ** np.ceil(np.log2(nsampl + flen - 1.0)))
+    sf = np.fft.fft(refs, n=n_fft, axis=1)
+    sef = np.fft.fft(est, n=n_fft, axis=1)
+    G = np.zeros((nref * flen, nref * flen))
+    for i in range(nref):
+        for j in range(i + 1):
+            ssf = np.real(np.fft.ifft(sf[i] * np.conj(sf[j])))
+            ss = toeplitz(np.hstack((ssf[0], ssf[-1:-flen:-1])), r=ssf[:flen])
+            G[i * flen:(i + 1) * flen, j * flen:(j + 1) * flen] = ss
+            G[j * flen:(j + 1) * flen, i * flen:(i + 1) * flen] = ss.T
+    D = np.zeros((nref * flen, nchan))
+    for k in range(nref):
+        for c in range(nchan):
+            ssef = np.real(np.fft.ifft(sf[k] * np.conj(sef[c])))
+            D[k * flen:(k + 1) * flen, c] = np.hstack((ssef[0], ssef[-1:-flen:-1]))
+    try:
+        C = np.linalg.solve(G, D)
+    except np.linalg.LinAlgError:
+        C = np.linalg.lstsq(G, D, rcond=None)[0]
+    C = C.reshape(flen, nref, nchan, order="F")
+    sproj = np.zeros((nchan, nsampl + flen - 1))
+    for k in range(nref):
+        for c in range(nchan):
+            sproj[c] += fftconvolve(C[:, k, c], refs[k])[:nsampl + flen - 1]
+    return sproj
+
+
+def _decompose_images(reference_sources, estimated_source, j, flen):
+    """estimate (nsampl, nchan) = s_true + e_spat + e_interf + e_artif with respect to the image of reference source j of
+    reference_sources (nsrc, nsampl, nchan); each part (nchan, nsampl + flen - 1)."""
+    nsrc, nsampl, nchan = reference_sources.shape
+    est = estimated_source.T
+    s_true = np.hstack((reference_sources[j].T, np.zeros((nchan, flen - 1))))
+    e_spat = _project_images(reference_sources[j].T, est, flen) - s_true
+    all_channels = reference_sources.transpose(0, 2, 1).reshape(nsrc * nchan, nsampl)
+    e_interf = _project_images(all_channels, est, flen) - s_true - e_spat
+    e_artif = -s_true - e_spat - e_interf
+    e_artif[:, :nsampl] += est
+    return s_true, e_spat, e_interf, e_artif
+
+
+def _image_criteria(s_true, e_spat, e_interf, e_artif):
+    sdr = _safe_db(np.sum(s_true ** 2), np.sum((e_spat + e_interf + e_artif) ** 2))
+    isr = _safe_db(np.sum(s_true ** 2), np.sum(e_spat ** 2))
+    sir = _safe_db(np.sum((s_true + e_spat) ** 2), np.sum(e_interf ** 2))
+    sar = _safe_db(np.sum((s_true + e_spat + e_interf) ** 2), np.sum(e_artif ** 2))
+    return sdr, isr, sir, sar
+
+
+def _images_3d(x, what):
+    x = np.asarray(x, dtype=np.float64)
+    x = x[:, :, np.newaxis] if x.ndim == 2 else x
+    if x.ndim != 3:
+        raise ValueError(f"{what} must be (nsrc, nsampl) or (nsrc, nsampl, nchan), got shape {x.shape}")
+    return x
+
+
+def _best_sir_permutation(sir):
+    """The rule of bss_eval_sources: sir[estimate, reference] -> perm with the best mean SIR."""
+    nsrc = sir.shape[1]
+    perms = list(itertools.permutations(range(nsrc)))
+    idx = np.arange(nsrc)
+    return list(perms[int(np.argmax([np.mean(sir[list(p), idx]) for p in perms]))])
+
+
+def bss_eval_images(reference_sources, estimated_sources, compute_permutation=True, flen=FILTER_LEN):
+    """(sdr, isr, sir, sar, perm) per reference source for images of shape (nsrc, nsampl, nchan), as
+    mir_eval.separation.bss_eval_images (mir_eval 0.8.2) returns them.  PARITY UNPINNED: mir_eval is not installed here;
+    this restates the published BSS-eval v3 image algorithm (Vincent et al.): every channel of the estimate is projected
+    onto all channels of the reference source (e_spat) and of all sources (e_interf) delayed by 0 .. flen-1 samples, and
+    the sums of the four ratios run over samples and channels.  perm[i] is the estimate matched to reference i."""
+    ref, est = _images_3d(reference_sources, "reference"), _images_3d(estimated_sources, "estimate")
+    if ref.shape != est.shape:
+        raise ValueError(f"reference {ref.shape} and estimate {est.shape} must have the same shape")
+    nsrc = ref.shape[0]
+    if not compute_permutation:
+        out = np.array([_image_criteria(*_decompose_images(ref, est[j], j, flen)) for j in range(nsrc)])
+        return out[:, 0], out[:, 1], out[:, 2], out[:, 3], np.arange(nsrc)
+    crit = np.empty((4, nsrc, nsrc))
+    for jest in range(nsrc):
+        for jtrue in range(nsrc):
+            crit[:, jest, jtrue] = _image_criteria(*_decompose_images(ref, est[jest], jtrue, flen))
+    popt, idx = _best_sir_permutation(crit[2]), np.arange(nsrc)
+    return crit[0][popt, idx], crit[1][popt, idx], crit[2][popt, idx], crit[3][popt, idx], np.asarray(popt)
+
+
+def _any_silent_image(images):
+    return bool(np.any(np.all(images == 0, axis=(1, 2))))
+
+
+def bss_eval_images_framewise(reference_sources, estimated_sources, window=30 * 44100, hop=15 * 44100,
+                              compute_permutation=False, flen=FILTER_LEN):
+    """(sdr, isr, sir, sar, perm), each (nsrc, nwin): bss_eval_images of every window [k*hop, k*hop + window), with the
+    rules of bss_eval_sources_framewise (PARITY UNPINNED, as there): nwin = frame_count(n, window, hop), fewer than two
+    windows score the whole signal, and a window in which a reference or an estimate source is all zeros in every channel
+    is NaN in all five outputs."""
+    ref, est = _images_3d(reference_sources, "reference"), _images_3d(estimated_sources, "estimate")
+    if ref.shape != est.shape:
+        raise ValueError(f"reference {ref.shape} and estimate {est.shape} must have the same shape")
+    window, hop = _frame_args(window, hop)
+    nsrc, n, _ = ref.shape
+    nwin = frame_count(n, window, hop)
+    if nwin < 2:
+        return tuple(np.expand_dims(v, -1) for v in bss_eval_images(ref, est, compute_permutation, flen))
+    out = tuple(np.full((nsrc, nwin), np.nan) for _ in range(5))
+    for k in range(nwin):
+        r, e = ref[:, k * hop:k * hop + window], est[:, k * hop:k * hop + window]
+        if not (_any_silent_image(r) or _any_silent_image(e)):
+            for o, v in zip(out, bss_eval_images(r, e, compute_permutation, flen)):
+                o[:, k] = v
+    return out
+
+
+def _image_metrics_from_gram(e_ref, e_est, cross, proj_one, proj_all, compute_permutation=True):
+    """(sdr, isr, sir, sar, perm) of bss_eval_images from channel-summed energies (the image formulas in the module
+    docstring).  e_ref[j] = |s_j|^2; e_est[a] = |e_a|^2; cross[a, j] = sum_c <s_jc, e_ac>; proj_one[a, j] = |P_j e_a|^2;
+    proj_all[a] = |P_all e_a|^2 (proj_one[:, 0] for one source).  Denominators that rounded to <= 0 follow _db."""
+    e_ref, e_est, cross, proj_one, proj_all = (np.asarray(v, dtype=np.float64)
+                                               for v in (e_ref, e_est, cross, proj_one, proj_all))
+    nest, nsrc = proj_one.shape
+    crit = np.empty((4, nest, nsrc))
+    for a in range(nest):
+        for j in range(nsrc):
+            p1, pa = proj_one[a, j], proj_all[a]
+            crit[0, a, j] = _db(e_ref[j], e_est[a] - 2.0 * cross[a, j] + e_ref[j])
+            crit[1, a, j] = _db(e_ref[j], p1 - 2.0 * cross[a, j] + e_ref[j])
+            crit[2, a, j] = _db(p1, pa - p1)
+            crit[3, a, j] = _db(pa, e_est[a] - pa)
+    idx = np.arange(nsrc)
+    popt = _best_sir_permutation(crit[2]) if compute_permutation else list(idx)
+    return crit[0][popt, idx], crit[1][popt, idx], crit[2][popt, idx], crit[3][popt, idx], np.asarray(popt)
+
+
+def _gpu_image_projections(sig, window, hop, nwin, solves, energies, crosses, flen, ws_budget):
+    """_gpu_window_projections through the image entry points (svs_bss_img_corr_windows, svs_bss_img_solve_batched: up to
+    4 reference rows per solve, rank-deficient Gram matrices handled on the device), with the lag-0 cross terms
+    <sig[a], sig[b]> of the row pairs `crosses` as a second result: numpy (energy (nwin, len(energies)), cross (nwin,
+    len(crosses)), [|P e|^2 (nwin, nrhs) per solve], [status (nwin,) per solve]).  A status that is not 0 marks a window
+    whose factorisation met a pivot below minus the rank tolerance (G numerically indefinite)."""
+    import torch
+    from . import _lib
+    L = _lib.lib()
+    pairs, off = [], {}
+
+    def need(a, b, nl):
+        if (a, b, nl) not in off:
+            off[(a, b, nl)] = sum(p[2] for p in pairs)
+            pairs.append((a, b, nl))
+        return off[(a, b, nl)]
+
+    plans, ycols = [], 0
+    for refs, ests in solves:
+        gram = [need(i, j, flen) for i in refs for j in refs]
+        rhs = [need(e, i, flen) for e in ests for i in refs]
+        k, nr = len(refs), len(ests)
+        nb = int(max(1, min(nwin, MAX_BATCH, ws_budget // L.svs_bss_img_solve_batched_workspace_bytes(1, k, flen, nr))))
+        plans.append((k, np.asarray(gram, dtype=np.int64), np.asarray(rhs, dtype=np.int64), nr, nb, ycols))
+        ycols += nr
+    eoff = [need(e, e, 1) for e in energies]
+    xoff = [need(a, b, 1) for a, b in crosses]
+    stride = sum(p[2] for p in pairs)
+    flat = np.asarray([v for p in pairs for v in p], dtype=np.int32)
+    dev = sig.device
+    n = sig.shape[1]
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr()
+        ws_bytes = L.svs_bss_img_corr_windows_workspace_bytes(window, nwin, len(pairs), flat.ctypes.data)
+        if ws_bytes == 0:
+            raise ValueError(f"{nwin} windows of {window} samples and {len(pairs)} pairs do not fit one correlation launch")
+        ws_bytes = max([ws_bytes] +
+                       [L.svs_bss_img_solve_batched_workspace_bytes(nb, k, flen, nr) for k, _, _, nr, nb, _ in plans])
+        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+        corr = torch.empty(nwin, stride, dtype=torch.float64, device=dev)
+        _lib.check(L.svs_bss_img_corr_windows(sig.data_ptr(), sig.stride(0), sig.shape[0], n, window, hop, nwin,
+                                              flat.ctypes.data, len(pairs), corr.data_ptr(), stride, ws.data_ptr(),
+                                              ws.numel(), stream), "svs_bss_img_corr_windows")
+        y = torch.empty(nwin * ycols, dtype=torch.float64, device=dev)
+        status = torch.empty(len(plans), nwin, dtype=torch.int32, device=dev)
+        skipped = torch.empty(len(plans), nwin, dtype=torch.int32, device=dev)
+        for s, (k, gram, rhs, nr, nb, y0) in enumerate(plans):
+            for w0 in range(0, nwin, nb):
+                b = min(nb, nwin - w0)
+                base = np.arange(w0, w0 + b, dtype=np.int64)[:, None] * stride
+                g, r = np.ascontiguousarray(base + gram), np.ascontiguousarray(base + rhs)
+                _lib.check(L.svs_bss_img_solve_batched(corr.data_ptr(), b, k, flen, g.ctypes.data, r.ctypes.data, nr,
+                                                       y[nwin * y0 + w0 * nr:].data_ptr(), status[s, w0:].data_ptr(),
+                                                       skipped[s, w0:].data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                           "svs_bss_img_solve_batched")
+        energy, cross, y, status = (t.cpu().numpy() for t in (corr[:, eoff], corr[:, xoff], y, status))
+    return (energy, cross, [y[nwin * y0:nwin * (y0 + nr)].reshape(nwin, nr) for _, _, _, nr, _, y0 in plans],
+            list(status))
+
+
+def _images_gpu(reference_sources, estimated_sources, window, hop, compute_permutation, flen, ws_budget=WS_BUDGET,
+                mix=None):
+    """((sdr, isr, sir, sar, perm), each (nsrc, nwin); image-SDR (nwin,) of `mix` ((n, nchan)) taken as the estimate of
+    source 0, or None) of nsrc = 1 or 2 images of nchan = 1 or 2 channels over the windows of _windows.  Rows of the one
+    correlation pass: reference channels (source-major), estimate channels, mixture channels."""
+    import torch
+    ref, est = (x.unsqueeze(-1) if x.dim() == 2 else x for x in map(_device_f64, (reference_sources, estimated_sources)))
+    if ref.dim() != 3 or ref.shape != est.shape:
+        raise ValueError(f"reference {tuple(ref.shape)} and estimate {tuple(est.shape)} must have the same "
+                         "(nsrc, nsampl, nchan) shape")
+    nsrc, n, nchan = ref.shape
+    if nsrc not in (1, 2) or nchan not in (1, 2):
+        raise ValueError(f"the GPU BSS-eval images handle 1 or 2 sources of 1 or 2 channels, got {nsrc} sources of "
+                         f"{nchan} channels (use bss_eval_images)")
+    if not 1 <= flen <= 512:
+        raise ValueError(f"flen = {flen}: the GPU path supports filter lengths 1 .. 512")
+    window, hop, nwin, framed = _windows(n, window, hop)
+    est = est.to(ref.device)
+    R = nsrc * nchan
+    rows = [ref.transpose(1, 2).reshape(R, n), est.transpose(1, 2).reshape(R, n)]
+    if mix is not None:
+        rows.append(_device_f64(mix).to(ref.device).reshape(n, nchan).t())
+    src = [tuple(range(j * nchan, (j + 1) * nchan)) for j in range(nsrc)]
+    ests = list(range(R, 2 * R))
+    solves = [(s, ests) for s in src] + ([(tuple(range(R)), ests)] if nsrc == 2 else [])
+    crosses = [(R + a * nchan + c, j * nchan + c) for a in range(nsrc) for j in range(nsrc) for c in range(nchan)]
+    crosses += [(2 * R + c, c) for c in range(nchan)] if mix is not None else []
+    nrows = 2 * R + (nchan if mix is not None else 0)
+    energy, cross, y, status = _gpu_image_projections(torch.cat(rows).contiguous(), window, hop, nwin, solves,
+                                                      list(range(nrows)), crosses, flen, ws_budget)
+    e_ref = energy[:, :R].reshape(nwin, nsrc, nchan).sum(axis=2)
+    e_est = energy[:, R:2 * R].reshape(nwin, nsrc, nchan).sum(axis=2)
+    x = cross[:, :nsrc * R].reshape(nwin, nsrc, nsrc, nchan).sum(axis=3)
+    proj = [v.reshape(nwin, nsrc, nchan).sum(axis=2) for v in y]
+    host = _host_windows((ref.transpose(1, 2), est.transpose(1, 2)), window, hop)      # time last, as it slices
+    out = [np.full((nsrc, nwin), np.nan) for _ in range(5)]
+    for w in range(nwin):
+        if framed and ((e_ref[w] == 0).any() or (e_est[w] == 0).any()):
+            continue
+        if any(s[w] for s in status):
+            r = bss_eval_images(*(v.transpose(0, 2, 1) for v in host(w)), compute_permutation, flen)
+        else:
+            proj_one = np.stack([proj[j][w] for j in range(nsrc)], axis=1)
+            r = _image_metrics_from_gram(e_ref[w], e_est[w], x[w], proj_one, proj[nsrc][w] if nsrc == 2 else proj_one[:, 0],
+                                         compute_permutation)
+        for o, v in zip(out, r):
+            o[:, w] = v
+    if not framed:
+        out[4] = out[4].astype(np.int64)
+    sdr_mix = None
+    if mix is not None:
+        e_mix, x_mix = energy[:, 2 * R:].sum(axis=1), cross[:, nsrc * R:].sum(axis=1)
+        sdr_mix = np.array([np.nan if framed and (e_ref[w, 0] == 0 or e_mix[w] == 0) else
+                            _db(e_ref[w, 0], e_mix[w] - 2.0 * x_mix[w] + e_ref[w, 0]) for w in range(nwin)])
+    return tuple(out), sdr_mix
+
+
+def bss_eval_images_gpu(reference_sources, estimated_sources, compute_permutation=True, flen=FILTER_LEN):
+    """bss_eval_images on the GPU (numpy or torch inputs, nsrc and nchan 1 or 2, flen <= 512): the same (sdr, isr, sir,
+    sar, perm).  Rank-deficient images (identical or silent channels) are handled on the device; a numerically indefinite
+    Gram matrix makes the call return the numpy bss_eval_images result, with a RuntimeWarning."""
+    out, _ = _images_gpu(reference_sources, estimated_sources, None, None, compute_permutation, flen)
+    return tuple(v[:, 0] for v in out)
+
+
+def bss_eval_images_framewise_gpu(reference_sources, estimated_sources, window=30 * 44100, hop=15 * 44100,
+                                  compute_permutation=False, flen=FILTER_LEN, ws_budget=WS_BUDGET):
+    """bss_eval_images_framewise on the GPU (nsrc and nchan 1 or 2, flen <= 512): the same (sdr, isr, sir, sar, perm)."""
+    return _images_gpu(reference_sources, estimated_sources, window, hop, compute_permutation, flen, ws_budget)[0]
+
+
+def _stereo_2d(x, what):
+    x = np.asarray(x, dtype=np.float64) if not hasattr(x, "dim") else x
+    x = x[:, None] if len(x.shape) == 1 else x
+    if len(x.shape) != 2:
+        raise ValueError(f"{what} must be (n,) or (n, nchan), got shape {tuple(x.shape)}")
+    return x
+
+
+def _image_sdr_direct(ref, est):
+    """10 log10(|s|^2 / |e - s|^2) over samples and channels: the image SDR, which needs no projection."""
+    return _safe_db(np.sum(ref ** 2), np.sum((est - ref) ** 2))
+
+
+def _vocal_image_frames(mix, vocal_ref, vocal_est, window, hop, compute_permutation, device, ws_budget=WS_BUDGET):
+    """Frames {"SDR", "ISR", "SIR", "SAR", "NSDR", "start"} of the vocal over the windows of _windows, for (n, nchan)
+    waveforms: the problem (vocal, mix - vocal) against (estimate, mix - estimate)."""
+    mix, vocal_ref, vocal_est = _stereo_2d(mix, "mix"), _stereo_2d(vocal_ref, "vocal"), _stereo_2d(vocal_est, "estimate")
+    if not (tuple(mix.shape) == tuple(vocal_ref.shape) == tuple(vocal_est.shape)):
+        raise ValueError(f"mix {tuple(mix.shape)}, vocal {tuple(vocal_ref.shape)} and estimate {tuple(vocal_est.shape)} "
+                         "must have one (n, nchan) shape")
+    n = mix.shape[0]
+    w_, h_, nwin, framed = _windows(n, window, hop)
+    if device == "gpu":
+        m, v, ve = _device_f64(mix), _device_f64(vocal_ref), _device_f64(vocal_est)
+        v, ve = v.to(m.device), ve.to(m.device)
+        import torch
+        out, sdr_mix = _images_gpu(torch.stack([v, m - v]), torch.stack([ve, m - ve]), window if framed else None, hop,
+                                   compute_permutation, FILTER_LEN, ws_budget, mix=m)
+    elif device == "cpu":
+        ref, est = np.stack([vocal_ref, mix - vocal_ref]), np.stack([vocal_est, mix - vocal_est])
+        if framed:
+            out = bss_eval_images_framewise(ref, est, w_, h_, compute_permutation, FILTER_LEN)
+        else:
+            out = tuple(np.expand_dims(v, -1) for v in bss_eval_images(ref, est, compute_permutation, FILTER_LEN))
+        sdr_mix = np.full(nwin, np.nan)
+        for w in range(nwin):
+            s, m = vocal_ref[w * h_:w * h_ + w_], mix[w * h_:w * h_ + w_]
+            if not (framed and (not s.any() or not m.any())):
+                sdr_mix[w] = _image_sdr_direct(s, m)
+    else:
+        raise ValueError(f"device must be 'cpu' or 'gpu', got {device!r}")
+    sdr, isr, sir, sar, perm = out
+    sel = [0 if np.isnan(perm[0, w]) else int(perm[0, w]) for w in range(nwin)]     # estimate matched to the vocal
+    pick = lambda v: np.array([v[sel[w], w] for w in range(nwin)])
+    sdr = pick(sdr)
+    return {"SDR": sdr, "ISR": pick(isr), "SIR": pick(sir), "SAR": pick(sar), "NSDR": sdr - sdr_mix,
+            "start": np.arange(nwin) * h_}
+
+
+def image_metrics_from_waveforms(mix, vocal_ref, vocal_est, device="cpu"):
+    """{"SDR", "ISR", "SIR", "SAR", "NSDR"} of the vocal image for (n, nchan) waveforms (a 1-D array is nchan 1):
+    bss_eval_images of (vocal, mix - vocal) against (estimate, mix - estimate), with the permutation;
+    NSDR = SDR - image-SDR of the mixture taken as the vocal estimate (lag-0 terms only: no projection)."""
+    frames = _vocal_image_frames(mix, vocal_ref, vocal_est, None, None, True, device)
+    return {k: float(frames[k][0]) for k in IMAGE_METRICS}
+
+
+def image_metrics_from_waveforms_framewise(mix, vocal_ref, vocal_est, window, hop, device="cpu", ws_budget=WS_BUDGET):
+    """Framewise image_metrics_from_waveforms: 1-D arrays over the windows of bss_eval_images_framewise plus "start",
+    scored without a permutation; NSDR is NaN where the vocal or the mixture is silent."""
+    _frame_args(window, hop)
+    return _vocal_image_frames(mix, vocal_ref, vocal_est, window, hop, False, device, ws_budget)
+
+
+def _load_track_channels(mix_path, vocal_ref_path, vocal_est_path):
+    mix, sr_mix = load_audio_channels(mix_path)
+    vocal_ref, sr_ref = load_audio_channels(vocal_ref_path)
+    vocal_est, sr_est = load_audio_channels(vocal_est_path)
+    if not (sr_mix == sr_ref == sr_est):
+        raise ValueError(f"Sample rate mismatch: mix={sr_mix}, ref={sr_ref}, est={sr_est}")
+    if not (mix.shape[1] == vocal_ref.shape[1] == vocal_est.shape[1]):
+        raise ValueError(f"Channel count mismatch: mix={mix.shape[1]}, ref={vocal_ref.shape[1]}, est={vocal_est.shape[1]}")
+    if mix.shape[1] > 2:
+        raise ValueError(f"--stereo scores 1 or 2 channels, got {mix.shape[1]}")
+    n = min(len(mix), len(vocal_ref), len(vocal_est))
+    return mix[:n], vocal_ref[:n], vocal_est[:n], sr_mix
+
+
+def compute_image_metrics_for_track(mix_path, vocal_ref_path, vocal_est_path, device="cpu"):
+    """compute_metrics_for_track without the downmix: image_metrics_from_waveforms of the files' channels."""
+    mix, vocal_ref, vocal_est, _ = _load_track_channels(mix_path, vocal_ref_path, vocal_est_path)
+    return image_metrics_from_waveforms(mix, vocal_ref, vocal_est, device)
+
+
+def compute_image_frame_metrics_for_track(mix_path, vocal_ref_path, vocal_est_path, window_s, hop_s=None, device="cpu"):
+    """compute_frame_metrics_for_track without the downmix (image_metrics_from_waveforms_framewise)."""
+    mix, vocal_ref, vocal_est, sr = _load_track_channels(mix_path, vocal_ref_path, vocal_est_path)
+    window = frame_samples(window_s, sr)
+    hop = frame_samples(window_s if hop_s is None else hop_s, sr)
+    frames = image_metrics_from_waveforms_framewise(mix, vocal_ref, vocal_est, window, hop, device)
+    frames["start_s"] = frames["start"] / sr
+    return frames
+
+
 def main(argv=None):
-    parser = argparse.ArgumentParser(description="Evaluate SVS results with SDR / SIR / SAR / NSDR (vocal only).")
+    parser =argparse.ArgumentParser(description="Evaluate SVS results with SDR / SIR / SAR / NSDR (vocal only).")
     parser.add_argument("--est", type=str, required=True, help="folder of predicted vocal wav files")
     parser.add_argument("--mix", type=str, required=True, help="folder of mixture wav files")
     parser.add_argument("--ref", type=str, required=True, help="folder of reference vocal wav files")
@@ -512,7 +904,13 @@ def main(argv=None):
                         help="hop between frames (default: the window)")
     parser.add_argument("--frames_csv", type=str, default=None, metavar="PATH",
                         help="write every frame: track, frame, start_s, SDR, SIR, SAR, NSDR")
+    parser.add_argument("--stereo", action="store_true",
+                        help="score the files' channels as images (BSS-eval images, no downmix): adds ISR, the figure "
+                             "that reacts to a wrong stereo balance")
     args = parser.parse_args(argv)
+    metrics = IMAGE_METRICS if args.stereo else METRICS
+    track_metrics = compute_image_metrics_for_track if args.stereo else compute_metrics_for_track
+    track_frames = compute_image_frame_metrics_for_track if args.stereo else compute_frame_metrics_for_track
     framewise = args.frame_window is not None
     if framewise and not args.frame_window > 0:
         parser.error("--frame_window must be > 0")
@@ -543,23 +941,22 @@ def main(argv=None):
             continue
         try:
             if framewise:
-                frames = compute_frame_metrics_for_track(mix_path, ref_path, pred_path, args.frame_window, args.frame_hop,
-                                                         args.device)
-                m = frame_summary(frames)
+                frames = track_frames(mix_path, ref_path, pred_path, args.frame_window, args.frame_hop, args.device)
+                m = frame_summary(frames, metrics)
             else:
-                m = compute_metrics_for_track(mix_path, ref_path, pred_path, args.device)
+                m = track_metrics(mix_path, ref_path, pred_path, args.device)
         except Exception as e:                          # evaluate.py:127-131
             print(f"[Error] Failed on {base}: {e}")
             continue
         name = os.path.splitext(base)[0]
-        line = f"{name[:20]}:\tSDR={m['SDR']:.3f} dB,\tSIR={m['SIR']:.3f} dB,\tSAR={m['SAR']:.3f} dB,\tNSDR={m['NSDR']:.3f} dB"
+        line = f"{name[:20]}:\t" + ",\t".join(f"{k}={m[k]:.3f} dB" for k in metrics)
         if framewise:
             if m["frames"] == 0:
                 print(f"[Error] No valid frame in {base} ({frames['SDR'].size} frames, all silent)")
                 continue
             line += f",\tframes={m['frames']}/{frames['SDR'].size}"
             frame_rows += [{"track": name, "frame": i, "start_s": float(frames["start_s"][i]),
-                            **{k: float(frames[k][i]) for k in METRICS}} for i in range(frames["SDR"].size)]
+                            **{k: float(frames[k][i]) for k in metrics}} for i in range(frames["SDR"].size)]
         print(line)
         results.append({"track": name, **m})
     if not results:
@@ -567,17 +964,17 @@ def main(argv=None):
         return
     print("\n=== Overall Mean Metrics (vocal) ===" if not framewise else
           "\n=== Overall Mean Metrics (vocal, per-track medians over frames) ===")
-    for k in ("SDR", "SIR", "SAR", "NSDR"):
+    for k in metrics:
         print(f"Mean {k:4s}: {float(np.mean([r[k] for r in results])):.3f} dB")
     if args.out_csv is not None:
         with open(args.out_csv, "w", newline="", encoding="utf-8") as f:
-            w = csv.DictWriter(f, fieldnames=["track", "SDR", "SIR", "SAR", "NSDR"] + (["frames"] if framewise else []))
+            w = csv.DictWriter(f, fieldnames=["track", *metrics] + (["frames"] if framewise else []))
             w.writeheader()
             w.writerows(results)
         print(f"\n[Info] Results saved to {args.out_csv}")
     if args.frames_csv is not None:
         with open(args.frames_csv, "w", newline="", encoding="utf-8") as f:
-            w = csv.DictWriter(f, fieldnames=["track", "frame", "start_s", *METRICS])
+            w = csv.DictWriter(f, fieldnames=["track", "frame", "start_s", *metrics])
             w.writeheader()
             w.writerows(frame_rows)
         print(f"[Info] Frame results saved to {args.frames_csv}")

@@ -6,6 +6,8 @@ and the numpy path, on a seeded synthetic 240 s track at 8192 Hz and at 44,100 H
     rocprofv3 --kernel-trace --stats -d DIR -o bss --output-format csv -- python tools/bss_bench.py --rates 8192 --no-numpy
     python tools/bss_bench.py --kernel-stats DIR --rates 8192 --seconds 240
     python tools/bss_bench.py --frame_window 1 [--frame_hop 1] [--ws-budget BYTES]   # framewise metrics instead
+    python tools/bss_bench.py --stereo [--frame_window 1]       # the image metrics (SDR / ISR / SIR / SAR / NSDR) of a stereo track
+    python tools/bss_bench.py --ab-solve                        # the image solve against svs_bss_solve_batched, and at order 2048
 
 Timing: host clock around metrics_from_waveforms(device="gpu") followed by a device synchronise (the call ends with a
 copy back to the host anyway), after one warm-up call; median and minimum of --reps calls.  The numpy path is timed once.
@@ -42,6 +44,115 @@ def track(seconds, rate, seed=0):
     vocal += 0.05 * np.convolve(rng.standard_normal(n), np.ones(8) / 8)[:n]
     acc = 0.3 * np.convolve(rng.standard_normal(n), [1.0, -0.5, 0.25])[:n]
     return vocal + acc, vocal, vocal + 0.08 * acc + 0.02 * rng.standard_normal(n)
+
+
+def stereo_track(seconds, rate, seed=0):
+    """track() made stereo, each (n, 2): the vocal near the centre, the accompaniment wide, the estimate with a wrong balance."""
+    mix, vocal, est = track(seconds, rate, seed)
+    _, vocal2, _ = track(seconds, rate, seed + 1)
+    rng = np.random.default_rng(seed + 2)
+    n = vocal.size
+    v = np.stack([vocal, 0.8 * vocal + 0.2 * vocal2], axis=1)
+    acc = np.stack([mix - vocal, 0.3 * np.convolve(rng.standard_normal(n), [1.0, -0.5, 0.25])[:n]], axis=1)
+    return v + acc, v, v * [1.0, 0.9] + 0.08 * acc + 0.02 * rng.standard_normal((n, 2))
+
+
+def stereo_record(args, rate):
+    """--stereo: GPU and numpy image metrics on the stereo track (whole track, or frames with --frame_window); the largest
+    |delta| over all figures."""
+    import torch
+    mix, vocal, est = stereo_track(args.seconds, rate)
+    if args.frame_window is None:
+        run = lambda device: ev.image_metrics_from_waveforms(mix, vocal, est, device)
+        rec = {}
+    else:
+        window = ev.frame_samples(args.frame_window, rate)
+        hop = ev.frame_samples(args.frame_window if args.frame_hop is None else args.frame_hop, rate)
+        gpu_kw = {"ws_budget": args.ws_budget}
+        run = lambda device: ev.image_metrics_from_waveforms_framewise(mix, vocal, est, window, hop, device,
+                                                                       **(gpu_kw if device == "gpu" else {}))
+        rec = {"window": window, "hop": hop, "ws_budget": args.ws_budget}
+    run("gpu")
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        g = run("gpu")
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    rec = {"stereo": True, "rate": rate, "seconds": args.seconds, "n": mix.shape[0], **rec,
+           "gpu_ms_median": 1e3 * statistics.median(ts), "gpu_ms_min": 1e3 * min(ts), "reps": args.reps}
+    g = {k: np.atleast_1d(g[k]) for k in ev.IMAGE_METRICS}
+    rec["frames"] = int(g["SDR"].size)
+    rec["gpu_median"] = {k: float(np.nanmedian(g[k])) for k in ev.IMAGE_METRICS}
+    if not args.no_numpy:
+        t0 = time.perf_counter()
+        c = run("cpu")
+        rec["numpy_s"] = time.perf_counter() - t0
+        c = {k: np.atleast_1d(c[k]) for k in ev.IMAGE_METRICS}
+        rec["nan_frames_equal"] = all(np.array_equal(np.isnan(g[k]), np.isnan(c[k])) for k in ev.IMAGE_METRICS)
+        rec["max_abs_diff_db"] = max(float(np.max(np.abs(g[k] - c[k])[~np.isnan(c[k])], initial=0.0)) for k in ev.IMAGE_METRICS)
+        rec["speedup"] = rec["numpy_s"] / (rec["gpu_ms_median"] / 1e3)
+    return rec
+
+
+def ab_solve(reps):
+    """svs_bss_img_solve_batched (the diagonal tile factored once per step) against svs_bss_solve_batched (every panel block
+    factors it) on identical K = 2, flen 512 batches of 120 systems, the two alternating in one process, medians of device
+    time; and the new entry point alone at K = 4, flen 512, 30 systems, which the old one does not take."""
+    import torch
+    from svs_unet_pytorch_amd import _lib
+    L, dev, flen, window = _lib.lib(), torch.device("cuda"), ev.FILTER_LEN, 8192
+    out = []
+    for K, nrhs, nbatch, sides in ((2, 2, 120, ("img", "old")), (4, 4, 30, ("img",))):
+        rng = np.random.default_rng(K)
+        sig = torch.from_numpy(rng.standard_normal((K + nrhs, nbatch * window))).to(dev)
+        sig[K:] += sig[:K].sum(dim=0)
+        pairs = [(i, j, flen) for i in range(K) for j in range(K)] + [(K + e, i, flen) for e in range(nrhs) for i in range(K)]
+        flat = np.asarray(pairs, dtype=np.int32).ravel()
+        stride = len(pairs) * flen
+        corr = torch.empty(nbatch, stride, dtype=torch.float64, device=dev)
+        ws = torch.empty(int(max(L.svs_bss_img_corr_windows_workspace_bytes(window, nbatch, len(pairs), flat.ctypes.data),
+                                 L.svs_bss_img_solve_batched_workspace_bytes(nbatch, K, flen, nrhs))), dtype=torch.uint8,
+                         device=dev)
+        stream = _lib.stream_ptr()
+        _lib.check(L.svs_bss_img_corr_windows(sig.data_ptr(), sig.stride(0), K + nrhs, sig.shape[1], window, window, nbatch,
+                                              flat.ctypes.data, len(pairs), corr.data_ptr(), stride, ws.data_ptr(), ws.numel(),
+                                              stream), "svs_bss_img_corr_windows")
+        base = np.arange(nbatch, dtype=np.int64)[:, None] * stride
+        g = np.ascontiguousarray(base + np.arange(K * K) * flen)
+        r = np.ascontiguousarray(base + (K * K + np.arange(K * nrhs)) * flen)
+        y = {s: torch.empty(nbatch, nrhs, dtype=torch.float64, device=dev) for s in sides}
+        status, skipped = (torch.empty(nbatch, dtype=torch.int32, device=dev) for _ in range(2))
+
+        def call(side):
+            if side == "old":
+                _lib.check(L.svs_bss_solve_batched(corr.data_ptr(), nbatch, K, flen, g.ctypes.data, r.ctypes.data, nrhs,
+                                                   y[side].data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                           "svs_bss_solve_batched")
+                return
+            _lib.check(L.svs_bss_img_solve_batched(corr.data_ptr(), nbatch, K, flen, g.ctypes.data, r.ctypes.data, nrhs,
+                                                   y[side].data_ptr(), status.data_ptr(), skipped.data_ptr(), ws.data_ptr(),
+                                                   ws.numel(), stream), "svs_bss_img_solve_batched")
+
+        ms = {s: [] for s in sides}
+        for rep in range(reps + 1):
+            for s in sides:
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                call(s)
+                t1.record()
+                torch.cuda.synchronize()
+                if rep:                                                # the first round warms up
+                    ms[s].append(t0.elapsed_time(t1))
+        rec = {"ab_solve": " vs ".join(sides), "K": K, "flen": flen, "nrhs": nrhs, "nbatch": nbatch, "reps": reps,
+               **{f"{s}_ms_median": statistics.median(ms[s]) for s in sides}}
+        if len(sides) == 2:
+            a, b = (y[s].cpu().numpy() for s in sides)
+            rec["ratio"] = statistics.median(ms[sides[1]]) / statistics.median(ms[sides[0]])
+            rec["max_rel_diff"] = float(np.max(np.abs(a - b) / np.abs(b)))
+        out.append(rec)
+    return out
 
 
 def time_gpu(mix, vocal, est, reps):
@@ -99,7 +210,8 @@ def kernel_stats(path, n):
     for r in rows:
         name = r["Name"]
         short = next((k for k in ("bss_corr_reduce_kernel", "bss_corr_kernel", "bss_expand_kernel", "bss_panel_kernel",
-                                  "bss_update_kernel", "bss_norm_kernel") if k in name), None)
+                                  "bss_update_kernel", "bss_norm_kernel", "bss_img_corr_kernel", "bss_img_reduce_kernel",
+                                  "bss_img_diag_kernel", "bss_img_panel_kernel") if k in name), None)
         if short:
             out[short] = {"calls": int(r["Calls"]), "avg_us": float(r["AverageNs"]) / 1e3,
                           "total_us": float(r["TotalDurationNs"]) / 1e3}
@@ -121,6 +233,8 @@ def main():
     ap.add_argument("--frame_window", type=float, default=None, help="seconds: time the framewise metrics instead")
     ap.add_argument("--frame_hop", type=float, default=None, help="seconds (default: the window)")
     ap.add_argument("--ws-budget", type=int, default=ev.WS_BUDGET, help="workspace bytes of one batch of factorisations")
+    ap.add_argument("--stereo", action="store_true", help="the image metrics of a stereo track (evaluate.py --stereo)")
+    ap.add_argument("--ab-solve", action="store_true", help="A/B of svs_bss_img_solve_batched (see ab_solve)")
     args = ap.parse_args()
     if args.kernel_stats:
         n = args.seconds * args.rates[0]
@@ -129,7 +243,14 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bss_bench.py needs a ROCm device")
+    if args.ab_solve:
+        for rec in ab_solve(args.reps):
+            print(json.dumps(rec), flush=True)
+        return
     for rate in args.rates:
+        if args.stereo:
+            print(json.dumps(stereo_record(args, rate)), flush=True)
+            continue
         mix, vocal, est = track(args.seconds, rate)
         if args.frame_window is not None:
             print(json.dumps(frames_record(args, rate, mix, vocal, est)), flush=True)
