@@ -316,6 +316,9 @@ int svs_unet_eval_loss(const void* prepared, const float* mix, const float* voc,
 /* training = 0: the workspace of svs_unet_forward_eval, 1: of the svs_unet_train_* calls, 2: of svs_unet_forward_eval_bf16
  * (names "cat1" .. "cat5" and "c6" only; see below what they hold). */
 int64_t svs_unet_ws_offset(const char* name, int B, int H, int W, int training);  /* bytes, <0 unknown */
+/* Inside mr_ws of svs_unet_train_fwd_loss_mr, after the call: "wav_pred", "wav_tgt" (the two re-synthesised waveforms) and
+ * "d_wav" (alpha_mr * d(MR part)/d(wav_pred)), each B rows of hop * (W - 1) floats. */
+int64_t svs_unet_mr_ws_offset(const char* name, int B, int W, int hop);  /* bytes, <0 unknown */
 
 /* bf16 eval forward (BASELINE configs[4]: "bf16 convs on MFMA"): the same network with bf16 NHWC activations and bf16
  * weights on v_mfma_f32_16x16x32_bf16, fp32 accumulation, BatchNorm folded, mix and mask still fp32.  Not bit-comparable with

@@ -85,6 +85,7 @@ _SIGS = {
     "svs_unet_eval_loss_workspace_bytes": (Z, [I, I, I, I]),
     "svs_unet_eval_loss": (I, [P, P, P, P, P, I, I, I, I, D, D, P, P, P, P, Z, P]),
     "svs_unet_ws_offset": (L, [C.c_char_p, I, I, I, I]),
+    "svs_unet_mr_ws_offset": (L, [C.c_char_p, I, I, I]),
     "svs_stft_frames": (I, [L, I]),
     "svs_stft_fwd": (I, [P, L, I, I, P, P, P]),
     "svs_istft_workspace_bytes": (Z, [I, I, I]),

@@ -766,6 +766,14 @@ extern "C" size_t svs_unet_train_mr_workspace_bytes(int B, int W, int hop) {
   if (B <= 0 || W < 2 || hop <= 0) return 0;
   return mr_train_layout(B, W, hop, nullptr).total;
 }
+// where the waveforms and their gradient live inside mr_ws (tests read them): "wav_pred", "wav_tgt", "d_wav"
+extern "C" int64_t svs_unet_mr_ws_offset(const char* name, int B, int W, int hop) {
+  if (!name || B <= 0 || W < 2 || hop <= 0) return -1;
+  char* const base = (char*)256;   // non-null dummy so the arena hands out addresses
+  const MrTrainWs m = mr_train_layout(B, W, hop, base);
+  const WsName tab[] = {{"wav_pred", 0, 0, &m.wav_pred}, {"wav_tgt", 0, 0, &m.wav_tgt}, {"d_wav", 0, 0, &m.d_wav}};
+  return ws_find(tab, sizeof(tab) / sizeof(tab[0]), name, base);
+}
 extern "C" int svs_unet_train_fwd_loss_mr(const float* params, float* bn_buffers, int64_t* num_batches_tracked, const float* mix,
                                           const float* voc, const float* mix_phase, const float* voc_phase, const float* drop,
                                           int B, int H, int W, int hop, float alpha_l1, float alpha_mr, float* mask, float* losses,

@@ -117,6 +117,23 @@ def test_named_workspace_buffers_are_aligned_disjoint_and_inside(lib, training):
         assert lib.svs_unet_ws_offset(b"dcat3", B, H, W, training) == lib.svs_unet_ws_offset(b"raw_e1", B, H, W, training) == -1
 
 
+@pytest.mark.parametrize("B,W,hop", [(5, 32, 100), (20, 32, 128), (5, 4, 1024), (3, 128, 768)])
+def test_named_mr_workspace_buffers_are_aligned_disjoint_and_inside(lib, B, W, hop):
+    """svs_unet_mr_ws_offset: the two waveforms and d_wav of svs_unet_train_fwd_loss_mr's MR workspace, B rows of hop (W - 1)
+    floats each, 256-byte aligned, in the order the call fills them, inside svs_unet_train_mr_workspace_bytes; other names and
+    sizes the workspace query refuses are unknown."""
+    total = lib.svs_unet_train_mr_workspace_bytes(B, W, hop)
+    nbytes = 4 * B * hop * (W - 1)
+    offs = [lib.svs_unet_mr_ws_offset(name, B, W, hop) for name in (b"wav_pred", b"wav_tgt", b"d_wav")]
+    assert offs[0] == 0 and all(o % 256 == 0 for o in offs)
+    assert offs[0] + nbytes <= offs[1] and offs[1] + nbytes <= offs[2] and offs[2] + nbytes < total
+    for name in (b"nope", b"", b"d_wav0", b"wav", b"wav_pred ", b"mask", b"d_logit"):
+        assert lib.svs_unet_mr_ws_offset(name, B, W, hop) == -1, name
+    assert lib.svs_unet_mr_ws_offset(None, B, W, hop) == -1
+    for bad in ((0, W, hop), (B, 1, hop), (B, W, 0)):
+        assert lib.svs_unet_mr_ws_offset(b"d_wav", *bad) == -1 and lib.svs_unet_train_mr_workspace_bytes(*bad) == 0
+
+
 def test_invalid_arguments_are_reported_without_touching_the_gpu(lib):
     rc = lib.svs_enc_block_fwd(None, 16, 1, 8, 8, 16, None, None, None, None, 0.0, None, 32, 32, 0, None, 0, None)
     assert rc == -1 and b"null pointer" in lib.svs_last_error_string()
