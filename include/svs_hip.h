@@ -224,6 +224,33 @@ int svs_l1_mask_loss_fwd(const float* mask, const float* mix, const float* voc, 
 int svs_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                   double eps, int step, float grad_scale, hipStream_t stream);
 
+/* Optimiser options the reference does not have (it clips nothing and runs plain Adam, model.py:116, train.py:298-300:
+ * `optim.zero_grad(); loss.backward(); optim.step()`); csrc/optim.hip.  Both work on device-resident scalars: `stats` is a
+ * caller-owned device double[4], zeroed by the caller once, never read by the host inside a step.
+ *
+ * svs_grad_norm: the L2 norm of grad_scale * g over the flat gradient -- every element widened to double before it is squared,
+ * double partial sums in a fixed order (per-thread stride, wave, block, then one finalise block folding the block partials in
+ * a fixed tree), no atomics: the same (g, n, alignment of g modulo 16 bytes) gives the same bits.  g may be any 4-byte-aligned
+ * pointer.  It writes
+ *   stats[0] = the norm,
+ *   stats[1] = the clip coefficient of torch.nn.utils.clip_grad_norm_: min(1, max_norm / (norm + 1e-6)); 1 when
+ *              max_norm <= 0 (clipping off); 0 when the norm is not finite,
+ *   stats[2] += 1 when the coefficient is below 1,   stats[3] += 1 when the norm is not finite.
+ * ws: svs_grad_norm_workspace_bytes(n) bytes, 8-byte aligned.  Two launches. */
+size_t svs_grad_norm_workspace_bytes(int64_t n);
+int svs_grad_norm(const float* g, int64_t n, float grad_scale, double max_norm, double* stats, void* ws, size_t ws_bytes,
+                  hipStream_t stream);
+/* svs_adam_step with decoupled weight decay, clipping, a skip and an average of the weights, in one launch and one pass:
+ *   skip:  stats != NULL and stats[1] == 0: nothing is touched -- no NaN reaches p, m, v or ema;
+ *   clip:  the gradient is g[i] * gs with the one float product gs = grad_scale * (float)stats[1] (gs = grad_scale when stats
+ *          is NULL); with weight_decay == 0, p, m and v are bit for bit those of svs_adam_step at grad_scale = gs;
+ *   decay: p *= (float)(1 - lr * weight_decay) before the Adam update, on every element (torch.optim.AdamW's default);
+ *   ema:   ema != NULL: ema[i] = d * ema[i] + (1 - d) * p[i] after the update, d = ema_decay in [0, 1), 1 - d derived in double.
+ * The bias corrections use the caller's `step`; a skipped step still advances the caller's count. */
+int svs_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
+                   double eps, int step, float grad_scale, double weight_decay, const double* stats, float* ema,
+                   double ema_decay, hipStream_t stream);
+
 /* inference.py:100-107: out = mix * mask, or mix * (1 - mask) when invert != 0. */
 int svs_apply_mask(const float* mix, const float* mask, float* out, int64_t n, int invert, hipStream_t stream);
 

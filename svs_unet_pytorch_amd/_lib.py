@@ -62,6 +62,9 @@ _SIGS = {
     "svs_l1_mask_loss_fwd_bwd": (I, [P, P, P, L, F, P, P, P, Z, P]),
     "svs_l1_mask_loss_fwd": (I, [P, P, P, L, P, P, Z, P]),
     "svs_adam_step": (I, [P, P, P, P, L, D, D, D, D, I, F, P]),
+    "svs_grad_norm_workspace_bytes": (Z, [L]),
+    "svs_grad_norm": (I, [P, L, F, D, P, P, Z, P]),
+    "svs_adamw_step": (I, [P, P, P, P, L, D, D, D, D, I, F, D, P, P, D, P]),
     "svs_apply_mask": (I, [P, P, P, L, I, P]),
     "svs_unet_param_offset": (L, [I]),
     "svs_unet_buffer_offset": (L, [I, I]),

@@ -49,13 +49,23 @@ def separate(model: UNet, mix_spec, seg_len: int = INPUT_LEN, vocal_solo: bool =
     return separate_spectrogram_device(model, spec.to(model._flat.device), seg_len, vocal_solo, max_batch, tile_hop).cpu().numpy()
 
 
-def load_checkpoint_model(path: str, device):
-    """A UNet on `device` in eval mode with the checkpoint's model_state_dict; a checkpoint that does not load is reported and
-    ends the process with status 1 (inference.py:49-51)."""
+def no_ema_message(tool: str, path: str) -> str:
+    return (f"{tool}: --ema: {path} has no ema_state_dict (only the resume checkpoint of a `train.py --ema_decay` run has one; the "
+            "best-validation checkpoint of such a run already carries the EMA weights as its model_state_dict: load it without --ema)")
+
+
+def load_checkpoint_model(path: str, device, ema: bool = False, tool: str = "inference.py"):
+    """A UNet on `device` in eval mode with the checkpoint's model_state_dict -- with `ema`, its ema_state_dict (the resume
+    checkpoint of `train.py --ema_decay`), and the process ends with a message when it has none; a checkpoint that does not load
+    is reported and ends the process with status 1 (inference.py:49-51)."""
     model = UNet().to(device)
     try:
         checkpoint = torch.load(path, map_location=device)
-        if isinstance(checkpoint, dict) and "model_state_dict" in checkpoint:
+        if ema and not (isinstance(checkpoint, dict) and "ema_state_dict" in checkpoint):
+            raise SystemExit(no_ema_message(tool, path))
+        if ema:
+            model.load_state_dict(checkpoint["ema_state_dict"])
+        elif isinstance(checkpoint, dict) and "model_state_dict" in checkpoint:
             model.load_state_dict(checkpoint["model_state_dict"])
     except Exception as e:
         print(f"Failed to load the model: {e}")
@@ -71,6 +81,7 @@ def main(argv=None):
     parser.add_argument("--vocal_solo", type=int, default=1, help="1: keep the vocal, 0: remove it")
     parser.add_argument("--tile_hop", type=int, default=INPUT_LEN,
                         help=f"frames between tiles: {INPUT_LEN} = disjoint tiles as the reference cuts them; 64 or 32 = overlapped tiles with cross-faded masks")
+    parser.add_argument("--ema", action="store_true", help="load the checkpoint's ema_state_dict (train.py --ema_decay) instead of its live weights")
     args = parser.parse_args(argv)
     try:
         check_tile_hop(args.tile_hop, INPUT_LEN)
@@ -84,7 +95,7 @@ def main(argv=None):
     device = torch.device("cuda")
     print(f"Inference using device: {device}")
 
-    model = load_checkpoint_model(args.model_path, device)
+    model = load_checkpoint_model(args.model_path, device, ema=args.ema)
 
     files = sorted(f for f in os.listdir(args.mixture_folder) if f.endswith("_spec.npy"))[:20]   # inference.py:58-59
     print(f"Found {len(files)} files, separating...")

@@ -20,6 +20,7 @@ see SURVEY.md section 0) and train.py:281-282 calls `model.crit(pred, target)` w
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import numpy as np
@@ -78,10 +79,25 @@ class WeightedL1Loss(nn.Module):
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam(lr=1e-3) semantics (model.py:116) as one `svs_adam_step` launch over the
     model's flat parameter / gradient / moment buffers.  state_dict() has torch.optim.Adam's
-    per-parameter layout (step, exp_avg, exp_avg_sq) so reference checkpoints load and save."""
+    per-parameter layout (step, exp_avg, exp_avg_sq) so reference checkpoints load and save.
 
-    def __init__(self, model: "UNet", lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    Three options the reference does not have, all 0 = off (with all three off `step()` is that one launch, nothing else):
+    `weight_decay` (decoupled, torch.optim.AdamW: p *= 1 - lr * weight_decay before the update, on every parameter),
+    `max_grad_norm` (torch.nn.utils.clip_grad_norm_ over the whole flat gradient, after any all-reduce, 1/world folded in) and
+    `ema_decay` (model._ema_flat = d * ema + (1 - d) * p after the update).  With any of them on, `step()` is `svs_grad_norm`
+    then `svs_adamw_step` on the same stream; the norm, the clip coefficient and the counts of clipped and skipped steps stay
+    on the device in `model.optim_stats`, and a step whose gradient norm is not finite changes nothing.  The step count -- and
+    with it the bias corrections -- advances on a skipped step too: the host never learns of the skip inside a step.  The
+    attributes are not part of state_dict(): the caller sets them, as it sets the learning rate."""
+
+    def __init__(self, model: "UNet", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0, ema_decay=0.0):
+        if weight_decay < 0 or max_grad_norm < 0 or not 0 <= ema_decay < 1:
+            raise ValueError(f"FusedAdam: weight_decay {weight_decay} and max_grad_norm {max_grad_norm} must be >= 0, ema_decay {ema_decay} in [0, 1)")
         self._model = model
+        self.weight_decay = float(weight_decay)
+        self.max_grad_norm = float(max_grad_norm)
+        self.ema_decay = float(ema_decay)
+        self._norm_ws = None
         super().__init__(list(model.parameters()), dict(lr=lr, betas=betas, eps=eps, weight_decay=0,
                                                         amsgrad=False, maximize=False))
         self._step = 0
@@ -118,10 +134,26 @@ class FusedAdam(torch.optim.Optimizer):
         self._ensure_state()
         g = self.param_groups[0]
         self._step += 1
-        check(lib().svs_adam_step(ptr(model._flat), ptr(model._gflat), ptr(self._m), ptr(self._v),
-                                  model._flat.numel(), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
-                                  float(g["eps"]), int(self._step), float(self.grad_scale), _lib.stream_ptr()),
-              "svs_adam_step")
+        if not (self.weight_decay or self.max_grad_norm or self.ema_decay):
+            check(lib().svs_adam_step(ptr(model._flat), ptr(model._gflat), ptr(self._m), ptr(self._v),
+                                      model._flat.numel(), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
+                                      float(g["eps"]), int(self._step), float(self.grad_scale), _lib.stream_ptr()),
+                  "svs_adam_step")
+        else:
+            n = model._flat.numel()
+            if model._ema_swapped:
+                raise RuntimeError("FusedAdam.step() inside UNet.ema_weights(): the parameters are the EMA there")
+            if self.ema_decay:
+                model.start_ema()
+            if self._norm_ws is None or self._norm_ws.device != model._flat.device:
+                self._norm_ws = torch.empty(int(lib().svs_grad_norm_workspace_bytes(n)), dtype=torch.uint8, device=model._flat.device)
+            check(lib().svs_grad_norm(ptr(model._gflat), n, float(self.grad_scale), self.max_grad_norm, ptr(model.optim_stats),
+                                      ptr(self._norm_ws), self._norm_ws.numel(), _lib.stream_ptr()), "svs_grad_norm")
+            check(lib().svs_adamw_step(ptr(model._flat), ptr(model._gflat), ptr(self._m), ptr(self._v), n, float(g["lr"]),
+                                       float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), int(self._step),
+                                       float(self.grad_scale), self.weight_decay, ptr(model.optim_stats),
+                                       ptr(model._ema_flat) if self.ema_decay else None, self.ema_decay, _lib.stream_ptr()),
+                  "svs_adamw_step")
         model._param_epoch += 1
         return loss
 
@@ -199,6 +231,9 @@ class UNet(nn.Module):
         self._bn_list = [getattr(self, f"conv{k + 1}")[1] for k in range(6)] + \
                         [getattr(self, f"deconv{j + 1}_BAD")[0] for j in range(5)]
         self._flat = self._gflat = self._bn_flat = self._nbt_flat = None
+        self._ema_flat = None           # EMA of _flat (FusedAdam.ema_decay): allocated by start_ema() or a checkpoint that has one
+        self._ema_swapped = False       # inside ema_weights()
+        self.optim_stats = None         # device double[4]: last gradient norm, last clip coefficient, clipped steps, skipped steps
         self._param_epoch = 0
         self._prepared = None
         self._prepared_key = None
@@ -247,6 +282,12 @@ class UNet(nn.Module):
                 bn.num_batches_tracked = nbt[i]
                 off += 2 * c
         self._flat, self._gflat, self._bn_flat, self._nbt_flat = flat, gflat, bn_flat, nbt
+        if self._ema_flat is not None:                      # follows the parameters, as the optimiser's moments do
+            self._ema_flat = self._ema_flat.to(dev)
+        stats = torch.zeros(4, dtype=torch.float64, device=dev)
+        if self.optim_stats is not None:
+            stats.copy_(self.optim_stats)
+        self.optim_stats = stats
         self._prepared = None
         self._prepared_key = None
         self._ws = {}
@@ -279,6 +320,8 @@ class UNet(nn.Module):
             self.load_state_dict(state["model_state_dict"], strict=False)
             if "optim" in state:
                 self.optim.load_state_dict(state["optim"])
+            if "ema_state_dict" in state:
+                self.load_ema_state_dict(state["ema_state_dict"])
             self.dropout_step = int(state.get("dropout_step", self.optim._step))     # masks do not replay after a resume
         else:
             print("Pre-trained model {} is not exist...".format(path))
@@ -286,10 +329,66 @@ class UNet(nn.Module):
     def save(self, path):
         state = {"model_state_dict": self.state_dict(), "optim": self.optim.state_dict(), "dropout_step": self.dropout_step}
         state.update(getattr(self, "stft_geometry", None) or {})    # train.py: {"win_size", "hop_size"} of the set it trains on
+        if self._ema_flat is not None and not self._ema_swapped:    # (inside ema_weights() the EMA is model_state_dict: an export)
+            state["ema_state_dict"] = self.ema_state_dict()
+            state["ema_decay"] = self.optim.ema_decay
         for key in self.__dict__:
             if "loss_list" in key:
                 state[key] = getattr(self, key)
         torch.save(state, path)
+
+    # ==============================================================================
+    #   EMA of the weights (FusedAdam.ema_decay; the reference has none)
+    # ==============================================================================
+    def start_ema(self):
+        """Allocates the EMA as a copy of the current parameters; a no-op when there is one already."""
+        if self._ema_flat is None:
+            self._ema_flat = self._flat.detach().clone()
+
+    def _swap_ema(self):
+        with torch.no_grad():
+            live = self._flat.clone()
+            self._flat.copy_(self._ema_flat)
+            self._ema_flat.copy_(live)
+        self._ema_swapped = not self._ema_swapped
+        self._param_epoch += 1          # the folded eval weights are stale
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model's parameters ARE the EMA (the contents of `_flat` and `_ema_flat` are swapped, and
+        swapped back on exit, by torch copies: this runs once per validation, not per step).  The BatchNorm running statistics
+        stay the live model's: they are exponential averages of the batch statistics already."""
+        if self._ema_flat is None:
+            raise RuntimeError("UNet.ema_weights(): no EMA -- set optim.ema_decay and take a step, or load a checkpoint that has one")
+        if self._ema_swapped:
+            raise RuntimeError("UNet.ema_weights() does not nest")
+        self._swap_ema()
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+
+    def ema_state_dict(self):
+        """state_dict() -- the same 79 keys in the same order -- with the parameters taken from the EMA; the BatchNorm buffers
+        are the live model's (see ema_weights).  Every tensor is a copy."""
+        if self._ema_flat is None:
+            raise RuntimeError("UNet.ema_state_dict(): no EMA")
+        ema = self._flat if self._ema_swapped else self._ema_flat
+        out = self.state_dict()
+        for key in out:                                  # a snapshot: state_dict()'s tensors alias the live buffers
+            out[key] = out[key].detach().clone()
+        for (name, p), (off, n) in zip(self.named_parameters(), self._param_spans):
+            out[name] = ema[off:off + n].detach().clone().view(p.shape)
+        return out
+
+    def load_ema_state_dict(self, state):
+        """Restores the EMA from the parameters of an `ema_state_dict()` (its BatchNorm buffers are not read)."""
+        if self._ema_swapped:
+            raise RuntimeError("UNet.load_ema_state_dict() inside ema_weights()")
+        self.start_ema()
+        with torch.no_grad():
+            for (name, p), (off, n) in zip(self.named_parameters(), self._param_spans):
+                self._ema_flat[off:off + n].copy_(state[name].reshape(-1))
 
     # ==============================================================================
     #   Set & Get  (model.py:157-167)

@@ -60,6 +60,7 @@ def main(argv=None):
                         help="phase-refinement updates before the last inverse STFT: 0 = the mixture's phase; N > 0 = N Griffin-Lim updates (MISI with --tar_accomp)")
     parser.add_argument("--wiener_iters", type=int, default=0,
                         help="updates of the multichannel Wiener filter after the mask: 0 = none; 1..8 (one or two channels; not with --phase_iters)")
+    parser.add_argument("--ema", action="store_true", help="load the checkpoint's ema_state_dict (train.py --ema_decay) instead of its live weights")
     args = parser.parse_args(argv)
     if args.phase_iters < 0:
         parser.error(f"--phase_iters {args.phase_iters}: must be 0 (the mixture's phase) or a positive number of updates")
@@ -82,7 +83,7 @@ def main(argv=None):
         print("separate.py needs a ROCm device (hand-written gfx950 kernels, no CPU path).")
         sys.exit(1)
     device = torch.device("cuda")
-    model = load_checkpoint_model(args.model_path, device)
+    model = load_checkpoint_model(args.model_path, device, ema=args.ema, tool="separate.py")
 
     if os.path.isdir(args.src):
         os.makedirs(args.tar, exist_ok=True)

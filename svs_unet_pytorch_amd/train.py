@@ -40,10 +40,19 @@ checkpoint.
 over the accompaniment of another, formed from the complex spectra so that it is the STFT of the re-mixed audio.  --gain_range,
 --remix_prob and --augment_seed set it; an epoch's table depends on (seed, epoch) only, goes up in one copy, and each step is one
 launch.  Validation is never augmented; the checkpoint format is unchanged.
+
+--weight_decay X, --clip_grad_norm X, --ema_decay X (all 0 = off: the optimiser step is then the reference's Adam, one launch) turn on
+decoupled weight decay, clipping by the global gradient norm and an exponential moving average of the weights inside the optimiser
+step (csrc/optim.hip: `svs_grad_norm` + `svs_adamw_step`, nothing read back inside a step; a step whose gradient norm is not finite
+is skipped).  --lr X sets the rate and switches the epoch-400 rule off; --warmup_steps N makes the rate lr * min(1, t / N) at
+optimiser step t.  With --ema_decay validation runs on the EMA weights, svs_best_<label>.pth carries them as its model_state_dict,
+and the resume checkpoint keeps the live weights and adds `ema_state_dict` / `ema_decay`; per epoch rank 0 prints the last gradient
+norm and the counts of clipped and skipped steps.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import random
 
@@ -64,6 +73,41 @@ def check_geometry(win_size, hop_size):
     if not 0 < hop_size <= win_size:
         return f"--hop_size {hop_size}: must be in 1..{win_size} (a larger hop leaves samples that no frame covers)"
     return None
+
+
+REFERENCE_LR = 1e-3            # model.py:116
+REFERENCE_LR_DROP = (400, 5e-4)      # train.py:251-262: epoch, rate
+
+
+def check_optim(weight_decay, clip_grad_norm, ema_decay, lr, warmup_steps):
+    """The message for optimiser flags that cannot be trained with, or None."""
+    import math
+    if not (math.isfinite(weight_decay) and weight_decay >= 0):
+        return f"--weight_decay {weight_decay}: must be >= 0 (decoupled decay, p *= 1 - lr * weight_decay per step; 0 = off)"
+    if not (math.isfinite(clip_grad_norm) and clip_grad_norm >= 0):
+        return f"--clip_grad_norm {clip_grad_norm}: must be >= 0 (the largest global gradient norm a step is taken with; 0 = off)"
+    if not 0 <= ema_decay < 1:
+        return f"--ema_decay {ema_decay}: must be in [0, 1) (ema = d * ema + (1 - d) * weights per step; 0 = off)"
+    if lr is not None and not (math.isfinite(lr) and lr > 0):
+        return f"--lr {lr}: must be > 0 (without the flag: {REFERENCE_LR}, halved at epoch {REFERENCE_LR_DROP[0]})"
+    if warmup_steps < 0:
+        return f"--warmup_steps {warmup_steps}: must be >= 0 (the rate is lr * min(1, t / N) at step t; 0 = off)"
+    return None
+
+
+def warmup_lr(lr, t, warmup_steps):
+    """The rate of step t (1-based; t = 0 is before the first step) under a linear warm-up of `warmup_steps` steps."""
+    return lr if warmup_steps <= 0 else lr * min(1.0, t / warmup_steps)
+
+
+def lr_drop_applies(epoch, lr_flag):
+    """The reference's drop to 5e-4 with its snapshot (train.py:251-262): at epoch 400, unless --lr set the rate."""
+    return lr_flag is None and epoch == REFERENCE_LR_DROP[0]
+
+
+def reference_lr(epoch):
+    """The reference's rate while epoch `epoch` runs."""
+    return REFERENCE_LR_DROP[1] if epoch >= REFERENCE_LR_DROP[0] else REFERENCE_LR
 
 
 def checkpoint_geometry(checkpoint):
@@ -352,10 +396,24 @@ def main(argv=None):
     parser.add_argument("--remix_prob", type=float, default=augment.REMIX_PROB,
                         help="share of the items whose accompaniment comes from a random crop of a random song (default 0.5: a choice, not a tuned value)")
     parser.add_argument("--augment_seed", type=int, default=0, help="the tables of an epoch depend on (this, epoch) only")
+    parser.add_argument("--weight_decay", type=float, default=0.0, help="decoupled weight decay (torch.optim.AdamW), on every parameter; 0 = off")
+    parser.add_argument("--clip_grad_norm", type=float, default=0.0,
+                        help="clip the global gradient norm to this (after the all-reduce under data parallelism); 0 = off")
+    parser.add_argument("--ema_decay", type=float, default=0.0,
+                        help="keep an exponential moving average of the weights with this decay, 0 <= d < 1: validation and the best "
+                             "checkpoint use it, the resume checkpoint keeps both; 0 = off")
+    parser.add_argument("--lr", type=float, default=None,
+                        help=f"initial learning rate; without it the reference's {REFERENCE_LR} and its drop at epoch {REFERENCE_LR_DROP[0]}, "
+                             "with it no drop")
+    parser.add_argument("--warmup_steps", type=int, default=0, help="the rate is lr * min(1, t / N) at step t; 0 = off")
     args = parser.parse_args(argv)
     bad = check_geometry(args.win_size, args.hop_size)          # data.py:24-25 lets both vary; before any device is touched
     if bad:
         parser.error(bad)
+    bad = check_optim(args.weight_decay, args.clip_grad_norm, args.ema_decay, args.lr, args.warmup_steps)
+    if bad:
+        parser.error(bad)
+    optim_options = bool(args.weight_decay or args.clip_grad_norm or args.ema_decay)
     aug = None
     if args.augment != "none":                                  # `none` reaches nothing of augment.py beyond the flags' defaults
         bad = augment.check_settings(args.augment, args.gain_range, args.remix_prob)
@@ -424,6 +482,7 @@ def main(argv=None):
     model.stft_geometry = geometry                                        # model.save (the best-validation checkpoint) records it too
     start_epoch = 0
     scheduler = None
+    resumed = os.path.exists(args.load_path)
     if os.path.exists(args.load_path):                                    # train.py:205-237
         model.load(args.load_path)
         checkpoint = torch.load(args.load_path, map_location=device)
@@ -440,6 +499,21 @@ def main(argv=None):
         from .parallel import GradAllReduce, broadcast_parameters
         broadcast_parameters(model, 0)
         grad_sync = GradAllReduce(model)
+    # optimiser options (all off by default: FusedAdam.step is then the reference's Adam, one launch)
+    model.optim.weight_decay, model.optim.max_grad_norm, model.optim.ema_decay = args.weight_decay, args.clip_grad_norm, args.ema_decay
+    if args.ema_decay:
+        if model._ema_flat is None:                                       # (after the broadcast: every rank starts the same average)
+            model.start_ema()
+            if resumed:
+                print(f"{args.load_path} has no ema_state_dict: the EMA starts from the loaded weights.")
+    elif model._ema_flat is not None:
+        model._ema_flat = None
+        print(f"{args.load_path} carries an EMA of the weights; without --ema_decay it is dropped.")
+    # the rate: untouched (the optimiser's own, a checkpoint's included, and the epoch-400 rule) unless --lr or --warmup_steps
+    target_lr = args.lr if args.lr is not None else (reference_lr(start_epoch) if args.warmup_steps else None)
+    if target_lr is not None:
+        for group in model.optim.param_groups:
+            group["lr"] = warmup_lr(target_lr, model.optim._step + 1, args.warmup_steps)
 
     # objective: the reference's alpha_L1 * L1 + alpha_MR * MR-STFT (train.py:296) unless SVS_OBJECTIVE=l1 or no phases
     full = os.environ.get("SVS_OBJECTIVE", "full") != "l1"
@@ -468,7 +542,9 @@ def main(argv=None):
         model.train()
         if sampler is not None:
             sampler.set_epoch(ep)
-        if ep == 400:                                                      # train.py:251-262
+        if lr_drop_applies(ep, args.lr):                                   # train.py:251-262
+            if target_lr is not None:
+                target_lr = 5e-4
             for group in model.optim.param_groups:
                 group["lr"] = 5e-4
             if rank == 0:
@@ -489,6 +565,9 @@ def main(argv=None):
         for batch in stream:
             mix, voc = batch[0], batch[1]
             mph, vph = (batch[2], batch[3]) if full else (None, None)
+            if args.warmup_steps:                                          # a double argument of the launch: nothing goes to the device
+                for group in model.optim.param_groups:
+                    group["lr"] = warmup_lr(target_lr, model.optim._step + 1, args.warmup_steps)
             l1 = model.train_step(mix, voc, loss_scale=ALPHA_L1, grad_sync=grad_sync, mix_phase=mph, voc_phase=vph,
                                   alpha_mr=alpha_mr, hop=args.hop_size)                     # train.py:271-300
             loss_sum += ALPHA_L1 * l1                                                       # no host sync per step
@@ -496,31 +575,39 @@ def main(argv=None):
                 loss_sum += alpha_mr * model.last_mr_loss
         avg_train_loss = float(loss_sum) / max(steps, 1)
         log_buffer.append(f"{avg_train_loss}\n")
+        if optim_options:                                                  # the epoch's one read-back of the optimiser's device scalars
+            norm, _, clipped, skipped = model.optim_stats.cpu().tolist()
+            model.optim_stats[2:].zero_()
+            if rank == 0:
+                print(f"Epoch {ep + 1} last grad norm {norm:.4e} | clipped {int(clipped)} / {steps} steps | skipped (non-finite) {int(skipped)}")
 
         if world > 1:                                                      # one set of running statistics for validation / checkpoints
             from .parallel import average_bn_buffers
             average_bn_buffers(model)
         if (valid_loader or valid_resident is not None) and (ep + 1) % args.val_interval == 0:             # train.py:317-363
             model.eval()
-            if valid_resident is not None:                                 # on the device: one library call per batch, one read-back
-                with torch.no_grad():
-                    acc, n_val = validation_pass(model, valid_resident, max(args.batch_size // world, 1),
-                                                 valid_dataset.with_phase and valid_resident.has_phase, args.win_size, args.hop_size)
-                avg_val_loss = float(acc.cpu()[0]) / n_val
-            else:                                                          # SVS_DATA_LOADER != resident: the reference's host loop
-                val_sum = 0.0
-                with torch.no_grad():
-                    for mix, voc, mph, vph in valid_loader:
-                        mix, voc = mix.to(device), voc.to(device)
-                        val_sum += ALPHA_L1 * float(l1_terms(model, mix, voc))
-                        if full and valid_dataset.with_phase:              # train.py:341-346
-                            val_sum += alpha_mr * float(mr_term(model, mix, voc, mph.to(device), vph.to(device), args.win_size, args.hop_size))
-                avg_val_loss = val_sum / len(valid_loader)
-            log_buffer.append(f"Val {avg_val_loss}\n")
-            print(f"\n[Epoch {ep + 1}] Train Loss: {avg_train_loss:.4e} | Val Loss: {avg_val_loss:.4e}")
-            if avg_val_loss < best_val_loss and rank == 0:
-                best_val_loss = avg_val_loss
-                model.save(best_weight)
+            # --ema_decay: the pass and the best checkpoint see the EMA weights (model.save inside the context writes them as
+            # model_state_dict, so every downstream tool loads them unchanged)
+            with model.ema_weights() if args.ema_decay else contextlib.nullcontext():
+                if valid_resident is not None:                             # on the device: one library call per batch, one read-back
+                    with torch.no_grad():
+                        acc, n_val = validation_pass(model, valid_resident, max(args.batch_size // world, 1),
+                                                     valid_dataset.with_phase and valid_resident.has_phase, args.win_size, args.hop_size)
+                    avg_val_loss = float(acc.cpu()[0]) / n_val
+                else:                                                      # SVS_DATA_LOADER != resident: the reference's host loop
+                    val_sum = 0.0
+                    with torch.no_grad():
+                        for mix, voc, mph, vph in valid_loader:
+                            mix, voc = mix.to(device), voc.to(device)
+                            val_sum += ALPHA_L1 * float(l1_terms(model, mix, voc))
+                            if full and valid_dataset.with_phase:          # train.py:341-346
+                                val_sum += alpha_mr * float(mr_term(model, mix, voc, mph.to(device), vph.to(device), args.win_size, args.hop_size))
+                    avg_val_loss = val_sum / len(valid_loader)
+                log_buffer.append(f"Val {avg_val_loss}\n")
+                print(f"\n[Epoch {ep + 1}] Train Loss: {avg_train_loss:.4e} | Val Loss: {avg_val_loss:.4e}")
+                if avg_val_loss < best_val_loss and rank == 0:
+                    best_val_loss = avg_val_loss
+                    model.save(best_weight)
             if rank == 0:
                 try:
                     with open(log_file, "a") as f:
@@ -535,6 +622,9 @@ def main(argv=None):
             checkpoint = {"epoch": ep + 1, "model_state_dict": model.state_dict(), "optim": model.optim.state_dict(),
                           "scheduler": scheduler.state_dict() if scheduler is not None else None,
                           "dropout_step": model.dropout_step, **geometry}
+            if args.ema_decay:                                             # the live weights above, the average beside them
+                checkpoint["ema_state_dict"] = model.ema_state_dict()
+                checkpoint["ema_decay"] = args.ema_decay
             for key in model.__dict__:
                 if key.startswith("loss_list"):
                     checkpoint[key] = getattr(model, key)

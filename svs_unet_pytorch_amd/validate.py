@@ -3,7 +3,7 @@ own, from the HBM-resident set -- `train.validation_pass`: one `svs_crop_tiles` 
 read-back per pass.  This is how two checkpoints are compared on the same folder.
 
     python -m svs_unet_pytorch_amd.validate --model_path CKPT/svs_x.pth --valid_folder spec/valid \
-        [--batch_size 64] [--win_size 512|1024|2048] [--hop_size N] [--seed N] [--passes K]
+        [--batch_size 64] [--win_size 512|1024|2048] [--hop_size N] [--seed N] [--passes K] [--ema]
 
 The STFT geometry defaults to the one the checkpoint records (`win_size` / `hop_size`, written by train.py; the config's
 1024 / 768 for a checkpoint from before those keys); a flag that contradicts the checkpoint is an error, and so are a
@@ -12,6 +12,8 @@ device is touched.  A pass draws its crops from `random.Random(seed)`, one gener
 the same items, starts and values.  Per pass it prints the objective ALPHA_L1 * L1 + ALPHA_MR * MR-STFT (the `Val` value
 train.py logs: the mean of per-batch totals) and its two parts, then their means over the passes; `main()` returns them.  A
 folder without *_phase.npy files is scored on the L1 part only, with a warning (MR = 0).  The fp32 network always.
+--ema scores the checkpoint's `ema_state_dict` (the resume checkpoint of `train.py --ema_decay`) and exits with a message when
+it has none.
 """
 from __future__ import annotations
 
@@ -34,6 +36,7 @@ def main(argv=None):
     parser.add_argument("--hop_size", type=int, default=None, help="hop the folder was written with (default: the checkpoint's)")
     parser.add_argument("--seed", type=int, default=0, help="seed of the crops' random starts")
     parser.add_argument("--passes", type=int, default=1, help="validation passes to average over")
+    parser.add_argument("--ema", action="store_true", help="score the checkpoint's ema_state_dict (train.py --ema_decay) instead of its live weights")
     args = parser.parse_args(argv)
     if args.batch_size < 1 or args.passes < 1:
         parser.error("--batch_size and --passes must be at least 1")
@@ -47,6 +50,9 @@ def main(argv=None):
         raise SystemExit(f"validate.py: cannot load {args.model_path}: {e}")
     if not isinstance(checkpoint, dict) or "model_state_dict" not in checkpoint:
         raise SystemExit(f"validate.py: {args.model_path} has no model_state_dict (not a checkpoint of train.py)")
+    if args.ema and "ema_state_dict" not in checkpoint:
+        from .inference import no_ema_message
+        raise SystemExit(no_ema_message("validate.py", args.model_path))
     ck_win, ck_hop = checkpoint_geometry(checkpoint)
     win_size = ck_win if args.win_size is None else args.win_size
     hop_size = ck_hop if args.hop_size is None else args.hop_size
@@ -71,7 +77,7 @@ def main(argv=None):
         sys.exit(1)
     device = torch.device("cuda")
     model = UNet().to(device)
-    model.load_state_dict(checkpoint["model_state_dict"])
+    model.load_state_dict(checkpoint["ema_state_dict" if args.ema else "model_state_dict"])
     model.eval()
     resident = ResidentSpectrograms(dataset, device, with_phase=with_phase)
     with_phase = with_phase and resident.has_phase
