@@ -104,6 +104,29 @@ int svs_crop_remix_tiles(const float* mix_songs, const float* voc_songs, const f
                          const int64_t* offset, const int32_t* frames, const int32_t* song_v, const int32_t* start_v,
                          const int32_t* song_a, const int32_t* start_a, const float* gain_v, const float* gain_a, int B, int F,
                          int seg, float* mix, float* voc, float* mix_phase, float* voc_phase, hipStream_t stream);
+/* Time-stretch augmentation of the same items (csrc/stretch.hip; Cohen-Hadria, Roebel and Peeters 2019 -- the reference's
+ * SpectrogramDataset, train.py:86-143, has no augmentation): a phase vocoder on each source before the mix.  Storage, tables, gains
+ * and padding are those of svs_crop_remix_tiles; rate_v / rate_a are Q10 rates q (r = q / 1024; augment.check_stretch_table keeps
+ * 512 <= q <= 2048).  The sources are the vocal of A = song_v[b] from column s_v = start_v[b] at q_v, and the accompaniment
+ * M cis(phi_m) - V cis(phi_v) of B = song_a[b] from s_a at q_a (song_a[b] < 0: B = A, s_a = s_v, q_a = q_v, the same complex path).
+ * For a source S, row f (bin = f + 1) and output frame t:  n = t q, k = s + (n >> 10), alpha = (n & 1023) / 1024,
+ *   mag_t = (1 - alpha) |S[k]| + alpha |S[k+1]|,   out_t = mag_t cis(acc_t),   acc_0 = arg S[s],
+ *   acc_{t+1} = acc_t + w + wrap(arg S[k+1] - arg S[k] - w),   w = 2 pi ((hop bin) mod n_fft) / n_fft,   wrap to [-pi, pi)
+ * (arg of an exactly zero magnitude is 0; columns outside [0, T) are zero), and the item is
+ *   z = g_v PV(vocal) + g_a PV(accompaniment):  mix = |z|, mix_phase = arg z, voc = g_v mag_v, voc_phase = acc_v in [-pi, pi],
+ * a phase being 0 wherever its magnitude is exactly 0.  The mixture is the sum of the stretched sources, never a stretched mixture.
+ * acc is carried as a 32-bit fraction of a turn (exact wrapping integer sums: no error that grows with hop * bin, and the same bits
+ * whatever the grid, the batch size or an item's place in the batch); magnitudes, sincosf / atan2f / hypotf are fp32.  The angle
+ * sources are required (there is no magnitude-only stretch).  mix_phase == voc_phase == NULL: only mix and voc are written, bit for
+ * bit those of the four-output call.  Refused with SVS_ERR_INVALID before any launch: a null pointer or table, one phase output
+ * alone, seg % 4 != 0, an output that is not 16-byte aligned, n_fft other than 512 / 1024 / 2048, hop outside 1..n_fft, F outside
+ * 1..n_fft / 2 (rows are bins 1..F; augment.crop_stretch passes F == n_fft / 2).  The kernel trusts its tables: song indices in
+ * range, 0 <= start, 512 <= q <= 2048 (checked on the host).  One launch, no workspace, no atomics.  Outputs: (B, 1, F, seg). */
+int svs_crop_stretch_tiles(const float* mix_songs, const float* voc_songs, const float* mix_ang, const float* voc_ang,
+                           const int64_t* offset, const int32_t* frames, const int32_t* song_v, const int32_t* start_v,
+                           const int32_t* song_a, const int32_t* start_a, const float* gain_v, const float* gain_a,
+                           const int32_t* rate_v, const int32_t* rate_a, int B, int F, int seg, int n_fft, int hop, float* mix,
+                           float* voc, float* mix_phase, float* voc_phase, hipStream_t stream);
 int svs_dropout_mask(float* out, int B, int C, int layer, uint32_t seed, int step, int rank, hipStream_t stream);
 /* The five decoder masks of one step in one launch: out = [B*256 | B*128 | B*64 | B*32 | B*16] floats, each block
  * bit-identical to svs_dropout_mask(layer = 0..4) -- the layout svs_unet_train_* take as `drop`. */

@@ -39,7 +39,8 @@ checkpoint.
 (augment.py, csrc/augment.hip; the reference has no augmentation): a random gain per source and, for remix, the vocal of one crop
 over the accompaniment of another, formed from the complex spectra so that it is the STFT of the re-mixed audio.  --gain_range,
 --remix_prob and --augment_seed set it; an epoch's table depends on (seed, epoch) only, goes up in one copy, and each step is one
-launch.  Validation is never augmented; the checkpoint format is unchanged.
+launch.  --stretch_range LO HI (with --augment gain|remix; csrc/stretch.hip) also time-stretches every source before the mix, a phase
+vocoder on the resident spectra at a rate of its own per source.  Validation is never augmented; the checkpoint format is unchanged.
 
 --weight_decay X, --clip_grad_norm X, --ema_decay X (all 0 = off: the optimiser step is then the reference's Adam, one launch) turn on
 decoupled weight decay, clipping by the global gradient norm and an exponential moving average of the weights inside the optimiser
@@ -300,17 +301,27 @@ class ResidentSpectrograms:
         for i in range(0, len(order), batch_size):
             yield self.crop(*self.draw(order[i:i + batch_size]), with_phase=with_phase)
 
-    def augmented_batches(self, batch_size, rank=0, world=1, epoch=0, with_phase: bool = False, aug=None):
+    def augmented_batches(self, batch_size, rank=0, world=1, epoch=0, with_phase: bool = False, aug=None, hop=HOP_SIZE):
         """One epoch of `batches` with gain / remix augmentation (augment.py): the same permutation and sharding of the items, each
         item's sources, starts and gains from `augment.draw_epoch` -- a function of (aug.seed, epoch), so every rank draws the same
         table.  The rank's whole epoch goes up in ONE pinned copy (four int32 rows and two float32 rows of one buffer, as
         `validation_pass` uploads its pass); a batch is a slice of it and one `svs_crop_remix_tiles` launch: no per-step
-        host-to-device copy, no read-back."""
+        host-to-device copy, no read-back.  With aug.stretch_range set, every source is also time-stretched at a rate of its own:
+        `augment.draw_epoch_stretch`'s table (eight rows) and one `svs_crop_stretch_tiles` launch per batch, at the window the set was
+        written with (2 * rows) and `hop`."""
         from . import augment
         if aug is None or aug.mode == "none":
             raise ValueError("augmented_batches needs augmentation settings other than 'none' (`batches` is the plain path)")
         order = epoch_order(len(self), True, rank, world, epoch)
         if not order:
+            return
+        remix_prob = aug.remix_prob if aug.mode == "remix" else 0.0
+        if aug.stretch_range is not None:
+            drawn = augment.draw_epoch_stretch(len(self), self.frames_host, INPUT_LEN, epoch, aug.seed, aug.gain_range, remix_prob,
+                                               aug.stretch_range)
+            table = augment.upload_stretch_table(self, drawn, order)
+            for lo in range(0, len(order), batch_size):
+                yield augment.crop_stretch(self, table, lo, min(lo + batch_size, len(order)), 2 * self.rows, hop, with_phase)
             return
         drawn = augment.draw_epoch(len(self), self.frames_host, INPUT_LEN, epoch, aug.seed, aug.gain_range,
                                    aug.remix_prob if aug.mode == "remix" else 0.0)
@@ -396,6 +407,11 @@ def main(argv=None):
     parser.add_argument("--remix_prob", type=float, default=augment.REMIX_PROB,
                         help="share of the items whose accompaniment comes from a random crop of a random song (default 0.5: a choice, not a tuned value)")
     parser.add_argument("--augment_seed", type=int, default=0, help="the tables of an epoch depend on (this, epoch) only")
+    parser.add_argument("--stretch_range", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                        help="with --augment gain|remix: time-stretch every source before the mix by a phase vocoder on the device, at a "
+                             "rate uniform in [LO, HI] within 0.5 .. 2 (needs *_phase.npy; default: no stretch; the range one would start "
+                             "with, 0.8 1.25, is a choice, not a tuned value).  At the default 768-of-1024 hop the phase estimate is "
+                             "unambiguous only within about +-2/3 bin: folders written with a smaller --hop_size stretch more cleanly")
     parser.add_argument("--weight_decay", type=float, default=0.0, help="decoupled weight decay (torch.optim.AdamW), on every parameter; 0 = off")
     parser.add_argument("--clip_grad_norm", type=float, default=0.0,
                         help="clip the global gradient norm to this (after the all-reduce under data parallelism); 0 = off")
@@ -415,8 +431,10 @@ def main(argv=None):
         parser.error(bad)
     optim_options = bool(args.weight_decay or args.clip_grad_norm or args.ema_decay)
     aug = None
+    if args.stretch_range is not None and args.augment == "none":
+        parser.error("--stretch_range: the stretch is part of the augmented tile cut, it needs --augment gain or --augment remix")
     if args.augment != "none":                                  # `none` reaches nothing of augment.py beyond the flags' defaults
-        bad = augment.check_settings(args.augment, args.gain_range, args.remix_prob)
+        bad = augment.check_settings(args.augment, args.gain_range, args.remix_prob, args.stretch_range)
         if bad:
             parser.error(bad)
         loader = os.environ.get("SVS_DATA_LOADER", "resident")
@@ -426,7 +444,12 @@ def main(argv=None):
         if args.augment == "remix" and not folder_has_phase_files(args.train_folder):
             raise SystemExit(f"train.py: --augment remix needs the *_phase.npy files of every song of {args.train_folder} (the accompaniment "
                              "is mixture minus vocal as complex spectra); --augment gain works without them")
-        aug = augment.Augment(args.augment, (float(args.gain_range[0]), float(args.gain_range[1])), float(args.remix_prob), args.augment_seed)
+        if args.stretch_range is not None and not folder_has_phase_files(args.train_folder):
+            raise SystemExit(f"train.py: --stretch_range needs the *_phase.npy files of every song of {args.train_folder} (the phase vocoder "
+                             "reads the sources' angles; there is no magnitude-only stretch)")
+        stretch = None if args.stretch_range is None else (float(args.stretch_range[0]), float(args.stretch_range[1]))
+        aug = augment.Augment(args.augment, (float(args.gain_range[0]), float(args.gain_range[1])), float(args.remix_prob), args.augment_seed,
+                              stretch)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -557,7 +580,7 @@ def main(argv=None):
             if aug is None:
                 stream = resident.batches(per_rank_batch, True, rank, world, ep, with_phase=full)
             else:
-                stream = resident.augmented_batches(per_rank_batch, rank, world, ep, with_phase=full, aug=aug)
+                stream = resident.augmented_batches(per_rank_batch, rank, world, ep, with_phase=full, aug=aug, hop=args.hop_size)
         else:
             steps = len(train_loader)
             to_dev = lambda t: t.to(device, non_blocking=True)
