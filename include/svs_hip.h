@@ -500,44 +500,47 @@ int svs_scale_by_inv(float* x, int64_t n, const float* denom /*device scalar; 0 
 #define SVS_BSS_MAX_PAIRS 16
 #define SVS_BSS_MAX_LAG 512
 #define SVS_BSS_MAX_RHS 16
-/* Lagged correlations of signals x[s*ld + m], 0 <= s < nsig, 0 <= m < n (zero outside [0, n)).  pairs (HOST array of
- * 3*npairs ints): pair q = (a, b, nlags), 1 <= nlags <= SVS_BSS_MAX_LAG, asks for
- *   out[off_q + k] = sum_m x_a[m+k] x_b[m],   0 <= k < nlags,   off_q = sum of the nlags of the pairs before q.
+/* Lagged correlations of signals x[s*ld + m], 0 <= s < nsig, 0 <= m < n, for every window w < nwin of
+ * x[:, w*hop .. w*hop + window), each window zero past its end (the halo included) and past n; a whole signal is the one
+ * window with window = hop = n.  pairs (HOST array of 3*npairs ints): pair q = (a, b, nlags), 1 <= nlags <=
+ * SVS_BSS_MAX_LAG, asks for
+ *   out[w*out_stride + off_q + k] = sum_m x_a[m+k] x_b[m],   0 <= k < nlags,   off_q = sum of the nlags of the pairs before q,
+ * out_stride >= the sum of the nlags; window, hop, nwin >= 1.  One correlation launch and one reduce launch whatever nwin is.
  * _project's toeplitz(...) block of G is R_ij[q-p] with R_ij[k] = pair (i, j) for k >= 0 and pair (j, i) at -k; its ssef
- * vector D is pair (estimate, reference); a signal's energy is pair (s, s, 1).  Fixed-order sums: bitwise reproducible. */
-size_t svs_bss_corr_workspace_bytes(int64_t n, int npairs, const int* pairs);
-int svs_bss_corr(const double* x, int64_t ld, int nsig, int64_t n, const int* pairs, int npairs, double* out,
-                 void* ws, size_t ws_bytes, hipStream_t stream);
-/* Projection energies |P_S e|^2 = D^T G^-1 D = |y|^2 (G = L L^T, L y = D) of _project, K <= 2 references, filter length
- * flen (order K*flen of G), from correlations `corr` laid out as svs_bss_corr writes them.  gram_off (HOST, K*K ints):
- * gram_off[i*K + j] = offset in corr of R_ij[0 .. flen); rhs_off (HOST, K*nrhs ints): rhs_off[r*K + i] = offset of the
- * D block of reference i for right-hand side r.  ynorm2[r] = |y_r|^2 (nrhs doubles).  *status (device int) = 0, or
- * 1 + the index of the first pivot of the Cholesky factorisation that was not > 0 (a singular G, e.g. a silent
- * reference: ynorm2 is then meaningless; _project solves by least squares instead). */
-size_t svs_bss_solve_workspace_bytes(int K, int flen, int nrhs);
-int svs_bss_solve(const double* corr, int K, int flen, const int* gram_off, const int* rhs_off, int nrhs, double* ynorm2,
-                  int* status, void* ws, size_t ws_bytes, hipStream_t stream);
-/* Framewise form of svs_bss_corr (evaluate.py: bss_eval_sources_framewise): the same correlations for every window
- * w < nwin of x[:, w*hop .. w*hop + window), each window zero past its end (the halo included) and past n, in one
- * correlation launch and one reduce launch whatever nwin is:
- *   out[w*out_stride + off_q + k],   out_stride >= the sum of the nlags.   window, hop, nwin >= 1.
- * Fixed-order sums, no atomics: bitwise reproducible.  The query is 0 for invalid arguments and for a grid too wide for
- * one launch. */
+ * vector D is pair (estimate, reference); a signal's energy is pair (s, s, 1).  Fixed-order sums, no atomics: bitwise
+ * reproducible.  The query is 0 for invalid arguments and for a grid too wide for one launch. */
 size_t svs_bss_corr_windows_workspace_bytes(int64_t window, int64_t nwin, int npairs, const int* pairs);
 int svs_bss_corr_windows(const double* x, int64_t ld, int nsig, int64_t n, int64_t window, int64_t hop, int64_t nwin,
                          const int* pairs, int npairs, double* out, int64_t out_stride, void* ws, size_t ws_bytes,
                          hipStream_t stream);
-/* Batched form of svs_bss_solve: nbatch independent systems of one shape (K, flen, nrhs).  System s takes its offsets,
- * absolute in corr, from gram_off[s*K*K ..] and rhs_off[s*K*nrhs ..] (HOST int64 arrays, read before the call returns),
- * and writes ynorm2[s*nrhs + r] and status[s] (device).  The launches (expand, one panel and one update launch per
- * 64-column step, norms) do not depend on nbatch; a bad pivot in one system changes no other system's result.  The
- * query is 0 for invalid arguments and for a batch too wide for one launch. */
+/* Projection energies |P_S e|^2 = D^T G^-1 D = |y|^2 (G = L L^T, L y = D) of _project, K <= 2 references, filter length
+ * flen (order K*flen of G), for nbatch independent systems of one shape (K, flen, nrhs), from correlations `corr` laid out
+ * as svs_bss_corr_windows writes them.  System s takes its offsets, absolute in corr, from HOST int64 arrays read before
+ * the call returns: gram_off[s*K*K + i*K + j] = offset of R_ij[0 .. flen); rhs_off[s*K*nrhs + r*K + i] = offset of the D
+ * block of reference i for right-hand side r.  It writes ynorm2[s*nrhs + r] = |y_r|^2 and status[s] (device) = 0, or
+ * 1 + the index of the first pivot of the Cholesky factorisation that was not > 0 (a singular G, e.g. a silent
+ * reference: ynorm2 is then meaningless; _project solves by least squares instead).  The launches (expand, one panel and
+ * one update launch per 64-column step, norms) do not depend on nbatch; a bad pivot in one system changes no other
+ * system's result.  svs_bss_solve_workspace_bytes is the size of
+ * one system's matrix; the batched query is 0 for invalid arguments and for a batch too wide for one launch. */
+size_t svs_bss_solve_workspace_bytes(int K, int flen, int nrhs);
+/* The one-window and one-system forms, kept as the reference the GPU tests hold the windowed and batched forms against.
+ * svs_bss_corr is svs_bss_corr_windows with window = hop = n, nwin = 1 and out_stride = the sum of the nlags.
+ * svs_bss_solve is one system of svs_bss_solve_batched with its offsets (HOST ints, relative to corr) in the kernel
+ * arguments: no table, and a workspace of svs_bss_solve_workspace_bytes.  The same kernels, the same bits. */
+size_t svs_bss_corr_workspace_bytes(int64_t n, int npairs, const int* pairs);
+int svs_bss_corr(const double* x, int64_t ld, int nsig, int64_t n, const int* pairs, int npairs, double* out,
+                 void* ws, size_t ws_bytes, hipStream_t stream);
+int svs_bss_solve(const double* corr, int K, int flen, const int* gram_off, const int* rhs_off, int nrhs, double* ynorm2,
+                  int* status, void* ws, size_t ws_bytes, hipStream_t stream);
 size_t svs_bss_solve_batched_workspace_bytes(int64_t nbatch, int K, int flen, int nrhs);
 int svs_bss_solve_batched(const double* corr, int64_t nbatch, int K, int flen, const int64_t* gram_off,
                           const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, void* ws, size_t ws_bytes,
                           hipStream_t stream);
 /* BSS-eval images (evaluate.py: bss_eval_images -- stereo stems): the two stages above at the sizes of a stereo two-source
- * problem, through entry points and kernels of their own; the limits of the entry points above do not change. */
+ * problem, through entry points of their own; the limits of the entry points above do not change.  The correlation has
+ * kernels of its own; the solve shares the host side and the expand, update and norm kernels of svs_bss_solve_batched,
+ * under another pivot rule. */
 #define SVS_BSS_IMG_MAX_SIGNALS 12
 #define SVS_BSS_IMG_MAX_PAIRS 64
 #define SVS_BSS_IMG_MAX_REFS 4

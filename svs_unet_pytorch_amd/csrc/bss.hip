@@ -14,7 +14,10 @@
 // The solve kernels take a batch of independent systems of one shape: the system is the leading part of the flattened
 // block index, so a batch costs the launches of one system.  A pivot that is not > 0 (a silent reference: G singular) is
 // reported through the system's status word; the factorisation goes on with a unit pivot so that nothing faults, and the
-// caller discards that system's result.
+// caller discards that system's result.  The image entry points (below) share the host side and the expand, update and
+// norm kernels; their tile factorisation (the rank rule, the diagonal tile factored once per step) and their panel kernel
+// stay beside the mono ones: one templated tile routine gave the same bits but cost the mono path 3 to 4 % in three forms
+// (DESIGN.md section 9).
 #include <algorithm>
 #include <vector>
 
@@ -35,8 +38,8 @@ constexpr int NB = 64;                               // Cholesky panel width
 // hit distinct banks
 __device__ __forceinline__ int pidx(int i) { return i + (i >> 3); }
 
-// Window w of a launch is x[:, w*hop .. w*hop + window), zero past its end and past n; the whole-signal call is one window
-// (hop 0, window n).  chunks: per window; gx: blocks per window (the grid is nwin * gx blocks wide); rblocks: reduce blocks
+// Window w of a launch is x[:, w*hop .. w*hop + window), zero past its end and past n; a whole signal is one window
+// (window = hop = n).  chunks: per window; gx: blocks per window (the grid is nwin * gx blocks wide); rblocks: reduce blocks
 // per window.  Slab [window][block][lag]; window w's correlations go to out + w * out_stride.
 struct CorrArgs {
   const double* x; long ld; long n; int nsig, npairs, runs, chunks;
@@ -127,8 +130,8 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_corr_reduce_kernel(CorrArgs a
   a.out[(long)w * a.out_stride + a.off[p] + k] = s;
 }
 
-// blocks per window: one per chunk while the whole grid stays within BSS_MAX_BLOCKS (one window: the whole-signal grid)
-int corr_blocks(long window, int runs, long nwin = 1) {
+// blocks per window: one per chunk while the whole grid stays within BSS_MAX_BLOCKS
+int corr_blocks(long window, int runs, long nwin) {
   const long chunks = (window + BSS_T - 1) / BSS_T;
   const long ygroups = (runs + BSS_THREADS - 1) / BSS_THREADS;
   return (int)std::min<long>(chunks, std::max<long>(1, BSS_MAX_BLOCKS / (ygroups * nwin)));
@@ -147,23 +150,22 @@ bool pairs_valid(int npairs, const int* pairs) {
   return true;
 }
 
-// the pair table of both correlation entry points; the launch geometry (window, hop, chunks, gx, rblocks) is the caller's
-int corr_setup(CorrArgs& a, const double* x, int64_t ld, int nsig, int64_t n, const int* pairs, int npairs, double* out,
-               void* ws, const char* who) {
-  SVS_REQUIRE(x && out && pairs && n >= 1 && ld >= n && nsig >= 1 && nsig <= SVS_BSS_MAX_SIGNALS && npairs >= 1 &&
-              npairs <= SVS_BSS_MAX_PAIRS, "%s: bad arguments", who);
-  a.x = x; a.ld = ld; a.n = n; a.nsig = nsig; a.npairs = npairs; a.out = out; a.slab = (double*)ws;
-  int off = 0, runs = 0;
+// the argument checks of both correlation entry points (`who`), which differ in their signal and pair limits
+int corr_check(const char* who, int max_signals, int max_pairs, const double* x, int64_t ld, int nsig, int64_t n,
+               int64_t window, int64_t hop, int64_t nwin, const int* pairs, int npairs, const double* out,
+               int64_t out_stride) {
+  SVS_REQUIRE(x && out && pairs && n >= 1 && ld >= n && nsig >= 1 && nsig <= max_signals && npairs >= 1 &&
+              npairs <= max_pairs, "%s: bad arguments", who);
+  long lags = 0;
   for (int q = 0; q < npairs; ++q) {
     const int px = pairs[3 * q], py = pairs[3 * q + 1], nl = pairs[3 * q + 2];
     SVS_REQUIRE(px >= 0 && px < nsig && py >= 0 && py < nsig && nl >= 1 && nl <= SVS_BSS_MAX_LAG,
                 "%s: pair %d = (%d, %d, %d) out of range", who, q, px, py, nl);
-    a.px[q] = px; a.py[q] = py; a.nl[q] = nl; a.off[q] = off; a.run0[q] = runs;
-    off += nl;
-    runs += (nl + BSS_RUN - 1) / BSS_RUN;
+    lags += nl;
   }
-  a.run0[npairs] = runs;
-  a.runs = runs;
+  SVS_REQUIRE(window >= 1 && hop >= 1 && nwin >= 1 && out_stride >= lags,
+              "%s: window = %ld, hop = %ld, nwin = %ld, out_stride = %ld (>= %ld lags) out of range", who, (long)window,
+              (long)hop, (long)nwin, (long)out_stride, lags);
   return SVS_OK;
 }
 
@@ -219,9 +221,60 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_expand_kernel(SolveArgs a, in
   M[e] = v;
 }
 
-// Step k: block b factors the diagonal tile (k,k) in LDS (every block, the same bits) and either reports its first bad
-// pivot (b == 0) or solves tile (k+b, k) against it: X L_kk^T = A.  The factor is never written back: the blocks of one
-// launch may start at any time, and a late block must still read the unfactored tile.  Nothing later reads tile (k,k).
+// The rank rule on the 64 x 64 tile in L (lower part), all threads of the block; col0 is the tile's first column and kf the
+// order of G (the identity padding past it is never counted).  bad: first failing column of the tile or -1; nskip: skipped.
+__device__ __forceinline__ void img_factor_tile(double (*L)[NB + 1], double thr, int col0, int kf, int& bad, int& nskip) {
+  const int tid = threadIdx.x;
+  bad = -1; nskip = 0;
+  for (int c = 0; c < NB; ++c) {
+    __syncthreads();
+    const double d = L[c][c];
+    const bool ok = d > thr;                           // false for NaN
+    if (!ok && col0 + c < kf) {
+      if (fabs(d) <= thr) ++nskip;
+      else if (bad < 0) bad = c;
+    }
+    const double piv = ok ? sqrt(d) : 0.0;
+    __syncthreads();
+    if (tid == c) L[c][c] = piv;
+    else if (tid > c && tid < NB) L[tid][c] = ok ? L[tid][c] / piv : 0.0;
+    __syncthreads();
+    for (int e = tid; e < NB * NB; e += BSS_THREADS) {
+      const int r = e / NB, q = e % NB;
+      if (q > c && r >= q) L[r][q] -= L[r][c] * L[q][c];
+    }
+  }
+  __syncthreads();
+}
+
+// thr = order * 2^-52 * max diag G (LAPACK dpstrf's tolerance)
+__device__ __forceinline__ double rank_threshold(const SolveArgs& a, int s) {
+  double top = 0.0;
+  for (int i = 0; i < a.K; ++i) top = fmax(top, a.corr[gram_at(a, s, i * a.K + i)]);
+  return (double)(a.K * a.flen) * 0x1p-52 * top;
+}
+
+// Step k of the image solve, one block per system: factor tile (k,k) in place under the rank rule.
+__global__ __launch_bounds__(BSS_THREADS) void bss_diag_kernel(SolveArgs a, int* skipped, int k) {
+  __shared__ double L[NB][NB + 1];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const long ld = a.np;
+  double* dk = a.M + s * a.mstride + (long)k * NB * ld + (long)k * NB;
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) L[e / NB][e % NB] = dk[(e / NB) * ld + e % NB];
+  int bad, nskip;
+  img_factor_tile(L, rank_threshold(a, s), k * NB, a.K * a.flen, bad, nskip);
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) dk[(e / NB) * ld + e % NB] = L[e / NB][e % NB];
+  if (tid == 0) {
+    if (bad >= 0 && a.status[s] == 0) a.status[s] = k * NB + bad + 1;
+    skipped[s] = (k ? skipped[s] : 0) + nskip;         // one block per system and step, steps in stream order
+  }
+}
+
+// Step k of the mono solve: block b factors the diagonal tile (k,k) in LDS (every block, the same bits) and either reports
+// its first bad pivot (b == 0) or solves tile (k+b, k) against it: X L_kk^T = A.  The factor is never written back: the
+// blocks of one launch may start at any time, and a late block must still read the unfactored tile.  Nothing later reads
+// tile (k,k).  A whole track is a batch of one system, where this costs a launch less per step than factoring once
+// (DESIGN.md section 9).
 __global__ __launch_bounds__(BSS_THREADS) void bss_panel_kernel(SolveArgs a, int k) {
   __shared__ double L[NB][NB + 1];
   __shared__ double A[NB][NB + 1];
@@ -268,6 +321,36 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_panel_kernel(SolveArgs a, int
   }
   double* dst = M + (long)i * NB * ld + (long)k * NB;
   for (int e = tid; e < NB * NB; e += BSS_THREADS) dst[(e / NB) * ld + e % NB] = A[e / NB][e % NB];
+}
+
+// Step k of the image solve: tile (i, k), i > k, becomes X with X L_kk^T = A against the factor bss_diag_kernel left in
+// tile (k,k); a skipped column (L_kk[c][c] == 0) of X is zero.  Block index: system, then tile row.
+__global__ __launch_bounds__(BSS_THREADS) void bss_img_panel_kernel(SolveArgs a, int k) {
+  __shared__ double L[NB][NB + 1];
+  __shared__ double A[NB][NB + 1];
+  const int nt = a.rows / NB - k - 1;
+  const int s = blockIdx.x / nt;
+  const int tid = threadIdx.x, i = k + 1 + blockIdx.x % nt;
+  const long ld = a.np;
+  double* M = a.M + s * a.mstride;
+  const double* dk = M + (long)k * NB * ld + (long)k * NB;
+  double* di = M + (long)i * NB * ld + (long)k * NB;
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) {
+    L[e / NB][e % NB] = dk[(e / NB) * ld + e % NB];
+    A[e / NB][e % NB] = di[(e / NB) * ld + e % NB];
+  }
+  __syncthreads();
+  for (int c = 0; c < NB; ++c) {
+    const double piv = L[c][c];
+    if (tid < NB) A[tid][c] = piv != 0.0 ? A[tid][c] / piv : 0.0;
+    __syncthreads();
+    for (int e = tid; e < NB * NB; e += BSS_THREADS) {
+      const int r = e / NB, q = e % NB;
+      if (q > c) A[r][q] -= A[r][c] * L[q][c];
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) di[(e / NB) * ld + e % NB] = A[e / NB][e % NB];
 }
 
 // Step k: tile (i, j), k < j <= i, j a column tile of G: A_ij -= L_ik L_jk^T.  Thread (tr, tc) owns rows tr + 16 a and
@@ -322,10 +405,13 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_norm_kernel(SolveArgs a) {
   if (tid == 0) a.ynorm2[(long)s * a.nrhs + r] = red[0];
 }
 
-int solve_dims(int K, int flen, int nrhs, int& np, int& rows) {
+void solve_dims(int K, int flen, int nrhs, int& np, int& rows) {
   np = (K * flen + NB - 1) / NB * NB;
   rows = np + (nrhs + NB - 1) / NB * NB;
-  return 0;
+}
+
+bool solve_shape_valid(int max_refs, int K, int flen, int nrhs) {
+  return K >= 1 && K <= max_refs && flen >= 1 && flen <= SVS_BSS_MAX_LAG && nrhs >= 1 && nrhs <= SVS_BSS_MAX_RHS;
 }
 
 // systems that fit one batch: the widest launch of one system (the expand launch, or the first update launch of a small
@@ -342,15 +428,31 @@ size_t solve_table_bytes(long nbatch, int K, int nrhs) {
   return svs_align_up((size_t)nbatch * (K * K + K * nrhs) * sizeof(int64_t), 256);
 }
 
-// expand; per panel step one panel launch and one update launch; the norms -- each over all nsys systems at once
-int solve_launch(const SolveArgs& a, long nsys, hipStream_t stream) {
+// the offset table, then nbatch matrices; 0: the shape is invalid or the batch too large for one launch
+size_t solve_batched_ws_bytes(int max_refs, long nbatch, int K, int flen, int nrhs) {
+  if (!solve_shape_valid(max_refs, K, flen, nrhs) || nbatch < 1 || nbatch > solve_max_systems(K, flen, nrhs)) return 0;
+  int np, rows;
+  solve_dims(K, flen, nrhs, np, rows);
+  return solve_table_bytes(nbatch, K, nrhs) + (size_t)nbatch * rows * np * sizeof(double);
+}
+
+// expand; per step the panel launch (images: after the diagonal launch) and the update launch; the norms -- each over all
+// nsys systems at once
+int solve_launch(const SolveArgs& a, int* skipped, long nsys, bool rank, hipStream_t stream) {
   const int tc = a.np / NB, tr = a.rows / NB;
   const int per = svs_cdiv((long)a.rows * a.np, BSS_THREADS);
   hipLaunchKernelGGL(bss_expand_kernel, dim3((unsigned)(nsys * per)), dim3(BSS_THREADS), 0, stream, a, per);
   SVS_CHECK_LAUNCH("bss_expand");
   for (int k = 0; k < tc; ++k) {
-    hipLaunchKernelGGL(bss_panel_kernel, dim3((unsigned)(nsys * (tr - k))), dim3(BSS_THREADS), 0, stream, a, k);
-    SVS_CHECK_LAUNCH("bss_panel");
+    if (rank) {
+      hipLaunchKernelGGL(bss_diag_kernel, dim3((unsigned)nsys), dim3(BSS_THREADS), 0, stream, a, skipped, k);
+      SVS_CHECK_LAUNCH("bss_diag");
+      hipLaunchKernelGGL(bss_img_panel_kernel, dim3((unsigned)(nsys * (tr - k - 1))), dim3(BSS_THREADS), 0, stream, a, k);
+      SVS_CHECK_LAUNCH("bss_img_panel");
+    } else {
+      hipLaunchKernelGGL(bss_panel_kernel, dim3((unsigned)(nsys * (tr - k))), dim3(BSS_THREADS), 0, stream, a, k);
+      SVS_CHECK_LAUNCH("bss_panel");
+    }
     if (k + 1 < tc) {
       hipLaunchKernelGGL(bss_update_kernel, dim3((unsigned)(nsys * (tc - k - 1) * (tr - k - 1))), dim3(BSS_THREADS), 0,
                          stream, a, k);
@@ -362,30 +464,41 @@ int solve_launch(const SolveArgs& a, long nsys, hipStream_t stream) {
   return SVS_OK;
 }
 
-}  // namespace
-
-extern "C" size_t svs_bss_corr_workspace_bytes(int64_t n, int npairs, const int* pairs) {
-  if (n < 1 || npairs < 1 || npairs > SVS_BSS_MAX_PAIRS || !pairs) return 0;
-  const int runs = count_runs(npairs, pairs);
-  return (size_t)corr_blocks(n, runs) * runs * BSS_RUN * sizeof(double);
-}
-
-extern "C" int svs_bss_corr(const double* x, int64_t ld, int nsig, int64_t n, const int* pairs, int npairs, double* out,
-                            void* ws, size_t ws_bytes, hipStream_t stream) {
-  CorrArgs a{};
-  const int rc = corr_setup(a, x, ld, nsig, n, pairs, npairs, out, ws, "svs_bss_corr");
-  if (rc != SVS_OK) return rc;
-  SVS_REQUIRE((n + BSS_T - 1) / BSS_T < (1L << 31), "svs_bss_corr: n = %ld too large", (long)n);
-  if (!ws || ws_bytes < svs_bss_corr_workspace_bytes(n, npairs, pairs)) {
-    svs_set_error("svs_bss_corr: workspace too small");
+// the body of both batched-solve entry points (`who`): K <= max_refs; rank: the image pivot rule, which fills skipped
+int solve_batched(const char* who, int max_refs, bool rank, const double* corr, int64_t nbatch, int K, int flen,
+                  const int64_t* gram_off, const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, int* skipped,
+                  void* ws, size_t ws_bytes, hipStream_t stream) {
+  SVS_REQUIRE(corr && gram_off && rhs_off && ynorm2 && status && (skipped || !rank) && nbatch >= 1 &&
+              solve_shape_valid(max_refs, K, flen, nrhs), "%s: bad arguments", who);
+  SVS_REQUIRE(nbatch <= solve_max_systems(K, flen, nrhs), "%s: nbatch = %ld too large for one launch", who, (long)nbatch);
+  const int ng = K * K, nr = K * nrhs;
+  std::vector<int64_t> tab((size_t)nbatch * (ng + nr));
+  for (long s = 0; s < nbatch; ++s) {
+    for (int q = 0; q < ng; ++q) {
+      SVS_REQUIRE(gram_off[s * ng + q] >= 0, "%s: negative offset (system %ld)", who, s);
+      tab[s * (ng + nr) + q] = gram_off[s * ng + q];
+    }
+    for (int q = 0; q < nr; ++q) {
+      SVS_REQUIRE(rhs_off[s * nr + q] >= 0, "%s: negative offset (system %ld)", who, s);
+      tab[s * (ng + nr) + ng + q] = rhs_off[s * nr + q];
+    }
+  }
+  if (!ws || ws_bytes < solve_batched_ws_bytes(max_refs, nbatch, K, flen, nrhs)) {
+    svs_set_error("%s: workspace too small", who);
     return SVS_ERR_WORKSPACE;
   }
-  a.hop = 0; a.window = n; a.out_stride = 0;
-  a.chunks = (int)((n + BSS_T - 1) / BSS_T);
-  a.gx = corr_blocks(n, a.runs);
-  a.rblocks = svs_cdiv((long)a.runs * BSS_RUN, BSS_THREADS);
-  return corr_launch(a, 1, stream);
+  SolveArgs a{};
+  a.corr = corr; a.K = K; a.flen = flen; a.nrhs = nrhs; a.status = status; a.ynorm2 = ynorm2;
+  solve_dims(K, flen, nrhs, a.np, a.rows);
+  a.tab = (const int64_t*)ws;
+  a.M = (double*)((char*)ws + solve_table_bytes(nbatch, K, nrhs));
+  a.mstride = (long)a.rows * a.np;
+  // from pageable memory: the runtime has staged `tab` by the time the copy call returns
+  SVS_HIP(hipMemcpyAsync((void*)a.tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+  return solve_launch(a, skipped, nbatch, rank, stream);
 }
+
+}  // namespace
 
 extern "C" size_t svs_bss_corr_windows_workspace_bytes(int64_t window, int64_t nwin, int npairs, const int* pairs) {
   if (window < 1 || nwin < 1 || !pairs_valid(npairs, pairs) || (window + BSS_T - 1) / BSS_T >= (1L << 31)) return 0;
@@ -398,19 +511,23 @@ extern "C" size_t svs_bss_corr_windows_workspace_bytes(int64_t window, int64_t n
 extern "C" int svs_bss_corr_windows(const double* x, int64_t ld, int nsig, int64_t n, int64_t window, int64_t hop,
                                     int64_t nwin, const int* pairs, int npairs, double* out, int64_t out_stride, void* ws,
                                     size_t ws_bytes, hipStream_t stream) {
-  CorrArgs a{};
-  const int rc = corr_setup(a, x, ld, nsig, n, pairs, npairs, out, ws, "svs_bss_corr_windows");
+  const int rc = corr_check("svs_bss_corr_windows", SVS_BSS_MAX_SIGNALS, SVS_BSS_MAX_PAIRS, x, ld, nsig, n, window, hop, nwin,
+                            pairs, npairs, out, out_stride);
   if (rc != SVS_OK) return rc;
-  const long lags = a.off[npairs - 1] + a.nl[npairs - 1];
-  SVS_REQUIRE(window >= 1 && hop >= 1 && nwin >= 1 && out_stride >= lags,
-              "svs_bss_corr_windows: window = %ld, hop = %ld, nwin = %ld, out_stride = %ld (>= %ld lags) out of range",
-              (long)window, (long)hop, (long)nwin, (long)out_stride, lags);
   const size_t need = svs_bss_corr_windows_workspace_bytes(window, nwin, npairs, pairs);
   SVS_REQUIRE(need > 0, "svs_bss_corr_windows: %ld windows of %ld samples do not fit one launch", (long)nwin, (long)window);
   if (!ws || ws_bytes < need) {
     svs_set_error("svs_bss_corr_windows: workspace too small");
     return SVS_ERR_WORKSPACE;
   }
+  CorrArgs a{};
+  a.x = x; a.ld = ld; a.n = n; a.nsig = nsig; a.npairs = npairs; a.out = out; a.slab = (double*)ws;
+  for (int q = 0, off = 0; q < npairs; ++q) {
+    a.px[q] = pairs[3 * q]; a.py[q] = pairs[3 * q + 1]; a.nl[q] = pairs[3 * q + 2]; a.off[q] = off; a.run0[q] = a.runs;
+    off += a.nl[q];
+    a.runs += (a.nl[q] + BSS_RUN - 1) / BSS_RUN;
+  }
+  a.run0[npairs] = a.runs;
   a.hop = hop; a.window = window; a.out_stride = out_stride;
   a.chunks = (int)((window + BSS_T - 1) / BSS_T);
   a.gx = corr_blocks(window, a.runs, nwin);
@@ -418,17 +535,33 @@ extern "C" int svs_bss_corr_windows(const double* x, int64_t ld, int nsig, int64
   return corr_launch(a, nwin, stream);
 }
 
+// The whole-signal correlation is the one-window call: the same launch geometry (corr_blocks(n, runs, 1), window base 0),
+// the same bits.
+extern "C" size_t svs_bss_corr_workspace_bytes(int64_t n, int npairs, const int* pairs) {
+  return svs_bss_corr_windows_workspace_bytes(n, 1, npairs, pairs);
+}
+
+extern "C" int svs_bss_corr(const double* x, int64_t ld, int nsig, int64_t n, const int* pairs, int npairs, double* out,
+                            void* ws, size_t ws_bytes, hipStream_t stream) {
+  int64_t lags = 0;
+  if (pairs && npairs >= 1 && npairs <= SVS_BSS_MAX_PAIRS)
+    for (int q = 0; q < npairs; ++q) lags += pairs[3 * q + 2];
+  return svs_bss_corr_windows(x, ld, nsig, n, n, n, 1, pairs, npairs, out, lags, ws, ws_bytes, stream);
+}
+
+// the bytes of one system's matrix [G; D^T] (K <= 2)
 extern "C" size_t svs_bss_solve_workspace_bytes(int K, int flen, int nrhs) {
-  if (K < 1 || K > 2 || flen < 1 || flen > SVS_BSS_MAX_LAG || nrhs < 1 || nrhs > SVS_BSS_MAX_RHS) return 0;
+  if (!solve_shape_valid(2, K, flen, nrhs)) return 0;
   int np, rows;
   solve_dims(K, flen, nrhs, np, rows);
   return (size_t)rows * np * sizeof(double);
 }
 
+// one system with its offsets in the kernel arguments: no table, no host-to-device copy
 extern "C" int svs_bss_solve(const double* corr, int K, int flen, const int* gram_off, const int* rhs_off, int nrhs,
                              double* ynorm2, int* status, void* ws, size_t ws_bytes, hipStream_t stream) {
-  SVS_REQUIRE(corr && gram_off && rhs_off && ynorm2 && status && K >= 1 && K <= 2 && flen >= 1 &&
-              flen <= SVS_BSS_MAX_LAG && nrhs >= 1 && nrhs <= SVS_BSS_MAX_RHS, "svs_bss_solve: bad arguments");
+  SVS_REQUIRE(corr && gram_off && rhs_off && ynorm2 && status && solve_shape_valid(2, K, flen, nrhs),
+              "svs_bss_solve: bad arguments");
   SolveArgs a{};
   a.corr = corr; a.K = K; a.flen = flen; a.nrhs = nrhs; a.M = (double*)ws; a.status = status; a.ynorm2 = ynorm2;
   for (int q = 0; q < K * K; ++q) {
@@ -444,61 +577,32 @@ extern "C" int svs_bss_solve(const double* corr, int K, int flen, const int* gra
     svs_set_error("svs_bss_solve: workspace too small");
     return SVS_ERR_WORKSPACE;
   }
-  return solve_launch(a, 1, stream);
+  return solve_launch(a, nullptr, 1, false, stream);
 }
 
 extern "C" size_t svs_bss_solve_batched_workspace_bytes(int64_t nbatch, int K, int flen, int nrhs) {
-  const size_t one = svs_bss_solve_workspace_bytes(K, flen, nrhs);
-  if (!one || nbatch < 1 || nbatch > solve_max_systems(K, flen, nrhs)) return 0;
-  return solve_table_bytes(nbatch, K, nrhs) + (size_t)nbatch * one;
+  return solve_batched_ws_bytes(2, nbatch, K, flen, nrhs);
 }
 
 extern "C" int svs_bss_solve_batched(const double* corr, int64_t nbatch, int K, int flen, const int64_t* gram_off,
                                      const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, void* ws,
                                      size_t ws_bytes, hipStream_t stream) {
-  SVS_REQUIRE(corr && gram_off && rhs_off && ynorm2 && status && nbatch >= 1 && K >= 1 && K <= 2 && flen >= 1 &&
-              flen <= SVS_BSS_MAX_LAG && nrhs >= 1 && nrhs <= SVS_BSS_MAX_RHS, "svs_bss_solve_batched: bad arguments");
-  SVS_REQUIRE(nbatch <= solve_max_systems(K, flen, nrhs), "svs_bss_solve_batched: nbatch = %ld too large for one launch",
-              (long)nbatch);
-  const int ng = K * K, nr = K * nrhs;
-  std::vector<int64_t> tab((size_t)nbatch * (ng + nr));
-  for (long s = 0; s < nbatch; ++s) {
-    for (int q = 0; q < ng; ++q) {
-      SVS_REQUIRE(gram_off[s * ng + q] >= 0, "svs_bss_solve_batched: negative offset (system %ld)", s);
-      tab[s * (ng + nr) + q] = gram_off[s * ng + q];
-    }
-    for (int q = 0; q < nr; ++q) {
-      SVS_REQUIRE(rhs_off[s * nr + q] >= 0, "svs_bss_solve_batched: negative offset (system %ld)", s);
-      tab[s * (ng + nr) + ng + q] = rhs_off[s * nr + q];
-    }
-  }
-  if (!ws || ws_bytes < svs_bss_solve_batched_workspace_bytes(nbatch, K, flen, nrhs)) {
-    svs_set_error("svs_bss_solve_batched: workspace too small");
-    return SVS_ERR_WORKSPACE;
-  }
-  SolveArgs a{};
-  a.corr = corr; a.K = K; a.flen = flen; a.nrhs = nrhs; a.status = status; a.ynorm2 = ynorm2;
-  solve_dims(K, flen, nrhs, a.np, a.rows);
-  a.tab = (const int64_t*)ws;
-  a.M = (double*)((char*)ws + solve_table_bytes(nbatch, K, nrhs));
-  a.mstride = (long)a.rows * a.np;
-  // from pageable memory: the runtime has staged `tab` by the time the copy call returns
-  SVS_HIP(hipMemcpyAsync((void*)a.tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-  return solve_launch(a, nbatch, stream);
+  return solve_batched("svs_bss_solve_batched", 2, false, corr, nbatch, K, flen, gram_off, rhs_off, nrhs, ynorm2, status,
+                       nullptr, ws, ws_bytes, stream);
 }
 
 // ---- BSS-eval images: stereo stems (evaluate.py: bss_eval_images) ------------------------------
-// The same two stages at the sizes a stereo two-source problem needs -- 10 signals, about 50 pairs, 4 reference channels
-// (order 2048) -- with entry points and kernels of their own; the ones above keep their limits.
+// The correlation at the sizes a stereo two-source problem needs -- 10 signals, about 50 pairs -- with an entry point and
+// kernels of its own, and the solve above for up to 4 reference channels (order 2048) under the rank rule:
+//   bss_diag_kernel         factors the diagonal tile (k,k) ONCE per system and step and writes the factor back;
+//   bss_img_panel_kernel    the panel blocks then only solve X L_kk^T = A against it (bss_panel_kernel's scheme, every block
+//                           factoring the tile for itself, measured 9 % slower at order 2048: DESIGN.md section 9).
 //   bss_img_corr_kernel     the sweep of bss_corr_kernel.  The pair table no longer fits the kernel arguments, so it lives in
 //                           device memory at the head of the workspace, one int4 per thread slot.  The host packs whole
 //                           pairs into groups of 256 slots (blockIdx.y) that touch at most SVS_BSS_MAX_SIGNALS signals, and a
 //                           block stages only its group's signals: the LDS stays at the 83 KB of the kernel above and two
 //                           blocks share a CU, whatever the number of signals.
 //   bss_img_reduce_kernel   the fixed-order sum over blocks, one thread per (slot, lag of its run).
-//   bss_img_diag_kernel     factors the diagonal tile (k,k) ONCE per system and step and writes the factor back;
-//   bss_img_panel_kernel    the panel blocks then only solve X L_kk^T = A against it (bss_panel_kernel's scheme, every block
-//                           factoring the tile for itself, measured 9 % slower at order 2048: DESIGN.md section 9).
 // Rank rule (img_factor_tile): stereo images make G singular as a rule (L == R, a silent channel).  With
 // thr = order * 2^-52 * max diag G (LAPACK dpstrf's tolerance), a pivot d <= thr with |d| <= thr marks a delayed channel that
 // depends on the earlier columns: its column of L and its y component are zero, so |y|^2 is the energy of the projection on
@@ -569,7 +673,7 @@ __global__ __launch_bounds__(BSS_THREADS) void bss_img_reduce_kernel(ImgCorrArgs
 }
 
 struct ImgCorrPlan {
-  int ngroups = 0; long lags = 0;
+  int ngroups = 0;
   std::vector<int> slots, gsig;      // the device table: slots (4 ints per slot), then gsig
 };
 
@@ -587,7 +691,7 @@ bool img_pairs_valid(int npairs, const int* pairs) {
 ImgCorrPlan img_corr_plan(int npairs, const int* pairs) {
   ImgCorrPlan p;
   std::vector<int> off(npairs);
-  for (int q = 0; q < npairs; ++q) { off[q] = (int)p.lags; p.lags += pairs[3 * q + 2]; }
+  for (int q = 0, lags = 0; q < npairs; ++q) { off[q] = lags; lags += pairs[3 * q + 2]; }
   std::vector<bool> done(npairs, false);
   for (int left = npairs; left > 0;) {
     int staged[SVS_BSS_MAX_SIGNALS], nstaged = 0, used = 0;
@@ -636,110 +740,6 @@ size_t img_corr_ws_bytes(long window, long nwin, const ImgCorrPlan& p) {
   return img_corr_table_bytes(p.ngroups) + (size_t)nwin * gx * p.ngroups * BSS_THREADS * BSS_RUN * sizeof(double);
 }
 
-// The rank rule on the 64 x 64 tile in L (lower part), all threads of the block; col0 is the tile's first column and kf the
-// order of G (the identity padding past it is never counted).  bad: first failing column of the tile or -1; nskip: skipped.
-__device__ __forceinline__ void img_factor_tile(double (*L)[NB + 1], double thr, int col0, int kf, int& bad, int& nskip) {
-  const int tid = threadIdx.x;
-  bad = -1; nskip = 0;
-  for (int c = 0; c < NB; ++c) {
-    __syncthreads();
-    const double d = L[c][c];
-    const bool ok = d > thr;                           // false for NaN
-    if (!ok && col0 + c < kf) {
-      if (fabs(d) <= thr) ++nskip;
-      else if (bad < 0) bad = c;
-    }
-    const double piv = ok ? sqrt(d) : 0.0;
-    __syncthreads();
-    if (tid == c) L[c][c] = piv;
-    else if (tid > c && tid < NB) L[tid][c] = ok ? L[tid][c] / piv : 0.0;
-    __syncthreads();
-    for (int e = tid; e < NB * NB; e += BSS_THREADS) {
-      const int r = e / NB, q = e % NB;
-      if (q > c && r >= q) L[r][q] -= L[r][c] * L[q][c];
-    }
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ double img_threshold(const SolveArgs& a, int s) {
-  double top = 0.0;
-  for (int i = 0; i < a.K; ++i) top = fmax(top, a.corr[gram_at(a, s, i * a.K + i)]);
-  return (double)(a.K * a.flen) * 0x1p-52 * top;
-}
-
-// Step k, one block per system: factor tile (k,k) in place.
-__global__ __launch_bounds__(BSS_THREADS) void bss_img_diag_kernel(SolveArgs a, int* skipped, int k) {
-  __shared__ double L[NB][NB + 1];
-  const int s = blockIdx.x, tid = threadIdx.x;
-  const long ld = a.np;
-  double* dk = a.M + s * a.mstride + (long)k * NB * ld + (long)k * NB;
-  for (int e = tid; e < NB * NB; e += BSS_THREADS) L[e / NB][e % NB] = dk[(e / NB) * ld + e % NB];
-  int bad, nskip;
-  img_factor_tile(L, img_threshold(a, s), k * NB, a.K * a.flen, bad, nskip);
-  for (int e = tid; e < NB * NB; e += BSS_THREADS) dk[(e / NB) * ld + e % NB] = L[e / NB][e % NB];
-  if (tid == 0) {
-    if (bad >= 0 && a.status[s] == 0) a.status[s] = k * NB + bad + 1;
-    skipped[s] = (k ? skipped[s] : 0) + nskip;         // one block per system and step, steps in stream order
-  }
-}
-
-// Step k: tile (i, k), i > k, becomes X with X L_kk^T = A against the factor bss_img_diag_kernel left in tile (k,k); a
-// skipped column (L_kk[c][c] == 0) of X is zero.  Block index: system, then tile row.
-__global__ __launch_bounds__(BSS_THREADS) void bss_img_panel_kernel(SolveArgs a, int k) {
-  __shared__ double L[NB][NB + 1];
-  __shared__ double A[NB][NB + 1];
-  const int nt = a.rows / NB - k - 1;
-  const int s = blockIdx.x / nt;
-  const int tid = threadIdx.x, i = k + 1 + blockIdx.x % nt;
-  const long ld = a.np;
-  double* M = a.M + s * a.mstride;
-  const double* dk = M + (long)k * NB * ld + (long)k * NB;
-  double* di = M + (long)i * NB * ld + (long)k * NB;
-  for (int e = tid; e < NB * NB; e += BSS_THREADS) {
-    L[e / NB][e % NB] = dk[(e / NB) * ld + e % NB];
-    A[e / NB][e % NB] = di[(e / NB) * ld + e % NB];
-  }
-  __syncthreads();
-  for (int c = 0; c < NB; ++c) {
-    const double piv = L[c][c];
-    if (tid < NB) A[tid][c] = piv != 0.0 ? A[tid][c] / piv : 0.0;
-    __syncthreads();
-    for (int e = tid; e < NB * NB; e += BSS_THREADS) {
-      const int r = e / NB, q = e % NB;
-      if (q > c) A[r][q] -= A[r][c] * L[q][c];
-    }
-    __syncthreads();
-  }
-  for (int e = tid; e < NB * NB; e += BSS_THREADS) di[(e / NB) * ld + e % NB] = A[e / NB][e % NB];
-}
-
-// expand; per step the diagonal, the panel and the update launch; the norms -- each over all nsys systems at once
-int img_solve_launch(const SolveArgs& a, int* skipped, long nsys, hipStream_t stream) {
-  const int tc = a.np / NB, tr = a.rows / NB;
-  const int per = svs_cdiv((long)a.rows * a.np, BSS_THREADS);
-  hipLaunchKernelGGL(bss_expand_kernel, dim3((unsigned)(nsys * per)), dim3(BSS_THREADS), 0, stream, a, per);
-  SVS_CHECK_LAUNCH("bss_expand");
-  for (int k = 0; k < tc; ++k) {
-    hipLaunchKernelGGL(bss_img_diag_kernel, dim3((unsigned)nsys), dim3(BSS_THREADS), 0, stream, a, skipped, k);
-    SVS_CHECK_LAUNCH("bss_img_diag");
-    hipLaunchKernelGGL(bss_img_panel_kernel, dim3((unsigned)(nsys * (tr - k - 1))), dim3(BSS_THREADS), 0, stream, a, k);
-    SVS_CHECK_LAUNCH("bss_img_panel");
-    if (k + 1 < tc) {
-      hipLaunchKernelGGL(bss_update_kernel, dim3((unsigned)(nsys * (tc - k - 1) * (tr - k - 1))), dim3(BSS_THREADS), 0,
-                         stream, a, k);
-      SVS_CHECK_LAUNCH("bss_update");
-    }
-  }
-  hipLaunchKernelGGL(bss_norm_kernel, dim3((unsigned)(nsys * a.nrhs)), dim3(BSS_THREADS), 0, stream, a);
-  SVS_CHECK_LAUNCH("bss_norm");
-  return SVS_OK;
-}
-
-bool img_solve_shape_valid(int K, int flen, int nrhs) {
-  return K >= 1 && K <= SVS_BSS_IMG_MAX_REFS && flen >= 1 && flen <= SVS_BSS_MAX_LAG && nrhs >= 1 && nrhs <= SVS_BSS_MAX_RHS;
-}
-
 }  // namespace
 
 extern "C" size_t svs_bss_img_corr_windows_workspace_bytes(int64_t window, int64_t nwin, int npairs, const int* pairs) {
@@ -750,17 +750,10 @@ extern "C" size_t svs_bss_img_corr_windows_workspace_bytes(int64_t window, int64
 extern "C" int svs_bss_img_corr_windows(const double* x, int64_t ld, int nsig, int64_t n, int64_t window, int64_t hop,
                                         int64_t nwin, const int* pairs, int npairs, double* out, int64_t out_stride,
                                         void* ws, size_t ws_bytes, hipStream_t stream) {
-  SVS_REQUIRE(x && out && pairs && n >= 1 && ld >= n && nsig >= 1 && nsig <= SVS_BSS_IMG_MAX_SIGNALS && npairs >= 1 &&
-              npairs <= SVS_BSS_IMG_MAX_PAIRS, "svs_bss_img_corr_windows: bad arguments");
-  for (int q = 0; q < npairs; ++q) {
-    const int px = pairs[3 * q], py = pairs[3 * q + 1], nl = pairs[3 * q + 2];
-    SVS_REQUIRE(px >= 0 && px < nsig && py >= 0 && py < nsig && nl >= 1 && nl <= SVS_BSS_MAX_LAG,
-                "svs_bss_img_corr_windows: pair %d = (%d, %d, %d) out of range", q, px, py, nl);
-  }
+  const int rc = corr_check("svs_bss_img_corr_windows", SVS_BSS_IMG_MAX_SIGNALS, SVS_BSS_IMG_MAX_PAIRS, x, ld, nsig, n, window,
+                            hop, nwin, pairs, npairs, out, out_stride);
+  if (rc != SVS_OK) return rc;
   const ImgCorrPlan p = img_corr_plan(npairs, pairs);
-  SVS_REQUIRE(window >= 1 && hop >= 1 && nwin >= 1 && out_stride >= p.lags,
-              "svs_bss_img_corr_windows: window = %ld, hop = %ld, nwin = %ld, out_stride = %ld (>= %ld lags) out of range",
-              (long)window, (long)hop, (long)nwin, (long)out_stride, p.lags);
   const size_t need = img_corr_ws_bytes(window, nwin, p);
   SVS_REQUIRE(need > 0, "svs_bss_img_corr_windows: %ld windows of %ld samples do not fit one launch", (long)nwin,
               (long)window);
@@ -789,42 +782,12 @@ extern "C" int svs_bss_img_corr_windows(const double* x, int64_t ld, int nsig, i
 }
 
 extern "C" size_t svs_bss_img_solve_batched_workspace_bytes(int64_t nbatch, int K, int flen, int nrhs) {
-  if (!img_solve_shape_valid(K, flen, nrhs) || nbatch < 1 || nbatch > solve_max_systems(K, flen, nrhs)) return 0;
-  int np, rows;
-  solve_dims(K, flen, nrhs, np, rows);
-  return solve_table_bytes(nbatch, K, nrhs) + (size_t)nbatch * rows * np * sizeof(double);
+  return solve_batched_ws_bytes(SVS_BSS_IMG_MAX_REFS, nbatch, K, flen, nrhs);
 }
 
 extern "C" int svs_bss_img_solve_batched(const double* corr, int64_t nbatch, int K, int flen, const int64_t* gram_off,
                                          const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, int* skipped,
                                          void* ws, size_t ws_bytes, hipStream_t stream) {
-  SVS_REQUIRE(corr && gram_off && rhs_off && ynorm2 && status && skipped && nbatch >= 1 && img_solve_shape_valid(K, flen, nrhs),
-              "svs_bss_img_solve_batched: bad arguments");
-  SVS_REQUIRE(nbatch <= solve_max_systems(K, flen, nrhs), "svs_bss_img_solve_batched: nbatch = %ld too large for one launch",
-              (long)nbatch);
-  const int ng = K * K, nr = K * nrhs;
-  std::vector<int64_t> tab((size_t)nbatch * (ng + nr));
-  for (long s = 0; s < nbatch; ++s) {
-    for (int q = 0; q < ng; ++q) {
-      SVS_REQUIRE(gram_off[s * ng + q] >= 0, "svs_bss_img_solve_batched: negative offset (system %ld)", s);
-      tab[s * (ng + nr) + q] = gram_off[s * ng + q];
-    }
-    for (int q = 0; q < nr; ++q) {
-      SVS_REQUIRE(rhs_off[s * nr + q] >= 0, "svs_bss_img_solve_batched: negative offset (system %ld)", s);
-      tab[s * (ng + nr) + ng + q] = rhs_off[s * nr + q];
-    }
-  }
-  if (!ws || ws_bytes < svs_bss_img_solve_batched_workspace_bytes(nbatch, K, flen, nrhs)) {
-    svs_set_error("svs_bss_img_solve_batched: workspace too small");
-    return SVS_ERR_WORKSPACE;
-  }
-  SolveArgs a{};
-  a.corr = corr; a.K = K; a.flen = flen; a.nrhs = nrhs; a.status = status; a.ynorm2 = ynorm2;
-  solve_dims(K, flen, nrhs, a.np, a.rows);
-  a.tab = (const int64_t*)ws;
-  a.M = (double*)((char*)ws + solve_table_bytes(nbatch, K, nrhs));
-  a.mstride = (long)a.rows * a.np;
-  // from pageable memory: the runtime has staged `tab` by the time the copy call returns
-  SVS_HIP(hipMemcpyAsync((void*)a.tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-  return img_solve_launch(a, skipped, nbatch, stream);
+  return solve_batched("svs_bss_img_solve_batched", SVS_BSS_IMG_MAX_REFS, true, corr, nbatch, K, flen, gram_off, rhs_off, nrhs,
+                       ynorm2, status, skipped, ws, ws_bytes, stream);
 }

@@ -19,9 +19,10 @@ wav files are read with scipy.io.wavfile (mono downmix, native sample rate: eval
 mir_eval.separation.bss_eval_sources_framewise does.  `bss_eval_sources_gpu`, `bss_eval_sources_framewise_gpu` and
 `device="gpu"` of the two metrics functions (CLI `--device gpu`) compute the same metrics with fp64 gfx950 kernels
 (csrc/bss.hip) from the Gram-matrix form below; the numpy functions stay the reference they are tested against.  The GPU
-path is one path over windows: one windowed correlation pass, then the Gram matrices of all windows factored in batches;
-a whole signal is its one-window case.  Per window, an output that needs a factorisation with a pivot that is not > 0
-comes from the numpy bss_eval_sources on that window's slice, with one RuntimeWarning per call.
+path is one path over windows (_gpu_projections, the only caller of the library, for mono sources and stereo images
+alike): one windowed correlation pass, then the Gram matrices of all windows factored in batches; a whole signal is its
+one-window case.  Per window, an output that needs a factorisation with a pivot that is not > 0 comes from the numpy
+bss_eval_sources on that window's slice, with one RuntimeWarning per call.
 
 The Gram-matrix form of _project / _criteria.  References s_0 .. s_{K-1} and an estimate e of length n, zero outside
 [0, n); filter length F; x(.-p) is x delayed by p samples.  _project builds
@@ -52,8 +53,10 @@ The Gram form of the images (_image_metrics_from_gram).  Per estimate a and sour
     SIR = P1 / (Pa - P1),   SAR = Pa / (E_e - Pa)            the spans are nested, as in the mono case
 with every P a |y|^2 of a system whose references are the nchan (P_j) or nsrc * nchan (P_all) reference channels: order up to
 4 * 512 = 2048 for a stereo two-source problem.  Such G are singular as a rule, not as an exception -- a centre-panned vocal
-has L == R, a hard-panned stem a silent channel -- so the device factorisation skips dependent columns (include/svs_hip.h,
-svs_bss_img_solve_batched): the projection onto the remaining columns is the projection onto the same span.
+has L == R, a hard-panned stem a silent channel -- so the image entry points run the mono factorisation under another pivot
+rule that skips dependent columns (include/svs_hip.h, svs_bss_img_solve_batched): the projection onto the remaining columns
+is the projection onto the same span.  The numpy reference is shared the same way: _project and _decompose are the
+one-channel cases of _project_images and _decompose_images.
 """
 from __future__ import annotations
 
@@ -96,45 +99,16 @@ def load_mono_audio(path):
 
 
 def _project(reference_sources, estimated_source, flen):
-    """Least-squares projection of the estimate onto the references delayed by 0 .. flen-1 samples."""
-    from scipy.linalg import toeplitz
-    from scipy.signal import fftconvolve
-    nsrc, nsampl = reference_sources.shape
-    refs = np.hstack((reference_sources, np.zeros((nsrc, flen - 1))))
-    est = np.hstack((estimated_source, np.zeros(flen - 1)))
-    n_fft = int(2 ** np.ceil(np.log2(nsampl + flen - 1.0)))
-    sf = np.fft.fft(refs, n=n_fft, axis=1)
-    sef = np.fft.fft(est, n=n_fft)
-    G = np.zeros((nsrc * flen, nsrc * flen))
-    for i in range(nsrc):
-        for j in range(i + 1):
-            ssf = np.real(np.fft.ifft(sf[i] * np.conj(sf[j])))
-            ss = toeplitz(np.hstack((ssf[0], ssf[-1:-flen:-1])), r=ssf[:flen])
-            G[i * flen:(i + 1) * flen, j * flen:(j + 1) * flen] = ss
-            G[j * flen:(j + 1) * flen, i * flen:(i + 1) * flen] = ss.T
-    D = np.zeros(nsrc * flen)
-    for i in range(nsrc):
-        ssef = np.real(np.fft.ifft(sf[i] * np.conj(sef)))
-        D[i * flen:(i + 1) * flen] = np.hstack((ssef[0], ssef[-1:-flen:-1]))
-    try:
-        C = np.linalg.solve(G, D).reshape(flen, nsrc, order="F")
-    except np.linalg.LinAlgError:
-        C = np.linalg.lstsq(G, D, rcond=None)[0].reshape(flen, nsrc, order="F")
-    sproj = np.zeros(nsampl + flen - 1)
-    for i in range(nsrc):
-        sproj += fftconvolve(C[:, i], refs[i])[:nsampl + flen - 1]
-    return sproj
+    """Least-squares projection of the estimate onto the references delayed by 0 .. flen-1 samples: _project_images with
+    one estimate row."""
+    return _project_images(reference_sources, estimated_source[np.newaxis], flen)[0]
 
 
 def _decompose(reference_sources, estimated_source, j, flen):
-    """estimate = s_true + e_spat + e_interf + e_artif with respect to reference source j."""
-    nsampl = estimated_source.size
-    s_true = np.hstack((reference_sources[j], np.zeros(flen - 1)))
-    e_spat = _project(reference_sources[j, np.newaxis, :], estimated_source, flen) - s_true
-    e_interf = _project(reference_sources, estimated_source, flen) - s_true - e_spat
-    e_artif = -s_true - e_spat - e_interf
-    e_artif[:nsampl] += estimated_source
-    return s_true, e_spat, e_interf, e_artif
+    """estimate = s_true + e_spat + e_interf + e_artif with respect to reference source j: _decompose_images of
+    one-channel images."""
+    parts = _decompose_images(reference_sources[:, :, np.newaxis], estimated_source[:, np.newaxis], j, flen)
+    return tuple(v[0] for v in parts)
 
 
 def _safe_db(num, den):
@@ -164,10 +138,7 @@ def bss_eval_sources(reference_sources, estimated_sources, compute_permutation=T
     for jest in range(nsrc):
         for jtrue in range(nsrc):
             sdr[jest, jtrue], sir[jest, jtrue], sar[jest, jtrue] = _criteria(*_decompose(ref, est[jest], jtrue, flen))
-    perms = list(itertools.permutations(range(nsrc)))
-    idx = np.arange(nsrc)
-    mean_sir = [np.mean(sir[list(p), idx]) for p in perms]
-    popt = list(perms[int(np.argmax(mean_sir))])
+    popt, idx = _best_sir_permutation(sir), np.arange(nsrc)
     return sdr[popt, idx], sir[popt, idx], sar[popt, idx], np.asarray(popt)
 
 
@@ -196,9 +167,7 @@ def _metrics_from_gram(energy, proj_one, proj_all, compute_permutation=True):
     idx = np.arange(nsrc)
     if not compute_permutation:
         return sdr[idx, idx], sir[idx, idx], sar[idx, idx], idx
-    perms = list(itertools.permutations(range(nsrc)))
-    mean_sir = [np.mean(sir[list(p), idx]) for p in perms]
-    popt = list(perms[int(np.argmax(mean_sir))])
+    popt = _best_sir_permutation(sir)
     return sdr[popt, idx], sir[popt, idx], sar[popt, idx], np.asarray(popt)
 
 
@@ -347,16 +316,27 @@ def _device_f64(x):
     return t.to(device=t.device if t.is_cuda else torch.device("cuda"), dtype=torch.float64)
 
 
-def _gpu_window_projections(sig, window, hop, nwin, solves, energies, flen, ws_budget):
+# entry points of the two families; the image family takes up to 4 reference rows per solve and fills a `skipped` buffer
+_ENTRY = {False: ("svs_bss_corr_windows", "svs_bss_solve_batched"),
+          True: ("svs_bss_img_corr_windows", "svs_bss_img_solve_batched")}
+
+
+def _gpu_projections(sig, window, hop, nwin, solves, energies, crosses, flen, ws_budget, images):
     """Projection energies of the Gram form for every window [w*hop, w*hop + window) of the rows of `sig` ((S, n) float64 on
     a ROCm device): ONE windowed correlation pass, then per solve batched factorisations over all windows, in batches whose
     workspace stays within ws_budget bytes (at least one system).  solves: [(reference rows, estimate rows)], one Cholesky
-    factorisation per window each; energies: rows whose |x|^2 is wanted.  Returns numpy (energy (nwin, len(energies)),
-    [|P e|^2 (nwin, nrhs) per solve], [status (nwin,) per solve]); a status that is not 0 marks a window whose factorisation
-    met a pivot that was not > 0 (singular G: _project then solves by least squares)."""
+    factorisation per window each; energies: rows whose |x|^2 is wanted; crosses: row pairs (a, b) whose lag-0 term
+    <sig[a], sig[b]> is wanted.  images: the image entry points (up to 4 reference rows per solve, rank-deficient Gram
+    matrices handled on the device) instead of the mono ones.  Returns numpy (energy (nwin, len(energies)), cross (nwin,
+    len(crosses)), [|P e|^2 (nwin, nrhs) per solve], [status (nwin,) per solve]); a status that is not 0 marks a window
+    whose factorisation met a bad pivot: mono, one that was not > 0 (singular G: _project then solves by least squares);
+    images, one below minus the rank tolerance (G numerically indefinite)."""
     import torch
     from . import _lib
     L = _lib.lib()
+    corr_name, solve_name = _ENTRY[bool(images)]
+    corr_fn, solve_fn = getattr(L, corr_name), getattr(L, solve_name)
+    corr_bytes, solve_bytes = getattr(L, corr_name + "_workspace_bytes"), getattr(L, solve_name + "_workspace_bytes")
     pairs, off = [], {}
 
     def need(a, b, nl):                              # offset of pair (a, b, nl) in one window's correlations
@@ -370,40 +350,56 @@ def _gpu_window_projections(sig, window, hop, nwin, solves, energies, flen, ws_b
         gram = [need(i, j, flen) for i in refs for j in refs]
         rhs = [need(e, i, flen) for e in ests for i in refs]
         k, nr = len(refs), len(ests)
-        nb = int(max(1, min(nwin, MAX_BATCH, ws_budget // L.svs_bss_solve_batched_workspace_bytes(1, k, flen, nr))))
+        nb = int(max(1, min(nwin, MAX_BATCH, ws_budget // solve_bytes(1, k, flen, nr))))
         plans.append((k, np.asarray(gram, dtype=np.int64), np.asarray(rhs, dtype=np.int64), nr, nb, ycols))
         ycols += nr
     eoff = [need(e, e, 1) for e in energies]
+    xoff = [need(a, b, 1) for a, b in crosses]
     stride = sum(p[2] for p in pairs)
     flat = np.asarray([v for p in pairs for v in p], dtype=np.int32)
     dev = sig.device
     n = sig.shape[1]
     with torch.cuda.device(dev):
         stream = _lib.stream_ptr()
-        ws_bytes = L.svs_bss_corr_windows_workspace_bytes(window, nwin, len(pairs), flat.ctypes.data)
+        ws_bytes = corr_bytes(window, nwin, len(pairs), flat.ctypes.data)
         if ws_bytes == 0:
-            raise ValueError(f"{nwin} windows of {window} samples do not fit one correlation launch")
+            raise ValueError(f"{nwin} windows of {window} samples and {len(pairs)} pairs do not fit one correlation launch")
         # one workspace and one result buffer of each kind for the whole call: the launches share a stream, and every
         # copy back to the host is a synchronisation
-        ws_bytes = max([ws_bytes] +
-                       [L.svs_bss_solve_batched_workspace_bytes(nb, k, flen, nr) for k, _, _, nr, nb, _ in plans])
+        ws_bytes = max([ws_bytes] + [solve_bytes(nb, k, flen, nr) for k, _, _, nr, nb, _ in plans])
         ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
         corr = torch.empty(nwin, stride, dtype=torch.float64, device=dev)
-        _lib.check(L.svs_bss_corr_windows(sig.data_ptr(), sig.stride(0), sig.shape[0], n, window, hop, nwin,
-                                          flat.ctypes.data, len(pairs), corr.data_ptr(), stride, ws.data_ptr(),
-                                          ws.numel(), stream), "svs_bss_corr_windows")
+        _lib.check(corr_fn(sig.data_ptr(), sig.stride(0), sig.shape[0], n, window, hop, nwin, flat.ctypes.data, len(pairs),
+                           corr.data_ptr(), stride, ws.data_ptr(), ws.numel(), stream), corr_name)
         y = torch.empty(nwin * ycols, dtype=torch.float64, device=dev)      # per solve a contiguous (nwin, nrhs) block
         status = torch.empty(len(plans), nwin, dtype=torch.int32, device=dev)
+        skipped = torch.empty(len(plans), nwin, dtype=torch.int32, device=dev) if images else None
         for s, (k, gram, rhs, nr, nb, y0) in enumerate(plans):
             for w0 in range(0, nwin, nb):
                 b = min(nb, nwin - w0)
                 base = np.arange(w0, w0 + b, dtype=np.int64)[:, None] * stride
                 g, r = np.ascontiguousarray(base + gram), np.ascontiguousarray(base + rhs)
-                _lib.check(L.svs_bss_solve_batched(corr.data_ptr(), b, k, flen, g.ctypes.data, r.ctypes.data, nr,
-                                                   y[nwin * y0 + w0 * nr:].data_ptr(), status[s, w0:].data_ptr(),
-                                                   ws.data_ptr(), ws.numel(), stream), "svs_bss_solve_batched")
+                extra = (skipped[s, w0:].data_ptr(),) if images else ()
+                _lib.check(solve_fn(corr.data_ptr(), b, k, flen, g.ctypes.data, r.ctypes.data, nr,
+                                    y[nwin * y0 + w0 * nr:].data_ptr(), status[s, w0:].data_ptr(), *extra, ws.data_ptr(),
+                                    ws.numel(), stream), solve_name)
         energy, y, status = (t.cpu().numpy() for t in (corr[:, eoff], y, status))
-    return energy, [y[nwin * y0:nwin * (y0 + nr)].reshape(nwin, nr) for _, _, _, nr, _, y0 in plans], list(status)
+        cross = corr[:, xoff].cpu().numpy() if xoff else np.empty((nwin, 0))
+    return (energy, cross, [y[nwin * y0:nwin * (y0 + nr)].reshape(nwin, nr) for _, _, _, nr, _, y0 in plans],
+            list(status))
+
+
+def _gpu_window_projections(sig, window, hop, nwin, solves, energies, flen, ws_budget):
+    """_gpu_projections through the mono entry points, without cross terms: (energy, [|P e|^2 per solve], [status per
+    solve]).  The seam at which the host tests put numpy in place of the library."""
+    energy, _, y, status = _gpu_projections(sig, window, hop, nwin, solves, energies, [], flen, ws_budget, images=False)
+    return energy, y, status
+
+
+def _gpu_image_projections(sig, window, hop, nwin, solves, energies, crosses, flen, ws_budget):
+    """_gpu_projections through the image entry points: (energy, cross, [|P e|^2 per solve], [status per solve]).  The
+    seam at which the host tests put numpy in place of the library."""
+    return _gpu_projections(sig, window, hop, nwin, solves, energies, crosses, flen, ws_budget, images=True)
 
 
 def _windows(n, window, hop):
@@ -661,66 +657,6 @@ def _image_metrics_from_gram(e_ref, e_est, cross, proj_one, proj_all, compute_pe
     idx = np.arange(nsrc)
     popt = _best_sir_permutation(crit[2]) if compute_permutation else list(idx)
     return crit[0][popt, idx], crit[1][popt, idx], crit[2][popt, idx], crit[3][popt, idx], np.asarray(popt)
-
-
-def _gpu_image_projections(sig, window, hop, nwin, solves, energies, crosses, flen, ws_budget):
-    """_gpu_window_projections through the image entry points (svs_bss_img_corr_windows, svs_bss_img_solve_batched: up to
-    4 reference rows per solve, rank-deficient Gram matrices handled on the device), with the lag-0 cross terms
-    <sig[a], sig[b]> of the row pairs `crosses` as a second result: numpy (energy (nwin, len(energies)), cross (nwin,
-    len(crosses)), [|P e|^2 (nwin, nrhs) per solve], [status (nwin,) per solve]).  A status that is not 0 marks a window
-    whose factorisation met a pivot below minus the rank tolerance (G numerically indefinite)."""
-    import torch
-    from . import _lib
-    L = _lib.lib()
-    pairs, off = [], {}
-
-    def need(a, b, nl):
-        if (a, b, nl) not in off:
-            off[(a, b, nl)] = sum(p[2] for p in pairs)
-            pairs.append((a, b, nl))
-        return off[(a, b, nl)]
-
-    plans, ycols = [], 0
-    for refs, ests in solves:
-        gram = [need(i, j, flen) for i in refs for j in refs]
-        rhs = [need(e, i, flen) for e in ests for i in refs]
-        k, nr = len(refs), len(ests)
-        nb = int(max(1, min(nwin, MAX_BATCH, ws_budget // L.svs_bss_img_solve_batched_workspace_bytes(1, k, flen, nr))))
-        plans.append((k, np.asarray(gram, dtype=np.int64), np.asarray(rhs, dtype=np.int64), nr, nb, ycols))
-        ycols += nr
-    eoff = [need(e, e, 1) for e in energies]
-    xoff = [need(a, b, 1) for a, b in crosses]
-    stride = sum(p[2] for p in pairs)
-    flat = np.asarray([v for p in pairs for v in p], dtype=np.int32)
-    dev = sig.device
-    n = sig.shape[1]
-    with torch.cuda.device(dev):
-        stream = _lib.stream_ptr()
-        ws_bytes = L.svs_bss_img_corr_windows_workspace_bytes(window, nwin, len(pairs), flat.ctypes.data)
-        if ws_bytes == 0:
-            raise ValueError(f"{nwin} windows of {window} samples and {len(pairs)} pairs do not fit one correlation launch")
-        ws_bytes = max([ws_bytes] +
-                       [L.svs_bss_img_solve_batched_workspace_bytes(nb, k, flen, nr) for k, _, _, nr, nb, _ in plans])
-        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
-        corr = torch.empty(nwin, stride, dtype=torch.float64, device=dev)
-        _lib.check(L.svs_bss_img_corr_windows(sig.data_ptr(), sig.stride(0), sig.shape[0], n, window, hop, nwin,
-                                              flat.ctypes.data, len(pairs), corr.data_ptr(), stride, ws.data_ptr(),
-                                              ws.numel(), stream), "svs_bss_img_corr_windows")
-        y = torch.empty(nwin * ycols, dtype=torch.float64, device=dev)
-        status = torch.empty(len(plans), nwin, dtype=torch.int32, device=dev)
-        skipped = torch.empty(len(plans), nwin, dtype=torch.int32, device=dev)
-        for s, (k, gram, rhs, nr, nb, y0) in enumerate(plans):
-            for w0 in range(0, nwin, nb):
-                b = min(nb, nwin - w0)
-                base = np.arange(w0, w0 + b, dtype=np.int64)[:, None] * stride
-                g, r = np.ascontiguousarray(base + gram), np.ascontiguousarray(base + rhs)
-                _lib.check(L.svs_bss_img_solve_batched(corr.data_ptr(), b, k, flen, g.ctypes.data, r.ctypes.data, nr,
-                                                       y[nwin * y0 + w0 * nr:].data_ptr(), status[s, w0:].data_ptr(),
-                                                       skipped[s, w0:].data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                           "svs_bss_img_solve_batched")
-        energy, cross, y, status = (t.cpu().numpy() for t in (corr[:, eoff], corr[:, xoff], y, status))
-    return (energy, cross, [y[nwin * y0:nwin * (y0 + nr)].reshape(nwin, nr) for _, _, _, nr, _, y0 in plans],
-            list(status))
 
 
 def _images_gpu(reference_sources, estimated_sources, window, hop, compute_permutation, flen, ws_budget=WS_BUDGET,

@@ -13,6 +13,7 @@ from svs_unet_pytorch_amd import _lib
 from svs_unet_pytorch_amd import evaluate as ev
 from test_bss_gram import corr
 from test_bss_images import (assert_image_frames_close, assert_images_close, degenerate_case, image_cases, stereo_track)
+from test_gpu_bss_framewise import batched_problem, gpu_solve_batched
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -104,15 +105,8 @@ def img_problem(K, flen, nrhs, seed, zero=None, same=None, negative=None):
     return np.concatenate(chunks), offs[:K * K], offs[K * K:], G, D
 
 
-def gpu_img_solve(problems, K, flen, nrhs):
-    """One batched call over problems [(corr, gram_off, rhs_off, ...)]: (ynorm2 (nbatch, nrhs), status, skipped)."""
+def gpu_img_solve_batched(corr_dev, nbatch, K, flen, goffs, roffs, nrhs):
     L = _lib.lib()
-    nbatch, base, goffs, roffs = len(problems), 0, [], []
-    for c, g, r, *_ in problems:
-        goffs += [base + v for v in g]
-        roffs += [base + v for v in r]
-        base += c.size
-    corr_dev = torch.from_numpy(np.concatenate([p[0] for p in problems])).to(DEV)
     ws = torch.empty(int(L.svs_bss_img_solve_batched_workspace_bytes(nbatch, K, flen, nrhs)), dtype=torch.uint8, device=DEV)
     assert ws.numel() > 0
     y = torch.empty(nbatch, nrhs, dtype=torch.float64, device=DEV)
@@ -122,6 +116,17 @@ def gpu_img_solve(problems, K, flen, nrhs):
                                            status.data_ptr(), skipped.data_ptr(), ws.data_ptr(), ws.numel(),
                                            _lib.stream_ptr()), "svs_bss_img_solve_batched")
     return y.cpu().numpy(), status.cpu().numpy(), skipped.cpu().numpy()
+
+
+def gpu_img_solve(problems, K, flen, nrhs):
+    """One batched call over problems [(corr, gram_off, rhs_off, ...)]: (ynorm2 (nbatch, nrhs), status, skipped)."""
+    base, goffs, roffs = 0, [], []
+    for c, g, r, *_ in problems:
+        goffs += [base + v for v in g]
+        roffs += [base + v for v in r]
+        base += c.size
+    corr_dev = torch.from_numpy(np.concatenate([p[0] for p in problems])).to(DEV)
+    return gpu_img_solve_batched(corr_dev, len(problems), K, flen, goffs, roffs, nrhs)
 
 
 @pytest.mark.parametrize("K,flen,nrhs", [(4, 512, 4), (4, 100, 3), (3, 37, 16), (2, 512, 5), (1, 64, 1)])
@@ -159,6 +164,22 @@ def test_img_solve_reports_an_indefinite_system():
     assert list(status) == [0, flen + 1] and skipped[0] == 0                    # the first pivot of channel 1
     alone, status, _ = gpu_img_solve(probs[:1], K, flen, nrhs)                  # the stream is still usable
     assert status[0] == 0 and np.array_equal(alone[0], y[0])
+
+
+@pytest.mark.parametrize("K,flen,nrhs", [(1, 64, 1), (2, 37, 16), (2, 100, 3), (2, 512, 2)])
+def test_mono_and_image_solves_agree_bitwise_on_regular_systems(K, flen, nrhs):
+    """svs_bss_solve_batched and svs_bss_img_solve_batched factor a tile with the same operations in the same order and
+    differ in the pivot rule and in who factors the diagonal tile (every panel block, or one block once), so on systems
+    where every pivot passes both rules they give the same bits: one tile with no update launch (order 64), two
+    tiles with identity padding (74), a full-width right-hand-side block (16), the largest mono order (1024).  The seeds
+    are ones for which the numpy skip_cholesky of test_bss_images skips nothing and reports status 0."""
+    seeds = [K * 1000 + flen + s for s in range(3)]
+    corr_dev, goffs, roffs = batched_problem(K, flen, nrhs, seeds)
+    mono, mono_status = gpu_solve_batched(corr_dev, len(seeds), K, flen, goffs, roffs, nrhs)
+    img, img_status, skipped = gpu_img_solve_batched(corr_dev, len(seeds), K, flen, goffs, roffs, nrhs)
+    assert not mono_status.any() and not img_status.any()
+    assert list(skipped) == [0, 0, 0]
+    assert np.array_equal(mono, img)
 
 
 # ---- the scorers ------------------------------------------------------------------------------

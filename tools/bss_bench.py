@@ -7,7 +7,7 @@ and the numpy path, on a seeded synthetic 240 s track at 8192 Hz and at 44,100 H
     python tools/bss_bench.py --kernel-stats DIR --rates 8192 --seconds 240
     python tools/bss_bench.py --frame_window 1 [--frame_hop 1] [--ws-budget BYTES]   # framewise metrics instead
     python tools/bss_bench.py --stereo [--frame_window 1]       # the image metrics (SDR / ISR / SIR / SAR / NSDR) of a stereo track
-    python tools/bss_bench.py --ab-solve                        # the image solve against svs_bss_solve_batched, and at order 2048
+    python tools/bss_bench.py --ab-solve                        # the two solve entry points on one batch, and order 2048
 
 Timing: host clock around metrics_from_waveforms(device="gpu") followed by a device synchronise (the call ends with a
 copy back to the host anyway), after one warm-up call; median and minimum of --reps calls.  The numpy path is timed once.
@@ -97,9 +97,11 @@ def stereo_record(args, rate):
 
 
 def ab_solve(reps):
-    """svs_bss_img_solve_batched (the diagonal tile factored once per step) against svs_bss_solve_batched (every panel block
-    factors it) on identical K = 2, flen 512 batches of 120 systems, the two alternating in one process, medians of device
-    time; and the new entry point alone at K = 4, flen 512, 30 systems, which the old one does not take."""
+    """svs_bss_img_solve_batched (the diagonal tile factored once per step) against svs_bss_solve_batched ("old": every
+    panel block factors it) on identical K = 2, flen 512 batches of 120 systems, the two alternating in one process, medians
+    of device time.  The two factor a tile with the same operations in the same order, so this row is a standing check
+    that they give identical bits on regular systems (max_rel_diff 0.0), and it records what factoring once gains on a
+    large batch.  And the image entry point alone at K = 4, flen 512, 30 systems, which the mono one does not take."""
     import torch
     from svs_unet_pytorch_amd import _lib
     L, dev, flen, window = _lib.lib(), torch.device("cuda"), ev.FILTER_LEN, 8192
@@ -209,9 +211,9 @@ def kernel_stats(path, n):
     out = {}
     for r in rows:
         name = r["Name"]
-        short = next((k for k in ("bss_corr_reduce_kernel", "bss_corr_kernel", "bss_expand_kernel", "bss_panel_kernel",
-                                  "bss_update_kernel", "bss_norm_kernel", "bss_img_corr_kernel", "bss_img_reduce_kernel",
-                                  "bss_img_diag_kernel", "bss_img_panel_kernel") if k in name), None)
+        short = next((k for k in ("bss_corr_reduce_kernel", "bss_corr_kernel", "bss_expand_kernel", "bss_diag_kernel",
+                                  "bss_panel_kernel", "bss_update_kernel", "bss_norm_kernel", "bss_img_corr_kernel",
+                                  "bss_img_reduce_kernel", "bss_img_panel_kernel") if k in name), None)
         if short:
             out[short] = {"calls": int(r["Calls"]), "avg_us": float(r["AverageNs"]) / 1e3,
                           "total_us": float(r["TotalDurationNs"]) / 1e3}
@@ -234,7 +236,7 @@ def main():
     ap.add_argument("--frame_hop", type=float, default=None, help="seconds (default: the window)")
     ap.add_argument("--ws-budget", type=int, default=ev.WS_BUDGET, help="workspace bytes of one batch of factorisations")
     ap.add_argument("--stereo", action="store_true", help="the image metrics of a stereo track (evaluate.py --stereo)")
-    ap.add_argument("--ab-solve", action="store_true", help="A/B of svs_bss_img_solve_batched (see ab_solve)")
+    ap.add_argument("--ab-solve", action="store_true", help="the two solve entry points on identical batches (see ab_solve)")
     args = ap.parse_args()
     if args.kernel_stats:
         n = args.seconds * args.rates[0]
