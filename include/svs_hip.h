@@ -127,6 +127,32 @@ int svs_crop_stretch_tiles(const float* mix_songs, const float* voc_songs, const
                            const int32_t* song_a, const int32_t* start_a, const float* gain_v, const float* gain_a,
                            const int32_t* rate_v, const int32_t* rate_a, int B, int F, int seg, int n_fft, int hop, float* mix,
                            float* voc, float* mix_phase, float* voc_phase, hipStream_t stream);
+/* Pitch-shift augmentation of the same items (csrc/pitch.hip; Cohen-Hadria, Roebel and Peeters 2019 -- the reference's
+ * SpectrogramDataset, train.py:86-143, has no augmentation): svs_crop_stretch_tiles' phase vocoder with the frequency axis resampled
+ * and the phase advance scaled.  Everything is as there; pitch_v / pitch_a are Q10 pitches P (p = P / 1024; augment.check_pitch_table
+ * keeps 512 <= P <= 2048; a gain item, song_a[b] < 0, also takes P_a = P_v).  Rows of a source S are bins 1..F and every bin
+ * outside 1..F is zero.  For output row f (b = f + 1) and output frame t:  n = t q, k = s + (n >> 10), alpha = (n & 1023) / 1024,
+ *   N = 1024 b,  j0 = N div P,  gamma = (N mod P) / P,  j = clamp((2 N + P) div 2 P, 1, F)       (integers; j is j0 or j0 + 1)
+ *   tm(i) = (1 - alpha) |S[i, k]| + alpha |S[i, k+1]|,   mag_t = (1 - gamma) tm(j0) + gamma tm(j0 + 1),   out_t = mag_t cis(acc_t)
+ *   w = 2 pi ((hop j) mod n_fft) / n_fft,   d = wrap(arg S[j, k+1] - arg S[j, k] - w) to [-pi, pi)
+ *   w' = 2 pi ((hop j P) mod (1024 n_fft)) / (1024 n_fft),   acc_0 = arg S[j, s],   acc_{t+1} = acc_t + w' + p d
+ * (arg of an exactly zero magnitude is 0; columns outside [0, T) are zero), and the item is
+ *   z = g_v PV(vocal) + g_a PV(accompaniment):  mix = |z|, mix_phase = arg z, voc = g_v mag_v, voc_phase = acc_v in [-pi, pi],
+ * a phase being 0 wherever its magnitude is exactly 0.  The magnitude is the source's at the fractional bin b / p, the phase follows
+ * the nearest source bin (ties up) with its true advance per hop multiplied by p.  At P = 1024 this is svs_crop_stretch_tiles, and
+ * voc_phase is bit for bit its voc_phase.  acc is a 32-bit fraction of a turn: w' is an exact integer (hop j P formed in 64 bits),
+ * p d is (int64(d) P) >> 10 (the only rounding, below 2^-32 turn per frame), the sums wrap: the same bits whatever the grid, the
+ * batch size or an item's place in the batch.  The angle sources are required (there is no magnitude-only shift).
+ * mix_phase == voc_phase == NULL: only mix and voc are written, bit for bit those of the four-output call.  Refused with
+ * SVS_ERR_INVALID before any launch: a null pointer or table (pitch_v and pitch_a included), one phase output alone, seg % 4 != 0,
+ * an output that is not 16-byte aligned, n_fft other than 512 / 1024 / 2048, hop outside 1..n_fft, F outside 1..n_fft / 2 (rows are
+ * bins 1..F; augment.crop_pitch passes F == n_fft / 2).  The kernel trusts its tables: song indices in range, 0 <= start,
+ * 512 <= q <= 2048, 512 <= P <= 2048 (checked on the host).  One launch, no workspace, no atomics.  Outputs: (B, 1, F, seg). */
+int svs_crop_pitch_tiles(const float* mix_songs, const float* voc_songs, const float* mix_ang, const float* voc_ang,
+                         const int64_t* offset, const int32_t* frames, const int32_t* song_v, const int32_t* start_v,
+                         const int32_t* song_a, const int32_t* start_a, const float* gain_v, const float* gain_a,
+                         const int32_t* rate_v, const int32_t* rate_a, const int32_t* pitch_v, const int32_t* pitch_a, int B, int F,
+                         int seg, int n_fft, int hop, float* mix, float* voc, float* mix_phase, float* voc_phase, hipStream_t stream);
 int svs_dropout_mask(float* out, int B, int C, int layer, uint32_t seed, int step, int rank, hipStream_t stream);
 /* The five decoder masks of one step in one launch: out = [B*256 | B*128 | B*64 | B*32 | B*16] floats, each block
  * bit-identical to svs_dropout_mask(layer = 0..4) -- the layout svs_unet_train_* take as `drop`. */

@@ -38,6 +38,7 @@ _SIGS = {
     "svs_phase_angle": (I, [P, P, L, P]),
     "svs_crop_remix_tiles": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P, P, P, P, P]),
     "svs_crop_stretch_tiles": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P]),
+    "svs_crop_pitch_tiles": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P]),
     "svs_dropout_mask": (I, [P, I, I, I, U32, I, I, P]),
     "svs_dropout_masks_all": (I, [P, I, U32, I, I, P]),
     "svs_pack_weight_gather": (I, [P, P, I, I, P]),

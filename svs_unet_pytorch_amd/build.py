@@ -43,9 +43,10 @@ def _stale(target, deps):
 # (v_mfma_f32_16x16x32_bf16) of any other wave -- another stream, another process -- is executing on the CU
 # (reproduced with two-line kernels: DESIGN.md section 5).  No other source file produces that form; wiener.hip's complex
 # arithmetic is fp64, but its fp32 loads and stores sit beside it, so it is built the same way; stretch.hip forms and sums complex
-# fp32 sources per lane and is built the same way too (it does not include fft_wave.h).
+# fp32 sources per lane and is built the same way too (it does not include fft_wave.h), and so is pitch.hip, which does the same
+# at four points per source.
 EXTRA_FLAGS = {"stft.hip": ["-fno-slp-vectorize"], "mrstft.hip": ["-fno-slp-vectorize"], "wiener.hip": ["-fno-slp-vectorize"],
-               "stretch.hip": ["-fno-slp-vectorize"]}
+               "stretch.hip": ["-fno-slp-vectorize"], "pitch.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src):

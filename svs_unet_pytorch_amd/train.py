@@ -40,7 +40,9 @@ checkpoint.
 over the accompaniment of another, formed from the complex spectra so that it is the STFT of the re-mixed audio.  --gain_range,
 --remix_prob and --augment_seed set it; an epoch's table depends on (seed, epoch) only, goes up in one copy, and each step is one
 launch.  --stretch_range LO HI (with --augment gain|remix; csrc/stretch.hip) also time-stretches every source before the mix, a phase
-vocoder on the resident spectra at a rate of its own per source.  Validation is never augmented; the checkpoint format is unchanged.
+vocoder on the resident spectra at a rate of its own per source.  --pitch_range LO HI (semitones; with --augment gain|remix, with or
+without --stretch_range; csrc/pitch.hip) also shifts the pitch of every source before the mix: the same vocoder with the frequency
+axis resampled and the phase advance scaled.  Validation is never augmented; the checkpoint format is unchanged.
 
 --weight_decay X, --clip_grad_norm X, --ema_decay X (all 0 = off: the optimiser step is then the reference's Adam, one launch) turn on
 decoupled weight decay, clipping by the global gradient norm and an exponential moving average of the weights inside the optimiser
@@ -308,7 +310,9 @@ class ResidentSpectrograms:
         `validation_pass` uploads its pass); a batch is a slice of it and one `svs_crop_remix_tiles` launch: no per-step
         host-to-device copy, no read-back.  With aug.stretch_range set, every source is also time-stretched at a rate of its own:
         `augment.draw_epoch_stretch`'s table (eight rows) and one `svs_crop_stretch_tiles` launch per batch, at the window the set was
-        written with (2 * rows) and `hop`."""
+        written with (2 * rows) and `hop`.  With aug.pitch_range set, every source is also pitch-shifted by an amount of its own (and
+        stretched if aug.stretch_range is set as well): `augment.draw_epoch_pitch`'s table (ten rows) and one `svs_crop_pitch_tiles`
+        launch per batch."""
         from . import augment
         if aug is None or aug.mode == "none":
             raise ValueError("augmented_batches needs augmentation settings other than 'none' (`batches` is the plain path)")
@@ -316,6 +320,13 @@ class ResidentSpectrograms:
         if not order:
             return
         remix_prob = aug.remix_prob if aug.mode == "remix" else 0.0
+        if aug.pitch_range is not None:
+            drawn = augment.draw_epoch_pitch(len(self), self.frames_host, INPUT_LEN, epoch, aug.seed, aug.gain_range, remix_prob,
+                                             aug.pitch_range, aug.stretch_range)
+            table = augment.upload_pitch_table(self, drawn, order)
+            for lo in range(0, len(order), batch_size):
+                yield augment.crop_pitch(self, table, lo, min(lo + batch_size, len(order)), 2 * self.rows, hop, with_phase)
+            return
         if aug.stretch_range is not None:
             drawn = augment.draw_epoch_stretch(len(self), self.frames_host, INPUT_LEN, epoch, aug.seed, aug.gain_range, remix_prob,
                                                aug.stretch_range)
@@ -412,6 +423,11 @@ def main(argv=None):
                              "rate uniform in [LO, HI] within 0.5 .. 2 (needs *_phase.npy; default: no stretch; the range one would start "
                              "with, 0.8 1.25, is a choice, not a tuned value).  At the default 768-of-1024 hop the phase estimate is "
                              "unambiguous only within about +-2/3 bin: folders written with a smaller --hop_size stretch more cleanly")
+    parser.add_argument("--pitch_range", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                        help="with --augment gain|remix, with or without --stretch_range: shift the pitch of every source before the mix "
+                             "by a frequency-scaling phase vocoder on the device, by semitones uniform in [LO, HI] within -12 .. 12 (needs "
+                             "*_phase.npy; default: no shift; -2 2 is a starting point, not a tuned value).  The shift moves formants with "
+                             "the pitch and widens every partial by the pitch ratio")
     parser.add_argument("--weight_decay", type=float, default=0.0, help="decoupled weight decay (torch.optim.AdamW), on every parameter; 0 = off")
     parser.add_argument("--clip_grad_norm", type=float, default=0.0,
                         help="clip the global gradient norm to this (after the all-reduce under data parallelism); 0 = off")
@@ -433,8 +449,10 @@ def main(argv=None):
     aug = None
     if args.stretch_range is not None and args.augment == "none":
         parser.error("--stretch_range: the stretch is part of the augmented tile cut, it needs --augment gain or --augment remix")
+    if args.pitch_range is not None and args.augment == "none":
+        parser.error("--pitch_range: the pitch shift is part of the augmented tile cut, it needs --augment gain or --augment remix")
     if args.augment != "none":                                  # `none` reaches nothing of augment.py beyond the flags' defaults
-        bad = augment.check_settings(args.augment, args.gain_range, args.remix_prob, args.stretch_range)
+        bad = augment.check_settings(args.augment, args.gain_range, args.remix_prob, args.stretch_range, args.pitch_range)
         if bad:
             parser.error(bad)
         loader = os.environ.get("SVS_DATA_LOADER", "resident")
@@ -447,9 +465,13 @@ def main(argv=None):
         if args.stretch_range is not None and not folder_has_phase_files(args.train_folder):
             raise SystemExit(f"train.py: --stretch_range needs the *_phase.npy files of every song of {args.train_folder} (the phase vocoder "
                              "reads the sources' angles; there is no magnitude-only stretch)")
+        if args.pitch_range is not None and not folder_has_phase_files(args.train_folder):
+            raise SystemExit(f"train.py: --pitch_range needs the *_phase.npy files of every song of {args.train_folder} (the phase vocoder "
+                             "reads the sources' angles; there is no magnitude-only shift)")
+        pitch = None if args.pitch_range is None else (float(args.pitch_range[0]), float(args.pitch_range[1]))
         stretch = None if args.stretch_range is None else (float(args.stretch_range[0]), float(args.stretch_range[1]))
         aug = augment.Augment(args.augment, (float(args.gain_range[0]), float(args.gain_range[1])), float(args.remix_prob), args.augment_seed,
-                              stretch)
+                              stretch, pitch)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
