@@ -713,6 +713,41 @@ int svs_wiener_stems(const float* mag, int64_t chan_stride, int seg, int rows, c
                      float* out_mag, int64_t out_chan_stride, int64_t out_mag_stem_stride, float* out_phase,
                      int64_t out_phase_stem_stride, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Integrated loudness, ITU-R BS.1770-4 / EBU R 128 (csrc/loudness.hip; the float64 definition is
+ * svs_unet_pytorch_amd/loudness.py).  The reference peak-normalises every written stem on its own (data.py:162-166) and has no
+ * meter; this is the measurement behind one loudness gain for all stems of a file.
+ *   K-weighting: two biquads from the analog prototypes by the bilinear transform, at any rate 4000 <= fs <= 768000.
+ *   svs_loudness_coeffs writes c[10] = shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 (a0 = 1), bit for bit loudness.k_weighting.
+ *   Blocks: e_k = floor(k*fs/10); block j covers samples [e_j, e_j+4) (400 ms, 75 % overlap);
+ *   svs_loudness_nblocks = the blocks that are complete, e_j+4 <= n: max(0, floor((10*n + 9)/fs) - 3), which is
+ *   max(0, floor(10*n/fs) - 3) whenever 10 divides fs; host arithmetic (-1 + error for invalid arguments).
+ * svs_loudness_blocks: x holds planar fp32 rows, (stem s, channel c) at x + s*ld_stem + c*ld_ch, n samples each (ld_ch >= n).
+ *   stems 1 or 2: the stems are added per sample in fp64 before the filter; channels 1..8, each with weight 1.
+ *   z[j] = sum_c mean(y_c[e_j : e_j+4]^2), y the K-weighted signal, for j < svs_loudness_nblocks (nothing is written for
+ *   n under 400 ms).  Recurrence and energies are fp64 and the recurrence is exact from the first sample (no warm-up): the
+ *   filter state is carried over the whole signal by a scan of per-chunk end states.  Every sum has one fixed order, no
+ *   atomics: two calls on the same input give the same bits.  Indices are 64-bit.  z and ws 8-byte aligned.
+ * svs_loudness_workspace_bytes: bytes of its workspace (0 for invalid arguments).
+ * svs_loudness_gain: one block gates z (absolute gate l_j > -70 with l_j = -0.691 + 10 log10 z_j, then the relative gate 10 LU
+ *   under the loudness of what the first kept) and applies the gain rule, all on the device:
+ *     info[0] = L = -0.691 + 10 log10(mean z of the kept blocks), -inf when none is kept;   info[1] = kept blocks
+ *     peak = max |peaks[i]|, i < npeaks (fp32, device; as svs_resample_peaks leaves them)
+ *     target: target_dev[0] when target_dev is given (a device double, e.g. another call's info[0]), else `target`
+ *     target NaN: measurement only, info[2] = NaN, info[3] = 0, gain_out untouched (may be NULL with channels = 0)
+ *     info[2] = unlimited gain 10^((target - L)/20) (+inf for L = -inf);   cap = ceiling / peak (+inf for peak = 0)
+ *     gain_out[c] = (float)min(unlimited, cap) for c < channels, all equal (1 when both are infinite);
+ *     info[3] = 1 when the cap was the smaller.
+ *   gain_out is what svs_resample_encode takes as `gain`.  No host synchronisation. */
+int svs_loudness_coeffs(int fs, double* c /* [10], host */);
+int64_t svs_loudness_nblocks(int64_t n, int fs);
+size_t svs_loudness_workspace_bytes(int64_t n, int channels, int fs);
+int svs_loudness_blocks(const float* x, int stems, int channels, int64_t n, int64_t ld_stem, int64_t ld_ch, int fs,
+                        double* z /* [svs_loudness_nblocks], device */, void* ws, size_t ws_bytes, hipStream_t stream);
+int svs_loudness_gain(const double* z, int64_t nblocks, const float* peaks, int npeaks, double target,
+                      const double* target_dev /* nullable */, double ceiling, float* gain_out /* [channels], device */,
+                      int channels, double* info /* [4], device */, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

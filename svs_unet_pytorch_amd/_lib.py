@@ -142,6 +142,11 @@ _SIGS = {
     "svs_wiener_workspace_bytes": (Z, [I, I, I, I]),
     "svs_wiener_model": (I, [P, L, I, I, P, P, P, I, I, P, L, P, D, D, P, L, P, P, Z, P]),
     "svs_wiener_stems": (I, [P, L, I, I, P, P, I, I, P, L, P, D, I, P, L, L, P, L, P]),
+    "svs_loudness_coeffs": (I, [I, C.POINTER(D)]),
+    "svs_loudness_nblocks": (L, [L, I]),
+    "svs_loudness_workspace_bytes": (Z, [L, I, I]),
+    "svs_loudness_blocks": (I, [P, I, I, L, L, L, I, P, P, Z, P]),
+    "svs_loudness_gain": (I, [P, L, P, I, D, P, D, P, I, P, P]),
 }
 
 

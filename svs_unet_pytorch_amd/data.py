@@ -241,15 +241,23 @@ def write_wav(path: str, y: np.ndarray, sr: int):
     wavfile.write(path, sr, np.asarray(y, dtype=np.float32))
 
 
-def save_wav_device(path: str, y_dev: torch.Tensor, sr: int, sr_out: int | None = None, subtype: str = "PCM_16", peak: float | None = 0.9):
+def save_wav_device(path: str, y_dev: torch.Tensor, sr: int, sr_out: int | None = None, subtype: str = "PCM_16", peak: float | None = 0.9,
+                    loudness: float | None = None, ceiling: float = 0.9):
     """float32 device samples (n,) or (channels, n) at rate `sr` -> a wav file at `sr_out` (default: sr) with the samples of
     `subtype` ("PCM_16", the reference's sf.write format for a .wav name, "PCM_32" or "FLOAT"), peak-normalised to `peak` at
     the rate that is written (data.py:162-166; None: not normalised; one gain for all channels).  Resampling, gain, sample
-    conversion and interleaving are resample.resample_encode_gpu; one device -> host copy of the encoded samples follows."""
+    conversion and interleaving are resample.resample_encode_gpu; one device -> host copy of the encoded samples follows.
+    loudness (LUFS) replaces the peak rule: the file is brought to that integrated loudness (loudness.py), no sample above
+    `ceiling`; the four numbers of the measurement are returned (None without loudness)."""
     from scipy.io import wavfile
     from .resample import resample_encode_gpu
     sr_out = int(sr if sr_out is None else sr_out)
     fr = Fraction(sr_out, int(sr))
+    if loudness is not None:
+        pcm, info = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=subtype, loudness=loudness,
+                                        ceiling=ceiling, rate=sr_out)
+        wavfile.write(path, sr_out, pcm.cpu().numpy())
+        return info.cpu().tolist()
     pcm = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=subtype, peak=peak, common_gain=True)
     wavfile.write(path, sr_out, pcm.cpu().numpy())
 
@@ -315,13 +323,14 @@ def to_wave(args, device):
             m = min(mag.shape[1], phase.shape[1])                                                              # data.py:151-153
             sr_out = getattr(args, "sr_out", None) or args.sr
             subtype = getattr(args, "subtype", "FLOAT")
-            encode = sr_out != args.sr or subtype != "FLOAT"          # else: float32 at --sr, written as it always was
+            loudness = getattr(args, "loudness", None)
+            encode = sr_out != args.sr or subtype != "FLOAT" or loudness is not None   # else: float32 at --sr, written as it always was
             y = istft(torch.from_numpy(np.ascontiguousarray(mag[:, :m])).to(device),
                       torch.from_numpy(np.ascontiguousarray(phase[:, :m]).astype(np.complex64)).to(device),
                       args.win_size, args.hop_size, peak=None if encode else 0.9)
             wav_path = os.path.join(args.tar, spec_name.replace("_spec.npy", ".wav"))
             if encode:
-                save_wav_device(wav_path, y, args.sr, sr_out, subtype, peak=0.9)
+                save_wav_device(wav_path, y, args.sr, sr_out, subtype, peak=0.9, loudness=loudness, ceiling=getattr(args, "peak_ceiling", 0.9))
             else:
                 write_wav(wav_path, y.cpu().numpy(), args.sr)
         except Exception as e:                                          # data.py:168-169
@@ -342,6 +351,9 @@ def main(argv=None):
     parser.add_argument("--sr_out", type=int, default=None, help="to_wave: rate of the written files (default: --sr)")
     parser.add_argument("--subtype", default="FLOAT", choices=["FLOAT", "PCM_16", "PCM_32"],
                         help="to_wave: sample format of the written files (PCM_16 is the reference's)")
+    parser.add_argument("--loudness", type=float, default=None,
+                        help="to_wave: integrated loudness of the written files in LUFS (ITU-R BS.1770-4) instead of peak 0.9")
+    parser.add_argument("--peak_ceiling", type=float, default=0.9, help="to_wave with --loudness: no written sample exceeds this")
     args = parser.parse_args(argv)
     if args.sr_out is not None and args.sr_out < 1:
         parser.error(f"--sr_out {args.sr_out}: must be positive")

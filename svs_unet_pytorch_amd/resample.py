@@ -235,7 +235,51 @@ def resample_peaks_gpu(y, up: int, down: int):
     return peaks
 
 
-def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | None = 0.9, common_gain: bool = True):
+def encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, rate, frames):
+    """resample_encode_gpu(loudness=): the stems (each (channels, n_in), float32, contiguous) are resampled into one float32 buffer
+    by svs_resample_poly -- bit for bit the float the fused encoder forms -- cut or zero-padded to `frames`, measured there
+    (svs_loudness_blocks on their sum, svs_resample_peaks per stem, svs_loudness_gain) and encoded 1/1 with the device gain.
+    Returns (list of PCM tensors, gain, info), all on the device."""
+    import torch
+    from . import loudness as ld
+    y = stems[0]
+    dev = y.device
+    channels, n_in = y.shape
+    L = _lib.lib()
+    n_out = int(L.svs_resample_out_len(n_in, up, down))
+    frames = n_out if frames is None else int(frames)
+    if frames < 1:
+        raise ValueError(f"frames must be positive, got {frames}")
+    width = max(n_out, frames)
+    table, ntaps = tap_table(up, down, dev)
+    one, _ = tap_table(1, 1, dev)
+    nst = len(stems)
+    alloc = torch.zeros if frames > n_out else torch.empty                # the padded frames are silence
+    buf = alloc((nst, channels, width), dtype=torch.float32, device=dev)
+    peaks = torch.empty(nst * channels, dtype=torch.float32, device=dev)
+    nbytes = int(L.svs_resample_peaks_workspace_bytes(frames, channels, 1, 1, 1))
+    if nbytes == 0:
+        raise _lib.SvsError(f"svs_resample_peaks_workspace_bytes({frames}, {channels}, 1, 1, 1): invalid arguments")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    outs = [torch.empty((frames, channels), dtype=getattr(torch, np.dtype(dtype).name), device=dev) for _ in stems]
+    with torch.cuda.device(dev):
+        s = _lib.stream_ptr(dev)
+        for k, stem in enumerate(stems):
+            _lib.check(L.svs_resample_poly(stem.data_ptr(), PCM_F32, 1, 0, n_in, n_in, channels, table.data_ptr(), ntaps, up, down,
+                                           buf[k].data_ptr(), width, s), "svs_resample_poly")
+            _lib.check(L.svs_resample_peaks(buf[k].data_ptr(), channels, frames, width, one.data_ptr(), 1, 1, 1,
+                                            peaks[k * channels:].data_ptr(), ws.data_ptr(), nbytes, s), "svs_resample_peaks")
+        view = buf[:, :, :frames]
+        gain, info = ld.loudness_gain_gpu(view if nst == 2 else view[0], rate, loudness, ceiling=ceiling, stems=nst, peaks=peaks,
+                                          channels=channels)
+        for k, out in enumerate(outs):
+            _lib.check(L.svs_resample_encode(buf[k].data_ptr(), channels, frames, width, one.data_ptr(), 1, 1, 1, gain.data_ptr(), code,
+                                             out.data_ptr(), s), "svs_resample_encode")
+    return outs, gain, info
+
+
+def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | None = 0.9, common_gain: bool = True,
+                        loudness=None, ceiling: float = 0.9, together=None, rate: int | None = None, frames: int | None = None):
     """float32 device tensor (n,) or (channels, n), planar -> device tensor (n_out,) or (n_out, channels) of int16 / int32 /
     float32 at rate * up / down, interleaved as a wav file stores it (svs_resample_encode; the rules: encode_pcm_reference).
     peak=None: the samples are encoded as they are.  Otherwise they are scaled by peak / max |resampled signal| on the way
@@ -244,8 +288,18 @@ def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | Non
     on the device, so nothing waits for the host.  common_gain=True: one gain
     for all channels, from the loudest (a stereo file keeps its balance; mono is the reference's rule); False: every channel
     is normalised on its own, as istft_from_tiles(peak=) does.  A silent signal (maximum 0) is divided by 1, the rule of
-    svs_scale_by_inv, and stays silent."""
+    svs_scale_by_inv, and stays silent.
+
+    loudness (LUFS: a number, or a float64 device tensor whose first element holds it) replaces the peak rule by a loudness
+    target (loudness.py): the samples at `rate` (required: the rate that is written, which K-weighting depends on) are brought to
+    that integrated loudness by one gain for all channels, min(10^((loudness - L) / 20), ceiling / peak).  together: a second
+    stem of y's shape that is written with it; L is then the loudness of the two stems' sum, peak the larger of theirs, and both
+    get the same gain, so their balance is kept.  frames: cut or zero-pad to this many frames before measuring, so that what is
+    measured is what is written.  Returns (pcm, info) or, with together, (pcm, pcm of together, info); info: 4 device doubles
+    (L before the gain, kept blocks, unlimited gain, 1 when the ceiling limited it).  peak and common_gain are not read."""
     import torch
+    if loudness is None and (together is not None or frames is not None):
+        raise ValueError("together= and frames= belong to loudness=")
     if not y.is_cuda:
         raise ValueError("resample_encode_gpu needs a device tensor (there is no CPU path)")
     if y.dtype != torch.float32:
@@ -257,6 +311,18 @@ def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | Non
     squeeze = y.dim() == 1
     y = (y[None] if squeeze else y).contiguous()
     channels, n_in = y.shape
+    if loudness is not None:
+        if rate is None:
+            raise ValueError("loudness= needs rate=, the sample rate that is written")
+        stems = [y]
+        if together is not None:
+            t = (together[None] if together.dim() == 1 else together).contiguous()
+            if not t.is_cuda or t.dtype != torch.float32 or t.shape != y.shape:
+                raise ValueError(f"together must be a float32 device tensor of the same shape, got {tuple(together.shape)}")
+            stems.append(t)
+        outs, _, info = encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, int(rate), frames)
+        outs = [o[:, 0] if squeeze else o for o in outs]
+        return (*outs, info)
     L = _lib.lib()
     n_out = int(L.svs_resample_out_len(n_in, up, down))
     table, ntaps = tap_table(up, down, y.device)

@@ -8,7 +8,7 @@ evaluate.py accepts it beside the source's stems.
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src wav_folder --tar out_folder \
         [--vocal_solo 0|1] [--precision bf16] [--subtype PCM_16|PCM_32|FLOAT] [--no_keep_length] \
         [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder] [--tile_hop 128|64|32] [--phase_iters N]
-        [--wiener_iters N]
+        [--wiener_iters N] [--loudness LUFS|source] [--peak_ceiling 0.9]
 
 A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
 default) is what the reference's data.py writes (data.py:166).  --win_size / --hop_size (the config's 1024 / 768 by default;
@@ -23,7 +23,11 @@ Griffin-Lim updates of the written stem, or, with --tar_accomp, N MISI updates o
 to add up to.  --wiener_iters N (0 by default; 1..8; files of one or two channels; not beside --phase_iters) runs the multichannel
 Wiener filter after the mask (wiener.py): N updates of a power per bin and a spatial covariance per frequency for each of the two
 sources, then each written stem re-filtered from the complex stereo mixture -- magnitudes and phases of its own, the mixture's
-stereo balance kept, and with --tar_accomp two files that add up to the mixture.  The reference has no such command: it goes through
+stereo balance kept, and with --tar_accomp two files that add up to the mixture.  --loudness LUFS (off by default: every file is
+peak-normalised to 0.9 on its own, data.py:162-166) brings the written audio to that integrated loudness instead (ITU-R BS.1770-4,
+loudness.py; measured on the device on the samples that are written): one file to the target, or, with --tar_accomp, vocal +
+accompaniment to the target with one gain for both files, so that their balance is kept; --loudness source (with --tar_accomp only)
+aims at the source file's own loudness.  --peak_ceiling (0.9) bounds every written sample under that gain.  The reference has no such command: it goes through
 data.py to_spec, inference.py and data.py to_wave with .npy files in between.
 """
 from __future__ import annotations
@@ -37,6 +41,7 @@ import torch
 from .config import HOP_SIZE, INPUT_LEN, WINDOW_SIZE
 from .data import WINDOW_SIZES
 from .inference import load_checkpoint_model
+from .loudness import describe, parse_target
 from .overlap import check_tile_hop
 from .streaming import check_refinement, separate_to_wav
 
@@ -60,6 +65,10 @@ def main(argv=None):
                         help="phase-refinement updates before the last inverse STFT: 0 = the mixture's phase; N > 0 = N Griffin-Lim updates (MISI with --tar_accomp)")
     parser.add_argument("--wiener_iters", type=int, default=0,
                         help="updates of the multichannel Wiener filter after the mask: 0 = none; 1..8 (one or two channels; not with --phase_iters)")
+    parser.add_argument("--loudness", type=str, default=None,
+                        help="integrated loudness of what is written, in LUFS (for instance -23), instead of peak 0.9 per file; with --tar_accomp "
+                             "one gain for both files; `source` (with --tar_accomp only): the source file's own loudness")
+    parser.add_argument("--peak_ceiling", type=float, default=0.9, help="with --loudness: no written sample exceeds this (default 0.9)")
     parser.add_argument("--ema", action="store_true", help="load the checkpoint's ema_state_dict (train.py --ema_decay) instead of its live weights")
     args = parser.parse_args(argv)
     if args.phase_iters < 0:
@@ -76,6 +85,15 @@ def main(argv=None):
         parser.error(f"--win_size {args.win_size}: the STFT / iSTFT kernels are built for n_fft = {', '.join(map(str, WINDOW_SIZES))}")
     if not 0 < args.hop_size <= args.win_size:
         parser.error(f"--hop_size {args.hop_size}: must be in 1..{args.win_size} (a larger hop leaves samples that no frame covers)")
+    if args.loudness is not None:
+        try:
+            args.loudness = parse_target(args.loudness)
+        except ValueError as e:
+            parser.error(f"--loudness {e}")
+        if args.loudness == "source" and args.tar_accomp is None:
+            parser.error("--loudness source aims vocal + accompaniment at the source's loudness: it needs --tar_accomp (give a number of LUFS for one stem)")
+        if not args.peak_ceiling > 0:
+            parser.error(f"--peak_ceiling {args.peak_ceiling}: must be positive")
     if args.tar_accomp is not None and not args.vocal_solo:
         parser.error("--tar_accomp writes the vocal to --tar and the accompaniment to --tar_accomp: it cannot be combined with --vocal_solo 0")
 
@@ -95,11 +113,14 @@ def main(argv=None):
         jobs = [(args.src, args.tar, args.tar_accomp)]
     print(f"Found {len(jobs)} files, separating...")
     for src, dst, dst_accomp in jobs:
+        report = {}
         frames, channels = separate_to_wav(model, src, dst, vocal_solo=bool(args.vocal_solo), precision=args.precision,
                                            subtype=args.subtype, keep_length=not args.no_keep_length, n_fft=args.win_size,
                                            hop=args.hop_size, dst_accomp_path=dst_accomp, tile_hop=args.tile_hop,
-                                           phase_iters=args.phase_iters, wiener_iters=args.wiener_iters)
-        print(f"{dst}: {frames} frames x {channels}" + ("" if dst_accomp is None else f"; {dst_accomp}: the same"))
+                                           phase_iters=args.phase_iters, wiener_iters=args.wiener_iters, loudness=args.loudness,
+                                           ceiling=args.peak_ceiling, report=report)
+        print(f"{dst}: {frames} frames x {channels}" + ("" if dst_accomp is None else f"; {dst_accomp}: the same")
+              + (f"; {describe(report['info'], report['gain'])}" if report else ""))
     print("Separation finished!")
 
 

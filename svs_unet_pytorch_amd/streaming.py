@@ -191,7 +191,8 @@ def separated_frames(n_source: int, sr: int, hop: int = HOP_SIZE):
 @torch.no_grad()
 def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = True, precision: str | None = None,
                     subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
-                    dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN, phase_iters: int = 0, wiener_iters: int = 0):
+                    dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN, phase_iters: int = 0, wiener_iters: int = 0,
+                    loudness=None, ceiling: float = 0.9, report: dict | None = None):
     """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
     the PCM is copied as the file stores it (data.read_pcm), resample.resample_poly_gpu (no downmix) brings every channel to
     SAMPLE_RATE, separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
@@ -202,8 +203,18 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     another geometry runs on the n_fft / 2 rows of that window).  dst_accomp_path: also write the accompaniment there, from the
     same pass (separate_waveform(both_stems=True)): dst_path then holds the vocal whatever vocal_solo says, and each file is
     encoded with its own common gain at peak 0.9.  vocal_solo, precision, tile_hop, phase_iters and wiener_iters are
-    separate_waveform's.  Returns the (frames, channels) written (per file)."""
+    separate_waveform's.
+
+    loudness (None: the peak rule above, byte for byte): a number of LUFS, or "source" (only with dst_accomp_path): the written
+    audio is brought to that integrated loudness (ITU-R BS.1770-4, loudness.py) instead of to peak 0.9 -- one stem to the target, or,
+    with dst_accomp_path, vocal + accompaniment to the target with ONE gain for both files, so that their balance is kept and
+    they still add up.  "source": the target is the source file's own loudness, measured on the device at the file's rate.  The
+    gain never lifts a sample of any written file above `ceiling`.  The frames are cut or padded (keep_length) before the
+    measurement, so what is measured is what is written.  report: a dict that receives "info" (L before the gain, kept blocks,
+    unlimited gain, ceiling-limited) and "gain", read back after the PCM.  Returns the (frames, channels) written (per file)."""
     check_refinement(phase_iters, wiener_iters)
+    if isinstance(loudness, str) and (loudness != "source" or dst_accomp_path is None):
+        raise ValueError(f"loudness={loudness!r}: a number of LUFS, or \"source\" together with dst_accomp_path")
     from fractions import Fraction
 
     from scipy.io import wavfile
@@ -220,7 +231,23 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     y = y[None] if y.dim() == 1 else y                            # (channels, n) at the network rate
     sep = separate_waveform(model, y, vocal_solo=vocal_solo, n_fft=n_fft, hop=hop, peak=None, precision=precision,
                             both_stems=dst_accomp_path is not None, tile_hop=tile_hop, phase_iters=phase_iters, wiener_iters=wiener_iters)
-    for stem, path in ((sep, dst_path),) if dst_accomp_path is None else ((sep[0], dst_path), (sep[1], dst_accomp_path)):
+    jobs = ((sep, dst_path),) if dst_accomp_path is None else ((sep[0], dst_path), (sep[1], dst_accomp_path))
+    if loudness is not None:
+        from . import loudness as ld
+        from .resample import encode_loudness_gpu, pcm_format
+        target = loudness
+        if loudness == "source":                                   # info[0] of a measurement of the file itself; it stays on the device
+            target = ld.loudness_gain_gpu(resample_poly_gpu(pcm, 1, 1, channels=channels, downmix=False), int(rate))[1]
+        frames = n_source if keep_length else None
+        encs, gain, info = encode_loudness_gpu([stem.contiguous() for stem, _ in jobs], fr.denominator, fr.numerator, *pcm_format(subtype),
+                                               target, ceiling, int(rate), frames)
+        for enc, (_, path) in zip(encs, jobs):
+            out = enc.cpu().numpy()
+            wavfile.write(path, int(rate), out[:, 0] if channels == 1 else out)
+        if report is not None:
+            report["info"], report["gain"] = info.cpu().tolist(), float(gain[0].item())
+        return out.shape
+    for stem, path in jobs:
         enc = resample_encode_gpu(stem, fr.denominator, fr.numerator, fmt=subtype, peak=0.9, common_gain=True)
         if keep_length:
             keep, pad = kept_length(enc.shape[0], n_source)
