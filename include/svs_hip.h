@@ -229,8 +229,12 @@ int svs_dec_block_bwd_weight(const float* x, int64_t ldx, int B, int H, int W, i
  * kind 0 = gather GEMM (svs_enc_block_fwd / svs_dec_block_bwd_data), 1 = parity GEMM (svs_dec_block_fwd /
  * svs_enc_block_bwd_data), 2 = weight gradient (H,W,C: the strided image, N: channels of the windowed image), 3 / 4 = a gather
  * (conv4..conv6) / parity (deconv1..deconv5) layer of the bf16 eval network (svs_unet_forward_eval_bf16): conv_gemm_bf16_kernel
- * with its tile, or the parity_window_bf16_kernel instantiation; <0 for channel counts no bf16 layer has.  Host arithmetic
- * only: no GPU is touched.  Lets bench.py attribute its live HIP-event timings to the kernels of the rocprofv3 summary. */
+ * with its tile, or the parity_window_bf16_kernel instantiation; <0 for channel counts no bf16 layer has.  5 / 6 = kinds 0 / 1
+ * for the call with the folded-BatchNorm epilogue (scale != NULL), the form svs_unet_forward_eval issues for conv2..conv6 /
+ * deconv1..deconv5: the planner has rules of its own for those calls (tile, K-split), so the name and the split may differ
+ * from kinds 0 / 1 at the same geometry; same name format.  Any other kind is SVS_ERR_INVALID.  Host arithmetic only: no GPU
+ * is touched.  Lets bench.py attribute its live HIP-event timings to the kernels of the rocprofv3 summary (kinds 0..2), and
+ * the per-layer gates say which kernel a layer of an eval forward launched (kinds 3..6). */
 int svs_describe_plan(int kind, int B, int H, int W, int C, int Ho, int Wo, int N, char* buf, size_t buflen);
 
 /* ---------------------------------------------------------------------------------------------

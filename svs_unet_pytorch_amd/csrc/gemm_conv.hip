@@ -1384,11 +1384,12 @@ size_t svs_conv_gemm_workspace(int mode, int B, int H, int W, int C, int Ho, int
   return need;
 }
 
-// Name (as rocprofv3 prints it) and K-split of the kernel a training-kind call (no folded BatchNorm, y written, not accumulated)
-// of this shape launches -- bench.py groups its live per-layer timings by this name so that they can be matched against the
-// rocprofv3 kernel statistics.
-int svs_conv_gemm_describe(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, long ldx, char* buf, size_t n) {
-  const ConvPlan p = plan_conv_call(mode, B, H, W, C, Ho, Wo, N, ldx, false, false);
+// Name (as rocprofv3 prints it) and K-split of the kernel a call of this shape launches (y written, not accumulated) -- the
+// training-kind call (no folded BatchNorm), or with `inference` the eval forward's call with the folded-BatchNorm epilogue.
+// bench.py groups its live per-layer timings by the training-kind name so that they can be matched against the rocprofv3 kernel
+// statistics; the per-layer eval gate (tests/test_gpu_eval_layers.py) reports and asserts the inference-kind one.
+int svs_conv_gemm_describe(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, long ldx, bool inference, char* buf, size_t n) {
+  const ConvPlan p = plan_conv_call(mode, B, H, W, C, Ho, Wo, N, ldx, inference, false);
   switch (p.kind) {
     case CONV_GATHER_WINDOW: snprintf(buf, n, "gather_window_kernel"); break;
     case CONV_PARITY_WINDOW: snprintf(buf, n, "parity_window_kernel<%d, %d, %d, %d, true>", p.wC, p.wCW, p.wTN, p.wNT); break;

@@ -66,6 +66,6 @@ int svs_fft_twiddles(int n, hipStream_t stream, const float2** out);
 // the same for the periodic Hann window of n samples, entries 0 .. n / 2 (fft_tables.hip)
 int svs_fft_hann(int n, hipStream_t stream, const float** out);
 
-int svs_conv_gemm_describe(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, long ldx, char* buf, size_t n);
+int svs_conv_gemm_describe(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, long ldx, bool inference, char* buf, size_t n);
 int svs_wgrad_gemm_describe(int B, int Hs, int Ws, int Cs, int Cl, char* buf, size_t n);
 int svs_conv_bf16_describe(int mode, int B, int H, int W, int C, int Ho, int Wo, int N, char* buf, size_t n);   // gemm_bf16.hip

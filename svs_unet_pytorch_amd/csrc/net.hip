@@ -149,12 +149,14 @@ extern "C" int svs_dec_block_bwd_weight(const float* x, int64_t ldx, int B, int 
 
 // kind 0: gather GEMM (enc fwd / dec bwd_data), 1: parity GEMM (dec fwd / enc bwd_data), 2: weight-gradient GEMM
 // (then H,W,C = the strided image S and N = channels of the windowed image), 3 / 4: gather / parity layer of the bf16 eval
-// network.  Returns the K-split.
+// network, 5 / 6: the gather / parity GEMM call with the folded-BatchNorm epilogue (the fp32 eval forward's form of kinds 0 / 1:
+// plan_gemm_tile's `inference` rules).  Returns the K-split.
 extern "C" int svs_describe_plan(int kind, int B, int H, int W, int C, int Ho, int Wo, int N, char* buf, size_t buflen) {
   if (!buf || !buflen) return SVS_ERR_INVALID;
   if (kind == 2) return svs_wgrad_gemm_describe(B, H, W, C, N, buf, buflen);
   if (kind == 3 || kind == 4) return svs_conv_bf16_describe(kind == 4 ? SVS_MODE_PARITY : SVS_MODE_GATHER, B, H, W, C, Ho, Wo, N, buf, buflen);
-  return svs_conv_gemm_describe(kind == 1 ? SVS_MODE_PARITY : SVS_MODE_GATHER, B, H, W, C, Ho, Wo, N, C, buf, buflen);
+  SVS_REQUIRE(kind == 0 || kind == 1 || kind == 5 || kind == 6, "svs_describe_plan: unknown kind %d", kind);
+  return svs_conv_gemm_describe(kind == 1 || kind == 6 ? SVS_MODE_PARITY : SVS_MODE_GATHER, B, H, W, C, Ho, Wo, N, C, kind >= 5, buf, buflen);
 }
 
 // ---------------------------------------------------------------------------------------------

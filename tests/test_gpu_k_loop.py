@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 from svs_unet_pytorch_amd import _lib
 
-from test_gpu_ops import DEV, L, S, nchw, nhwc, pack_gather, pack_parity, relerr, rnd, ws_tensor
+from test_gpu_ops import DEV, L, S, nchw, nhwc, pack_gather, pack_parity, relerr, rnd, ws_guard, ws_tensor          # noqa: F401  (ws_guard is an autouse fixture)
 
 pytestmark = pytest.mark.gpu
 

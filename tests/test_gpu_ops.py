@@ -43,8 +43,46 @@ def relerr(got, want):
     return ((got.double().cpu() - want).abs().max() / want.abs().max().clamp_min(1e-30)).item()
 
 
+WS_SENTINEL = 0x7FC17FC1   # an fp32 NaN no kernel computes: a workspace element read before it is written shows in the result
+WS_GUARD = 4096            # bytes allocated past the workspace the library is told about
+_workspaces = []           # the workspaces of the running test (ws_guard checks and drops them)
+
+
+class Workspace:
+    """`nbytes` sentinel-filled bytes for a call's `ws, ws_bytes` pair, exactly as many as the library's own *_workspace_bytes
+    query asked for, with WS_GUARD more sentinel bytes behind them that the library is not told about.  numel() is what the
+    library is told; with nbytes = 0 the pointer is still a real one."""
+
+    def __init__(self, nbytes):
+        self.nbytes = int(nbytes)
+        self.buf = torch.full(((self.nbytes + WS_GUARD + 3) // 4,), WS_SENTINEL, dtype=torch.int32, device=DEV).view(torch.uint8)
+        self.tail = self.buf[self.nbytes:self.nbytes + WS_GUARD].clone()
+
+    def data_ptr(self):
+        return self.buf.data_ptr()
+
+    def numel(self):
+        return self.nbytes
+
+    def tail_intact(self):
+        return torch.equal(self.buf[self.nbytes:self.nbytes + WS_GUARD], self.tail)
+
+
 def ws_tensor(nbytes):
-    return torch.empty(max(int(nbytes), 16) + 4096, dtype=torch.uint8, device=DEV)
+    _workspaces.append(Workspace(nbytes))
+    return _workspaces[-1]
+
+
+@pytest.fixture(autouse=True)
+def ws_guard():
+    """After every test (of this module and of those that import it with ws_tensor): no call wrote past the size its own
+    workspace query returned."""
+    _workspaces.clear()
+    yield
+    torch.cuda.synchronize()
+    bad = [w.nbytes for w in _workspaces if not w.tail_intact()]
+    _workspaces.clear()
+    assert not bad, f"bytes past a workspace of {bad} bytes were written"
 
 
 def pack_gather(w):      # (N,C,5,5) -> device packed

@@ -9,7 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from svs_unet_pytorch_amd import _lib, synth
-from test_gpu_ops import DEV, L, S, nchw, nhwc, pack_parity, relerr, rnd, ws_tensor
+from test_gpu_ops import DEV, L, S, nchw, nhwc, pack_parity, relerr, rnd, ws_guard, ws_tensor          # noqa: F401  (ws_guard is an autouse fixture)
 from test_gpu_unet import _grads_by_name, make_model
 
 pytestmark = pytest.mark.gpu

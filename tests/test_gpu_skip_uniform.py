@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from svs_unet_pytorch_amd import _lib, synth
+from test_gpu_ops import ws_guard, ws_tensor          # noqa: F401  (ws_guard is an autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -93,7 +94,7 @@ def plan_name(kind, B, h, w, C, ho, wo, N):
 
 def workspace(kind, B, h, w, C, ho, wo, N):
     n = L().svs_enc_block_workspace_bytes(B, h, w, C, N) if kind in GATHER else L().svs_dec_block_workspace_bytes(B, h, w, C, ho, wo, N)
-    return torch.empty(max(int(n), 16) + 4096, dtype=torch.uint8, device=DEV)
+    return ws_tensor(n)                          # sentinel-filled, told to the library at the queried size; ws_guard checks its tail
 
 
 def run(kind, x, B, h, w, C, wp, bias, scale, shift, slope, y, ldy, ho, wo, N, accumulate, ws):

@@ -364,6 +364,66 @@ def test_described_plans_name_built_kernels_and_fit_the_workspace(lib, tune, tmp
                 where = f"{name} B={B} {H}x{W} {switch}: {buf.value.decode()}"
                 assert ks >= 1 and buf.value.decode() in kernels, where
                 assert ws >= need, (where, ws, need)
+                if name.endswith("fwd") and kind in (0, 1):         # the same call with the folded-BatchNorm epilogue (eval forward)
+                    ks = lib.svs_describe_plan(kind + 5, B, h, w, c, ho, wo, n, buf, 128)
+                    assert ks >= 1 and buf.value.decode() in kernels, (where, buf.value)
+                    assert ws >= (ks * B * ho * wo * n * 4 if ks > 1 else 0), (where, buf.value, ks, ws)
+
+
+# (layer, (H, W, C, Ho, Wo, N)) of the ten planned forward calls on a 512 x 128 tile
+FWD_CALLS = (("conv2", (256, 64, 16, 128, 32, 32)), ("conv3", (128, 32, 32, 64, 16, 64)), ("conv4", (64, 16, 64, 32, 8, 128)),
+             ("conv5", (32, 8, 128, 16, 4, 256)), ("conv6", (16, 4, 256, 8, 2, 512)), ("deconv1", (8, 2, 512, 16, 4, 256)),
+             ("deconv2", (16, 4, 512, 32, 8, 128)), ("deconv3", (32, 8, 256, 64, 16, 64)), ("deconv4", (64, 16, 128, 128, 32, 32)),
+             ("deconv5", (128, 32, 64, 256, 64, 16)))
+# batch -> "tile/K-split" (or the window kernel's arguments) per call of FWD_CALLS: the training-kind call (kinds 0 / 1) ...
+TRAIN_PLANS = {16: "gather_window 128x64/3 64x128s/6 64x64s/12 64x64s/24 64x64s/16 64x128s/16 64x64s/4 window<128,64,1,2> window<64,64,1,1>",
+               64: "gather_window 128x64/1 64x128u/3 64x128u/7 64x64u/7 64x64u/7 64x128u/4 64x64u/1 window<128,64,2,2> window<64,64,1,1>"}
+# ... and the call with the folded-BatchNorm epilogue (kinds 5 / 6): the 64x64 tile for N = 64 up to 16384 rows (conv3 at batch 16), no
+# 64x128 tile on the narrow N = 128 layers below 8192 / 2048 rows (conv4, deconv2 at batch 16), no 64x128 conv5 tile (batch 64), and
+# a K-split target of 512 blocks instead of 768 (conv3 .. conv6 at batch 16, conv4 at batch 64)
+EVAL_PLANS = {16: "gather_window 64x64/2 64x64s/4 64x64s/8 64x64s/16 64x64s/16 64x64s/8 64x64s/4 window<128,64,1,2> window<64,64,1,1>",
+              64: "gather_window 128x64/1 64x128u/2 64x64u/2 64x64u/7 64x64u/7 64x128u/4 64x64u/1 window<128,64,2,2> window<64,64,1,1>"}
+
+
+def test_describe_plan_eval_kinds(lib, tune):
+    """svs_describe_plan kinds 5 / 6 (host arithmetic only): the gather / parity call with the folded-BatchNorm epilogue, named in
+    the format of kinds 0 / 1.  The plans of the ten forward calls at batch 16 and 64 are written down for both kinds of call --
+    the training-kind rows are what kinds 0 / 1 gave before kinds 5 / 6 existed -- and differ exactly where plan_gemm_tile's
+    `inference` rules say; kinds 2, 3 and 4 still answer, and an unknown kind is an error."""
+    import re
+    buf = ctypes.create_string_buffer(160)
+
+    def short(kind, B, call):
+        ks = lib.svs_describe_plan(kind, B, *call, buf, 160)
+        full = buf.value.decode()
+        if full == "gather_window_kernel":
+            assert ks == 1
+            return "gather_window"
+        m = re.fullmatch(r"parity_window_kernel<(\d+), (\d+), (\d+), (\d+), true>", full)
+        if m:
+            assert ks == 1
+            return "window<" + ",".join(m.groups()) + ">"
+        m = re.fullmatch(r"conv_gemm_kernel<([01]), (\d+), (\d+), (\d+), (\d+), (true|false), (true|false), false, ([12])>", full)
+        assert m and int(m.group(1)) == kind % 5, (kind, full)
+        return f"{m.group(2)}x{m.group(3)}" + ("u" if m.group(6) == "true" else "s" if m.group(7) == "true" else "") + f"/{ks}"
+
+    for B in (16, 64):
+        train = " ".join(short(int(name.startswith("deconv")), B, call) for name, call in FWD_CALLS)
+        evalp = " ".join(short(5 + int(name.startswith("deconv")), B, call) for name, call in FWD_CALLS)
+        assert train == TRAIN_PLANS[B], (B, train)
+        assert evalp == EVAL_PLANS[B], (B, evalp)
+    # the kernels that take no tile from plan_gemm_tile do not depend on the kind of call: the direct kernels with the windows off
+    tune("CONV_WINDOW", 0)
+    for call, want in ((FWD_CALLS[9][1], "conv_direct_kernel<1, 4, 1>"), (FWD_CALLS[8][1], "conv_direct_kernel<1, 4, 2>")):
+        for kind in (1, 6):
+            assert lib.svs_describe_plan(kind, 16, *call, buf, 160) == 1 and buf.value.decode() == want, (kind, buf.value)
+    tune("CONV_WINDOW", -1)
+    assert lib.svs_describe_plan(2, 16, 8, 2, 512, 0, 0, 256, buf, 160) == 2 and buf.value == b"wgrad_gemm_kernel<64, 128, 1, 4, true, false, 2>"
+    assert lib.svs_describe_plan(3, 16, 64, 16, 64, 32, 8, 128, buf, 160) == 6 and buf.value == b"conv_gemm_bf16_kernel<0, 128, 128, 2, 2, 2>"
+    assert lib.svs_describe_plan(4, 16, 16, 4, 512, 32, 8, 128, buf, 160) >= 1 and buf.value.startswith(b"conv_gemm_bf16_kernel<1, ")
+    for kind in (-1, 7):
+        assert lib.svs_describe_plan(kind, 16, 64, 16, 64, 32, 8, 128, buf, 160) == -1
+        assert b"unknown kind" in lib.svs_last_error_string()
 
 
 def test_each_gemm_tile_is_built_with_one_prefetch_depth(lib, tmp_path):
