@@ -593,6 +593,37 @@ size_t svs_bss_img_solve_batched_workspace_bytes(int64_t nbatch, int K, int flen
 int svs_bss_img_solve_batched(const double* corr, int64_t nbatch, int K, int flen, const int64_t* gram_off,
                               const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, int* skipped, void* ws,
                               size_t ws_bytes, hipStream_t stream);
+/* BSS-eval v4 (evaluate.py: bss_eval_v4 -- museval's default mode: distortion filters from the whole track, figures per
+ * frame).  It needs what the entry points above never form: the filter coefficients and the projected signals.
+ * svs_bss_img_filters_batched is svs_bss_img_solve_batched -- the same arguments, layout, launches, workspace size, ynorm2,
+ * status and skipped, bit for bit -- followed by a back substitution L^T c = y in 64-column steps, which leaves the
+ * least-squares coefficients C = G^-1 D of _project_images in
+ *   coef[(s*nrhs + r)*K*flen + i*flen + tau]   (device, fp64): right-hand side r of system s, reference i, delay tau.
+ * A column that the rank rule skipped has the coefficient 0 exactly (no division by its pivot, no NaN): the projection it
+ * gives is the projection on the span of the remaining columns.  Coefficients of a system whose status is not 0 are
+ * meaningless. */
+size_t svs_bss_img_filters_batched_workspace_bytes(int64_t nbatch, int K, int flen, int nrhs);
+int svs_bss_img_filters_batched(const double* corr, int64_t nbatch, int K, int flen, const int64_t* gram_off,
+                                const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, int* skipped, double* coef,
+                                void* ws, size_t ws_bytes, hipStream_t stream);
+/* The frames of BSS-eval v4 (csrc/bss_v4.hip): filters applied and the seven energies accumulated in one pass, no projected
+ * signal stored.  x[s*ld + m] as svs_bss_corr_windows takes it; frame w < nwin is x[:, w*hop .. w*hop + window), zero before
+ * its start, past its end and past n (L = its samples that exist; every frame must start inside the signal).  nsrc, nchan in
+ * {1, 2}, R = nsrc*nchan; ref_rows / est_rows (HOST, R ints each): the row of channel c of reference / estimate source j at
+ * [j*nchan + c].  coef_one[((j*nchan + c)*nchan + i)*flen + tau]: the filter from channel i of reference j to channel c of
+ * estimate j (svs_bss_img_filters_batched of the nsrc systems with K = nrhs = nchan); coef_all[((j*nchan + c)*R + i)*flen + tau]:
+ * the same from reference channel i of all R (one system with K = nrhs = R; for nsrc = 1 pass coef_one).  With
+ *   p1_c[m] = sum_i sum_tau coef_one[j,c,i,tau] r_{j,i}[m - tau],   pa_c[m] = the same over all R channels with coef_all,
+ *   s_c = channel c of reference j,   e_c = channel c of estimate j,   0 <= m < L + flen - 1   (the filters' tail included),
+ * it writes sums[(w*nsrc + j)*7 + k] (device, fp64), summed over m and c:
+ *   k = 0: s^2   1: (e - s)^2   2: (p1 - s)^2   3: p1^2   4: (pa - p1)^2   5: pa^2   6: (e - pa)^2
+ * i.e. SDR = S0/S1, ISR = S0/S2, SIR = S3/S4, SAR = S5/S6 of bss_eval_v4.  Plain fp64 FMAs; per-block partials are added by
+ * a second launch in ascending order: no atomics, bitwise reproducible.  Indices are 64-bit.  The query is 0 for invalid
+ * arguments and for a grid too wide for one launch. */
+size_t svs_bss_project_frames_workspace_bytes(int64_t window, int64_t nwin, int nsrc, int flen);
+int svs_bss_project_frames(const double* x, int64_t ld, int nsig, int64_t n, int64_t window, int64_t hop, int64_t nwin,
+                           int flen, int nsrc, int nchan, const int* ref_rows, const int* est_rows, const double* coef_one,
+                           const double* coef_all, double* sums, void* ws, size_t ws_bytes, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Resampling to the network rate (csrc/resample.hip): the arithmetic half of librosa.load(path, sr=8192, mono=True),

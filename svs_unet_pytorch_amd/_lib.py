@@ -128,6 +128,10 @@ _SIGS = {
     "svs_bss_img_corr_windows": (I, [P, L, I, L, L, L, L, P, I, P, L, P, Z, P]),
     "svs_bss_img_solve_batched_workspace_bytes": (Z, [L, I, I, I]),
     "svs_bss_img_solve_batched": (I, [P, L, I, I, P, P, I, P, P, P, P, Z, P]),
+    "svs_bss_img_filters_batched_workspace_bytes": (Z, [L, I, I, I]),
+    "svs_bss_img_filters_batched": (I, [P, L, I, I, P, P, I, P, P, P, P, P, Z, P]),
+    "svs_bss_project_frames_workspace_bytes": (Z, [L, L, I, I]),
+    "svs_bss_project_frames": (I, [P, L, I, L, L, L, L, I, I, I, P, P, P, P, P, P, Z, P]),
     "svs_resample_out_len": (L, [L, I, I]),
     "svs_resample_table_bytes": (Z, [I, I, I]),
     "svs_resample_pack_taps": (I, [P, I, I, I, P, P]),

@@ -11,6 +11,8 @@
 //   bss_panel_kernel /      right-looking blocked Cholesky of G in 64-wide panels.  Because the right-hand sides are rows
 //   bss_update_kernel       under G, the same triangular solves and updates that form L turn them into y^T = (L^-1 D)^T.
 //   bss_norm_kernel         |y|^2 per right-hand side = D^T G^-1 D, the energy of the projection (fixed-order sums).
+//   bss_back_diag_kernel /  BSS-eval v4 only (at the end of this file): the back substitution L^T c = y that leaves the filter
+//   bss_back_update_kernel  coefficients c = G^-1 D; csrc/bss_v4.hip applies them to the frames.
 // The solve kernels take a batch of independent systems of one shape: the system is the leading part of the flattened
 // block index, so a batch costs the launches of one system.  A pivot that is not > 0 (a silent reference: G singular) is
 // reported through the system's status word; the factorisation goes on with a unit pivot so that nothing faults, and the
@@ -464,10 +466,11 @@ int solve_launch(const SolveArgs& a, int* skipped, long nsys, bool rank, hipStre
   return SVS_OK;
 }
 
-// the body of both batched-solve entry points (`who`): K <= max_refs; rank: the image pivot rule, which fills skipped
+// the body of the batched-solve entry points (`who`): K <= max_refs; rank: the image pivot rule, which fills skipped;
+// made: where the launches' arguments go for a caller that has more to launch on the factored systems
 int solve_batched(const char* who, int max_refs, bool rank, const double* corr, int64_t nbatch, int K, int flen,
                   const int64_t* gram_off, const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, int* skipped,
-                  void* ws, size_t ws_bytes, hipStream_t stream) {
+                  void* ws, size_t ws_bytes, hipStream_t stream, SolveArgs* made = nullptr) {
   SVS_REQUIRE(corr && gram_off && rhs_off && ynorm2 && status && (skipped || !rank) && nbatch >= 1 &&
               solve_shape_valid(max_refs, K, flen, nrhs), "%s: bad arguments", who);
   SVS_REQUIRE(nbatch <= solve_max_systems(K, flen, nrhs), "%s: nbatch = %ld too large for one launch", who, (long)nbatch);
@@ -495,6 +498,7 @@ int solve_batched(const char* who, int max_refs, bool rank, const double* corr, 
   a.mstride = (long)a.rows * a.np;
   // from pageable memory: the runtime has staged `tab` by the time the copy call returns
   SVS_HIP(hipMemcpyAsync((void*)a.tab, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+  if (made) *made = a;
   return solve_launch(a, skipped, nbatch, rank, stream);
 }
 
@@ -790,4 +794,89 @@ extern "C" int svs_bss_img_solve_batched(const double* corr, int64_t nbatch, int
                                          void* ws, size_t ws_bytes, hipStream_t stream) {
   return solve_batched("svs_bss_img_solve_batched", SVS_BSS_IMG_MAX_REFS, true, corr, nbatch, K, flen, gram_off, rhs_off, nrhs,
                        ynorm2, status, skipped, ws, ws_bytes, stream);
+}
+
+// ---- BSS-eval v4: the filter coefficients (evaluate.py: bss_eval_v4) ---------------------------
+// v4 applies filters estimated once per track to every frame (csrc/bss_v4.hip), so it needs the coefficients c = G^-1 D
+// themselves, not only |y|^2.  After the launches of the image solve the workspace holds L (tile (k,k) factored in place by
+// bss_diag_kernel, the tiles below it by bss_img_panel_kernel) and, in the rows under it, y^T.  The back substitution
+// L^T c = y mirrors the forward direction in 64-column steps, from the last step to the first:
+//   bss_back_diag_kernel    one block per system: c_k = L_kk^-T y_k for every right-hand side, in place and into coef;
+//   bss_back_update_kernel  one block per (system, tile j < k): y_j -= L_kj^T c_k.
+// A column that the rank rule skipped has the pivot 0, a zero column of L and y = 0: its coefficient is 0 (no division),
+// which is the solution on the span of the remaining columns.  The identity padding has y = 0 and gives c = 0.
+
+namespace {
+
+__global__ __launch_bounds__(BSS_THREADS) void bss_back_diag_kernel(SolveArgs a, double* coef, int k) {
+  __shared__ double L[NB][NB + 1];
+  __shared__ double Y[SVS_BSS_MAX_RHS][NB + 1];
+  const int s = blockIdx.x, tid = threadIdx.x, kf = a.K * a.flen;
+  const long ld = a.np;
+  double* M = a.M + s * a.mstride;
+  const double* dk = M + (long)k * NB * ld + (long)k * NB;
+  double* yk = M + (long)a.np * ld + (long)k * NB;
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) L[e / NB][e % NB] = dk[(e / NB) * ld + e % NB];
+  for (int e = tid; e < a.nrhs * NB; e += BSS_THREADS) Y[e / NB][e % NB] = yk[(e / NB) * ld + e % NB];
+  __syncthreads();
+  for (int c = NB - 1; c >= 0; --c) {
+    const double piv = L[c][c];
+    if (tid < a.nrhs) Y[tid][c] = piv != 0.0 ? Y[tid][c] / piv : 0.0;
+    __syncthreads();
+    for (int e = tid; e < a.nrhs * NB; e += BSS_THREADS) {
+      const int r = e / NB, q = e % NB;
+      if (q < c) Y[r][q] -= L[c][q] * Y[r][c];
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < a.nrhs * NB; e += BSS_THREADS) {
+    const int r = e / NB, q = e % NB, col = k * NB + q;
+    yk[r * ld + q] = Y[r][q];
+    if (col < kf) coef[((long)s * a.nrhs + r) * kf + col] = Y[r][q];
+  }
+}
+
+__global__ __launch_bounds__(BSS_THREADS) void bss_back_update_kernel(SolveArgs a, int k) {
+  __shared__ double L[NB][NB + 1];                   // tile (k, j): [p][q]
+  __shared__ double Ck[SVS_BSS_MAX_RHS][NB];
+  const int s = blockIdx.x / k, j = blockIdx.x % k, tid = threadIdx.x;
+  const long ld = a.np;
+  double* M = a.M + s * a.mstride;
+  const double* lkj = M + (long)k * NB * ld + (long)j * NB;
+  const double* ck = M + (long)a.np * ld + (long)k * NB;
+  double* yj = M + (long)a.np * ld + (long)j * NB;
+  for (int e = tid; e < NB * NB; e += BSS_THREADS) L[e / NB][e % NB] = lkj[(e / NB) * ld + e % NB];
+  for (int e = tid; e < a.nrhs * NB; e += BSS_THREADS) Ck[e / NB][e % NB] = ck[(e / NB) * ld + e % NB];
+  __syncthreads();
+  for (int e = tid; e < a.nrhs * NB; e += BSS_THREADS) {
+    const int r = e / NB, q = e % NB;
+    double acc = 0.0;
+    for (int p = 0; p < NB; ++p) acc = fma(L[p][q], Ck[r][p], acc);
+    yj[r * ld + q] -= acc;
+  }
+}
+
+}  // namespace
+
+extern "C" size_t svs_bss_img_filters_batched_workspace_bytes(int64_t nbatch, int K, int flen, int nrhs) {
+  return solve_batched_ws_bytes(SVS_BSS_IMG_MAX_REFS, nbatch, K, flen, nrhs);
+}
+
+extern "C" int svs_bss_img_filters_batched(const double* corr, int64_t nbatch, int K, int flen, const int64_t* gram_off,
+                                           const int64_t* rhs_off, int nrhs, double* ynorm2, int* status, int* skipped,
+                                           double* coef, void* ws, size_t ws_bytes, hipStream_t stream) {
+  SVS_REQUIRE(coef, "svs_bss_img_filters_batched: bad arguments");
+  SolveArgs a{};
+  const int rc = solve_batched("svs_bss_img_filters_batched", SVS_BSS_IMG_MAX_REFS, true, corr, nbatch, K, flen, gram_off,
+                               rhs_off, nrhs, ynorm2, status, skipped, ws, ws_bytes, stream, &a);
+  if (rc != SVS_OK) return rc;
+  for (int k = a.np / NB - 1; k >= 0; --k) {
+    hipLaunchKernelGGL(bss_back_diag_kernel, dim3((unsigned)nbatch), dim3(BSS_THREADS), 0, stream, a, coef, k);
+    SVS_CHECK_LAUNCH("bss_back_diag");
+    if (k > 0) {
+      hipLaunchKernelGGL(bss_back_update_kernel, dim3((unsigned)(nbatch * k)), dim3(BSS_THREADS), 0, stream, a, k);
+      SVS_CHECK_LAUNCH("bss_back_update");
+    }
+  }
+  return SVS_OK;
 }

@@ -57,6 +57,13 @@ has L == R, a hard-panned stem a silent channel -- so the image entry points run
 rule that skips dependent columns (include/svs_hip.h, svs_bss_img_solve_batched): the projection onto the remaining columns
 is the projection onto the same span.  The numpy reference is shared the same way: _project and _decompose are the
 one-channel cases of _project_images and _decompose_images.
+
+BSS-eval v4 (`--mode v4`): `bss_eval_v4` restates the mode in which MUSDB18 / SiSEC results are published (museval's default;
+PARITY UNPINNED as above): the 512-tap filters are estimated once from the whole track (_projection_filters, the solve that
+_project_images shares), applied to every frame's references (_apply_filters), and SDR / ISR / SIR / SAR are taken per frame,
+the track's figure being the median over frames.  Inside a frame the spans are not nested, so no Gram form serves:
+`bss_eval_v4_gpu` gets the coefficients from svs_bss_img_filters_batched (the image solve plus a back substitution) and the
+seven per-frame energies from svs_bss_project_frames (csrc/bss_v4.hip), which applies the filters without storing a signal.
 """
 from __future__ import annotations
 
@@ -413,6 +420,10 @@ def _windows(n, window, hop):
     return n, n, 1, False
 
 
+_FALLBACK_WARNING = ("BSS-eval: a Gram matrix has a pivot that is not > 0 in the GPU Cholesky (singular or numerically "
+                     "indefinite); scoring of the affected window(s) falls back to the numpy path")
+
+
 def _host_windows(signals, window, hop):
     """slices(w) -> window w of each of `signals` as numpy, for the windows that numpy has to score.  The first use copies
     the signals to the host and gives the one RuntimeWarning of the call (attributed to the caller of the public function)."""
@@ -420,9 +431,7 @@ def _host_windows(signals, window, hop):
 
     def slices(w):
         if not host:
-            warnings.warn("BSS-eval: a Gram matrix has a pivot that is not > 0 in the GPU Cholesky (singular or numerically "
-                          "indefinite); scoring of the affected window(s) falls back to the numpy path", RuntimeWarning,
-                          stacklevel=4)
+            warnings.warn(_FALLBACK_WARNING, RuntimeWarning, stacklevel=4)
             host.extend(t.cpu().numpy() for t in signals)
         return [x[..., w * hop:w * hop + window] for x in host]
     return slices
@@ -517,11 +526,10 @@ def _vocal_metrics_gpu(mix, vocal_ref, vocal_est, window, hop, compute_permutati
 
 # ---- stereo: BSS-eval images ------------------------------------------------------------------
 
-def _project_images(reference_channels, estimated_channels, flen):
-    """_project for images: every row of estimated_channels (nchan, nsampl) projected onto all rows of reference_channels
-    (R, nsampl) delayed by 0 .. flen-1 samples; (nchan, nsampl + flen - 1)."""
+def _projection_filters(reference_channels, estimated_channels, flen):
+    """The least-squares filters of _project_images: C (flen, R, nchan), C[tau, i, c] the coefficient of reference row i
+    delayed by tau samples in the projection of estimate row c."""
     from scipy.linalg import toeplitz
-    from scipy.signal import fftconvolve
     nref, nsampl = reference_channels.shape
     nchan = estimated_channels.shape[0]
     refs = np.hstack((reference_channels, np.zeros((nref, flen - 1))))
@@ -545,12 +553,27 @@ def _project_images(reference_channels, estimated_channels, flen):
         C = np.linalg.solve(G, D)
     except np.linalg.LinAlgError:
         C = np.linalg.lstsq(G, D, rcond=None)[0]
-    C = C.reshape(flen, nref, nchan, order="F")
+    return C.reshape(flen, nref, nchan, order="F")
+
+
+def _apply_filters(C, reference_channels):
+    """The filters C (flen, R, nchan) of _projection_filters applied to reference_channels (R, nsampl), zero outside
+    [0, nsampl): (nchan, nsampl + flen - 1), the filters' tail included."""
+    from scipy.signal import fftconvolve
+    flen, nref, nchan = C.shape
+    nsampl = reference_channels.shape[1]
+    refs = np.hstack((reference_channels, np.zeros((nref, flen - 1))))
     sproj = np.zeros((nchan, nsampl + flen - 1))
     for k in range(nref):
         for c in range(nchan):
             sproj[c] += fftconvolve(C[:, k, c], refs[k])[:nsampl + flen - 1]
     return sproj
+
+
+def _project_images(reference_channels, estimated_channels, flen):
+    """_project for images: every row of estimated_channels (nchan, nsampl) projected onto all rows of reference_channels
+    (R, nsampl) delayed by 0 .. flen-1 samples; (nchan, nsampl + flen - 1)."""
+    return _apply_filters(_projection_filters(reference_channels, estimated_channels, flen), reference_channels)
 
 
 def _decompose_images(reference_sources, estimated_source, j, flen):
@@ -824,6 +847,238 @@ def compute_image_frame_metrics_for_track(mix_path, vocal_ref_path, vocal_est_pa
     return frames
 
 
+# ---- BSS-eval v4: filters from the whole track, figures per frame ------------------------------
+# The module docstring's Gram form does not reach this mode.  Inside a frame the track-wide filters are not the frame's own
+# least-squares filters, so P_j e and P_all e are no orthogonal projections there, the spans are not nested, and the energies
+# of e_spat, e_interf and e_artif do not follow from |P e|^2: the projected signals themselves are needed.
+
+def _v4_figures(sums):
+    """(SDR, ISR, SIR, SAR) in dB from the seven sums of bss_eval_v4."""
+    return (_safe_db(sums[0], sums[1]), _safe_db(sums[0], sums[2]), _safe_db(sums[3], sums[4]), _safe_db(sums[5], sums[6]))
+
+
+def _v4_frame_sums(ref_frame, est_frame, j, c_one, c_all):
+    """The seven sums of one frame and source j: ref_frame (nsrc, nchan, L), est_frame (nchan, L) of estimate j, and the
+    track's filters c_one (flen, nchan, nchan) and c_all (flen, nsrc * nchan, nchan) of that source."""
+    flen, frame_len = c_one.shape[0], ref_frame.shape[2]
+    pad = np.zeros((ref_frame.shape[1], flen - 1))
+    s, e = np.hstack((ref_frame[j], pad)), np.hstack((est_frame, pad))
+    p1 = _apply_filters(c_one, ref_frame[j])
+    pa = _apply_filters(c_all, ref_frame.reshape(-1, frame_len))
+    return np.array([np.sum(s ** 2), np.sum((e - s) ** 2), np.sum((p1 - s) ** 2), np.sum(p1 ** 2), np.sum((pa - p1) ** 2),
+                     np.sum(pa ** 2), np.sum((e - pa) ** 2)])
+
+
+def _v4_args(ref, est, window, hop, compute_permutation):
+    if tuple(ref.shape) != tuple(est.shape):
+        raise ValueError(f"reference {tuple(ref.shape)} and estimate {tuple(est.shape)} must have the same shape")
+    if compute_permutation:
+        raise ValueError("BSS-eval v4 scores estimate j against reference j: there is no permutation search here "
+                         "(compute_permutation must be False)")
+    return _frame_args(window, hop)
+
+
+def bss_eval_v4(reference_sources, estimated_sources, window, hop, flen=FILTER_LEN, compute_permutation=False):
+    """(sdr, isr, sir, sar), each (nsrc, nwin): BSS-eval v4, the mode in which MUSDB18 / SiSEC figures are published and the
+    default of museval.evaluate -- the distortion filters are estimated ONCE from the whole track, the figures are taken per
+    frame (the track's figure is the median over frames: frame_summary).  PARITY UNPINNED: museval is not installed here;
+    this is the float64 definition, restated from the published algorithm as bss_eval_images restates mir_eval.  Images
+    (nsrc, nsampl, nchan), a 2-D input being one channel; estimate j is scored against reference j.
+      filters   per source j and channel c of its estimate: C_j (onto the channels of reference j) and C_all (onto all
+                reference channels), the least-squares filters of _project_images on the WHOLE signals;
+      frames    nwin = frame_count(n, window, hop), frame w = [w*hop, w*hop + window); fewer than two: the whole signal is the
+                one frame, and the result is bss_eval_images(..., compute_permutation=False); a frame in which a reference or
+                an estimate source is all zeros in every channel is NaN in all four outputs;
+      per frame the frame's own samples, zero outside it, give p1 = C_j * references of j and pa = C_all * all references over
+                L + flen - 1 samples (the filters' tail belongs to the frame, the samples before it do not), and
+                _image_criteria of (s, p1 - s, pa - p1, e - pa): SDR = |s|^2 / |e - s|^2, ISR = |s|^2 / |p1 - s|^2,
+                SIR = |p1|^2 / |pa - p1|^2, SAR = |pa|^2 / |e - pa|^2, summed over samples and channels."""
+    ref, est = _images_3d(reference_sources, "reference"), _images_3d(estimated_sources, "estimate")
+    window, hop = _v4_args(ref, est, window, hop, compute_permutation)
+    nsrc, n, nchan = ref.shape
+    rc, ec = ref.transpose(0, 2, 1), est.transpose(0, 2, 1)                      # time last
+    all_channels = rc.reshape(nsrc * nchan, n)
+    c_one = [_projection_filters(rc[j], ec[j], flen) for j in range(nsrc)]
+    c_all = [_projection_filters(all_channels, ec[j], flen) for j in range(nsrc)]
+    window, hop, nwin, framed = _windows(n, window, hop)
+    out = np.full((4, nsrc, nwin), np.nan)
+    for w in range(nwin):
+        r, e = rc[:, :, w * hop:w * hop + window], ec[:, :, w * hop:w * hop + window]
+        if framed and (np.any(np.all(r == 0, axis=(1, 2))) or np.any(np.all(e == 0, axis=(1, 2)))):
+            continue
+        for j in range(nsrc):
+            out[:, j, w] = _v4_figures(_v4_frame_sums(r, e[j], j, c_one[j], c_all[j]))
+    return tuple(out)
+
+
+def _gpu_v4_sums(sig, window, hop, nwin, nsrc, nchan, flen, energies, crosses):
+    """The device half of bss_eval_v4_gpu, and its only caller of the library.  sig: (S, n) float64 on a ROCm device, rows
+    0 .. R-1 the reference channels (source-major, R = nsrc * nchan), rows R .. 2R-1 the estimate channels the same way, then
+    whatever else `energies` (rows) and `crosses` (row pairs) name.  ONE whole-track correlation pass, the filter solves (the
+    nsrc systems onto a source's own channels in one batch, and for two sources the one system onto all R channels with all R
+    estimate channels as right-hand sides), one lag-0 correlation pass over the frames for the energies and cross terms, ONE
+    svs_bss_project_frames call, and one read-back.  Returns numpy (sums (nwin, nsrc, 7), energy (nwin, len(energies)), cross
+    (nwin, len(crosses)), status (int per system)); a status that is not 0 marks a whole-track Gram matrix that is numerically
+    indefinite (the sums are then meaningless).  The seam at which the host tests put numpy in place of the library."""
+    import torch
+    from . import _lib
+    L = _lib.lib()
+    S, n = sig.shape
+    R = nsrc * nchan
+    pairs = [(i, j, flen) for i in range(R) for j in range(R)] + [(R + e, i, flen) for e in range(R) for i in range(R)]
+    gram = lambda i, j: (i * R + j) * flen
+    rhs = lambda e, i: (R * R + e * R + i) * flen
+    lag0 = [(e, e, 1) for e in energies] + [(a, b, 1) for a, b in crosses]
+    flat, flat0 = (np.asarray(p, dtype=np.int32).ravel() for p in (pairs, lag0))
+    stride, stride0 = len(pairs) * flen, len(lag0)
+    src = [range(j * nchan, (j + 1) * nchan) for j in range(nsrc)]
+    g_one = np.asarray([gram(a, b) for s in src for a in s for b in s], dtype=np.int64)
+    r_one = np.asarray([rhs(c, i) for s in src for c in s for i in s], dtype=np.int64)
+    g_all = np.asarray([gram(a, b) for a in range(R) for b in range(R)], dtype=np.int64)
+    r_all = np.asarray([rhs(c, i) for c in range(R) for i in range(R)], dtype=np.int64)
+    rows = np.arange(2 * R, dtype=np.int32)
+    dev = sig.device
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr()
+        need = [L.svs_bss_img_corr_windows_workspace_bytes(n, 1, len(pairs), flat.ctypes.data),
+                L.svs_bss_img_corr_windows_workspace_bytes(window, nwin, len(lag0), flat0.ctypes.data) if lag0 else 1,
+                L.svs_bss_img_filters_batched_workspace_bytes(nsrc, nchan, flen, nchan),
+                L.svs_bss_img_filters_batched_workspace_bytes(1, R, flen, R),
+                L.svs_bss_project_frames_workspace_bytes(window, nwin, nsrc, flen)]
+        if min(need) == 0:
+            raise ValueError(f"{nwin} frames of {window} samples do not fit one launch")
+        ws = torch.empty(int(max(need)), dtype=torch.uint8, device=dev)
+        corr = torch.empty(stride, dtype=torch.float64, device=dev)
+        _lib.check(L.svs_bss_img_corr_windows(sig.data_ptr(), sig.stride(0), S, n, n, n, 1, flat.ctypes.data, len(pairs),
+                                              corr.data_ptr(), stride, ws.data_ptr(), ws.numel(), stream),
+                   "svs_bss_img_corr_windows")
+        coef_one = torch.empty(nsrc * nchan * nchan * flen, dtype=torch.float64, device=dev)
+        coef_all = torch.empty(R * R * flen, dtype=torch.float64, device=dev) if nsrc == 2 else coef_one
+        ynorm2 = torch.empty(R * R + nsrc * nchan, dtype=torch.float64, device=dev)
+        words = torch.zeros(2, nsrc + 1, dtype=torch.int32, device=dev)           # status, skipped: per system
+        _lib.check(L.svs_bss_img_filters_batched(corr.data_ptr(), nsrc, nchan, flen, g_one.ctypes.data, r_one.ctypes.data,
+                                                 nchan, ynorm2.data_ptr(), words[0].data_ptr(), words[1].data_ptr(),
+                                                 coef_one.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                   "svs_bss_img_filters_batched")
+        if nsrc == 2:
+            _lib.check(L.svs_bss_img_filters_batched(corr.data_ptr(), 1, R, flen, g_all.ctypes.data, r_all.ctypes.data, R,
+                                                     ynorm2[nsrc * nchan:].data_ptr(), words[0, nsrc:].data_ptr(),
+                                                     words[1, nsrc:].data_ptr(), coef_all.data_ptr(), ws.data_ptr(),
+                                                     ws.numel(), stream), "svs_bss_img_filters_batched")
+        out = torch.empty(nwin * (nsrc * 7 + stride0), dtype=torch.float64, device=dev)     # the sums, then the lag-0 terms
+        lag0_out = out[nwin * nsrc * 7:]
+        if stride0:
+            _lib.check(L.svs_bss_img_corr_windows(sig.data_ptr(), sig.stride(0), S, n, window, hop, nwin, flat0.ctypes.data,
+                                                  len(lag0), lag0_out.data_ptr(), stride0, ws.data_ptr(), ws.numel(), stream),
+                       "svs_bss_img_corr_windows")
+        _lib.check(L.svs_bss_project_frames(sig.data_ptr(), sig.stride(0), S, n, window, hop, nwin, flen, nsrc, nchan,
+                                            rows[:R].ctypes.data, rows[R:].ctypes.data, coef_one.data_ptr(),
+                                            coef_all.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                   "svs_bss_project_frames")
+        out, words = out.cpu().numpy(), words.cpu().numpy()
+    sums = out[:nwin * nsrc * 7].reshape(nwin, nsrc, 7)
+    lag0_host = out[nwin * nsrc * 7:].reshape(nwin, stride0)
+    return sums, lag0_host[:, :len(energies)], lag0_host[:, len(energies):], words[0, :nsrc + (nsrc == 2)]
+
+
+def _v4_gpu(reference_sources, estimated_sources, window, hop, flen, compute_permutation=False, mix=None):
+    """((sdr, isr, sir, sar), each (nsrc, nwin); image-SDR (nwin,) of `mix` ((n, nchan)) taken as the estimate of source 0, or
+    None) of bss_eval_v4 through _gpu_v4_sums.  Rows: reference channels (source-major), estimate channels, mixture channels."""
+    import torch
+    ref, est = (x.unsqueeze(-1) if x.dim() == 2 else x for x in map(_device_f64, (reference_sources, estimated_sources)))
+    if ref.dim() != 3:
+        raise ValueError(f"reference must be (nsrc, nsampl) or (nsrc, nsampl, nchan), got shape {tuple(ref.shape)}")
+    window, hop = _v4_args(ref, est, window, hop, compute_permutation)
+    nsrc, n, nchan = ref.shape
+    if nsrc not in (1, 2) or nchan not in (1, 2):
+        raise ValueError(f"the GPU BSS-eval v4 handles 1 or 2 sources of 1 or 2 channels, got {nsrc} sources of {nchan} "
+                         "channels (use bss_eval_v4)")
+    if not 1 <= flen <= 512:
+        raise ValueError(f"flen = {flen}: the GPU path supports filter lengths 1 .. 512")
+    window, hop, nwin, framed = _windows(n, window, hop)
+    est = est.to(ref.device)
+    R = nsrc * nchan
+    rows = [ref.transpose(1, 2).reshape(R, n), est.transpose(1, 2).reshape(R, n)]
+    crosses = []
+    if mix is not None:
+        mix = _device_f64(mix).to(ref.device).reshape(n, nchan)
+        rows.append(mix.t())
+        crosses = [(2 * R + c, c) for c in range(nchan)]
+    nrows = 2 * R + (nchan if mix is not None else 0)
+    sums, energy, cross, status = _gpu_v4_sums(torch.cat(rows).contiguous(), window, hop, nwin, nsrc, nchan, flen,
+                                               list(range(nrows)), crosses)
+    e_ref = energy[:, :R].reshape(nwin, nsrc, nchan).sum(axis=2)
+    e_est = energy[:, R:2 * R].reshape(nwin, nsrc, nchan).sum(axis=2)
+    if np.any(status):                                 # the track's filters are the whole score: numpy for the track
+        warnings.warn(_FALLBACK_WARNING, RuntimeWarning, stacklevel=3)
+        out = bss_eval_v4(ref.cpu().numpy(), est.cpu().numpy(), window, hop, flen)
+    else:
+        out = np.full((4, nsrc, nwin), np.nan)
+        for w in range(nwin):
+            if not (framed and ((e_ref[w] == 0).any() or (e_est[w] == 0).any())):
+                for j in range(nsrc):
+                    out[:, j, w] = _v4_figures(sums[w, j])
+        out = tuple(out)
+    sdr_mix = None
+    if mix is not None:                                # lag-0 terms only: no filter enters the mixture's SDR
+        e_mix, x_mix = energy[:, 2 * R:].sum(axis=1), cross.sum(axis=1)
+        sdr_mix = np.array([np.nan if framed and (e_ref[w, 0] == 0 or e_mix[w] == 0) else
+                            _db(e_ref[w, 0], e_mix[w] - 2.0 * x_mix[w] + e_ref[w, 0]) for w in range(nwin)])
+    return out, sdr_mix
+
+
+def bss_eval_v4_gpu(reference_sources, estimated_sources, window, hop, flen=FILTER_LEN, compute_permutation=False):
+    """bss_eval_v4 on the GPU (numpy or torch inputs, nsrc and nchan 1 or 2, flen <= 512): the same (sdr, isr, sir, sar).  The
+    filters come from one whole-track correlation pass and svs_bss_img_filters_batched, the frames from one
+    svs_bss_project_frames call (csrc/bss_v4.hip).  Rank-deficient images (identical or silent channels) are handled on the
+    device; a numerically indefinite whole-track Gram matrix makes the call return the numpy bss_eval_v4 result, with a
+    RuntimeWarning."""
+    return _v4_gpu(reference_sources, estimated_sources, window, hop, flen, compute_permutation)[0]
+
+
+def image_metrics_from_waveforms_v4(mix, vocal_ref, vocal_est, window, hop, device="cpu"):
+    """The frames {"SDR", "ISR", "SIR", "SAR", "NSDR", "start"} of the vocal under BSS-eval v4 for (n, nchan) waveforms (a 1-D
+    array is nchan 1): bss_eval_v4 of (vocal, mix - vocal) against (estimate, mix - estimate), the vocal being row 0;
+    NSDR = SDR - SDR(mixture taken as the vocal estimate), which needs no filter: the direct ratio per frame, NaN where the
+    vocal or the mixture is silent.  frame_summary(frames, IMAGE_METRICS) gives the track's figures."""
+    mix, vocal_ref, vocal_est = _stereo_2d(mix, "mix"), _stereo_2d(vocal_ref, "vocal"), _stereo_2d(vocal_est, "estimate")
+    if not (tuple(mix.shape) == tuple(vocal_ref.shape) == tuple(vocal_est.shape)):
+        raise ValueError(f"mix {tuple(mix.shape)}, vocal {tuple(vocal_ref.shape)} and estimate {tuple(vocal_est.shape)} "
+                         "must have one (n, nchan) shape")
+    _frame_args(window, hop)
+    w_, h_, nwin, framed = _windows(mix.shape[0], window, hop)
+    if device == "gpu":
+        import torch
+        m, v, ve = _device_f64(mix), _device_f64(vocal_ref), _device_f64(vocal_est)
+        v, ve = v.to(m.device), ve.to(m.device)
+        out, sdr_mix = _v4_gpu(torch.stack([v, m - v]), torch.stack([ve, m - ve]), window, hop, FILTER_LEN, mix=m)
+    elif device == "cpu":
+        out = bss_eval_v4(np.stack([vocal_ref, mix - vocal_ref]), np.stack([vocal_est, mix - vocal_est]), window, hop,
+                          FILTER_LEN)
+        sdr_mix = np.full(nwin, np.nan)
+        for w in range(nwin):
+            s, m = vocal_ref[w * h_:w * h_ + w_], mix[w * h_:w * h_ + w_]
+            if not (framed and (not s.any() or not m.any())):
+                sdr_mix[w] = _image_sdr_direct(s, m)
+    else:
+        raise ValueError(f"device must be 'cpu' or 'gpu', got {device!r}")
+    sdr, isr, sir, sar = (v[0] for v in out)
+    return {"SDR": sdr, "ISR": isr, "SIR": sir, "SAR": sar, "NSDR": sdr - sdr_mix, "start": np.arange(nwin) * h_}
+
+
+def compute_v4_frame_metrics_for_track(mix_path, vocal_ref_path, vocal_est_path, window_s=1.0, hop_s=None, device="cpu",
+                                       stereo=False):
+    """image_metrics_from_waveforms_v4 of one track, frames given in seconds (hop: the window by default), of the files'
+    channels (stereo) or of their downmix; adds "start_s", the start of each frame in seconds."""
+    load = _load_track_channels if stereo else _load_track
+    mix, vocal_ref, vocal_est, sr = load(mix_path, vocal_ref_path, vocal_est_path)
+    window = frame_samples(window_s, sr)
+    hop = frame_samples(window_s if hop_s is None else hop_s, sr)
+    frames = image_metrics_from_waveforms_v4(mix, vocal_ref, vocal_est, window, hop, device)
+    frames["start_s"] = frames["start"] / sr
+    return frames
+
+
 def main(argv=None):
     parser =argparse.ArgumentParser(description="Evaluate SVS results with SDR / SIR / SAR / NSDR (vocal only).")
     parser.add_argument("--est", type=str, required=True, help="folder of predicted vocal wav files")
@@ -843,10 +1098,19 @@ def main(argv=None):
     parser.add_argument("--stereo", action="store_true",
                         help="score the files' channels as images (BSS-eval images, no downmix): adds ISR, the figure "
                              "that reacts to a wrong stereo balance")
+    parser.add_argument("--mode", choices=["v3", "v4"], default="v3",
+                        help="v4: BSS-eval v4, the mode of published MUSDB18 / SiSEC figures (museval's default): filters from "
+                             "the whole track, SDR / ISR / SIR / SAR / NSDR per frame (--frame_window, default 1 s), the "
+                             "median over frames per track; the downmix is scored unless --stereo is given")
     args = parser.parse_args(argv)
-    metrics = IMAGE_METRICS if args.stereo else METRICS
+    v4 = args.mode == "v4"
+    if v4 and args.frame_window is None:
+        args.frame_window = 1.0
+    metrics = IMAGE_METRICS if args.stereo or v4 else METRICS
     track_metrics = compute_image_metrics_for_track if args.stereo else compute_metrics_for_track
     track_frames = compute_image_frame_metrics_for_track if args.stereo else compute_frame_metrics_for_track
+    if v4:
+        track_frames = lambda *a: compute_v4_frame_metrics_for_track(*a, stereo=args.stereo)
     framewise = args.frame_window is not None
     if framewise and not args.frame_window > 0:
         parser.error("--frame_window must be > 0")

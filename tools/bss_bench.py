@@ -8,6 +8,7 @@ and the numpy path, on a seeded synthetic 240 s track at 8192 Hz and at 44,100 H
     python tools/bss_bench.py --frame_window 1 [--frame_hop 1] [--ws-budget BYTES]   # framewise metrics instead
     python tools/bss_bench.py --stereo [--frame_window 1]       # the image metrics (SDR / ISR / SIR / SAR / NSDR) of a stereo track
     python tools/bss_bench.py --ab-solve                        # the two solve entry points on one batch, and order 2048
+    python tools/bss_bench.py --v4                              # BSS-eval v4 (evaluate.py --mode v4) of the stereo track, 1 s frames
 
 Timing: host clock around metrics_from_waveforms(device="gpu") followed by a device synchronise (the call ends with a
 copy back to the host anyway), after one warm-up call; median and minimum of --reps calls.  The numpy path is timed once.
@@ -93,6 +94,75 @@ def stereo_record(args, rate):
         rec["nan_frames_equal"] = all(np.array_equal(np.isnan(g[k]), np.isnan(c[k])) for k in ev.IMAGE_METRICS)
         rec["max_abs_diff_db"] = max(float(np.max(np.abs(g[k] - c[k])[~np.isnan(c[k])], initial=0.0)) for k in ev.IMAGE_METRICS)
         rec["speedup"] = rec["numpy_s"] / (rec["gpu_ms_median"] / 1e3)
+    return rec
+
+
+def v4_record(args, rate):
+    """--v4: BSS-eval v4 of the stereo two-source track, 1 s frames.  In every repetition, one after the other: bss_eval_v4_gpu
+    (host clock around the call, which ends in its read-back, then a device synchronise), the existing --stereo --frame_window 1
+    device path on the same track (for scale: it re-estimates the filters in every frame) and svs_bss_project_frames alone on
+    device-resident inputs (HIP events; seeded coefficients, which the time does not depend on), after one warm-up round;
+    medians with min and max.  The float64 numpy definition is timed once on the host.  FMAs of the projection: per source,
+    frame, estimate channel and output sample, flen taps of the source's nchan and of all R reference channels."""
+    import torch
+    from svs_unet_pytorch_amd import _lib
+    mix, vocal, est = stereo_track(args.seconds, rate)
+    ref2, est2 = np.stack([vocal, mix - vocal]), np.stack([est, mix - est])
+    n, nchan, nsrc, flen = mix.shape[0], 2, 2, ev.FILTER_LEN
+    window = hop = ev.frame_samples(1.0, rate)
+    nwin = ev.frame_count(n, window, hop)
+    L, dev, R = _lib.lib(), torch.device("cuda"), 4
+    rng = np.random.default_rng(7)
+    sig = torch.from_numpy(np.concatenate([ref2.transpose(0, 2, 1).reshape(R, n), est2.transpose(0, 2, 1).reshape(R, n)])).to(dev)
+    coef_one = torch.from_numpy(rng.standard_normal(nsrc * nchan * nchan * flen) / flen).to(dev)
+    coef_all = torch.from_numpy(rng.standard_normal(R * R * flen) / flen).to(dev)
+    sums = torch.empty(nwin * nsrc * 7, dtype=torch.float64, device=dev)
+    ws = torch.empty(int(L.svs_bss_project_frames_workspace_bytes(window, nwin, nsrc, flen)), dtype=torch.uint8, device=dev)
+    rows = np.arange(2 * R, dtype=np.int32)
+
+    def project():
+        _lib.check(L.svs_bss_project_frames(sig.data_ptr(), n, 2 * R, n, window, hop, nwin, flen, nsrc, nchan, rows[:R].ctypes.data,
+                                            rows[R:].ctypes.data, coef_one.data_ptr(), coef_all.data_ptr(), sums.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "svs_bss_project_frames")
+
+    def host_timed(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0), out
+
+    def event_timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1), None
+
+    sides = {"v4_gpu": lambda: host_timed(lambda: ev.bss_eval_v4_gpu(ref2, est2, window, hop)),
+             "v3_framewise_gpu": lambda: host_timed(lambda: ev.image_metrics_from_waveforms_framewise(mix, vocal, est, window, hop,
+                                                                                                      "gpu")),
+             "project_frames": lambda: event_timed(project)}
+    ms, last = {k: [] for k in sides}, {}
+    for rep in range(args.reps + 1):
+        for k, fn in sides.items():
+            t, last[k] = fn()
+            if rep:                                                    # the first round warms up
+                ms[k].append(t)
+    fma = float(nsrc * nwin * (window + flen - 1) * nchan * flen * (nchan + R))
+    rec = {"v4": True, "rate": rate, "seconds": args.seconds, "n": n, "window": window, "hop": hop, "frames": int(nwin),
+           "flen": flen, "reps": args.reps,
+           **{f"{k}_ms_{s}": f(v) for k, v in ms.items() for s, f in (("median", statistics.median), ("min", min), ("max", max))},
+           "project_frames_fma": fma, "project_frames_fp64_tflops": 2.0 * fma / (statistics.median(ms["project_frames"]) * 1e-3) / 1e12}
+    g = last["v4_gpu"]
+    rec["gpu_median_vocal"] = {k: float(np.nanmedian(v[0])) for k, v in zip(("SDR", "ISR", "SIR", "SAR"), g)}
+    if not args.no_numpy:
+        t0 = time.perf_counter()
+        c = ev.bss_eval_v4(ref2, est2, window, hop)
+        rec["numpy_s"] = time.perf_counter() - t0
+        rec["nan_frames_equal"] = all(np.array_equal(np.isnan(a), np.isnan(b)) for a, b in zip(g, c))
+        rec["max_abs_diff_db"] = max(float(np.max(np.abs(a - b)[~np.isnan(b)], initial=0.0)) for a, b in zip(g, c))
+        rec["speedup"] = rec["numpy_s"] / (rec["v4_gpu_ms_median"] / 1e3)
     return rec
 
 
@@ -237,6 +307,7 @@ def main():
     ap.add_argument("--ws-budget", type=int, default=ev.WS_BUDGET, help="workspace bytes of one batch of factorisations")
     ap.add_argument("--stereo", action="store_true", help="the image metrics of a stereo track (evaluate.py --stereo)")
     ap.add_argument("--ab-solve", action="store_true", help="the two solve entry points on identical batches (see ab_solve)")
+    ap.add_argument("--v4", action="store_true", help="BSS-eval v4 of the stereo track in 1 s frames (see v4_record)")
     args = ap.parse_args()
     if args.kernel_stats:
         n = args.seconds * args.rates[0]
@@ -250,6 +321,9 @@ def main():
             print(json.dumps(rec), flush=True)
         return
     for rate in args.rates:
+        if args.v4:
+            print(json.dumps(v4_record(args, rate)), flush=True)
+            continue
         if args.stereo:
             print(json.dumps(stereo_record(args, rate)), flush=True)
             continue
