@@ -783,6 +783,36 @@ int svs_loudness_gain(const double* z, int64_t nblocks, const float* peaks, int 
                       const double* target_dev /* nullable */, double ceiling, float* gain_out /* [channels], device */,
                       int channels, double* info /* [4], device */, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Full-band stems (csrc/fullband.hip; the float64 definition is svs_unet_pytorch_amd/fullband.py).  The network runs at 8,192 Hz,
+ * so a stem up-sampled to the file's rate is empty above 4,096 Hz; the reference never leaves the network rate (data.py:151-166
+ * writes at --sr).  With x the file's PCM, y the signal the network was given and U the up-sampling FIR of svs_resample_poly,
+ *   hi_c[i] = x_c[i] - U(y_c)[i],     out_s,c[i] = norm[c] * U(v_s,c)[i] + g_s,c(i) * hi_c[i],     g_vocal = g, g_accompaniment = 1 - g.
+ * svs_fullband_gains: tiles and mask in the standard tile addressing of svs_stft_tiles with first_bin = 1,
+ *     (channel c, row r, frame t) = base[c * chan_stride + ((t / seg) * rows + r) * seg + t % seg];
+ *   gf[c * frames + t] = sum_r mask * mag / sum_r mag over the top rows / 4 rows (r ascending, num = fmaf(mask, mag, num),
+ *   den += mag, one division), for t < frames; where sum_r mag is exactly 0 it is the plain mean of the mask over those rows.
+ *   The padded frames of the last tile are neither read into a result nor written.  Rules, checked before any launch: all sizes
+ *   positive, rows a multiple of 4, n_tiles * seg < 2^31, frames ending in the last tile, chan_stride at least a channel, pointers
+ *   non-null.
+ * svs_fullband_mix: stems: planar fp32, (stem s, channel c) at stems + s*ld_stem + c*ld_in, n_in samples each; nstems 1 or 2 (vocal,
+ *   accompaniment; invert != 0 with nstems 1: the one stem is the accompaniment).  y: channel c at y + c*ld_y, its first n_in
+ *   samples are read.  pcm: the file's frames as it stores them (interleaved, `channels` per frame, SVS_PCM_*, svs_resample_poly's
+ *   conversions), n_pcm frames; x is 0 past them.  table, ntaps, up, down: svs_resample_pack_taps' table of U.  The accumulators of
+ *   every stem row and of y are bitwise the floats svs_resample_poly writes for those rows.  norm: [channels], device.
+ *   gf: svs_fullband_gains' (channels, frames), or NULL for g = 0.  The frame coordinate of output i is i * down / (up * hop):
+ *   quotient k and remainder in 64-bit integers, frac = (float)remainder / (float)(up * hop), k and k + 1 clamped to frames - 1,
+ *   g = fmaf(frac, gf[k+1] - gf[k], gf[k]);  out = fmaf(g_s, x - acc_y, norm * acc_s) with g_accompaniment = 1.0f - g.
+ *   out: planar fp32, (s, c) at out + s*ld_out_stem + c*ld_out, svs_resample_out_len(n_in, up, down) samples each.
+ *   1 <= channels <= 8; 1 <= hop <= 2^20; every leading dimension at least what it strides over.  No atomics, bitwise
+ *   reproducible, 64-bit indices, nothing returns to the host. */
+int svs_fullband_gains(const float* tiles, const float* mask, int64_t chan_stride, int channels, int n_tiles, int rows, int seg,
+                       int frames, float* gf /* (channels, frames) */, hipStream_t stream);
+int svs_fullband_mix(const float* stems, int nstems, int64_t ld_stem, int64_t ld_in, const float* y, int64_t ld_y, int channels,
+                     int64_t n_in, const void* pcm, int pcm_fmt, int64_t n_pcm, const void* table, int ntaps, int up, int down,
+                     const float* norm, const float* gf /* nullable */, int frames, int hop, int invert, float* out, int64_t ld_out,
+                     int64_t ld_out_stem, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

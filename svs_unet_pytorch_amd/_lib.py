@@ -151,6 +151,8 @@ _SIGS = {
     "svs_loudness_workspace_bytes": (Z, [L, I, I]),
     "svs_loudness_blocks": (I, [P, I, I, L, L, L, I, P, P, Z, P]),
     "svs_loudness_gain": (I, [P, L, P, I, D, P, D, P, I, P, P]),
+    "svs_fullband_gains": (I, [P, P, L, I, I, I, I, I, P, P]),
+    "svs_fullband_mix": (I, [P, I, L, L, P, L, I, L, P, I, L, P, I, I, I, P, P, I, I, I, P, L, L, P]),
 }
 
 

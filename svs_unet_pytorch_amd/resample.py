@@ -252,30 +252,57 @@ def encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, rate, f
         raise ValueError(f"frames must be positive, got {frames}")
     width = max(n_out, frames)
     table, ntaps = tap_table(up, down, dev)
-    one, _ = tap_table(1, 1, dev)
     nst = len(stems)
     alloc = torch.zeros if frames > n_out else torch.empty                # the padded frames are silence
     buf = alloc((nst, channels, width), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        for k, stem in enumerate(stems):
+            _lib.check(L.svs_resample_poly(stem.data_ptr(), PCM_F32, 1, 0, n_in, n_in, channels, table.data_ptr(), ntaps, up, down,
+                                           buf[k].data_ptr(), width, _lib.stream_ptr(dev)), "svs_resample_poly")
+    outs, gains, info = encode_planar_gpu(buf, frames, code, dtype, loudness=loudness, ceiling=ceiling, rate=rate)
+    return outs, gains[0], info
+
+
+def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float = 0.9, rate=None, peak: float = 0.9):
+    """Stems that are at the written rate already -- buf: (stems, channels, width) float32, contiguous, the first `frames` of every row
+    being what is written -- measured and encoded 1/1 on existing kernels: svs_resample_peaks per stem, then either the loudness rule
+    (svs_loudness_blocks on the stems' sum, svs_loudness_gain: ONE gain for all stems) or the peak rule (per stem, one common gain
+    peak / its loudest channel's maximum), and svs_resample_encode with the one-tap table and the device gain.
+    Returns (list of PCM tensors (frames, channels), list of gain tensors, info or None), all on the device."""
+    import torch
+    from . import loudness as ld
+    dev = buf.device
+    nst, channels, width = buf.shape
+    frames = int(frames)
+    L = _lib.lib()
+    one, _ = tap_table(1, 1, dev)
     peaks = torch.empty(nst * channels, dtype=torch.float32, device=dev)
     nbytes = int(L.svs_resample_peaks_workspace_bytes(frames, channels, 1, 1, 1))
     if nbytes == 0:
         raise _lib.SvsError(f"svs_resample_peaks_workspace_bytes({frames}, {channels}, 1, 1, 1): invalid arguments")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    outs = [torch.empty((frames, channels), dtype=getattr(torch, np.dtype(dtype).name), device=dev) for _ in stems]
+    outs = [torch.empty((frames, channels), dtype=getattr(torch, np.dtype(dtype).name), device=dev) for _ in range(nst)]
     with torch.cuda.device(dev):
         s = _lib.stream_ptr(dev)
-        for k, stem in enumerate(stems):
-            _lib.check(L.svs_resample_poly(stem.data_ptr(), PCM_F32, 1, 0, n_in, n_in, channels, table.data_ptr(), ntaps, up, down,
-                                           buf[k].data_ptr(), width, s), "svs_resample_poly")
+        for k in range(nst):
             _lib.check(L.svs_resample_peaks(buf[k].data_ptr(), channels, frames, width, one.data_ptr(), 1, 1, 1,
                                             peaks[k * channels:].data_ptr(), ws.data_ptr(), nbytes, s), "svs_resample_peaks")
-        view = buf[:, :, :frames]
-        gain, info = ld.loudness_gain_gpu(view if nst == 2 else view[0], rate, loudness, ceiling=ceiling, stems=nst, peaks=peaks,
-                                          channels=channels)
+        info = None
+        if loudness is not None:
+            view = buf[:, :, :frames]
+            gain, info = ld.loudness_gain_gpu(view if nst == 2 else view[0], rate, loudness, ceiling=ceiling, stems=nst, peaks=peaks,
+                                              channels=channels)
+            gains = [gain] * nst
+        else:                                                              # data.py:162-164 per written file, one gain for its channels
+            gains = [torch.full((channels,), float(peak), dtype=torch.float32, device=dev) for _ in range(nst)]
+            top = torch.empty(nst, dtype=torch.float32, device=dev)
+            for k, gain in enumerate(gains):
+                _lib.check(L.svs_max(peaks[k * channels:].data_ptr(), channels, top[k:].data_ptr(), s), "svs_max")
+                _lib.check(L.svs_scale_by_inv(gain.data_ptr(), channels, top[k:].data_ptr(), 1.0, s), "svs_scale_by_inv")
         for k, out in enumerate(outs):
-            _lib.check(L.svs_resample_encode(buf[k].data_ptr(), channels, frames, width, one.data_ptr(), 1, 1, 1, gain.data_ptr(), code,
+            _lib.check(L.svs_resample_encode(buf[k].data_ptr(), channels, frames, width, one.data_ptr(), 1, 1, 1, gains[k].data_ptr(), code,
                                              out.data_ptr(), s), "svs_resample_encode")
-    return outs, gain, info
+    return outs, gains, info
 
 
 def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | None = 0.9, common_gain: bool = True,

@@ -18,7 +18,8 @@ The stages of separate_waveform, in order, each written once:
 
 separate_spectrogram_device is the tiles / overlap / network / blend part for a magnitude that exists already (inference.py:65-127;
 inference.separate is its host wrapper), and separate_to_wav puts the file's PCM in front of separate_waveform and the fused
-resample + encode (resample.resample_encode_gpu) behind it.  Channels of a stereo signal are separated independently (the reference
+resample + encode (resample.resample_encode_gpu) behind it -- or, with fullband=, fullband.fullband_mix_gpu, which also shares the
+file's band above the network's out between the stems.  Channels of a stereo signal are separated independently (the reference
 itself downmixes to mono with librosa.load(mono=True), data.py:78); only the Wiener filter models both channels together.
 """
 from __future__ import annotations
@@ -28,6 +29,7 @@ import torch
 from . import _lib
 from .config import HOP_SIZE, INPUT_LEN, SAMPLE_RATE, WINDOW_SIZE
 from .data import _scale_rows, istft_from_tiles, istft_stems_from_tiles, read_pcm, stft_to_tiles
+from .fullband import check_fullband
 from .overlap import blend_masks, check_tile_hop, overlap_tiles
 from .rephase import check_phase_iters, refine_phase
 from .wiener import check_wiener_iters, wiener_filter
@@ -100,7 +102,7 @@ def separate_spectrogram_device(model, mag: torch.Tensor, seg_len: int = INPUT_L
 def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
                       peak: float | None = 0.9, max_batch: int = 256, precision: str | None = None, sr_in: int | None = None,
                       sr_out: int | None = None, both_stems: bool = False, tile_hop: int = INPUT_LEN, phase_iters: int = 0,
-                      wiener_iters: int = 0):
+                      wiener_iters: int = 0, aux: dict | None = None):
     """float32 samples (n,) or (channels, n) on the GPU -> separated samples (hop*(T-1),) or (channels, hop*(T-1)), through the
     stages the module docstring lists.  With the defaults that is ONE forward transform, one network forward per `max_batch` tiles,
     ONE inverse transform and the two per-channel normalisations, as the reference computes it.
@@ -117,7 +119,9 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     wiener_iters: N in 1..8 runs the multichannel Wiener filter after the (blended) mask (wiener.wiener_filter), for one or two
     channels: the requested stems are re-filtered from the complex mixture, on ONE scale for both channels, so the stereo balance
     is kept and the two stems add up to the mixture but for the regulariser; one inverse launch per stem.
-    check_refinement's rules are a ValueError before any device work."""
+    check_refinement's rules are a ValueError before any device work.
+    aux: a dict that receives what a post-filter at another rate needs (fullband.py): "y" (the (channels, n) signal at the network rate
+    that was transformed), "tiles", "mask" (the one the stems were made from, in the layout of the tiles), "norm" and "frames"."""
     if tile_hop != INPUT_LEN:
         check_tile_hop(tile_hop, INPUT_LEN)
     phase_iters, wiener_iters = check_refinement(phase_iters, wiener_iters)       # before the waveform or the model is looked at
@@ -135,6 +139,8 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
         mask = blend_masks(_network_masks(model, overlap_tiles(tiles, tile_hop), max_batch, precision), n_tiles, tile_hop)
     else:
         mask = _network_masks(model, tiles.view(C * n_tiles, 1, tiles.shape[3], tiles.shape[4]), max_batch, precision)
+    if aux is not None:
+        aux.update(y=y, tiles=tiles, mask=mask, norm=norm, frames=T)
 
     # the stems: per requested stem what a single-stem inverse takes -- (magnitude tiles, mask, phasors, invert)
     inverts = (False, True) if both_stems else (not vocal_solo,)
@@ -169,6 +175,38 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     return out[0] if squeeze else out
 
 
+def _write_fullband(mode, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, dst_accomp_path, vocal_solo, subtype, keep_length, loudness,
+                    ceiling, report):
+    """separate_to_wav(fullband=mode) from the separated stems on: frame gains, the mix at the file's rate, then frames, gain and
+    encoding on the kernels the default path uses at 1/1."""
+    from scipy.io import wavfile
+
+    from .fullband import frame_gains_gpu, fullband_mix_gpu
+    from .resample import encode_planar_gpu, pcm_format, resample_poly_gpu
+    both = dst_accomp_path is not None
+    stems = (sep if both else sep[None]).contiguous()                 # (S, channels, hop * (T - 1)) at the scale of the tiles
+    T = aux["frames"]
+    gf = frame_gains_gpu(aux["tiles"], aux["mask"], T) if mode == "mask" else None
+    n_source = pcm.shape[0]
+    n_out = int(_lib.lib().svs_resample_out_len(stems.shape[2], fr.denominator, fr.numerator))
+    frames = n_source if keep_length else n_out
+    buf = fullband_mix_gpu(stems, y, pcm, aux["norm"], gf, T, hop, fr.denominator, fr.numerator, invert=not both and not vocal_solo,
+                           width=max(n_out, frames))
+    target = loudness
+    if loudness == "source":
+        from . import loudness as ld
+        target = ld.loudness_gain_gpu(resample_poly_gpu(pcm, 1, 1, channels=channels, downmix=False), int(rate))[1]
+    encs, gains, info = encode_planar_gpu(buf, frames, *pcm_format(subtype), loudness=target, ceiling=ceiling, rate=int(rate))
+    for enc, path in zip(encs, (dst_path, dst_accomp_path)):
+        out = enc.cpu().numpy()
+        wavfile.write(path, int(rate), out[:, 0] if channels == 1 else out)
+    if report is not None:
+        report["gains"] = [float(g[0].item()) for g in gains]
+        if info is not None:
+            report["info"], report["gain"] = info.cpu().tolist(), report["gains"][0]
+    return out.shape
+
+
 def kept_length(n_encoded: int, n_source: int):
     """(frames to keep, zero frames to append) that turn n_encoded written frames into exactly n_source: a separated signal
     is short of its source by less than one hop at the network rate (the inverse STFT returns hop * (T - 1) samples; STFT ->
@@ -192,7 +230,7 @@ def separated_frames(n_source: int, sr: int, hop: int = HOP_SIZE):
 def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = True, precision: str | None = None,
                     subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
                     dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN, phase_iters: int = 0, wiener_iters: int = 0,
-                    loudness=None, ceiling: float = 0.9, report: dict | None = None):
+                    loudness=None, ceiling: float = 0.9, report: dict | None = None, fullband: str | None = None):
     """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
     the PCM is copied as the file stores it (data.read_pcm), resample.resample_poly_gpu (no downmix) brings every channel to
     SAMPLE_RATE, separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
@@ -211,8 +249,18 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     they still add up.  "source": the target is the source file's own loudness, measured on the device at the file's rate.  The
     gain never lifts a sample of any written file above `ceiling`.  The frames are cut or padded (keep_length) before the
     measurement, so what is measured is what is written.  report: a dict that receives "info" (L before the gain, kept blocks,
-    unlimited gain, ceiling-limited) and "gain", read back after the PCM.  Returns the (frames, channels) written (per file)."""
+    unlimited gain, ceiling-limited) and "gain", read back after the PCM.  Returns the (frames, channels) written (per file).
+
+    fullband (None: all of the above, byte for byte): "mask" or "accomp" (fullband.py): the band of the file above the network's
+    4,096 Hz, which the written stems otherwise lack, is shared out between them -- by the network's mask in its highest band, or all of
+    it to the accompaniment -- and every channel is multiplied by its `norm` again, so a stereo file keeps its balance.  One kernel
+    (svs_fullband_mix) up-samples the stems, takes the file's PCM and writes float32 at the file's rate; the frames are then cut or
+    padded, measured and encoded 1/1 (resample.encode_planar_gpu): the peak rule with one common gain per file, or `loudness` with one
+    gain for both files.  With dst_accomp_path the two files, each divided by its gain (report["gains"]), add up to the source.  It
+    composes with tile_hop, precision and phase_iters; wiener_iters beside it is a ValueError before any device work; a file at or
+    below SAMPLE_RATE has no such band, and the flag then changes nothing and says so in a warning."""
     check_refinement(phase_iters, wiener_iters)
+    fullband = check_fullband(fullband, wiener_iters)
     if isinstance(loudness, str) and (loudness != "source" or dst_accomp_path is None):
         raise ValueError(f"loudness={loudness!r}: a number of LUFS, or \"source\" together with dst_accomp_path")
     from fractions import Fraction
@@ -225,12 +273,21 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     dev = model._flat.device
     if separated_frames(n_source, rate, hop) == 0:
         raise ValueError(f"{src_path}: {n_source} frames at {rate} Hz are shorter than one hop ({hop} samples at {SAMPLE_RATE} Hz)")
+    if fullband is not None and int(rate) <= SAMPLE_RATE:
+        import warnings
+        warnings.warn(f"fullband={fullband}: a file at {rate} Hz has no band above the network's {SAMPLE_RATE // 2} Hz; the flag changes nothing")
+        fullband = None
     pcm = torch.from_numpy(data).to(dev)
     fr = Fraction(SAMPLE_RATE, int(rate))
     y = resample_poly_gpu(pcm, fr.numerator, fr.denominator, channels=channels, downmix=False)
     y = y[None] if y.dim() == 1 else y                            # (channels, n) at the network rate
+    aux = None if fullband is None else {}
     sep = separate_waveform(model, y, vocal_solo=vocal_solo, n_fft=n_fft, hop=hop, peak=None, precision=precision,
-                            both_stems=dst_accomp_path is not None, tile_hop=tile_hop, phase_iters=phase_iters, wiener_iters=wiener_iters)
+                            both_stems=dst_accomp_path is not None, tile_hop=tile_hop, phase_iters=phase_iters, wiener_iters=wiener_iters,
+                            aux=aux)
+    if fullband is not None:
+        return _write_fullband(fullband, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, dst_accomp_path, vocal_solo, subtype,
+                               keep_length, loudness, ceiling, report)
     jobs = ((sep, dst_path),) if dst_accomp_path is None else ((sep[0], dst_path), (sep[1], dst_accomp_path))
     if loudness is not None:
         from . import loudness as ld
