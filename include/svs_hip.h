@@ -784,6 +784,51 @@ int svs_loudness_gain(const double* z, int64_t nblocks, const float* peaks, int 
                       int channels, double* info /* [4], device */, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The rest of the EBU R 128 meter: momentary and short-term series, their maxima, the loudness range (EBU Tech 3341 / 3342) and
+ * the true peak (ITU-R BS.1770-4 Annex 2) (csrc/loudness.hip, csrc/r128.hip; the float64 definitions are
+ * svs_unet_pytorch_amd/loudness.py).  The reference normalises every written stem to its sample peak (data.py:162-166): it has
+ * no meter, and a sample peak lies under the peak of the signal the samples stand for (3.01 dB for a sine at fs/4 sampled at
+ * 45 degrees).
+ *   Windows: a window of `bins` 100 ms bins starting at bin j covers [e_j, e_j+bins); svs_loudness_nwindows = the complete ones,
+ *   max(0, floor((10*n + 9)/fs) - (bins - 1)), bins in 1..600; host arithmetic (-1 + error for invalid arguments).  bins = 4 is
+ *   svs_loudness_nblocks; bins = 30 is the short-term window, 3 s at a hop of 100 ms.
+ * svs_loudness_series: the arguments, rules and workspace of svs_loudness_blocks; the K-weighting passes run ONCE and both series
+ *   are summed from the same 100 ms energies, in the order of svs_loudness_blocks (parts, bins, channels ascending):
+ *     z_m[j], j < svs_loudness_nwindows(n, fs, 4), bit for bit svs_loudness_blocks' z;   z_s[j], j < svs_loudness_nwindows(n, fs, 30).
+ *   Either pointer may be NULL (that series is not written); 8-byte aligned.
+ * svs_loudness_stats: one block, all on the device.  With l(v) = -0.691 + 10 log10 v, evaluated as svs_loudness_gain evaluates it:
+ *     stats[0] = max_j l(z_m[j]),  stats[1] = max_j l(z_s[j])   (-inf for an empty series)
+ *     loudness range after Tech 3342: keep l(z_s[j]) > -70; Gamma = l(mean z of those) - 20; keep those above Gamma as well,
+ *     k[0..kept) ascending;  z_lo = k[floor((kept-1)*0.10 + 0.5)],  z_hi = k[floor((kept-1)*0.95 + 0.5)]  (nearest rank)
+ *     stats[2] = LRA = l(z_hi) - l(z_lo),  stats[3] = kept,  stats[4] = l(z_lo),  stats[5] = l(z_hi),  stats[6] = z_lo,  stats[7] = z_hi
+ *     kept = 0: LRA 0, both loudnesses -inf, both z 0.
+ *   The two order statistics are exact selections over the 64-bit patterns of the kept energies (positive doubles order as their
+ *   patterns): 64 counting passes, no sort, no atomics; equal values give the same result whichever is picked.  z_m may be NULL
+ *   with n_m = 0, z_s with n_s = 0; n_s < 2^31; every pointer 8-byte aligned.
+ * svs_loudness_stats_workspace_bytes: bytes of its workspace (0 for invalid n_s).
+ * svs_true_peaks: x holds planar fp32 rows addressed as in svs_loudness_blocks, row s*channels + c at x + s*ld_stem + c*ld_ch, n
+ *   samples each; the stems are NOT added: every row gets its own pair of peaks.  stems and channels in 1..8.  factor: the
+ *   over-sampling factor, 1, 2 or 4; taps: 12*factor + 1 floats on the device, h (loudness.true_peak_taps: a Kaiser-windowed sinc
+ *   whose phase 0 is the sample itself).  With x zero outside [0, n), for p = 1 .. factor-1 and 0 <= i < n
+ *     y[factor*i + p] = sum_{k=0..11} h[p + factor*k] * x[i + 6 - k]     (acc = fmaf(h, x, acc), k ascending, from 0)
+ *     sample_peaks[row] = max_i |x[i]|,    true_peaks[row] = max(sample_peaks[row], max_{i,p} |y[factor*i + p]|)
+ *   Either output may be NULL; factor 1 reads no taps (NULL allowed) and gives true peak = sample peak.  One launch over all rows
+ *   (a block stages 2048 samples and a 6-sample halo each side in LDS from 16-byte loads) and one reduce launch; max is
+ *   order-independent, so the result is bitwise reproducible.  64-bit indices, no atomics, nothing returns to the host.
+ * svs_true_peaks_workspace_bytes: bytes of its workspace for rows = stems * channels (0 for invalid arguments). */
+int64_t svs_loudness_nwindows(int64_t n, int fs, int bins);
+int svs_loudness_series(const float* x, int stems, int channels, int64_t n, int64_t ld_stem, int64_t ld_ch, int fs,
+                        double* z_m /* [nwindows(4)], device, nullable */, double* z_s /* [nwindows(30)], device, nullable */,
+                        void* ws, size_t ws_bytes, hipStream_t stream);
+size_t svs_loudness_stats_workspace_bytes(int64_t n_s);
+int svs_loudness_stats(const double* z_m, int64_t n_m, const double* z_s, int64_t n_s, double* stats /* [8], device */, void* ws,
+                       size_t ws_bytes, hipStream_t stream);
+size_t svs_true_peaks_workspace_bytes(int64_t n, int rows);
+int svs_true_peaks(const float* x, int stems, int channels, int64_t n, int64_t ld_stem, int64_t ld_ch,
+                   const float* taps /* device, 12*factor + 1 */, int factor, float* sample_peaks, float* true_peaks /* [stems*channels] each, nullable */,
+                   void* ws, size_t ws_bytes, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Full-band stems (csrc/fullband.hip; the float64 definition is svs_unet_pytorch_amd/fullband.py).  The network runs at 8,192 Hz,
  * so a stem up-sampled to the file's rate is empty above 4,096 Hz; the reference never leaves the network rate (data.py:151-166
  * writes at --sr).  With x the file's PCM, y the signal the network was given and U the up-sampling FIR of svs_resample_poly,

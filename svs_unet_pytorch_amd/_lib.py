@@ -151,6 +151,12 @@ _SIGS = {
     "svs_loudness_workspace_bytes": (Z, [L, I, I]),
     "svs_loudness_blocks": (I, [P, I, I, L, L, L, I, P, P, Z, P]),
     "svs_loudness_gain": (I, [P, L, P, I, D, P, D, P, I, P, P]),
+    "svs_loudness_nwindows": (L, [L, I, I]),
+    "svs_loudness_series": (I, [P, I, I, L, L, L, I, P, P, P, Z, P]),
+    "svs_loudness_stats_workspace_bytes": (Z, [L]),
+    "svs_loudness_stats": (I, [P, L, P, L, P, P, Z, P]),
+    "svs_true_peaks_workspace_bytes": (Z, [L, I]),
+    "svs_true_peaks": (I, [P, I, I, L, L, L, P, I, P, P, P, Z, P]),
     "svs_fullband_gains": (I, [P, P, L, I, I, I, I, I, P, P]),
     "svs_fullband_mix": (I, [P, I, L, L, P, L, I, L, P, I, L, P, I, I, I, P, P, I, I, I, P, L, L, P]),
 }

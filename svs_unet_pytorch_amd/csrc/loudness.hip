@@ -14,7 +14,7 @@
 //             run of segments, a Kogge-Stone scan over the lanes composes the runs, every lane walks its run again from its true
 //             state.  Segment lengths take two values, floor and ceil of a bin over P, so two matrices serve.
 // The matrix powers are host arithmetic (repeated squaring in double) and travel as kernel arguments.  Every sum -- the block
-// reduction of y^2, the parts of a bin, the four bins of a block, the channels -- is taken in one fixed order: no atomics, and two
+// reduction of y^2, the parts of a bin, the bins of a window (4 of a block, 30 of a short-term window), the channels -- is taken in one fixed order: no atomics, and two
 // calls on the same input give the same bits.  Indices into the signal are 64-bit.
 #include <cmath>
 
@@ -350,37 +350,57 @@ __global__ __launch_bounds__(LD_THREADS) void loud_scan_kernel(const double* __r
   }
 }
 
-// z[j] = sum_c (energy of bins j .. j + 3 of channel c) / (e_j+4 - e_j): parts, bins and channels in ascending order
-__global__ __launch_bounds__(256) void loud_blocks_kernel(const double* __restrict__ energy, long nseg, int P, long fs, int channels, long nblocks,
-                                                          double* __restrict__ z) {
+// z[j] = sum_c (energy of bins j .. j + w - 1 of channel c) / (e_j+w - e_j): parts, bins and channels in ascending order.  w = 4 is
+// the 400 ms block of the integrated and momentary loudness, w = 30 the 3 s window of the short-term loudness (EBU Tech 3341 / 3342).
+__global__ __launch_bounds__(256) void loud_blocks_kernel(const double* __restrict__ energy, long nseg, int P, long fs, int channels, long nwin,
+                                                          int w, double* __restrict__ z) {
   const long j = (long)blockIdx.x * 256 + threadIdx.x;
-  if (j >= nblocks) return;
-  const double count = (double)((j + 4) * fs / 10 - j * fs / 10);
+  if (j >= nwin) return;
+  const double count = (double)((j + w) * fs / 10 - j * fs / 10);
   double sum = 0.0;
   for (int c = 0; c < channels; ++c) {
     double e = 0.0;
-    for (long s = j * P; s < (j + 4) * P; ++s) e += energy[(long)c * nseg + s];
+    for (long s = j * P; s < (j + w) * P; ++s) e += energy[(long)c * nseg + s];
     sum += e / count;
   }
   z[j] = sum;
 }
 
-extern "C" int svs_loudness_blocks(const float* x, int stems, int channels, int64_t n, int64_t ld_stem, int64_t ld_ch, int fs, double* z,
-                                   void* ws, size_t ws_bytes, hipStream_t stream) {
-  SVS_REQUIRE(stems == 1 || stems == 2, "svs_loudness_blocks: stems must be 1 or 2, got %d", stems);
-  SVS_REQUIRE(channels >= 1 && channels <= LD_MAX_CH, "svs_loudness_blocks: channels must be in 1..%d, got %d", LD_MAX_CH, channels);
-  SVS_REQUIRE(loud_fs_ok(fs), "svs_loudness_blocks: fs must be in %d..%d, got %d", LD_FS_MIN, LD_FS_MAX, fs);
+#define LD_BINS_M 4          // 400 ms
+#define LD_BINS_S 30         // 3 s
+#define LD_BINS_MAX 600
+
+extern "C" int64_t svs_loudness_nwindows(int64_t n, int fs, int bins) {
+  if (n < 0 || !loud_fs_ok(fs) || n > (INT64_MAX / 16) || bins < 1 || bins > LD_BINS_MAX) {
+    svs_set_error("svs_loudness_nwindows: n must not be negative, fs must be in %d..%d and bins in 1..%d, got n=%lld fs=%d bins=%d", LD_FS_MIN,
+                  LD_FS_MAX, LD_BINS_MAX, (long long)n, fs, bins);
+    return -1;
+  }
+  const int64_t k = (10 * n + 9) / fs;                            // the largest k with e_k <= n
+  return k > bins - 1 ? k - (bins - 1) : 0;
+}
+
+// The body of svs_loudness_blocks and svs_loudness_series: the argument rules under the caller's name, passes A, scan and B once, then
+// the window sums that were asked for.  need_zm: svs_loudness_blocks' rule that z is given.
+static int loud_run(const char* who, const float* x, int stems, int channels, int64_t n, int64_t ld_stem, int64_t ld_ch, int fs, double* z_m,
+                    double* z_s, bool need_zm, void* ws, size_t ws_bytes, hipStream_t stream) {
+  SVS_REQUIRE(stems == 1 || stems == 2, "%s: stems must be 1 or 2, got %d", who, stems);
+  SVS_REQUIRE(channels >= 1 && channels <= LD_MAX_CH, "%s: channels must be in 1..%d, got %d", who, LD_MAX_CH, channels);
+  SVS_REQUIRE(loud_fs_ok(fs), "%s: fs must be in %d..%d, got %d", who, LD_FS_MIN, LD_FS_MAX, fs);
   LoudPlan p{};
-  SVS_REQUIRE(n >= 0 && loud_plan(n, fs, &p), "svs_loudness_blocks: n must not be negative, got %lld", (long long)n);
-  SVS_REQUIRE(ld_ch >= n, "svs_loudness_blocks: ld_ch must be at least n = %lld, got %lld", (long long)n, (long long)ld_ch);
-  SVS_REQUIRE(p.nseg < (1L << 31), "svs_loudness_blocks: %lld segments do not fit a grid", (long long)p.nseg);
+  SVS_REQUIRE(n >= 0 && loud_plan(n, fs, &p), "%s: n must not be negative, got %lld", who, (long long)n);
+  SVS_REQUIRE(ld_ch >= n, "%s: ld_ch must be at least n = %lld, got %lld", who, (long long)n, (long long)ld_ch);
+  SVS_REQUIRE(p.nseg < (1L << 31), "%s: %lld segments do not fit a grid", who, (long long)p.nseg);
   if (p.nblocks == 0) return SVS_OK;                              // under 400 ms: nothing to write
-  SVS_REQUIRE(x && z, "svs_loudness_blocks: null pointer");
-  SVS_REQUIRE((((uintptr_t)z) & 7u) == 0 && (((uintptr_t)ws) & 7u) == 0, "svs_loudness_blocks: z and the workspace must be 8-byte aligned");
+  SVS_REQUIRE(x && (z_m || !need_zm), "%s: null pointer", who);
+  SVS_REQUIRE((((uintptr_t)z_m) & 7u) == 0 && (((uintptr_t)z_s) & 7u) == 0 && (((uintptr_t)ws) & 7u) == 0,
+              "%s: z and the workspace must be 8-byte aligned", who);
   if (!ws || ws_bytes < loud_ws_bytes(p, channels)) {
-    svs_set_error("svs_loudness_blocks: workspace too small (%zu bytes, need %zu)", ws_bytes, loud_ws_bytes(p, channels));
+    svs_set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws_bytes, loud_ws_bytes(p, channels));
     return SVS_ERR_WORKSPACE;
   }
+  const long nwin_s = p.nbins > LD_BINS_S - 1 ? (long)(p.nbins - (LD_BINS_S - 1)) : 0;
+  if (!z_m && (!z_s || nwin_s == 0)) return SVS_OK;               // nothing was asked for
   LoudTab tab;
   loud_tab(fs, p, &tab);
   const size_t per = (size_t)channels * (size_t)p.nseg;
@@ -407,10 +427,27 @@ extern "C" int svs_loudness_blocks(const float* x, int stems, int channels, int6
                        p.Lc, tab, (const double*)starts, energy);
   }
   SVS_CHECK_LAUNCH("loudness pass B");
-  hipLaunchKernelGGL(loud_blocks_kernel, dim3((unsigned)svs_cdiv(p.nblocks, 256)), dim3(256), 0, stream, (const double*)energy, (long)p.nseg, p.P,
-                     (long)fs, channels, (long)p.nblocks, z);
-  SVS_CHECK_LAUNCH("loudness blocks");
+  if (z_m) {
+    hipLaunchKernelGGL(loud_blocks_kernel, dim3((unsigned)svs_cdiv(p.nblocks, 256)), dim3(256), 0, stream, (const double*)energy, (long)p.nseg, p.P,
+                       (long)fs, channels, (long)p.nblocks, LD_BINS_M, z_m);
+    SVS_CHECK_LAUNCH("loudness blocks");
+  }
+  if (z_s && nwin_s > 0) {
+    hipLaunchKernelGGL(loud_blocks_kernel, dim3((unsigned)svs_cdiv(nwin_s, 256)), dim3(256), 0, stream, (const double*)energy, (long)p.nseg, p.P,
+                       (long)fs, channels, nwin_s, LD_BINS_S, z_s);
+    SVS_CHECK_LAUNCH("loudness short-term windows");
+  }
   return SVS_OK;
+}
+
+extern "C" int svs_loudness_blocks(const float* x, int stems, int channels, int64_t n, int64_t ld_stem, int64_t ld_ch, int fs, double* z,
+                                   void* ws, size_t ws_bytes, hipStream_t stream) {
+  return loud_run("svs_loudness_blocks", x, stems, channels, n, ld_stem, ld_ch, fs, z, nullptr, true, ws, ws_bytes, stream);
+}
+
+extern "C" int svs_loudness_series(const float* x, int stems, int channels, int64_t n, int64_t ld_stem, int64_t ld_ch, int fs, double* z_m,
+                                   double* z_s, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return loud_run("svs_loudness_series", x, stems, channels, n, ld_stem, ld_ch, fs, z_m, z_s, false, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

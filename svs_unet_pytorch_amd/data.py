@@ -242,22 +242,28 @@ def write_wav(path: str, y: np.ndarray, sr: int):
 
 
 def save_wav_device(path: str, y_dev: torch.Tensor, sr: int, sr_out: int | None = None, subtype: str = "PCM_16", peak: float | None = 0.9,
-                    loudness: float | None = None, ceiling: float = 0.9):
+                    loudness: float | None = None, ceiling: float = 0.9, true_peak: bool = False):
     """float32 device samples (n,) or (channels, n) at rate `sr` -> a wav file at `sr_out` (default: sr) with the samples of
     `subtype` ("PCM_16", the reference's sf.write format for a .wav name, "PCM_32" or "FLOAT"), peak-normalised to `peak` at
     the rate that is written (data.py:162-166; None: not normalised; one gain for all channels).  Resampling, gain, sample
     conversion and interleaving are resample.resample_encode_gpu; one device -> host copy of the encoded samples follows.
     loudness (LUFS) replaces the peak rule: the file is brought to that integrated loudness (loudness.py), no sample above
-    `ceiling`; the four numbers of the measurement are returned (None without loudness)."""
+    `ceiling`; the four numbers of the measurement are returned (None without loudness).  true_peak: `ceiling` (or `peak`, which
+    must then be given) bounds the file's true peak, the over-sampled signal's (loudness.py), instead of its largest sample."""
     from scipy.io import wavfile
     from .resample import resample_encode_gpu
     sr_out = int(sr if sr_out is None else sr_out)
     fr = Fraction(sr_out, int(sr))
     if loudness is not None:
         pcm, info = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=subtype, loudness=loudness,
-                                        ceiling=ceiling, rate=sr_out)
+                                        ceiling=ceiling, rate=sr_out, true_peak=true_peak)
         wavfile.write(path, sr_out, pcm.cpu().numpy())
         return info.cpu().tolist()
+    if true_peak:
+        pcm = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=subtype, peak=peak, common_gain=True,
+                                  rate=sr_out, true_peak=True)
+        wavfile.write(path, sr_out, pcm.cpu().numpy())
+        return None
     pcm = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=subtype, peak=peak, common_gain=True)
     wavfile.write(path, sr_out, pcm.cpu().numpy())
 
@@ -324,13 +330,15 @@ def to_wave(args, device):
             sr_out = getattr(args, "sr_out", None) or args.sr
             subtype = getattr(args, "subtype", "FLOAT")
             loudness = getattr(args, "loudness", None)
-            encode = sr_out != args.sr or subtype != "FLOAT" or loudness is not None   # else: float32 at --sr, written as it always was
+            true_peak = bool(getattr(args, "true_peak", False))
+            encode = sr_out != args.sr or subtype != "FLOAT" or loudness is not None or true_peak   # else: float32 at --sr, written as it always was
             y = istft(torch.from_numpy(np.ascontiguousarray(mag[:, :m])).to(device),
                       torch.from_numpy(np.ascontiguousarray(phase[:, :m]).astype(np.complex64)).to(device),
                       args.win_size, args.hop_size, peak=None if encode else 0.9)
             wav_path = os.path.join(args.tar, spec_name.replace("_spec.npy", ".wav"))
             if encode:
-                save_wav_device(wav_path, y, args.sr, sr_out, subtype, peak=0.9, loudness=loudness, ceiling=getattr(args, "peak_ceiling", 0.9))
+                save_wav_device(wav_path, y, args.sr, sr_out, subtype, peak=0.9, loudness=loudness, ceiling=getattr(args, "peak_ceiling", 0.9),
+                                true_peak=true_peak)
             else:
                 write_wav(wav_path, y.cpu().numpy(), args.sr)
         except Exception as e:                                          # data.py:168-169
@@ -354,6 +362,8 @@ def main(argv=None):
     parser.add_argument("--loudness", type=float, default=None,
                         help="to_wave: integrated loudness of the written files in LUFS (ITU-R BS.1770-4) instead of peak 0.9")
     parser.add_argument("--peak_ceiling", type=float, default=0.9, help="to_wave with --loudness: no written sample exceeds this")
+    parser.add_argument("--true_peak", action="store_true",
+                        help="to_wave: bound the written files' true peak (the over-sampled signal's) instead of their largest sample")
     args = parser.parse_args(argv)
     if args.sr_out is not None and args.sr_out < 1:
         parser.error(f"--sr_out {args.sr_out}: must be positive")

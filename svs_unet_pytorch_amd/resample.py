@@ -235,10 +235,12 @@ def resample_peaks_gpu(y, up: int, down: int):
     return peaks
 
 
-def encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, rate, frames):
+def encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, rate, frames, true_peak: bool = False, peaks_out=None,
+                        peak: float = 0.9):
     """resample_encode_gpu(loudness=): the stems (each (channels, n_in), float32, contiguous) are resampled into one float32 buffer
     by svs_resample_poly -- bit for bit the float the fused encoder forms -- cut or zero-padded to `frames`, measured there
     (svs_loudness_blocks on their sum, svs_resample_peaks per stem, svs_loudness_gain) and encoded 1/1 with the device gain.
+    loudness None (with true_peak): the peak rule of encode_planar_gpu with `peak`.  true_peak, peaks_out: as encode_planar_gpu takes them.
     Returns (list of PCM tensors, gain, info), all on the device."""
     import torch
     from . import loudness as ld
@@ -259,15 +261,21 @@ def encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, rate, f
         for k, stem in enumerate(stems):
             _lib.check(L.svs_resample_poly(stem.data_ptr(), PCM_F32, 1, 0, n_in, n_in, channels, table.data_ptr(), ntaps, up, down,
                                            buf[k].data_ptr(), width, _lib.stream_ptr(dev)), "svs_resample_poly")
-    outs, gains, info = encode_planar_gpu(buf, frames, code, dtype, loudness=loudness, ceiling=ceiling, rate=rate)
+    outs, gains, info = encode_planar_gpu(buf, frames, code, dtype, loudness=loudness, ceiling=ceiling, rate=rate, true_peak=true_peak,
+                                          peaks_out=peaks_out, peak=peak)
     return outs, gains[0], info
 
 
-def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float = 0.9, rate=None, peak: float = 0.9):
+def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float = 0.9, rate=None, peak: float = 0.9, true_peak: bool = False,
+                      peaks_out=None):
     """Stems that are at the written rate already -- buf: (stems, channels, width) float32, contiguous, the first `frames` of every row
     being what is written -- measured and encoded 1/1 on existing kernels: svs_resample_peaks per stem, then either the loudness rule
     (svs_loudness_blocks on the stems' sum, svs_loudness_gain: ONE gain for all stems) or the peak rule (per stem, one common gain
     peak / its loudest channel's maximum), and svs_resample_encode with the one-tap table and the device gain.
+    true_peak (needs rate): the maxima that the ceiling, or the peak rule, is held against are the TRUE peaks of the rows at `rate`
+    (loudness.py; svs_true_peaks, one launch over all rows in place of the svs_resample_peaks launches), so that no inter-sample
+    peak of a written file exceeds `ceiling` (or `peak`); the gain rules themselves are unchanged.  peaks_out: a dict that receives
+    "sample_peaks" and "true_peaks", float32 device tensors (stems * channels,) of the rows before the gain, and "gains".
     Returns (list of PCM tensors (frames, channels), list of gain tensors, info or None), all on the device."""
     import torch
     from . import loudness as ld
@@ -276,15 +284,23 @@ def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float
     frames = int(frames)
     L = _lib.lib()
     one, _ = tap_table(1, 1, dev)
-    peaks = torch.empty(nst * channels, dtype=torch.float32, device=dev)
-    nbytes = int(L.svs_resample_peaks_workspace_bytes(frames, channels, 1, 1, 1))
-    if nbytes == 0:
-        raise _lib.SvsError(f"svs_resample_peaks_workspace_bytes({frames}, {channels}, 1, 1, 1): invalid arguments")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if true_peak:
+        if rate is None:
+            raise ValueError("true_peak= needs rate=, the sample rate that is written")
+        sample_peaks, peaks = ld.true_peaks_rows_gpu(buf.data_ptr(), nst, channels, frames, channels * width, width, ld.true_peak_factor(rate),
+                                                     dev, sample=peaks_out is not None)
+        if peaks_out is not None:
+            peaks_out["sample_peaks"], peaks_out["true_peaks"] = sample_peaks, peaks
+    else:
+        peaks = torch.empty(nst * channels, dtype=torch.float32, device=dev)
+        nbytes = int(L.svs_resample_peaks_workspace_bytes(frames, channels, 1, 1, 1))
+        if nbytes == 0:
+            raise _lib.SvsError(f"svs_resample_peaks_workspace_bytes({frames}, {channels}, 1, 1, 1): invalid arguments")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     outs = [torch.empty((frames, channels), dtype=getattr(torch, np.dtype(dtype).name), device=dev) for _ in range(nst)]
     with torch.cuda.device(dev):
         s = _lib.stream_ptr(dev)
-        for k in range(nst):
+        for k in range(0 if true_peak else nst):
             _lib.check(L.svs_resample_peaks(buf[k].data_ptr(), channels, frames, width, one.data_ptr(), 1, 1, 1,
                                             peaks[k * channels:].data_ptr(), ws.data_ptr(), nbytes, s), "svs_resample_peaks")
         info = None
@@ -302,11 +318,14 @@ def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float
         for k, out in enumerate(outs):
             _lib.check(L.svs_resample_encode(buf[k].data_ptr(), channels, frames, width, one.data_ptr(), 1, 1, 1, gains[k].data_ptr(), code,
                                              out.data_ptr(), s), "svs_resample_encode")
+    if true_peak and peaks_out is not None:
+        peaks_out["gains"] = gains
     return outs, gains, info
 
 
 def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | None = 0.9, common_gain: bool = True,
-                        loudness=None, ceiling: float = 0.9, together=None, rate: int | None = None, frames: int | None = None):
+                        loudness=None, ceiling: float = 0.9, together=None, rate: int | None = None, frames: int | None = None,
+                        true_peak: bool = False):
     """float32 device tensor (n,) or (channels, n), planar -> device tensor (n_out,) or (n_out, channels) of int16 / int32 /
     float32 at rate * up / down, interleaved as a wav file stores it (svs_resample_encode; the rules: encode_pcm_reference).
     peak=None: the samples are encoded as they are.  Otherwise they are scaled by peak / max |resampled signal| on the way
@@ -323,10 +342,19 @@ def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | Non
     stem of y's shape that is written with it; L is then the loudness of the two stems' sum, peak the larger of theirs, and both
     get the same gain, so their balance is kept.  frames: cut or zero-pad to this many frames before measuring, so that what is
     measured is what is written.  Returns (pcm, info) or, with together, (pcm, pcm of together, info); info: 4 device doubles
-    (L before the gain, kept blocks, unlimited gain, 1 when the ceiling limited it).  peak and common_gain are not read."""
+    (L before the gain, kept blocks, unlimited gain, 1 when the ceiling limited it).  peak and common_gain are not read.
+
+    true_peak (needs rate): the ceiling of the loudness rule is held against the true peaks at `rate` (loudness.py: the 4x / 2x
+    over-sampled signal) instead of the sample peaks.  Without loudness the signal goes by the planar buffer (svs_resample_poly to
+    float32, then encode_planar_gpu's peak rule with one common gain against the true peaks): peak must be given and common_gain
+    True; the return value is the PCM alone."""
     import torch
     if loudness is None and (together is not None or frames is not None):
         raise ValueError("together= and frames= belong to loudness=")
+    if true_peak and rate is None:
+        raise ValueError("true_peak= needs rate=, the sample rate that is written")
+    if true_peak and loudness is None and (peak is None or not common_gain):
+        raise ValueError("true_peak= without loudness= is the peak rule with one common gain: peak= must be given and common_gain True")
     if not y.is_cuda:
         raise ValueError("resample_encode_gpu needs a device tensor (there is no CPU path)")
     if y.dtype != torch.float32:
@@ -347,9 +375,12 @@ def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | Non
             if not t.is_cuda or t.dtype != torch.float32 or t.shape != y.shape:
                 raise ValueError(f"together must be a float32 device tensor of the same shape, got {tuple(together.shape)}")
             stems.append(t)
-        outs, _, info = encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, int(rate), frames)
+        outs, _, info = encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, int(rate), frames, true_peak)
         outs = [o[:, 0] if squeeze else o for o in outs]
         return (*outs, info)
+    if true_peak:
+        outs, _, _ = encode_loudness_gpu([y], up, down, code, dtype, None, ceiling, int(rate), None, True, peak=float(peak))
+        return outs[0][:, 0] if squeeze else outs[0]
     L = _lib.lib()
     n_out = int(L.svs_resample_out_len(n_in, up, down))
     table, ntaps = tap_table(up, down, y.device)

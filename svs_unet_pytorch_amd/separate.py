@@ -8,7 +8,7 @@ evaluate.py accepts it beside the source's stems.
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src wav_folder --tar out_folder \
         [--vocal_solo 0|1] [--precision bf16] [--subtype PCM_16|PCM_32|FLOAT] [--no_keep_length] \
         [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder] [--tile_hop 128|64|32] [--phase_iters N]
-        [--wiener_iters N] [--loudness LUFS|source] [--peak_ceiling 0.9] [--fullband mask|accomp]
+        [--wiener_iters N] [--loudness LUFS|source] [--peak_ceiling 0.9] [--true_peak] [--fullband mask|accomp]
 
 A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
 default) is what the reference's data.py writes (data.py:166).  --win_size / --hop_size (the config's 1024 / 768 by default;
@@ -27,7 +27,10 @@ stereo balance kept, and with --tar_accomp two files that add up to the mixture.
 peak-normalised to 0.9 on its own, data.py:162-166) brings the written audio to that integrated loudness instead (ITU-R BS.1770-4,
 loudness.py; measured on the device on the samples that are written): one file to the target, or, with --tar_accomp, vocal +
 accompaniment to the target with one gain for both files, so that their balance is kept; --loudness source (with --tar_accomp only)
-aims at the source file's own loudness.  --peak_ceiling (0.9) bounds every written sample under that gain.  --fullband (off by
+aims at the source file's own loudness.  --peak_ceiling (0.9) bounds every written sample under that gain.  --true_peak (off
+by default) holds that ceiling, or without --loudness the 0.9 of the peak rule, against the TRUE peak of every written file -- the peak
+of the 4x over-sampled signal (ITU-R BS.1770-4 Annex 2; loudness.py, csrc/r128.hip) -- instead of its largest sample: up-sampling
+to the file's rate produces inter-sample peaks that a sample-peak bound lets through.  --fullband (off by
 default: the network runs at 8,192 Hz, so every written stem is empty above 4,096 Hz) shares the file's band above 4,096 Hz out
 between the stems (fullband.py): `mask` by the network's own mask in its highest band, frame by frame; `accomp` all of it to the
 accompaniment (the vocal stays band-limited).  With --tar_accomp the two files, each divided by its gain, then add up to the source, and
@@ -74,6 +77,9 @@ def main(argv=None):
                         help="integrated loudness of what is written, in LUFS (for instance -23), instead of peak 0.9 per file; with --tar_accomp "
                              "one gain for both files; `source` (with --tar_accomp only): the source file's own loudness")
     parser.add_argument("--peak_ceiling", type=float, default=0.9, help="with --loudness: no written sample exceeds this (default 0.9)")
+    parser.add_argument("--true_peak", action="store_true",
+                        help="bound the true peak (the over-sampled signal's) of every written file instead of its largest sample: "
+                             "--peak_ceiling under --loudness, 0.9 otherwise")
     parser.add_argument("--fullband", default=None, choices=list(MODES),
                         help="share the file's band above the network's 4,096 Hz out between the stems: mask = by the network's mask in its "
                              "highest band; accomp = all of it to the accompaniment (default: band-limited stems; not with --wiener_iters)")
@@ -130,9 +136,11 @@ def main(argv=None):
                                            subtype=args.subtype, keep_length=not args.no_keep_length, n_fft=args.win_size,
                                            hop=args.hop_size, dst_accomp_path=dst_accomp, tile_hop=args.tile_hop,
                                            phase_iters=args.phase_iters, wiener_iters=args.wiener_iters, loudness=args.loudness,
-                                           ceiling=args.peak_ceiling, report=report, fullband=args.fullband)
+                                           ceiling=args.peak_ceiling, report=report, fullband=args.fullband,
+                                           true_peak=args.true_peak)
         print(f"{dst}: {frames} frames x {channels}" + ("" if dst_accomp is None else f"; {dst_accomp}: the same")
-              + (f"; {describe(report['info'], report['gain'])}" if "info" in report else ""))
+              + (f"; {describe(report['info'], report['gain'], args.true_peak)}" if "info" in report else "")
+              + (f"; true peak {max(max(row) for row in report['true_peaks']):.2f} dBTP" if "true_peaks" in report else ""))
     print("Separation finished!")
 
 

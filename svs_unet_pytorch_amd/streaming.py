@@ -175,8 +175,19 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     return out[0] if squeeze else out
 
 
+def _report_peaks(report, measured):
+    """report["sample_peaks"], report["true_peaks"]: per written file and channel in dBFS, from encode_planar_gpu's peaks_out (the
+    rows before the gain, and the gains); one read-back, after the PCM."""
+    if report is None or "true_peaks" not in measured:
+        return
+    gains = torch.stack(measured["gains"])                             # (files, channels)
+    both = torch.stack([measured["sample_peaks"].view_as(gains), measured["true_peaks"].view_as(gains)]) * gains
+    db = (20.0 * torch.log10(both.double())).cpu().tolist()            # a silent channel reads -inf
+    report["sample_peaks"], report["true_peaks"] = db
+
+
 def _write_fullband(mode, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, dst_accomp_path, vocal_solo, subtype, keep_length, loudness,
-                    ceiling, report):
+                    ceiling, report, true_peak=False):
     """separate_to_wav(fullband=mode) from the separated stems on: frame gains, the mix at the file's rate, then frames, gain and
     encoding on the kernels the default path uses at 1/1."""
     from scipy.io import wavfile
@@ -196,7 +207,9 @@ def _write_fullband(mode, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, d
     if loudness == "source":
         from . import loudness as ld
         target = ld.loudness_gain_gpu(resample_poly_gpu(pcm, 1, 1, channels=channels, downmix=False), int(rate))[1]
-    encs, gains, info = encode_planar_gpu(buf, frames, *pcm_format(subtype), loudness=target, ceiling=ceiling, rate=int(rate))
+    measured = {}
+    encs, gains, info = encode_planar_gpu(buf, frames, *pcm_format(subtype), loudness=target, ceiling=ceiling, rate=int(rate), true_peak=true_peak,
+                                          peaks_out=measured if true_peak and report is not None else None)
     for enc, path in zip(encs, (dst_path, dst_accomp_path)):
         out = enc.cpu().numpy()
         wavfile.write(path, int(rate), out[:, 0] if channels == 1 else out)
@@ -204,6 +217,7 @@ def _write_fullband(mode, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, d
         report["gains"] = [float(g[0].item()) for g in gains]
         if info is not None:
             report["info"], report["gain"] = info.cpu().tolist(), report["gains"][0]
+        _report_peaks(report, measured)
     return out.shape
 
 
@@ -230,7 +244,7 @@ def separated_frames(n_source: int, sr: int, hop: int = HOP_SIZE):
 def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = True, precision: str | None = None,
                     subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
                     dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN, phase_iters: int = 0, wiener_iters: int = 0,
-                    loudness=None, ceiling: float = 0.9, report: dict | None = None, fullband: str | None = None):
+                    loudness=None, ceiling: float = 0.9, report: dict | None = None, fullband: str | None = None, true_peak: bool = False):
     """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
     the PCM is copied as the file stores it (data.read_pcm), resample.resample_poly_gpu (no downmix) brings every channel to
     SAMPLE_RATE, separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
@@ -258,7 +272,13 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     padded, measured and encoded 1/1 (resample.encode_planar_gpu): the peak rule with one common gain per file, or `loudness` with one
     gain for both files.  With dst_accomp_path the two files, each divided by its gain (report["gains"]), add up to the source.  It
     composes with tile_hop, precision and phase_iters; wiener_iters beside it is a ValueError before any device work; a file at or
-    below SAMPLE_RATE has no such band, and the flag then changes nothing and says so in a warning."""
+    below SAMPLE_RATE has no such band, and the flag then changes nothing and says so in a warning.
+
+    true_peak (False: all of the above, byte for byte): `ceiling`, or without loudness the 0.9 of the peak rule, bounds the TRUE peak
+    of every written file -- the peak of the 4x (2x from 96 kHz) over-sampled signal, loudness.py -- instead of its largest sample; the
+    up-sampling on the way out produces inter-sample peaks that a sample-peak bound lets through.  One launch (svs_true_peaks)
+    measures all written rows in place of the sample-peak launches; without loudness the frames are cut or padded before the
+    measurement as well.  report then also receives "true_peaks" and "sample_peaks", per file and channel in dBFS of what was written."""
     check_refinement(phase_iters, wiener_iters)
     fullband = check_fullband(fullband, wiener_iters)
     if isinstance(loudness, str) and (loudness != "source" or dst_accomp_path is None):
@@ -287,22 +307,25 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
                             aux=aux)
     if fullband is not None:
         return _write_fullband(fullband, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, dst_accomp_path, vocal_solo, subtype,
-                               keep_length, loudness, ceiling, report)
+                               keep_length, loudness, ceiling, report, true_peak)
     jobs = ((sep, dst_path),) if dst_accomp_path is None else ((sep[0], dst_path), (sep[1], dst_accomp_path))
-    if loudness is not None:
+    if loudness is not None or true_peak:
         from . import loudness as ld
         from .resample import encode_loudness_gpu, pcm_format
         target = loudness
         if loudness == "source":                                   # info[0] of a measurement of the file itself; it stays on the device
             target = ld.loudness_gain_gpu(resample_poly_gpu(pcm, 1, 1, channels=channels, downmix=False), int(rate))[1]
         frames = n_source if keep_length else None
+        measured = {}
         encs, gain, info = encode_loudness_gpu([stem.contiguous() for stem, _ in jobs], fr.denominator, fr.numerator, *pcm_format(subtype),
-                                               target, ceiling, int(rate), frames)
+                                               target, ceiling, int(rate), frames, true_peak,
+                                               measured if true_peak and report is not None else None)
         for enc, (_, path) in zip(encs, jobs):
             out = enc.cpu().numpy()
             wavfile.write(path, int(rate), out[:, 0] if channels == 1 else out)
-        if report is not None:
+        if report is not None and info is not None:
             report["info"], report["gain"] = info.cpu().tolist(), float(gain[0].item())
+        _report_peaks(report, measured)
         return out.shape
     for stem, path in jobs:
         enc = resample_encode_gpu(stem, fr.denominator, fr.numerator, fmt=subtype, peak=0.9, common_gain=True)
