@@ -858,6 +858,36 @@ int svs_fullband_mix(const float* stems, int nstems, int64_t ld_stem, int64_t ld
                      const float* norm, const float* gf /* nullable */, int frames, int hop, int invert, float* out, int64_t ld_out,
                      int64_t ld_out_stem, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * 24-bit PCM in and out, and TPDF dither for the written stems (csrc/pcm.hip; the float64 / integer definitions are
+ * svs_unet_pytorch_amd/pcm.py).  replaces: nothing in the reference -- it writes 16-bit through libsndfile, data.py:166.
+ * SVS_PCM_* gets no code for 24 bits: the way in widens to SVS_PCM_I32, the way out is an encoder of its own.
+ * svs_pcm24_widen: packed: n_samples little-endian two's-complement 3-byte samples as a wav data chunk stores them (interleaved or
+ *   not); out[e] = (int32)(b0 << 8 | b1 << 16 | b2 << 24), the left-justified word with a zero low byte: what SVS_PCM_I32 takes for
+ *   a 24-bit file, so svs_resample_poly and svs_fullband_mix read it unchanged.  Rules, checked before any launch: pointers
+ *   non-null, n_samples >= 1, packed 4-byte aligned, out 16-byte aligned.  A thread takes 4 samples (3 dwords in, one 16-byte
+ *   store out), the last n_samples % 4 go by bytes.
+ * svs_pcm_encode_dither: x: planar fp32 rows at the written rate, channel c at x + c*ld_in, `frames` samples each, 1 <= channels
+ *   <= 8.  out: interleaved frames as a wav file stores them, int16 for bits = 16, packed 3-byte little-endian for bits = 24.
+ *     v = x * gain[c], one fp32 multiply (none when gain is NULL: svs_resample_encode's rule)
+ *     u(m) = (svs_u32(seed, m) >> 8) * 2^-24, the counter generator of svs_fill_uniform (synth.uniform); F = first_frame + i
+ *     dither 1 (TPDF):             d = u(2*(F*channels + c)) - u(2*(F*channels + c) + 1)
+ *     dither 2 (high-passed TPDF): d = u((F + 1)*channels + c) - u(F*channels + c), the first difference of one uniform sequence
+ *                                  per channel: the same triangular density per sample, a spectrum that rises 6 dB / octave
+ *     dither 0:                    d = 0.  Both differences are exact in fp32.
+ *     Q = 2^(bits-1) - 1.  dither 0 at 16 bits: s = rintf(v * 32767.0f), SVS_PCM_I16's rule bit for bit.  Every other case:
+ *     s = rint((double)v * Q + (double)d).  Then clamp to [-2^(bits-1), 2^(bits-1) - 1]; NaN -> 0, +-inf clamp.
+ *   The counters depend on the absolute frame alone: rows [a, b) encoded with first_frame = a give the bytes of the whole-signal
+ *   call, whatever the grid.  Rules, checked before any launch: bits 16 or 24, dither 0..2, channels 1..8, frames >= 1, ld_in >=
+ *   frames, first_frame >= 0, out 4-byte aligned, x and out non-null.  A thread owns 4 consecutive frames: a 16-byte load per
+ *   channel where x is 16-byte aligned and ld_in % 4 == 0 (scalar loads with the same results otherwise), and 3*channels (24 bits)
+ *   or 2*channels (16 bits) whole dwords out, as 16- or 8-byte stores where out is 16-byte aligned; the last frames % 4 frames go
+ *   by bytes.  No LDS, no atomics, 64-bit indices, bitwise reproducible, nothing returns to the host. */
+int svs_pcm24_widen(const void* packed, int64_t n_samples, int32_t* out, hipStream_t stream);
+int svs_pcm_encode_dither(const float* x, int channels, int64_t frames, int64_t ld_in, const float* gain /* [channels] device, nullable */,
+                          int bits /* 16 | 24 */, int dither /* 0 none, 1 tpdf, 2 high-passed tpdf */, uint32_t seed,
+                          int64_t first_frame, void* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,8 @@ _SIGS = {
     "svs_true_peaks": (I, [P, I, I, L, L, L, P, I, P, P, P, Z, P]),
     "svs_fullband_gains": (I, [P, P, L, I, I, I, I, I, P, P]),
     "svs_fullband_mix": (I, [P, I, L, L, P, L, I, L, P, I, L, P, I, I, I, P, P, I, I, I, P, L, L, P]),
+    "svs_pcm24_widen": (I, [P, L, P, P]),
+    "svs_pcm_encode_dither": (I, [P, I, L, L, P, I, I, U32, L, P, P]),
 }
 
 

@@ -14,7 +14,8 @@ to_wave (data.py:117-169): <name>_spec.npy times its phase -> inverse STFT -> pe
 up-sampled to RATE, peak-normalised at that rate and converted to the subtype's samples by one gfx950 kernel
 (csrc/resample.hip: svs_resample_encode, save_wav_device below), and only the bytes the file stores cross to the
 host.  --subtype PCM_16 is the reference's format: its sf.write(path, y, sr) (data.py:166) picks 16-bit PCM for a
-.wav name; FLOAT, the default here, is what this project has always written.
+.wav name; FLOAT, the default here, is what this project has always written.  --subtype PCM_24 writes 24-bit files and
+--dither tpdf | hp adds TPDF dither under the 16- or 24-bit quantiser (pcm.py, csrc/pcm.hip: svs_pcm_encode_dither).
 
 Out of the accelerated path: wav decoding (scipy.io.wavfile) and the wav
 container write (soundfile there, scipy.io.wavfile here).  Downmix + resampling to --sr (the reference uses
@@ -229,9 +230,9 @@ def read_pcm(path: str):
 
 
 def _load_wav_mono_device(path: str, sr: int, device) -> torch.Tensor:
+    from .pcm import read_pcm_device
     from .resample import resample_poly_gpu
-    rate, data, channels = read_pcm(path)
-    pcm = torch.from_numpy(data).to(device)
+    rate, pcm, channels = read_pcm_device(path, device)        # a 24-bit file crosses as its 3 bytes per sample (pcm.py)
     fr = Fraction(sr, rate)                                    # 1/1 (rate == sr): the call only converts and downmixes
     return resample_poly_gpu(pcm, fr.numerator, fr.denominator, channels=channels, downmix=True)
 
@@ -242,30 +243,43 @@ def write_wav(path: str, y: np.ndarray, sr: int):
 
 
 def save_wav_device(path: str, y_dev: torch.Tensor, sr: int, sr_out: int | None = None, subtype: str = "PCM_16", peak: float | None = 0.9,
-                    loudness: float | None = None, ceiling: float = 0.9, true_peak: bool = False):
+                    loudness: float | None = None, ceiling: float = 0.9, true_peak: bool = False, dither: str = "none", dither_seed: int = 0):
     """float32 device samples (n,) or (channels, n) at rate `sr` -> a wav file at `sr_out` (default: sr) with the samples of
-    `subtype` ("PCM_16", the reference's sf.write format for a .wav name, "PCM_32" or "FLOAT"), peak-normalised to `peak` at
+    `subtype` ("PCM_16", the reference's sf.write format for a .wav name, "PCM_24", "PCM_32" or "FLOAT"), peak-normalised to `peak` at
     the rate that is written (data.py:162-166; None: not normalised; one gain for all channels).  Resampling, gain, sample
     conversion and interleaving are resample.resample_encode_gpu; one device -> host copy of the encoded samples follows.
     loudness (LUFS) replaces the peak rule: the file is brought to that integrated loudness (loudness.py), no sample above
     `ceiling`; the four numbers of the measurement are returned (None without loudness).  true_peak: `ceiling` (or `peak`, which
-    must then be given) bounds the file's true peak, the over-sampled signal's (loudness.py), instead of its largest sample."""
+    must then be given) bounds the file's true peak, the over-sampled signal's (loudness.py), instead of its largest sample.
+    dither ("none", "tpdf", "hp") with dither_seed: TPDF dither under the 16- or 24-bit quantiser (pcm.py); PCM_24 and dither go by
+    svs_pcm_encode_dither (peak must then be given), and a 24-bit file is written by pcm.write_wav24."""
     from scipy.io import wavfile
+    from . import pcm as pcm24
     from .resample import resample_encode_gpu
     sr_out = int(sr if sr_out is None else sr_out)
     fr = Fraction(sr_out, int(sr))
+    bits = pcm24.encoder_bits(subtype, dither)                 # ValueError for dither beside PCM_32 / FLOAT, before any device work
+    how = {} if bits is None else dict(subtype_bits=bits, dither=dither, dither_seed=dither_seed)
+    fmt = "PCM_16" if bits is not None else subtype
+
+    def write(pcm):
+        if bits == 24:
+            pcm24.write_wav24(path, sr_out, pcm.cpu().numpy())
+        else:
+            wavfile.write(path, sr_out, pcm.cpu().numpy())
+
     if loudness is not None:
-        pcm, info = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=subtype, loudness=loudness,
-                                        ceiling=ceiling, rate=sr_out, true_peak=true_peak)
-        wavfile.write(path, sr_out, pcm.cpu().numpy())
+        pcm, info = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=fmt, loudness=loudness,
+                                        ceiling=ceiling, rate=sr_out, true_peak=true_peak, **how)
+        write(pcm)
         return info.cpu().tolist()
     if true_peak:
-        pcm = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=subtype, peak=peak, common_gain=True,
-                                  rate=sr_out, true_peak=True)
-        wavfile.write(path, sr_out, pcm.cpu().numpy())
+        pcm = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=fmt, peak=peak, common_gain=True,
+                                  rate=sr_out, true_peak=True, **how)
+        write(pcm)
         return None
-    pcm = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=subtype, peak=peak, common_gain=True)
-    wavfile.write(path, sr_out, pcm.cpu().numpy())
+    pcm = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=fmt, peak=peak, common_gain=True, **how)
+    write(pcm)
 
 
 def to_spec(args, device):
@@ -331,6 +345,7 @@ def to_wave(args, device):
             subtype = getattr(args, "subtype", "FLOAT")
             loudness = getattr(args, "loudness", None)
             true_peak = bool(getattr(args, "true_peak", False))
+            dither = getattr(args, "dither", "none")
             encode = sr_out != args.sr or subtype != "FLOAT" or loudness is not None or true_peak   # else: float32 at --sr, written as it always was
             y = istft(torch.from_numpy(np.ascontiguousarray(mag[:, :m])).to(device),
                       torch.from_numpy(np.ascontiguousarray(phase[:, :m]).astype(np.complex64)).to(device),
@@ -338,7 +353,7 @@ def to_wave(args, device):
             wav_path = os.path.join(args.tar, spec_name.replace("_spec.npy", ".wav"))
             if encode:
                 save_wav_device(wav_path, y, args.sr, sr_out, subtype, peak=0.9, loudness=loudness, ceiling=getattr(args, "peak_ceiling", 0.9),
-                                true_peak=true_peak)
+                                true_peak=true_peak, dither=dither, dither_seed=getattr(args, "dither_seed", 0))
             else:
                 write_wav(wav_path, y.cpu().numpy(), args.sr)
         except Exception as e:                                          # data.py:168-169
@@ -357,8 +372,11 @@ def main(argv=None):
     parser.add_argument("--resample", default="cpu", choices=["cpu", "gpu"],
                         help="to_spec: downmix + resample on the host (scipy, default) or on the device from the file's PCM")
     parser.add_argument("--sr_out", type=int, default=None, help="to_wave: rate of the written files (default: --sr)")
-    parser.add_argument("--subtype", default="FLOAT", choices=["FLOAT", "PCM_16", "PCM_32"],
+    parser.add_argument("--subtype", default="FLOAT", choices=["FLOAT", "PCM_16", "PCM_24", "PCM_32"],
                         help="to_wave: sample format of the written files (PCM_16 is the reference's)")
+    parser.add_argument("--dither", default="none", choices=["none", "tpdf", "hp"],
+                        help="to_wave with --subtype PCM_16 | PCM_24: TPDF dither under the quantiser, white (tpdf) or high-passed (hp)")
+    parser.add_argument("--dither_seed", type=int, default=0, help="seed of the dither's counter generator (files are reproducible)")
     parser.add_argument("--loudness", type=float, default=None,
                         help="to_wave: integrated loudness of the written files in LUFS (ITU-R BS.1770-4) instead of peak 0.9")
     parser.add_argument("--peak_ceiling", type=float, default=0.9, help="to_wave with --loudness: no written sample exceeds this")
@@ -367,6 +385,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.sr_out is not None and args.sr_out < 1:
         parser.error(f"--sr_out {args.sr_out}: must be positive")
+    if args.dither != "none" and args.subtype not in ("PCM_16", "PCM_24"):
+        parser.error(f"--dither {args.dither} belongs to --subtype PCM_16 or PCM_24: {args.subtype} samples have nothing below the 24th bit to linearise")
     if args.win_size not in WINDOW_SIZES:        # data.py:24 lets it vary; the gfx950 transforms are built for these three
         parser.error(f"--win_size {args.win_size}: the STFT / iSTFT kernels are built for n_fft = {', '.join(map(str, WINDOW_SIZES))} "
                      f"(default {WINDOW_SIZE}, config.WINDOW_SIZE); --hop_size may be anything in 1..win_size")

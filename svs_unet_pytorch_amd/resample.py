@@ -236,11 +236,12 @@ def resample_peaks_gpu(y, up: int, down: int):
 
 
 def encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, rate, frames, true_peak: bool = False, peaks_out=None,
-                        peak: float = 0.9):
+                        peak: float = 0.9, *, subtype_bits=None, dither: str = "none", dither_seed: int = 0):
     """resample_encode_gpu(loudness=): the stems (each (channels, n_in), float32, contiguous) are resampled into one float32 buffer
     by svs_resample_poly -- bit for bit the float the fused encoder forms -- cut or zero-padded to `frames`, measured there
     (svs_loudness_blocks on their sum, svs_resample_peaks per stem, svs_loudness_gain) and encoded 1/1 with the device gain.
-    loudness None (with true_peak): the peak rule of encode_planar_gpu with `peak`.  true_peak, peaks_out: as encode_planar_gpu takes them.
+    loudness None: the peak rule of encode_planar_gpu with `peak`.  true_peak, peaks_out, subtype_bits, dither, dither_seed: as
+    encode_planar_gpu takes them.
     Returns (list of PCM tensors, gain, info), all on the device."""
     import torch
     from . import loudness as ld
@@ -262,12 +263,12 @@ def encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, rate, f
             _lib.check(L.svs_resample_poly(stem.data_ptr(), PCM_F32, 1, 0, n_in, n_in, channels, table.data_ptr(), ntaps, up, down,
                                            buf[k].data_ptr(), width, _lib.stream_ptr(dev)), "svs_resample_poly")
     outs, gains, info = encode_planar_gpu(buf, frames, code, dtype, loudness=loudness, ceiling=ceiling, rate=rate, true_peak=true_peak,
-                                          peaks_out=peaks_out, peak=peak)
+                                          peaks_out=peaks_out, peak=peak, subtype_bits=subtype_bits, dither=dither, dither_seed=dither_seed)
     return outs, gains[0], info
 
 
 def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float = 0.9, rate=None, peak: float = 0.9, true_peak: bool = False,
-                      peaks_out=None):
+                      peaks_out=None, subtype_bits=None, dither: str = "none", dither_seed: int = 0):
     """Stems that are at the written rate already -- buf: (stems, channels, width) float32, contiguous, the first `frames` of every row
     being what is written -- measured and encoded 1/1 on existing kernels: svs_resample_peaks per stem, then either the loudness rule
     (svs_loudness_blocks on the stems' sum, svs_loudness_gain: ONE gain for all stems) or the peak rule (per stem, one common gain
@@ -276,9 +277,22 @@ def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float
     (loudness.py; svs_true_peaks, one launch over all rows in place of the svs_resample_peaks launches), so that no inter-sample
     peak of a written file exceeds `ceiling` (or `peak`); the gain rules themselves are unchanged.  peaks_out: a dict that receives
     "sample_peaks" and "true_peaks", float32 device tensors (stems * channels,) of the rows before the gain, and "gains".
+    subtype_bits (None: `code` decides, as above; 16: int16 whatever `code` says; 24: packed 24-bit frames, uint8 (frames, channels * 3))
+    and dither ("none", "tpdf", "hp"; pcm.py): with 24 bits or a dither the last launches are svs_pcm_encode_dither in place of
+    svs_resample_encode -- after the same gain, stem k with seed dither_seed + k, so the dither of two written files is uncorrelated.
+    Dither belongs to 16 and 24 bits: beside int32 or float32 it is a ValueError.  Peaks, loudness and the gain rules do not change.
     Returns (list of PCM tensors (frames, channels), list of gain tensors, info or None), all on the device."""
     import torch
     from . import loudness as ld
+    from . import pcm
+    dither_kind = pcm.dither_code(dither)
+    if subtype_bits not in (None, 16, 24):
+        raise ValueError(f"subtype_bits {subtype_bits}: None, 16 or 24")
+    if subtype_bits == 16:
+        code, dtype = _PCM["int16"]
+    if dither_kind and subtype_bits != 24 and code != PCM_I16:
+        raise ValueError(f"dither {dither!r} belongs to 16- and 24-bit output, not to {np.dtype(dtype).name}")
+    bits = 24 if subtype_bits == 24 else 16 if dither_kind else None     # None: svs_resample_encode writes `code`
     dev = buf.device
     nst, channels, width = buf.shape
     frames = int(frames)
@@ -297,7 +311,10 @@ def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float
         if nbytes == 0:
             raise _lib.SvsError(f"svs_resample_peaks_workspace_bytes({frames}, {channels}, 1, 1, 1): invalid arguments")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    outs = [torch.empty((frames, channels), dtype=getattr(torch, np.dtype(dtype).name), device=dev) for _ in range(nst)]
+    if bits == 24:
+        outs = [torch.empty((frames, channels * 3), dtype=torch.uint8, device=dev) for _ in range(nst)]
+    else:
+        outs = [torch.empty((frames, channels), dtype=getattr(torch, np.dtype(dtype).name), device=dev) for _ in range(nst)]
     with torch.cuda.device(dev):
         s = _lib.stream_ptr(dev)
         for k in range(0 if true_peak else nst):
@@ -316,6 +333,9 @@ def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float
                 _lib.check(L.svs_max(peaks[k * channels:].data_ptr(), channels, top[k:].data_ptr(), s), "svs_max")
                 _lib.check(L.svs_scale_by_inv(gain.data_ptr(), channels, top[k:].data_ptr(), 1.0, s), "svs_scale_by_inv")
         for k, out in enumerate(outs):
+            if bits is not None:
+                pcm.encode_dither_gpu(buf[k], frames, gains[k], bits, dither_kind, int(dither_seed) + k, out=out)
+                continue
             _lib.check(L.svs_resample_encode(buf[k].data_ptr(), channels, frames, width, one.data_ptr(), 1, 1, 1, gains[k].data_ptr(), code,
                                              out.data_ptr(), s), "svs_resample_encode")
     if true_peak and peaks_out is not None:
@@ -325,7 +345,7 @@ def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float
 
 def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | None = 0.9, common_gain: bool = True,
                         loudness=None, ceiling: float = 0.9, together=None, rate: int | None = None, frames: int | None = None,
-                        true_peak: bool = False):
+                        true_peak: bool = False, subtype_bits=None, dither: str = "none", dither_seed: int = 0):
     """float32 device tensor (n,) or (channels, n), planar -> device tensor (n_out,) or (n_out, channels) of int16 / int32 /
     float32 at rate * up / down, interleaved as a wav file stores it (svs_resample_encode; the rules: encode_pcm_reference).
     peak=None: the samples are encoded as they are.  Otherwise they are scaled by peak / max |resampled signal| on the way
@@ -347,8 +367,16 @@ def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | Non
     true_peak (needs rate): the ceiling of the loudness rule is held against the true peaks at `rate` (loudness.py: the 4x / 2x
     over-sampled signal) instead of the sample peaks.  Without loudness the signal goes by the planar buffer (svs_resample_poly to
     float32, then encode_planar_gpu's peak rule with one common gain against the true peaks): peak must be given and common_gain
-    True; the return value is the PCM alone."""
+    True; the return value is the PCM alone.
+
+    subtype_bits=24 (packed 24-bit frames, uint8 (n_out, channels * 3); fmt is then not read) and dither= "tpdf" / "hp" with dither_seed
+    (pcm.py; 16 and 24 bits only) are encode_planar_gpu's: the signal goes by the planar buffer as with true_peak, so without
+    loudness it is the peak rule with one common gain as well (peak given, common_gain True).  With together, y is encoded with
+    dither_seed and the second stem with dither_seed + 1."""
     import torch
+    planar = subtype_bits is not None or dither != "none"
+    if planar and loudness is None and (peak is None or not common_gain):
+        raise ValueError("subtype_bits= / dither= without loudness= is the peak rule with one common gain: peak= must be given and common_gain True")
     if loudness is None and (together is not None or frames is not None):
         raise ValueError("together= and frames= belong to loudness=")
     if true_peak and rate is None:
@@ -361,11 +389,12 @@ def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | Non
         raise TypeError(f"resample_encode_gpu: dtype {y.dtype} (float32)")
     if y.dim() not in (1, 2) or y.shape[-1] < 1:
         raise ValueError(f"input must be (n,) or (channels, n), got {tuple(y.shape)}")
-    code, dtype = pcm_format(fmt)
+    code, dtype = pcm_format("int16" if subtype_bits is not None else fmt)
     up, down = reduced(up, down)
     squeeze = y.dim() == 1
     y = (y[None] if squeeze else y).contiguous()
     channels, n_in = y.shape
+    how = dict(subtype_bits=subtype_bits, dither=dither, dither_seed=dither_seed)
     if loudness is not None:
         if rate is None:
             raise ValueError("loudness= needs rate=, the sample rate that is written")
@@ -375,12 +404,13 @@ def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | Non
             if not t.is_cuda or t.dtype != torch.float32 or t.shape != y.shape:
                 raise ValueError(f"together must be a float32 device tensor of the same shape, got {tuple(together.shape)}")
             stems.append(t)
-        outs, _, info = encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, int(rate), frames, true_peak)
-        outs = [o[:, 0] if squeeze else o for o in outs]
+        outs, _, info = encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, int(rate), frames, true_peak, **how)
+        outs = [o[:, 0] if squeeze and o.dtype != torch.uint8 else o for o in outs]
         return (*outs, info)
-    if true_peak:
-        outs, _, _ = encode_loudness_gpu([y], up, down, code, dtype, None, ceiling, int(rate), None, True, peak=float(peak))
-        return outs[0][:, 0] if squeeze else outs[0]
+    if true_peak or planar:
+        outs, _, _ = encode_loudness_gpu([y], up, down, code, dtype, None, ceiling, None if rate is None else int(rate), None, true_peak,
+                                         peak=float(peak), **how)
+        return outs[0][:, 0] if squeeze and outs[0].dtype != torch.uint8 else outs[0]
     L = _lib.lib()
     n_out = int(L.svs_resample_out_len(n_in, up, down))
     table, ntaps = tap_table(up, down, y.device)

@@ -6,12 +6,15 @@ evaluate.py accepts it beside the source's stems.
 
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src song.wav --tar out.wav
     python -m svs_unet_pytorch_amd.separate --model_path CKPT/svs_x.pth --src wav_folder --tar out_folder \
-        [--vocal_solo 0|1] [--precision bf16] [--subtype PCM_16|PCM_32|FLOAT] [--no_keep_length] \
+        [--vocal_solo 0|1] [--precision bf16] [--subtype PCM_16|PCM_24|PCM_32|FLOAT|source] [--dither none|tpdf|hp] [--dither_seed N] \
+        [--no_keep_length] \
         [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder] [--tile_hop 128|64|32] [--phase_iters N]
         [--wiener_iters N] [--loudness LUFS|source] [--peak_ceiling 0.9] [--true_peak] [--fullband mask|accomp]
 
 A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
-default) is what the reference's data.py writes (data.py:166).  --win_size / --hop_size (the config's 1024 / 768 by default;
+default) is what the reference's data.py writes (data.py:166); PCM_24 writes 24-bit files, `source` the word length of each source
+file, and --dither tpdf | hp adds TPDF dither under the 16- or 24-bit quantiser (pcm.py; csrc/pcm.hip; off by default: plain
+rounding, byte for byte what was written before).  --win_size / --hop_size (the config's 1024 / 768 by default;
 data.py:24-25 takes the same two flags) are the window and hop of the two transforms, for a checkpoint trained at another
 geometry.  --tar_accomp also writes the accompaniment (a file, or a folder with the names of --tar when --src is a folder) from
 the same pass: one STFT, one set of network forwards and one two-stem inverse STFT (svs_istft_stems_n), --tar then holding the
@@ -61,7 +64,13 @@ def main(argv=None):
     parser.add_argument("--tar", type=str, required=True, help="the wav file to write, or the target folder when --src is a folder")
     parser.add_argument("--vocal_solo", type=int, default=1, help="1: keep the vocal, 0: remove it")
     parser.add_argument("--precision", default=None, choices=["fp32", "bf16"], help="eval precision of the network (default: the model's)")
-    parser.add_argument("--subtype", default="PCM_16", choices=["PCM_16", "PCM_32", "FLOAT"], help="sample format of the written files")
+    parser.add_argument("--subtype", default="PCM_16", choices=["PCM_16", "PCM_32", "FLOAT", "PCM_24", "source"],
+                        help="sample format of the written files; source = the format of each source file (8-bit sources are written as PCM_16)")
+    parser.add_argument("--dither", default="none", choices=["none", "tpdf", "hp"],
+                        help="TPDF dither of 2 LSB peak to peak under the 16- or 24-bit quantiser: tpdf = white, hp = high-passed "
+                             "(first difference of one uniform sequence); default none = plain rounding")
+    parser.add_argument("--dither_seed", type=int, default=0,
+                        help="seed of the dither's counter generator (vocal: N, accompaniment: N + 1); the default 0 makes files reproducible")
     parser.add_argument("--no_keep_length", action="store_true", help="do not cut / pad the output to the source's frame count")
     parser.add_argument("--win_size", type=int, default=WINDOW_SIZE, help="window of the STFT / inverse STFT (512, 1024 or 2048)")
     parser.add_argument("--hop_size", type=int, default=HOP_SIZE, help="hop of the two transforms, 1..win_size")
@@ -85,6 +94,9 @@ def main(argv=None):
                              "highest band; accomp = all of it to the accompaniment (default: band-limited stems; not with --wiener_iters)")
     parser.add_argument("--ema", action="store_true", help="load the checkpoint's ema_state_dict (train.py --ema_decay) instead of its live weights")
     args = parser.parse_args(argv)
+    if args.dither != "none" and args.subtype in ("PCM_32", "FLOAT"):
+        parser.error(f"--dither {args.dither} belongs to --subtype PCM_16 or PCM_24: {args.subtype} samples have nothing below the 24th bit "
+                     "to linearise")
     if args.phase_iters < 0:
         parser.error(f"--phase_iters {args.phase_iters}: must be 0 (the mixture's phase) or a positive number of updates")
     try:
@@ -137,7 +149,7 @@ def main(argv=None):
                                            hop=args.hop_size, dst_accomp_path=dst_accomp, tile_hop=args.tile_hop,
                                            phase_iters=args.phase_iters, wiener_iters=args.wiener_iters, loudness=args.loudness,
                                            ceiling=args.peak_ceiling, report=report, fullband=args.fullband,
-                                           true_peak=args.true_peak)
+                                           true_peak=args.true_peak, dither=args.dither, dither_seed=args.dither_seed)
         print(f"{dst}: {frames} frames x {channels}" + ("" if dst_accomp is None else f"; {dst_accomp}: the same")
               + (f"; {describe(report['info'], report['gain'], args.true_peak)}" if "info" in report else "")
               + (f"; true peak {max(max(row) for row in report['true_peaks']):.2f} dBTP" if "true_peaks" in report else ""))

@@ -28,7 +28,7 @@ import torch
 
 from . import _lib
 from .config import HOP_SIZE, INPUT_LEN, SAMPLE_RATE, WINDOW_SIZE
-from .data import _scale_rows, istft_from_tiles, istft_stems_from_tiles, read_pcm, stft_to_tiles
+from .data import _scale_rows, istft_from_tiles, istft_stems_from_tiles, stft_to_tiles
 from .fullband import check_fullband
 from .overlap import blend_masks, check_tile_hop, overlap_tiles
 from .rephase import check_phase_iters, refine_phase
@@ -186,14 +186,35 @@ def _report_peaks(report, measured):
     report["sample_peaks"], report["true_peaks"] = db
 
 
+def _encoding(subtype, dither, dither_seed):
+    """(sample format for resample.pcm_format, the subtype_bits / dither / dither_seed keywords of the planar encoders -- empty when the
+    existing encoder writes `subtype`) for a subtype of pcm.SUBTYPES.  ValueError for dither beside PCM_32 / FLOAT."""
+    from .pcm import encoder_bits
+    bits = encoder_bits(subtype, dither)
+    if bits is None:
+        return subtype, {}
+    return "PCM_16", dict(subtype_bits=bits, dither=dither, dither_seed=int(dither_seed))
+
+
+def _write_pcm(path, rate, enc, channels, bits):
+    """One encoded device tensor -> its wav file (pcm.write_wav24 for packed 24-bit frames); returns the (frames, channels) written."""
+    out = enc.cpu().numpy()
+    if bits == 24:
+        from .pcm import write_wav24
+        write_wav24(path, int(rate), out)
+        return out.shape[0], channels
+    from scipy.io import wavfile
+    wavfile.write(path, int(rate), out[:, 0] if channels == 1 else out)
+    return out.shape
+
+
 def _write_fullband(mode, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, dst_accomp_path, vocal_solo, subtype, keep_length, loudness,
-                    ceiling, report, true_peak=False):
+                    ceiling, report, true_peak=False, dither="none", dither_seed=0):
     """separate_to_wav(fullband=mode) from the separated stems on: frame gains, the mix at the file's rate, then frames, gain and
     encoding on the kernels the default path uses at 1/1."""
-    from scipy.io import wavfile
-
     from .fullband import frame_gains_gpu, fullband_mix_gpu
     from .resample import encode_planar_gpu, pcm_format, resample_poly_gpu
+    fmt, how = _encoding(subtype, dither, dither_seed)
     both = dst_accomp_path is not None
     stems = (sep if both else sep[None]).contiguous()                 # (S, channels, hop * (T - 1)) at the scale of the tiles
     T = aux["frames"]
@@ -208,17 +229,16 @@ def _write_fullband(mode, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, d
         from . import loudness as ld
         target = ld.loudness_gain_gpu(resample_poly_gpu(pcm, 1, 1, channels=channels, downmix=False), int(rate))[1]
     measured = {}
-    encs, gains, info = encode_planar_gpu(buf, frames, *pcm_format(subtype), loudness=target, ceiling=ceiling, rate=int(rate), true_peak=true_peak,
-                                          peaks_out=measured if true_peak and report is not None else None)
+    encs, gains, info = encode_planar_gpu(buf, frames, *pcm_format(fmt), loudness=target, ceiling=ceiling, rate=int(rate), true_peak=true_peak,
+                                          peaks_out=measured if true_peak and report is not None else None, **how)
     for enc, path in zip(encs, (dst_path, dst_accomp_path)):
-        out = enc.cpu().numpy()
-        wavfile.write(path, int(rate), out[:, 0] if channels == 1 else out)
+        shape = _write_pcm(path, rate, enc, channels, how.get("subtype_bits"))
     if report is not None:
         report["gains"] = [float(g[0].item()) for g in gains]
         if info is not None:
             report["info"], report["gain"] = info.cpu().tolist(), report["gains"][0]
         _report_peaks(report, measured)
-    return out.shape
+    return shape
 
 
 def kept_length(n_encoded: int, n_source: int):
@@ -244,9 +264,10 @@ def separated_frames(n_source: int, sr: int, hop: int = HOP_SIZE):
 def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = True, precision: str | None = None,
                     subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
                     dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN, phase_iters: int = 0, wiener_iters: int = 0,
-                    loudness=None, ceiling: float = 0.9, report: dict | None = None, fullband: str | None = None, true_peak: bool = False):
+                    loudness=None, ceiling: float = 0.9, report: dict | None = None, fullband: str | None = None, true_peak: bool = False,
+                    dither: str = "none", dither_seed: int = 0):
     """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
-    the PCM is copied as the file stores it (data.read_pcm), resample.resample_poly_gpu (no downmix) brings every channel to
+    the PCM is copied as the file stores it (pcm.read_pcm_device), resample.resample_poly_gpu (no downmix) brings every channel to
     SAMPLE_RATE, separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
     peak-normalises to 0.9 with one gain for all channels (data.py:162-164), converts to `subtype` ("PCM_16", "PCM_32",
     "FLOAT") and interleaves; only those samples return to the host.  keep_length: the frames are cut or zero-padded to the
@@ -278,26 +299,35 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     of every written file -- the peak of the 4x (2x from 96 kHz) over-sampled signal, loudness.py -- instead of its largest sample; the
     up-sampling on the way out produces inter-sample peaks that a sample-peak bound lets through.  One launch (svs_true_peaks)
     measures all written rows in place of the sample-peak launches; without loudness the frames are cut or padded before the
-    measurement as well.  report then also receives "true_peaks" and "sample_peaks", per file and channel in dBFS of what was written."""
+    measurement as well.  report then also receives "true_peaks" and "sample_peaks", per file and channel in dBFS of what was written.
+
+    subtype "PCM_24" writes 24-bit files (pcm.write_wav24), "source" the subtype of the source file (pcm.subtype_of).  dither ("none":
+    all of the above, byte for byte; "tpdf"; "hp", its high-passed form; PCM_16 and PCM_24 only, anything else is a ValueError before
+    any device work) adds TPDF dither of 2 LSB peak to peak under the quantiser, from the counter generator with dither_seed for the
+    vocal and dither_seed + 1 for the accompaniment (pcm.py).  With 24 bits or dither the stems go by the planar buffer, as with
+    true_peak: the frames are cut or padded first, the peak rule is held against what is written, the gain is applied and
+    svs_pcm_encode_dither quantises.  A 24-bit source crosses to the device as its 3 bytes per sample (pcm.read_pcm_device)."""
     check_refinement(phase_iters, wiener_iters)
     fullband = check_fullband(fullband, wiener_iters)
+    if subtype == "source":
+        from .pcm import subtype_of
+        subtype = subtype_of(src_path)
+    fmt, how = _encoding(subtype, dither, dither_seed)
     if isinstance(loudness, str) and (loudness != "source" or dst_accomp_path is None):
         raise ValueError(f"loudness={loudness!r}: a number of LUFS, or \"source\" together with dst_accomp_path")
     from fractions import Fraction
 
-    from scipy.io import wavfile
-
+    from .pcm import read_pcm_device
     from .resample import resample_encode_gpu, resample_poly_gpu
-    rate, data, channels = read_pcm(src_path)
-    n_source = data.shape[0]
     dev = model._flat.device
+    rate, pcm, channels = read_pcm_device(src_path, dev)
+    n_source = pcm.shape[0]
     if separated_frames(n_source, rate, hop) == 0:
         raise ValueError(f"{src_path}: {n_source} frames at {rate} Hz are shorter than one hop ({hop} samples at {SAMPLE_RATE} Hz)")
     if fullband is not None and int(rate) <= SAMPLE_RATE:
         import warnings
         warnings.warn(f"fullband={fullband}: a file at {rate} Hz has no band above the network's {SAMPLE_RATE // 2} Hz; the flag changes nothing")
         fullband = None
-    pcm = torch.from_numpy(data).to(dev)
     fr = Fraction(SAMPLE_RATE, int(rate))
     y = resample_poly_gpu(pcm, fr.numerator, fr.denominator, channels=channels, downmix=False)
     y = y[None] if y.dim() == 1 else y                            # (channels, n) at the network rate
@@ -307,9 +337,9 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
                             aux=aux)
     if fullband is not None:
         return _write_fullband(fullband, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, dst_accomp_path, vocal_solo, subtype,
-                               keep_length, loudness, ceiling, report, true_peak)
+                               keep_length, loudness, ceiling, report, true_peak, dither, dither_seed)
     jobs = ((sep, dst_path),) if dst_accomp_path is None else ((sep[0], dst_path), (sep[1], dst_accomp_path))
-    if loudness is not None or true_peak:
+    if loudness is not None or true_peak or how:
         from . import loudness as ld
         from .resample import encode_loudness_gpu, pcm_format
         target = loudness
@@ -317,21 +347,19 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
             target = ld.loudness_gain_gpu(resample_poly_gpu(pcm, 1, 1, channels=channels, downmix=False), int(rate))[1]
         frames = n_source if keep_length else None
         measured = {}
-        encs, gain, info = encode_loudness_gpu([stem.contiguous() for stem, _ in jobs], fr.denominator, fr.numerator, *pcm_format(subtype),
+        encs, gain, info = encode_loudness_gpu([stem.contiguous() for stem, _ in jobs], fr.denominator, fr.numerator, *pcm_format(fmt),
                                                target, ceiling, int(rate), frames, true_peak,
-                                               measured if true_peak and report is not None else None)
+                                               measured if true_peak and report is not None else None, **how)
         for enc, (_, path) in zip(encs, jobs):
-            out = enc.cpu().numpy()
-            wavfile.write(path, int(rate), out[:, 0] if channels == 1 else out)
+            shape = _write_pcm(path, rate, enc, channels, how.get("subtype_bits"))
         if report is not None and info is not None:
             report["info"], report["gain"] = info.cpu().tolist(), float(gain[0].item())
         _report_peaks(report, measured)
-        return out.shape
+        return shape
     for stem, path in jobs:
         enc = resample_encode_gpu(stem, fr.denominator, fr.numerator, fmt=subtype, peak=0.9, common_gain=True)
         if keep_length:
             keep, pad = kept_length(enc.shape[0], n_source)
             enc = torch.nn.functional.pad(enc[:keep], (0, 0, 0, pad))
-        out = enc.cpu().numpy()
-        wavfile.write(path, int(rate), out[:, 0] if channels == 1 else out)
-    return out.shape
+        shape = _write_pcm(path, rate, enc, channels, None)
+    return shape
