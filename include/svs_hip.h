@@ -888,6 +888,37 @@ int svs_pcm_encode_dither(const float* x, int channels, int64_t frames, int64_t 
                           int bits /* 16 | 24 */, int dither /* 0 none, 1 tpdf, 2 high-passed tpdf */, uint32_t seed,
                           int64_t first_frame, void* out, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Look-ahead true-peak limiter for loud targets (csrc/limiter.hip; the float64 definition is svs_unet_pytorch_amd/limiter.py,
+ * DESIGN.md section 25).  replaces: nothing in the reference -- it peak-normalises every written stem (data.py:162-166), so one
+ * transient sets the level of the whole file; svs_loudness_gain's ceiling term does the same to a loudness target.  Three stages on
+ * the planar rows at the written rate, one gain curve for ALL rows (stems and channels), so the stems still add up and a stereo
+ * file keeps its balance.  All: gfx950, 64-bit indices, no atomics, bitwise reproducible, nothing returns to the host, arguments
+ * checked before any launch.
+ * svs_limiter_envelope: rows addressed as in svs_true_peaks (row s*channels + c at x + s*ld_stem + c*ld_ch, n samples, zero outside
+ *   [0, n)), the same taps and factor (1, 2 or 4; 1 reads no taps, NULL allowed).  With y svs_true_peaks' over-sampled signal,
+ *     e[i] = max_row max(|x[i]|, max_{p=1..factor-1} |y_row[factor*i + p]|),   0 <= i < n
+ *   The accumulators are bitwise svs_true_peaks' (one shared device helper), so max_i e[i] is its largest true peak.  A block stages
+ *   2048 samples of every row in turn with the 6-sample halo from 16-byte loads and keeps the running maxima in registers.
+ * svs_limiter_curve: G = G_dev[0] when G_dev is given (a device double: info[2] of svs_loudness_gain), else `G`; ceiling C > 0;
+ *   window: 2h + 1 floats on the device (limiter.window(h)), 1 <= h <= 1024.  r = 1 outside [0, n).
+ *     r[i] = 1 where G*(double)e[i] <= C, else (float)(C / (G*(double)e[i]))    (one fp64 product, one fp64 division, one rounding)
+ *     m[j] = min_{|k|<=h} r[j+k]                                                (exact)
+ *     a[i] = sum_{k=-h..h} window[k+h] * m[i+k]                                 (acc = fmaf(w, m, acc), k ascending, from 0)
+ *     g[i] = min(a[i], r[i])
+ *   G NaN, infinite, zero or negative: g = min(sum of the window, 1) everywhere, which is 1 for limiter.window's tables.
+ *   One kernel: a block owns 2048 outputs and stages 2048 + 4h values of r in LDS (one word of padding after every 8: 27 KB at
+ *   h = 1024); the minimum is taken by doubling, ceil(log2(2h+1)) passes of one min per element; for the smoothing a lane owns 8
+ *   consecutive outputs and slides a register window, one LDS read per 8 fmaf.
+ * svs_limiter_apply: x[row][i] *= g[i] in place, row r at x + r*ld_row, 1 <= rows <= 64, one fp32 multiply; 16-byte loads and stores
+ *   where x and g are 16-byte aligned and ld_row % 4 == 0, scalar accesses with the same results otherwise. */
+int svs_limiter_envelope(const float* x, int stems, int channels, int64_t n, int64_t ld_stem, int64_t ld_ch,
+                         const float* taps /* device, 12*factor + 1, nullable for factor 1 */, int factor, float* e /* [n], device */,
+                         hipStream_t stream);
+int svs_limiter_curve(const float* e, int64_t n, double G, const double* G_dev /* nullable */, double ceiling,
+                      const float* window /* [2h + 1], device */, int h, float* g /* [n], device */, hipStream_t stream);
+int svs_limiter_apply(float* x, int rows, int64_t n, int64_t ld_row, const float* g, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,9 @@ _SIGS = {
     "svs_fullband_mix": (I, [P, I, L, L, P, L, I, L, P, I, L, P, I, I, I, P, P, I, I, I, P, L, L, P]),
     "svs_pcm24_widen": (I, [P, L, P, P]),
     "svs_pcm_encode_dither": (I, [P, I, L, L, P, I, I, U32, L, P, P]),
+    "svs_limiter_envelope": (I, [P, I, I, L, L, L, P, I, P, P]),
+    "svs_limiter_curve": (I, [P, L, D, P, D, P, I, P, P]),
+    "svs_limiter_apply": (I, [P, I, L, L, P, P]),
 }
 
 

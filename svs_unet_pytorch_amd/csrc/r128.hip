@@ -18,14 +18,9 @@
 #include <cmath>
 
 #include "internal.h"
+#include "true_peak.h"                       // TP_*: the staging and the phase accumulator, shared with limiter.hip
 
 #define ST_THREADS 1024
-#define TP_THREADS 256
-#define TP_PER 8                             // samples per lane
-#define TP_BLOCK (TP_THREADS * TP_PER)       // samples per block
-#define TP_HALO 6
-#define TP_ORIGIN 8                          // LDS index of a block's first sample: the halo in front, and 16-byte aligned
-#define TP_LDS (TP_ORIGIN + TP_BLOCK + 8)    // a lane's last 16-byte read ends at TP_BLOCK - 4 + 20
 #define TP_MAX_ROWS 64
 
 // ------------------------------------------------------------------------------------------------
@@ -158,32 +153,7 @@ __global__ __launch_bounds__(TP_THREADS) void true_peaks_kernel(const float* __r
   const int row = blockIdx.y;
   const float* xr = x + (long)(row / channels) * ld_stem + (long)(row % channels) * ld_ch;
   const long b0 = (long)blockIdx.x * TP_BLOCK;
-  // in u = i + m the row's vectors are 16-byte aligned; the window [b0 - 6, b0 + TP_BLOCK + 6) is widened to whole vectors
-  const long m = (long)((((uintptr_t)xr) >> 2) & 3u);
-  const long u_first = b0 - TP_HALO + m;
-  const long u0 = (u_first >= 0 ? u_first / 4 : -((3 - u_first) / 4)) * 4;           // floor to a multiple of 4
-  const int nvec = (int)((b0 + TP_BLOCK + TP_HALO + m - u0 + 3) / 4);                // what falls outside the window is dropped
-  for (int v = tid; v < nvec; v += TP_THREADS) {
-    const long i = u0 + 4L * v - m;                              // the row index of the vector's first element
-    float4 q;
-    if (i >= 0 && i + 3 < n) {
-      q = *reinterpret_cast<const float4*>(xr + i);
-    } else {
-      q.x = (i >= 0 && i < n) ? xr[i] : 0.f;
-      q.y = (i + 1 >= 0 && i + 1 < n) ? xr[i + 1] : 0.f;
-      q.z = (i + 2 >= 0 && i + 2 < n) ? xr[i + 2] : 0.f;
-      q.w = (i + 3 >= 0 && i + 3 < n) ? xr[i + 3] : 0.f;
-    }
-    const float e[4] = {q.x, q.y, q.z, q.w};
-    const int l = (int)(i - b0) + TP_ORIGIN;                      // sample b0 sits at the 16-byte aligned LDS index TP_ORIGIN
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-      if (l + d >= TP_ORIGIN - TP_HALO && l + d < TP_ORIGIN + TP_BLOCK + TP_HALO) sx[l + d] = e[d];
-  }
-  if (tid < TP_ORIGIN - TP_HALO) {                                // the lanes' 16-byte reads reach these; no result depends on them
-    sx[tid] = 0.f;
-    sx[TP_ORIGIN + TP_BLOCK + TP_HALO + tid] = 0.f;
-  }
+  tp_stage(sx, xr, b0, n, tid);
   if (F > 1 && tid < 12 * F + 1) st[tid] = taps[tid];
   __syncthreads();
   float sp = 0.f, tp = 0.f;
@@ -192,21 +162,14 @@ __global__ __launch_bounds__(TP_THREADS) void true_peaks_kernel(const float* __r
     const int s0 = 4 * (tid + q * TP_THREADS);                     // four consecutive samples b0 + s0 + d from five 16-byte LDS reads
     if (b0 + s0 >= n) break;
     float r[20];                                                  // r[j] = x[b0 + s0 + j - TP_ORIGIN], zero outside the row
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const float4 a = *reinterpret_cast<const float4*>(sx + s0 + 4 * j);
-      r[4 * j] = a.x; r[4 * j + 1] = a.y; r[4 * j + 2] = a.z; r[4 * j + 3] = a.w;
-    }
+    tp_window(sx, s0, r);
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
       if (b0 + s0 + d >= n) break;
       sp = fmaxf(sp, fabsf(r[TP_ORIGIN + d]));
 #pragma unroll
       for (int p = 1; p < F; ++p) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) acc = fmaf(st[p + F * k], r[TP_ORIGIN + d + TP_HALO - k], acc);     // x[i + 6 - k]
-        tp = fmaxf(tp, fabsf(acc));
+        tp = fmaxf(tp, fabsf(tp_phase<F>(st, r, d, p)));
       }
     }
   }

@@ -243,7 +243,8 @@ def write_wav(path: str, y: np.ndarray, sr: int):
 
 
 def save_wav_device(path: str, y_dev: torch.Tensor, sr: int, sr_out: int | None = None, subtype: str = "PCM_16", peak: float | None = 0.9,
-                    loudness: float | None = None, ceiling: float = 0.9, true_peak: bool = False, dither: str = "none", dither_seed: int = 0):
+                    loudness: float | None = None, ceiling: float = 0.9, true_peak: bool = False, dither: str = "none", dither_seed: int = 0,
+                    limiter_ms: float | None = None):
     """float32 device samples (n,) or (channels, n) at rate `sr` -> a wav file at `sr_out` (default: sr) with the samples of
     `subtype` ("PCM_16", the reference's sf.write format for a .wav name, "PCM_24", "PCM_32" or "FLOAT"), peak-normalised to `peak` at
     the rate that is written (data.py:162-166; None: not normalised; one gain for all channels).  Resampling, gain, sample
@@ -252,11 +253,16 @@ def save_wav_device(path: str, y_dev: torch.Tensor, sr: int, sr_out: int | None 
     `ceiling`; the four numbers of the measurement are returned (None without loudness).  true_peak: `ceiling` (or `peak`, which
     must then be given) bounds the file's true peak, the over-sampled signal's (loudness.py), instead of its largest sample.
     dither ("none", "tpdf", "hp") with dither_seed: TPDF dither under the 16- or 24-bit quantiser (pcm.py); PCM_24 and dither go by
-    svs_pcm_encode_dither (peak must then be given), and a 24-bit file is written by pcm.write_wav24."""
+    svs_pcm_encode_dither (peak must then be given), and a 24-bit file is written by pcm.write_wav24.
+    limiter_ms (only with loudness, a ValueError before any device work otherwise): resample_encode_gpu's look-ahead limiter of that
+    half-width in milliseconds (limiter.py), so that a few peaks do not cap the loudness gain of the whole file."""
     from scipy.io import wavfile
     from . import pcm as pcm24
     from .resample import resample_encode_gpu
     sr_out = int(sr if sr_out is None else sr_out)
+    if limiter_ms is not None:
+        from .resample import _check_limiter
+        _check_limiter(limiter_ms, loudness, sr_out)
     fr = Fraction(sr_out, int(sr))
     bits = pcm24.encoder_bits(subtype, dither)                 # ValueError for dither beside PCM_32 / FLOAT, before any device work
     how = {} if bits is None else dict(subtype_bits=bits, dither=dither, dither_seed=dither_seed)
@@ -270,7 +276,7 @@ def save_wav_device(path: str, y_dev: torch.Tensor, sr: int, sr_out: int | None 
 
     if loudness is not None:
         pcm, info = resample_encode_gpu(y_dev.contiguous().float(), fr.numerator, fr.denominator, fmt=fmt, loudness=loudness,
-                                        ceiling=ceiling, rate=sr_out, true_peak=true_peak, **how)
+                                        ceiling=ceiling, rate=sr_out, true_peak=true_peak, limiter_ms=limiter_ms, **how)
         write(pcm)
         return info.cpu().tolist()
     if true_peak:
@@ -353,7 +359,8 @@ def to_wave(args, device):
             wav_path = os.path.join(args.tar, spec_name.replace("_spec.npy", ".wav"))
             if encode:
                 save_wav_device(wav_path, y, args.sr, sr_out, subtype, peak=0.9, loudness=loudness, ceiling=getattr(args, "peak_ceiling", 0.9),
-                                true_peak=true_peak, dither=dither, dither_seed=getattr(args, "dither_seed", 0))
+                                true_peak=true_peak, dither=dither, dither_seed=getattr(args, "dither_seed", 0),
+                                limiter_ms=getattr(args, "limiter", None))
             else:
                 write_wav(wav_path, y.cpu().numpy(), args.sr)
         except Exception as e:                                          # data.py:168-169
@@ -382,9 +389,20 @@ def main(argv=None):
     parser.add_argument("--peak_ceiling", type=float, default=0.9, help="to_wave with --loudness: no written sample exceeds this")
     parser.add_argument("--true_peak", action="store_true",
                         help="to_wave: bound the written files' true peak (the over-sampled signal's) instead of their largest sample")
+    parser.add_argument("--limiter", type=float, nargs="?", const=2.0, default=None, metavar="MS",
+                        help="to_wave with --loudness: look-ahead limiter of this half-width in milliseconds (2.0 when given without a value), "
+                             "so that a few peaks do not hold the whole file under the target (limiter.py)")
     args = parser.parse_args(argv)
     if args.sr_out is not None and args.sr_out < 1:
         parser.error(f"--sr_out {args.sr_out}: must be positive")
+    if args.limiter is not None:
+        if args.loudness is None:
+            parser.error("--limiter belongs to --loudness: the peak rule never exceeds its peak, so there is nothing to limit")
+        from .limiter import half_width
+        try:
+            half_width(args.sr_out or args.sr, args.limiter)
+        except ValueError as e:
+            parser.error(f"--limiter {args.limiter:g}: {e}")
     if args.dither != "none" and args.subtype not in ("PCM_16", "PCM_24"):
         parser.error(f"--dither {args.dither} belongs to --subtype PCM_16 or PCM_24: {args.subtype} samples have nothing below the 24th bit to linearise")
     if args.win_size not in WINDOW_SIZES:        # data.py:24 lets it vary; the gfx950 transforms are built for these three

@@ -291,10 +291,17 @@ def loudness_gain_gpu(x, fs, target=None, *, ceiling: float = 0.9, stems: int = 
     limited it.  target: LUFS as a number, a device float64 tensor whose first element holds it (another call's info), or None
     to measure only (gain is then None).  peaks: float32 device tensor of the maxima the ceiling is held against (None: no
     ceiling).  gain: float32 (channels,), all equal, as svs_resample_encode takes it."""
-    import torch
     z = block_energies_gpu(x, fs, stems)
     if channels is None:
         channels = x.shape[-2] if x.dim() > 1 else 1
+    return gain_from_blocks_gpu(z, target, ceiling=ceiling, peaks=peaks, channels=channels)
+
+
+def gain_from_blocks_gpu(z, target=None, *, ceiling: float = 0.9, peaks=None, channels: int = 1):
+    """loudness_gain_gpu's (gain, info) from block energies that are there already (block_energies_gpu's z): svs_loudness_gain alone.
+    The limiter's way out calls it twice on one z, without peaks for the unlimited gain and with the limited rows' peaks for the
+    written one."""
+    import torch
     dev = z.device
     info = torch.empty(4, dtype=torch.float64, device=dev)
     on_device = torch.is_tensor(target)

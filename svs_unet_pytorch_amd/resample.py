@@ -236,15 +236,16 @@ def resample_peaks_gpu(y, up: int, down: int):
 
 
 def encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, rate, frames, true_peak: bool = False, peaks_out=None,
-                        peak: float = 0.9, *, subtype_bits=None, dither: str = "none", dither_seed: int = 0):
+                        peak: float = 0.9, *, subtype_bits=None, dither: str = "none", dither_seed: int = 0, limiter_ms=None, limiter_out=None):
     """resample_encode_gpu(loudness=): the stems (each (channels, n_in), float32, contiguous) are resampled into one float32 buffer
     by svs_resample_poly -- bit for bit the float the fused encoder forms -- cut or zero-padded to `frames`, measured there
     (svs_loudness_blocks on their sum, svs_resample_peaks per stem, svs_loudness_gain) and encoded 1/1 with the device gain.
-    loudness None: the peak rule of encode_planar_gpu with `peak`.  true_peak, peaks_out, subtype_bits, dither, dither_seed: as
-    encode_planar_gpu takes them.
+    loudness None: the peak rule of encode_planar_gpu with `peak`.  true_peak, peaks_out, subtype_bits, dither, dither_seed, limiter_ms,
+    limiter_out: as encode_planar_gpu takes them (limiter_ms without loudness is a ValueError before any device work).
     Returns (list of PCM tensors, gain, info), all on the device."""
     import torch
     from . import loudness as ld
+    _check_limiter(limiter_ms, loudness, rate)
     y = stems[0]
     dev = y.device
     channels, n_in = y.shape
@@ -263,12 +264,26 @@ def encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, rate, f
             _lib.check(L.svs_resample_poly(stem.data_ptr(), PCM_F32, 1, 0, n_in, n_in, channels, table.data_ptr(), ntaps, up, down,
                                            buf[k].data_ptr(), width, _lib.stream_ptr(dev)), "svs_resample_poly")
     outs, gains, info = encode_planar_gpu(buf, frames, code, dtype, loudness=loudness, ceiling=ceiling, rate=rate, true_peak=true_peak,
-                                          peaks_out=peaks_out, peak=peak, subtype_bits=subtype_bits, dither=dither, dither_seed=dither_seed)
+                                          peaks_out=peaks_out, peak=peak, subtype_bits=subtype_bits, dither=dither, dither_seed=dither_seed,
+                                          limiter_ms=limiter_ms, limiter_out=limiter_out)
     return outs, gains[0], info
 
 
+def _check_limiter(limiter_ms, loudness, rate):
+    """The limiter's argument rules, before any device work: it belongs to a loudness target (the peak rule never exceeds its peak),
+    and its half-width at the written rate stays in 1..1024 samples.  Returns the half-width, or None without a limiter."""
+    if limiter_ms is None:
+        return None
+    if loudness is None:
+        raise ValueError("limiter_ms= belongs to loudness=: the peak rule never exceeds its peak, so there is nothing to limit")
+    if rate is None:
+        raise ValueError("limiter_ms= needs rate=, the sample rate that is written")
+    from . import limiter as lim
+    return lim.half_width(rate, limiter_ms)
+
+
 def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float = 0.9, rate=None, peak: float = 0.9, true_peak: bool = False,
-                      peaks_out=None, subtype_bits=None, dither: str = "none", dither_seed: int = 0):
+                      peaks_out=None, subtype_bits=None, dither: str = "none", dither_seed: int = 0, limiter_ms=None, limiter_out=None):
     """Stems that are at the written rate already -- buf: (stems, channels, width) float32, contiguous, the first `frames` of every row
     being what is written -- measured and encoded 1/1 on existing kernels: svs_resample_peaks per stem, then either the loudness rule
     (svs_loudness_blocks on the stems' sum, svs_loudness_gain: ONE gain for all stems) or the peak rule (per stem, one common gain
@@ -281,6 +296,14 @@ def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float
     and dither ("none", "tpdf", "hp"; pcm.py): with 24 bits or a dither the last launches are svs_pcm_encode_dither in place of
     svs_resample_encode -- after the same gain, stem k with seed dither_seed + k, so the dither of two written files is uncorrelated.
     Dither belongs to 16 and 24 bits: beside int32 or float32 it is a ValueError.  Peaks, loudness and the gain rules do not change.
+    limiter_ms (None: exactly the launches above; needs loudness and rate, a ValueError before any device work otherwise): a look-ahead
+    limiter of that half-width in milliseconds (limiter.py).  L and the unlimited gain G are measured first (svs_loudness_blocks,
+    svs_loudness_gain without peaks); then buf[:, :, :frames] is LIMITED IN PLACE -- the caller's buffer changes -- by one gain curve for
+    all stems and channels (envelope against the true peaks with true_peak, svs_limiter_envelope / _curve / _apply); then the peaks
+    of the limited rows are taken as above and svs_loudness_gain runs again with the block energies from BEFORE the limiter, the same
+    target and ceiling: the written gain is min(G, ceiling / peak of the limited rows), so the bound on every written file is the
+    one above.  limiter_out: a dict that receives "curve" (the gain curve, float32 device (frames,)) and "limited_info"
+    (svs_loudness_gain's 4 doubles measured on the limited rows, before the gain: one more svs_loudness_blocks).
     Returns (list of PCM tensors (frames, channels), list of gain tensors, info or None), all on the device."""
     import torch
     from . import loudness as ld
@@ -293,14 +316,25 @@ def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float
     if dither_kind and subtype_bits != 24 and code != PCM_I16:
         raise ValueError(f"dither {dither!r} belongs to 16- and 24-bit output, not to {np.dtype(dtype).name}")
     bits = 24 if subtype_bits == 24 else 16 if dither_kind else None     # None: svs_resample_encode writes `code`
+    _check_limiter(limiter_ms, loudness, rate)
     dev = buf.device
     nst, channels, width = buf.shape
     frames = int(frames)
     L = _lib.lib()
     one, _ = tap_table(1, 1, dev)
+    if true_peak and rate is None:
+        raise ValueError("true_peak= needs rate=, the sample rate that is written")
+    z_before = None
+    if limiter_ms is not None:
+        from . import limiter as lim
+        view = buf[:, :, :frames]
+        z_before = ld.block_energies_gpu(view if nst == 2 else view[0], rate, nst)
+        first = ld.gain_from_blocks_gpu(z_before, loudness, ceiling=ceiling, channels=channels)[1]
+        curve = lim.limit_rows_gpu(buf, frames, first[2:], ceiling, rate, limiter_ms, true_peak)
+        if limiter_out is not None:
+            limiter_out["curve"] = curve
+            limiter_out["limited_info"] = ld.loudness_gain_gpu(view if nst == 2 else view[0], rate, None, stems=nst)[1]
     if true_peak:
-        if rate is None:
-            raise ValueError("true_peak= needs rate=, the sample rate that is written")
         sample_peaks, peaks = ld.true_peaks_rows_gpu(buf.data_ptr(), nst, channels, frames, channels * width, width, ld.true_peak_factor(rate),
                                                      dev, sample=peaks_out is not None)
         if peaks_out is not None:
@@ -323,8 +357,11 @@ def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float
         info = None
         if loudness is not None:
             view = buf[:, :, :frames]
-            gain, info = ld.loudness_gain_gpu(view if nst == 2 else view[0], rate, loudness, ceiling=ceiling, stems=nst, peaks=peaks,
-                                              channels=channels)
+            if z_before is not None:
+                gain, info = ld.gain_from_blocks_gpu(z_before, loudness, ceiling=ceiling, peaks=peaks, channels=channels)
+            else:
+                gain, info = ld.loudness_gain_gpu(view if nst == 2 else view[0], rate, loudness, ceiling=ceiling, stems=nst, peaks=peaks,
+                                                  channels=channels)
             gains = [gain] * nst
         else:                                                              # data.py:162-164 per written file, one gain for its channels
             gains = [torch.full((channels,), float(peak), dtype=torch.float32, device=dev) for _ in range(nst)]
@@ -345,7 +382,7 @@ def encode_planar_gpu(buf, frames, code, dtype, *, loudness=None, ceiling: float
 
 def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | None = 0.9, common_gain: bool = True,
                         loudness=None, ceiling: float = 0.9, together=None, rate: int | None = None, frames: int | None = None,
-                        true_peak: bool = False, subtype_bits=None, dither: str = "none", dither_seed: int = 0):
+                        true_peak: bool = False, subtype_bits=None, dither: str = "none", dither_seed: int = 0, limiter_ms=None):
     """float32 device tensor (n,) or (channels, n), planar -> device tensor (n_out,) or (n_out, channels) of int16 / int32 /
     float32 at rate * up / down, interleaved as a wav file stores it (svs_resample_encode; the rules: encode_pcm_reference).
     peak=None: the samples are encoded as they are.  Otherwise they are scaled by peak / max |resampled signal| on the way
@@ -372,8 +409,12 @@ def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | Non
     subtype_bits=24 (packed 24-bit frames, uint8 (n_out, channels * 3); fmt is then not read) and dither= "tpdf" / "hp" with dither_seed
     (pcm.py; 16 and 24 bits only) are encode_planar_gpu's: the signal goes by the planar buffer as with true_peak, so without
     loudness it is the peak rule with one common gain as well (peak given, common_gain True).  With together, y is encoded with
-    dither_seed and the second stem with dither_seed + 1."""
+    dither_seed and the second stem with dither_seed + 1.
+
+    limiter_ms (only with loudness; a ValueError before any device work otherwise): encode_planar_gpu's look-ahead limiter of that
+    half-width in milliseconds, one gain curve for y and together; info is then that of the limited signal's gain."""
     import torch
+    _check_limiter(limiter_ms, loudness, rate)
     planar = subtype_bits is not None or dither != "none"
     if planar and loudness is None and (peak is None or not common_gain):
         raise ValueError("subtype_bits= / dither= without loudness= is the peak rule with one common gain: peak= must be given and common_gain True")
@@ -404,7 +445,7 @@ def resample_encode_gpu(y, up: int, down: int, *, fmt="int16", peak: float | Non
             if not t.is_cuda or t.dtype != torch.float32 or t.shape != y.shape:
                 raise ValueError(f"together must be a float32 device tensor of the same shape, got {tuple(together.shape)}")
             stems.append(t)
-        outs, _, info = encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, int(rate), frames, true_peak, **how)
+        outs, _, info = encode_loudness_gpu(stems, up, down, code, dtype, loudness, ceiling, int(rate), frames, true_peak, limiter_ms=limiter_ms, **how)
         outs = [o[:, 0] if squeeze and o.dtype != torch.uint8 else o for o in outs]
         return (*outs, info)
     if true_peak or planar:

@@ -10,6 +10,7 @@ evaluate.py accepts it beside the source's stems.
         [--no_keep_length] \
         [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder] [--tile_hop 128|64|32] [--phase_iters N]
         [--wiener_iters N] [--loudness LUFS|source] [--peak_ceiling 0.9] [--true_peak] [--fullband mask|accomp]
+        [--limiter [MS]]
 
 A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
 default) is what the reference's data.py writes (data.py:166); PCM_24 writes 24-bit files, `source` the word length of each source
@@ -33,7 +34,10 @@ accompaniment to the target with one gain for both files, so that their balance 
 aims at the source file's own loudness.  --peak_ceiling (0.9) bounds every written sample under that gain.  --true_peak (off
 by default) holds that ceiling, or without --loudness the 0.9 of the peak rule, against the TRUE peak of every written file -- the peak
 of the 4x over-sampled signal (ITU-R BS.1770-4 Annex 2; loudness.py, csrc/r128.hip) -- instead of its largest sample: up-sampling
-to the file's rate produces inter-sample peaks that a sample-peak bound lets through.  --fullband (off by
+to the file's rate produces inter-sample peaks that a sample-peak bound lets through.  --limiter [MS] (off by default; 2.0 ms when
+given without a value; only with --loudness) runs a look-ahead limiter before that gain (limiter.py; csrc/limiter.hip): one gain curve
+for every channel of both files dips around the peaks that would otherwise hold the whole file under the target, +-2 MS wide, and
+the ceiling then holds as before; the line printed per file names the deepest reduction and the loudness written.  --fullband (off by
 default: the network runs at 8,192 Hz, so every written stem is empty above 4,096 Hz) shares the file's band above 4,096 Hz out
 between the stems (fullband.py): `mask` by the network's own mask in its highest band, frame by frame; `accomp` all of it to the
 accompaniment (the vocal stays band-limited).  With --tar_accomp the two files, each divided by its gain, then add up to the source, and
@@ -52,8 +56,11 @@ from .config import HOP_SIZE, INPUT_LEN, WINDOW_SIZE
 from .data import WINDOW_SIZES
 from .fullband import MODES, check_fullband
 from .inference import load_checkpoint_model
+from .limiter import DEFAULT_MS, half_width
+from .limiter import describe as describe_limiter
 from .loudness import describe, parse_target
 from .overlap import check_tile_hop
+from .pcm import wav_info
 from .streaming import check_refinement, separate_to_wav
 
 
@@ -89,6 +96,9 @@ def main(argv=None):
     parser.add_argument("--true_peak", action="store_true",
                         help="bound the true peak (the over-sampled signal's) of every written file instead of its largest sample: "
                              "--peak_ceiling under --loudness, 0.9 otherwise")
+    parser.add_argument("--limiter", type=float, nargs="?", const=DEFAULT_MS, default=None, metavar="MS",
+                        help=f"with --loudness: look-ahead limiter of this half-width in milliseconds ({DEFAULT_MS} when given without a value), one "
+                             "gain curve for all written channels, so that a few peaks do not hold the whole file under the target (default: off)")
     parser.add_argument("--fullband", default=None, choices=list(MODES),
                         help="share the file's band above the network's 4,096 Hz out between the stems: mask = by the network's mask in its "
                              "highest band; accomp = all of it to the accompaniment (default: band-limited stems; not with --wiener_iters)")
@@ -124,6 +134,16 @@ def main(argv=None):
             parser.error("--loudness source aims vocal + accompaniment at the source's loudness: it needs --tar_accomp (give a number of LUFS for one stem)")
         if not args.peak_ceiling > 0:
             parser.error(f"--peak_ceiling {args.peak_ceiling}: must be positive")
+    if args.limiter is not None:
+        if args.loudness is None:
+            parser.error("--limiter belongs to --loudness: the peak rule never exceeds its peak, so there is nothing to limit")
+        sources = [os.path.join(args.src, f) for f in sorted(os.listdir(args.src)) if f.endswith(".wav")] if os.path.isdir(args.src) else [args.src]
+        for path in sources:                                           # the half-width is counted at the rate that is written: the file's
+            head = wav_info(path)
+            try:
+                half_width(head["rate"] if head else 44100, args.limiter)
+            except ValueError as e:
+                parser.error(f"--limiter {args.limiter:g}: {path}: {e}")
     if args.tar_accomp is not None and not args.vocal_solo:
         parser.error("--tar_accomp writes the vocal to --tar and the accompaniment to --tar_accomp: it cannot be combined with --vocal_solo 0")
 
@@ -149,9 +169,11 @@ def main(argv=None):
                                            hop=args.hop_size, dst_accomp_path=dst_accomp, tile_hop=args.tile_hop,
                                            phase_iters=args.phase_iters, wiener_iters=args.wiener_iters, loudness=args.loudness,
                                            ceiling=args.peak_ceiling, report=report, fullband=args.fullband,
-                                           true_peak=args.true_peak, dither=args.dither, dither_seed=args.dither_seed)
+                                           true_peak=args.true_peak, dither=args.dither, dither_seed=args.dither_seed,
+                                           limiter_ms=args.limiter)
         print(f"{dst}: {frames} frames x {channels}" + ("" if dst_accomp is None else f"; {dst_accomp}: the same")
               + (f"; {describe(report['info'], report['gain'], args.true_peak)}" if "info" in report else "")
+              + (f"; {describe_limiter(**report['limiter'])}" if "limiter" in report else "")
               + (f"; true peak {max(max(row) for row in report['true_peaks']):.2f} dBTP" if "true_peaks" in report else ""))
     print("Separation finished!")
 

@@ -186,6 +186,17 @@ def _report_peaks(report, measured):
     report["sample_peaks"], report["true_peaks"] = db
 
 
+def _report_limiter(report, limited, gain):
+    """report["limiter"]: {"reduction_db": 20 log10 of the smallest value of the gain curve, "loudness": the integrated loudness of the
+    written rows -- of the limited rows (encode_planar_gpu's limiter_out) plus the written gain}; one read-back, after the PCM."""
+    if report is None or "curve" not in limited:
+        return
+    import math
+    low, L = torch.stack([limited["curve"].min().double(), limited["limited_info"][0]]).cpu().tolist()
+    written = L + 20.0 * math.log10(gain) if gain > 0 and math.isfinite(L) else -math.inf
+    report["limiter"] = {"reduction_db": 20.0 * math.log10(low) if low > 0 else -math.inf, "loudness": written}
+
+
 def _encoding(subtype, dither, dither_seed):
     """(sample format for resample.pcm_format, the subtype_bits / dither / dither_seed keywords of the planar encoders -- empty when the
     existing encoder writes `subtype`) for a subtype of pcm.SUBTYPES.  ValueError for dither beside PCM_32 / FLOAT."""
@@ -209,7 +220,7 @@ def _write_pcm(path, rate, enc, channels, bits):
 
 
 def _write_fullband(mode, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, dst_accomp_path, vocal_solo, subtype, keep_length, loudness,
-                    ceiling, report, true_peak=False, dither="none", dither_seed=0):
+                    ceiling, report, true_peak=False, dither="none", dither_seed=0, limiter_ms=None):
     """separate_to_wav(fullband=mode) from the separated stems on: frame gains, the mix at the file's rate, then frames, gain and
     encoding on the kernels the default path uses at 1/1."""
     from .fullband import frame_gains_gpu, fullband_mix_gpu
@@ -228,15 +239,17 @@ def _write_fullband(mode, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, d
     if loudness == "source":
         from . import loudness as ld
         target = ld.loudness_gain_gpu(resample_poly_gpu(pcm, 1, 1, channels=channels, downmix=False), int(rate))[1]
-    measured = {}
+    measured, limited = {}, {}
     encs, gains, info = encode_planar_gpu(buf, frames, *pcm_format(fmt), loudness=target, ceiling=ceiling, rate=int(rate), true_peak=true_peak,
-                                          peaks_out=measured if true_peak and report is not None else None, **how)
+                                          peaks_out=measured if true_peak and report is not None else None, limiter_ms=limiter_ms,
+                                          limiter_out=limited if limiter_ms is not None and report is not None else None, **how)
     for enc, path in zip(encs, (dst_path, dst_accomp_path)):
         shape = _write_pcm(path, rate, enc, channels, how.get("subtype_bits"))
     if report is not None:
         report["gains"] = [float(g[0].item()) for g in gains]
         if info is not None:
             report["info"], report["gain"] = info.cpu().tolist(), report["gains"][0]
+            _report_limiter(report, limited, report["gain"])
         _report_peaks(report, measured)
     return shape
 
@@ -265,7 +278,7 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
                     subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
                     dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN, phase_iters: int = 0, wiener_iters: int = 0,
                     loudness=None, ceiling: float = 0.9, report: dict | None = None, fullband: str | None = None, true_peak: bool = False,
-                    dither: str = "none", dither_seed: int = 0):
+                    dither: str = "none", dither_seed: int = 0, limiter_ms: float | None = None):
     """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
     the PCM is copied as the file stores it (pcm.read_pcm_device), resample.resample_poly_gpu (no downmix) brings every channel to
     SAMPLE_RATE, separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
@@ -306,7 +319,16 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     any device work) adds TPDF dither of 2 LSB peak to peak under the quantiser, from the counter generator with dither_seed for the
     vocal and dither_seed + 1 for the accompaniment (pcm.py).  With 24 bits or dither the stems go by the planar buffer, as with
     true_peak: the frames are cut or padded first, the peak rule is held against what is written, the gain is applied and
-    svs_pcm_encode_dither quantises.  A 24-bit source crosses to the device as its 3 bytes per sample (pcm.read_pcm_device)."""
+    svs_pcm_encode_dither quantises.  A 24-bit source crosses to the device as its 3 bytes per sample (pcm.read_pcm_device).
+
+    limiter_ms (None: all of the above, byte for byte; only with loudness, anything else is a ValueError before any device work): a
+    look-ahead limiter of that half-width in milliseconds (limiter.py) bends the gain around the peaks that would otherwise cap the
+    loudness gain for the whole file: ONE gain curve for every channel of both files, against the true peaks with true_peak, then the
+    rule above on the limited signal, so the bound on every written sample (or true peak) is unchanged.  L is measured before the
+    limiter, so the written files read under the target by what the limiter removed; report then also receives "limiter":
+    {"reduction_db": the deepest gain reduction, "loudness": the integrated loudness of what was written}."""
+    if limiter_ms is not None and loudness is None:
+        raise ValueError("limiter_ms= belongs to loudness=: the peak rule never exceeds its peak, so there is nothing to limit")
     check_refinement(phase_iters, wiener_iters)
     fullband = check_fullband(fullband, wiener_iters)
     if subtype == "source":
@@ -320,6 +342,12 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     from .pcm import read_pcm_device
     from .resample import resample_encode_gpu, resample_poly_gpu
     dev = model._flat.device
+    if limiter_ms is not None:                                     # the half-width at the file's rate, from its header
+        from .limiter import half_width
+        from .pcm import wav_info
+        head = wav_info(src_path)
+        if head is not None:
+            half_width(head["rate"], limiter_ms)
     rate, pcm, channels = read_pcm_device(src_path, dev)
     n_source = pcm.shape[0]
     if separated_frames(n_source, rate, hop) == 0:
@@ -337,23 +365,25 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
                             aux=aux)
     if fullband is not None:
         return _write_fullband(fullband, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, dst_accomp_path, vocal_solo, subtype,
-                               keep_length, loudness, ceiling, report, true_peak, dither, dither_seed)
+                               keep_length, loudness, ceiling, report, true_peak, dither, dither_seed, limiter_ms)
     jobs = ((sep, dst_path),) if dst_accomp_path is None else ((sep[0], dst_path), (sep[1], dst_accomp_path))
-    if loudness is not None or true_peak or how:
+    if loudness is not None or true_peak or how:                   # (limiter_ms comes with loudness)
         from . import loudness as ld
         from .resample import encode_loudness_gpu, pcm_format
         target = loudness
         if loudness == "source":                                   # info[0] of a measurement of the file itself; it stays on the device
             target = ld.loudness_gain_gpu(resample_poly_gpu(pcm, 1, 1, channels=channels, downmix=False), int(rate))[1]
         frames = n_source if keep_length else None
-        measured = {}
+        measured, limited = {}, {}
         encs, gain, info = encode_loudness_gpu([stem.contiguous() for stem, _ in jobs], fr.denominator, fr.numerator, *pcm_format(fmt),
                                                target, ceiling, int(rate), frames, true_peak,
-                                               measured if true_peak and report is not None else None, **how)
+                                               measured if true_peak and report is not None else None, limiter_ms=limiter_ms,
+                                               limiter_out=limited if limiter_ms is not None and report is not None else None, **how)
         for enc, (_, path) in zip(encs, jobs):
             shape = _write_pcm(path, rate, enc, channels, how.get("subtype_bits"))
         if report is not None and info is not None:
             report["info"], report["gain"] = info.cpu().tolist(), float(gain[0].item())
+            _report_limiter(report, limited, report["gain"])
         _report_peaks(report, measured)
         return shape
     for stem, path in jobs:
