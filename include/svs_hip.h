@@ -919,6 +919,45 @@ int svs_limiter_curve(const float* e, int64_t n, double G, const double* G_dev /
                       const float* window /* [2h + 1], device */, int h, float* g /* [n], device */, hipStream_t stream);
 int svs_limiter_apply(float* x, int rows, int64_t n, int64_t ld_row, const float* g, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * YIN fundamental-frequency tracker (csrc/f0.hip; the float64 definition is svs_unet_pytorch_amd/f0.py):
+ * steps 1 to 5 of de Cheveigne & Kawahara, JASA 2002.  replaces: nothing in the reference -- it has no pitch estimator.
+ * Rows: planar fp32, row r at x + r*ld_row, n samples each.  Frame i of a call is frame F = first_frame + i of the signal and starts
+ * at sample t = F*hop; it reads the span = W + tau_max samples from t on.  Only whole frames exist, nothing is zero-padded.  Outputs
+ * are indexed [row][i], i < n_frames.  Per frame:
+ *     d(tau)  = sum_{j=0..W-1} ((double)(x[t+j] - x[t+j+tau]))^2,  0 <= tau <= tau_max   (one fp32 subtraction; the square and the
+ *               sum in fp64: acc = fma(v, v, acc), j ascending, one chain per lag)
+ *     S(tau)  = sum_{k=1..tau} d(k)                                                      (fp64 scan over the lags)
+ *     d'(0)   = 1;  d'(tau) = (float)(d(tau) * tau / S(tau)),  1 where S(tau) == 0       (rounded once to fp32)
+ *     rms     = (float)sqrt(sum_{j=0..W-1} (double)x[t+j]^2 / W)
+ *   pick, on the fp32 d':  tau = the smallest tau in [tau_min, tau_max] with (double)d'(tau) < threshold, then stepped to tau + 1
+ *     while tau + 1 <= tau_max and d'(tau+1) < d'(tau); found = 1.  No such tau: the smallest tau in the range that attains the
+ *     minimum of d', found = 0.  With a, b, c = d'(tau-1), d'(tau), d'(tau+1) in fp64: where tau - 1 >= 1, tau + 1 <= tau_max and
+ *     q = a - 2b + c > 0, delta = clamp(0.5 (a - c) / q, -1, 1), else delta = 0.
+ *     f0 = (float)(sr / (tau + delta));  ap = b;  voiced = found && rms >= rms_gate  (found alone where svs_f0_pick gets no rms)
+ * Rules, checked before any launch, each with its own message: 1 <= rows <= 64; 1 <= W <= 4096; 1 <= tau_max <= 2048; hop >= 1;
+ * first_frame, n_frames >= 0 (n_frames = 0 launches nothing); (first_frame + n_frames - 1)*hop + W + tau_max <= n; ld_row >= n for
+ * more than one row; 1 <= tau_min < tau_max; threshold and sr positive and finite; rms_gate finite, >= 0; pointers non-null (rms of
+ * svs_f0_cmnd and of svs_f0_pick may be NULL) and 4-byte aligned.
+ * svs_f0_cmnd: d' [rows][n_frames][tau_max + 1] and, where rms is given, rms [rows][n_frames].  One wave per frame, a block of 64 F
+ *   threads owns F <= 4 consecutive frames of one row and stages their span + (F - 1)*hop samples once in LDS (at most 48 KB with the
+ *   F rows of d'; F = 1 where hop >= span).  A lane owns 2, 4 or 8 consecutive lags (by tau_max) and slides a register window: two
+ *   LDS reads, one of them a broadcast, per 2 / 4 / 8 fp64 FMAs; one word of padding after every 2 / 4 / 8 keeps the lanes on
+ *   different banks.  F and the lags of a lane follow from (W, tau_max, hop) alone and no frame reads another's results: a frame's
+ *   values depend neither on the grid, nor on first_frame, nor on the frames that share its block.
+ * svs_f0_pick: the pick on `count` rows of d' in memory, one wave per row; the two searches are wave minima that keep the smallest
+ *   index on ties.
+ * svs_f0_track: both in one launch, d' never leaves LDS; the same device functions, so f0, ap, rms and voiced are bitwise those of
+ *   svs_f0_cmnd followed by svs_f0_pick, and frames [a, b) with first_frame = a are bitwise those of the whole-signal call.
+ * All: gfx950, 64-bit indices, no atomics, bitwise reproducible, nothing returns to the host. */
+int svs_f0_cmnd(const float* x, int rows, int64_t n, int64_t ld_row, int W, int tau_max, int hop, int64_t first_frame, int64_t n_frames,
+                float* dprime /* [rows][n_frames][tau_max+1] */, float* rms /* [rows][n_frames], nullable */, hipStream_t stream);
+int svs_f0_pick(const float* dprime, int64_t count /* rows*n_frames */, int tau_min, int tau_max, double threshold,
+                const float* rms /* [count], nullable */, float rms_gate, double sr, float* f0, float* ap, int32_t* voiced, hipStream_t stream);
+int svs_f0_track(const float* x, int rows, int64_t n, int64_t ld_row, int W, int tau_min, int tau_max, int hop, int64_t first_frame,
+                 int64_t n_frames, double threshold, float rms_gate, double sr, float* f0, float* ap, float* rms, int32_t* voiced,
+                 hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

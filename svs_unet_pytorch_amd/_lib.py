@@ -164,6 +164,9 @@ _SIGS = {
     "svs_limiter_envelope": (I, [P, I, I, L, L, L, P, I, P, P]),
     "svs_limiter_curve": (I, [P, L, D, P, D, P, I, P, P]),
     "svs_limiter_apply": (I, [P, I, L, L, P, P]),
+    "svs_f0_cmnd": (I, [P, I, L, L, I, I, I, L, L, P, P, P]),
+    "svs_f0_pick": (I, [P, L, I, I, D, P, F, D, P, P, P, P]),
+    "svs_f0_track": (I, [P, I, L, L, I, I, I, I, L, L, D, F, D, P, P, P, P, P]),
 }
 
 

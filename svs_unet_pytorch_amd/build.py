@@ -44,9 +44,11 @@ def _stale(target, deps):
 # (reproduced with two-line kernels: DESIGN.md section 5).  No other source file produces that form; wiener.hip's complex
 # arithmetic is fp64, but its fp32 loads and stores sit beside it, so it is built the same way; stretch.hip forms and sums complex
 # fp32 sources per lane and is built the same way too (it does not include fft_wave.h), and so is pitch.hip, which does the same
-# at four points per source.
+# at four points per source.  f0.hip needs it as well: its arithmetic is fp64 but for ONE fp32 subtraction per term, and a lane forms
+# 2, 4 or 8 of those side by side from one broadcast sample and a register window that rotates -- adjacent independent fp32
+# subtractions whose operands sit in shuffled registers are exactly what the vectoriser packs with op_sel.
 EXTRA_FLAGS = {"stft.hip": ["-fno-slp-vectorize"], "mrstft.hip": ["-fno-slp-vectorize"], "wiener.hip": ["-fno-slp-vectorize"],
-               "stretch.hip": ["-fno-slp-vectorize"], "pitch.hip": ["-fno-slp-vectorize"]}
+               "stretch.hip": ["-fno-slp-vectorize"], "pitch.hip": ["-fno-slp-vectorize"], "f0.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src):

@@ -64,6 +64,12 @@ _project_images shares), applied to every frame's references (_apply_filters), a
 the track's figure being the median over frames.  Inside a frame the spans are not nested, so no Gram form serves:
 `bss_eval_v4_gpu` gets the coefficients from svs_bss_img_filters_batched (the image solve plus a back substitution) and the
 seven per-frame energies from svs_bss_project_frames (csrc/bss_v4.hip), which applies the filters without storing a signal.
+
+Melody (`--melody`): BSS-eval says how much accompaniment leaked into the vocal, not whether its melody survived.  `melody_for_track`
+tracks the reference and the estimated vocal (mono downmix, the file's rate) with the same YIN parameters (f0.py: f0.track_gpu under
+`--device gpu`, the float64 definition f0.yin_reference otherwise) and scores the estimate's track against the reference's with the
+five frame-level measures of the MIREX melody task (f0.melody_metrics): VR, VFA, RPA, RCA, OA, as fractions.  `--rms_gate_db` (-50 dB
+re full scale by default in this mode) makes the silent passages of the reference count as unvoiced.
 """
 from __future__ import annotations
 
@@ -192,6 +198,31 @@ def compute_metrics_for_track(mix_path, vocal_ref_path, vocal_est_path, device="
     """evaluate.py:26-84: vocal SDR / SIR / SAR on (vocal, mixture - vocal) and NSDR against the mixture."""
     mix, vocal_ref, vocal_est, _ = _load_track(mix_path, vocal_ref_path, vocal_est_path)
     return metrics_from_waveforms(mix, vocal_ref, vocal_est, device)
+
+
+def melody_for_track(vocal_ref_path, vocal_est_path, device="cpu", **options):
+    """{"VR", "VFA", "RPA", "RCA", "OA"} of the estimated vocal's pitch track against the reference vocal's: both files as mono at
+    their common rate, cut to the shorter one, tracked as two rows of ONE call with the same parameters (options: f0.track_gpu's
+    keywords)."""
+    from . import f0 as f0m
+    ref, sr_ref = load_mono_audio(vocal_ref_path)
+    est, sr_est = load_mono_audio(vocal_est_path)
+    if sr_ref != sr_est:
+        raise ValueError(f"Sample rate mismatch: ref={sr_ref}, est={sr_est}")
+    n = min(len(ref), len(est))
+    both = np.stack([ref[:n], est[:n]]).astype(np.float32)
+    if device == "gpu":
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("the GPU tracker needs a ROCm device (gfx950 kernels, no CPU path; use device='cpu')")
+        track = f0m.track_gpu(torch.from_numpy(both).to("cuda"), sr_ref, **options)
+        f0, voiced = track.f0.cpu().numpy(), track.voiced.cpu().numpy()
+    elif device == "cpu":
+        track = f0m.yin_reference(both, sr_ref, **options)[0]
+        f0, voiced = track.f0, track.voiced
+    else:
+        raise ValueError(f"device must be 'cpu' or 'gpu', got {device!r}")
+    return f0m.melody_metrics(f0[0], voiced[0], f0[1], voiced[1])
 
 
 def frame_samples(seconds, sr):
@@ -1102,7 +1133,18 @@ def main(argv=None):
                         help="v4: BSS-eval v4, the mode of published MUSDB18 / SiSEC figures (museval's default): filters from "
                              "the whole track, SDR / ISR / SIR / SAR / NSDR per frame (--frame_window, default 1 s), the "
                              "median over frames per track; the downmix is scored unless --stereo is given")
+    parser.add_argument("--melody", action="store_true",
+                        help="also score the melody: YIN pitch tracks of the estimated and the reference vocal, compared by voicing "
+                             "recall / false alarm, raw pitch / chroma accuracy and overall accuracy (VR, VFA, RPA, RCA, OA)")
+    parser.add_argument("--rms_gate_db", type=float, default=None, metavar="DB",
+                        help="with --melody: frames whose rms lies below this level (dB re full scale) are unvoiced (default -50)")
     args = parser.parse_args(argv)
+    if args.rms_gate_db is not None and not args.melody:
+        parser.error("--rms_gate_db belongs to --melody")
+    melody = ()
+    if args.melody:
+        from .f0 import MELODY as melody, MELODY_GATE_DB, gate_from_db
+        melody_options = dict(rms_gate=gate_from_db(MELODY_GATE_DB if args.rms_gate_db is None else args.rms_gate_db))
     v4 = args.mode == "v4"
     if v4 and args.frame_window is None:
         args.frame_window = 1.0
@@ -1145,6 +1187,8 @@ def main(argv=None):
                 m = frame_summary(frames, metrics)
             else:
                 m = track_metrics(mix_path, ref_path, pred_path, args.device)
+            if melody:
+                m = {**m, **melody_for_track(ref_path, pred_path, args.device, **melody_options)}
         except Exception as e:                          # evaluate.py:127-131
             print(f"[Error] Failed on {base}: {e}")
             continue
@@ -1157,7 +1201,7 @@ def main(argv=None):
             line += f",\tframes={m['frames']}/{frames['SDR'].size}"
             frame_rows += [{"track": name, "frame": i, "start_s": float(frames["start_s"][i]),
                             **{k: float(frames[k][i]) for k in metrics}} for i in range(frames["SDR"].size)]
-        print(line)
+        print(line + "".join(f",\t{k}={m[k]:.3f}" for k in melody))
         results.append({"track": name, **m})
     if not results:
         print("\n[Error] No valid tracks evaluated.")
@@ -1166,9 +1210,11 @@ def main(argv=None):
           "\n=== Overall Mean Metrics (vocal, per-track medians over frames) ===")
     for k in metrics:
         print(f"Mean {k:4s}: {float(np.mean([r[k] for r in results])):.3f} dB")
+    for k in melody:
+        print(f"Mean {k:4s}: {float(np.mean([r[k] for r in results])):.3f}")
     if args.out_csv is not None:
         with open(args.out_csv, "w", newline="", encoding="utf-8") as f:
-            w = csv.DictWriter(f, fieldnames=["track", *metrics] + (["frames"] if framewise else []))
+            w = csv.DictWriter(f, fieldnames=["track", *metrics] + (["frames"] if framewise else []) + list(melody))
             w.writeheader()
             w.writerows(results)
         print(f"\n[Info] Results saved to {args.out_csv}")

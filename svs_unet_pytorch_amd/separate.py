@@ -10,7 +10,7 @@ evaluate.py accepts it beside the source's stems.
         [--no_keep_length] \
         [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder] [--tile_hop 128|64|32] [--phase_iters N]
         [--wiener_iters N] [--loudness LUFS|source] [--peak_ceiling 0.9] [--true_peak] [--fullband mask|accomp]
-        [--limiter [MS]]
+        [--limiter [MS]] [--f0_csv track.csv | csv_folder]
 
 A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
 default) is what the reference's data.py writes (data.py:166); PCM_24 writes 24-bit files, `source` the word length of each source
@@ -41,7 +41,11 @@ the ceiling then holds as before; the line printed per file names the deepest re
 default: the network runs at 8,192 Hz, so every written stem is empty above 4,096 Hz) shares the file's band above 4,096 Hz out
 between the stems (fullband.py): `mask` by the network's own mask in its highest band, frame by frame; `accomp` all of it to the
 accompaniment (the vocal stays band-limited).  With --tar_accomp the two files, each divided by its gain, then add up to the source, and
-a stereo file keeps its channel balance.  Not beside --wiener_iters; a file at or below 8,192 Hz has no such band.  The reference has no such command: it goes through
+a stereo file keeps its channel balance.  Not beside --wiener_iters; a file at or below 8,192 Hz has no such band.  --f0_csv PATH
+(a folder when --src is one: one NAME.csv per source file) also writes the pitch track of the vocal stem (f0.py; csrc/f0.hip): a YIN
+tracker on the mean of the stem's channels at the network's 8,192 Hz, after the Wiener or phase stages and before the way out, one
+launch; time,f0,voiced,aperiodicity,rms per 10 ms frame.  The wav files are byte for byte those written without the flag; --vocal_solo 0
+writes no vocal stem, so it cannot be combined with it.  The reference has no such command: it goes through
 data.py to_spec, inference.py and data.py to_wave with .npy files in between.
 """
 from __future__ import annotations
@@ -102,6 +106,9 @@ def main(argv=None):
     parser.add_argument("--fullband", default=None, choices=list(MODES),
                         help="share the file's band above the network's 4,096 Hz out between the stems: mask = by the network's mask in its "
                              "highest band; accomp = all of it to the accompaniment (default: band-limited stems; not with --wiener_iters)")
+    parser.add_argument("--f0_csv", type=str, default=None, metavar="PATH",
+                        help="also write the vocal stem's pitch track (YIN at the network rate): time,f0,voiced,aperiodicity,rms per frame; "
+                             "a csv file, or a folder when --src is one")
     parser.add_argument("--ema", action="store_true", help="load the checkpoint's ema_state_dict (train.py --ema_decay) instead of its live weights")
     args = parser.parse_args(argv)
     if args.dither != "none" and args.subtype in ("PCM_32", "FLOAT"):
@@ -144,6 +151,8 @@ def main(argv=None):
                 half_width(head["rate"] if head else 44100, args.limiter)
             except ValueError as e:
                 parser.error(f"--limiter {args.limiter:g}: {path}: {e}")
+    if args.f0_csv is not None and not args.vocal_solo:
+        parser.error("--f0_csv tracks the vocal stem, and --vocal_solo 0 writes none: drop one of the two")
     if args.tar_accomp is not None and not args.vocal_solo:
         parser.error("--tar_accomp writes the vocal to --tar and the accompaniment to --tar_accomp: it cannot be combined with --vocal_solo 0")
 
@@ -157,12 +166,15 @@ def main(argv=None):
         os.makedirs(args.tar, exist_ok=True)
         if args.tar_accomp is not None:
             os.makedirs(args.tar_accomp, exist_ok=True)
-        jobs = [(os.path.join(args.src, f), os.path.join(args.tar, f), None if args.tar_accomp is None else os.path.join(args.tar_accomp, f))
+        if args.f0_csv is not None:
+            os.makedirs(args.f0_csv, exist_ok=True)
+        jobs = [(os.path.join(args.src, f), os.path.join(args.tar, f), None if args.tar_accomp is None else os.path.join(args.tar_accomp, f),
+                 None if args.f0_csv is None else os.path.join(args.f0_csv, f[:-4] + ".csv"))
                 for f in sorted(os.listdir(args.src)) if f.endswith(".wav")]
     else:
-        jobs = [(args.src, args.tar, args.tar_accomp)]
+        jobs = [(args.src, args.tar, args.tar_accomp, args.f0_csv)]
     print(f"Found {len(jobs)} files, separating...")
-    for src, dst, dst_accomp in jobs:
+    for src, dst, dst_accomp, f0_csv in jobs:
         report = {}
         frames, channels = separate_to_wav(model, src, dst, vocal_solo=bool(args.vocal_solo), precision=args.precision,
                                            subtype=args.subtype, keep_length=not args.no_keep_length, n_fft=args.win_size,
@@ -170,11 +182,12 @@ def main(argv=None):
                                            phase_iters=args.phase_iters, wiener_iters=args.wiener_iters, loudness=args.loudness,
                                            ceiling=args.peak_ceiling, report=report, fullband=args.fullband,
                                            true_peak=args.true_peak, dither=args.dither, dither_seed=args.dither_seed,
-                                           limiter_ms=args.limiter)
+                                           limiter_ms=args.limiter, f0_csv_path=f0_csv)
         print(f"{dst}: {frames} frames x {channels}" + ("" if dst_accomp is None else f"; {dst_accomp}: the same")
               + (f"; {describe(report['info'], report['gain'], args.true_peak)}" if "info" in report else "")
               + (f"; {describe_limiter(**report['limiter'])}" if "limiter" in report else "")
-              + (f"; true peak {max(max(row) for row in report['true_peaks']):.2f} dBTP" if "true_peaks" in report else ""))
+              + (f"; true peak {max(max(row) for row in report['true_peaks']):.2f} dBTP" if "true_peaks" in report else "")
+              + (f"; {f0_csv}: {report['f0'].f0.shape[-1]} pitch frames" if "f0" in report else ""))
     print("Separation finished!")
 
 

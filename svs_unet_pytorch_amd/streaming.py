@@ -14,6 +14,7 @@ The stages of separate_waveform, in order, each written once:
                     wiener.wiener_filter's own tiles and phasors with no mask (wiener_iters)
     inverse         data.istft_from_tiles per stem, which applies the mask on load; the plain two-stem case is ONE launch
                     (data.istft_stems_from_tiles)
+    f0              f0= only: the vocal stem's pitch track at the network rate (f0.track_gpu), one launch
     peak            every stem and channel scaled to `peak` on its own (data.py:162-164), after the resampling to sr_out if any
 
 separate_spectrogram_device is the tiles / overlap / network / blend part for a magnitude that exists already (inference.py:65-127;
@@ -102,7 +103,7 @@ def separate_spectrogram_device(model, mag: torch.Tensor, seg_len: int = INPUT_L
 def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
                       peak: float | None = 0.9, max_batch: int = 256, precision: str | None = None, sr_in: int | None = None,
                       sr_out: int | None = None, both_stems: bool = False, tile_hop: int = INPUT_LEN, phase_iters: int = 0,
-                      wiener_iters: int = 0, aux: dict | None = None):
+                      wiener_iters: int = 0, aux: dict | None = None, f0=None):
     """float32 samples (n,) or (channels, n) on the GPU -> separated samples (hop*(T-1),) or (channels, hop*(T-1)), through the
     stages the module docstring lists.  With the defaults that is ONE forward transform, one network forward per `max_batch` tiles,
     ONE inverse transform and the two per-channel normalisations, as the reference computes it.
@@ -121,7 +122,18 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     is kept and the two stems add up to the mixture but for the regulariser; one inverse launch per stem.
     check_refinement's rules are a ValueError before any device work.
     aux: a dict that receives what a post-filter at another rate needs (fullband.py): "y" (the (channels, n) signal at the network rate
-    that was transformed), "tiles", "mask" (the one the stems were made from, in the layout of the tiles), "norm" and "frames"."""
+    that was transformed), "tiles", "mask" (the one the stems were made from, in the layout of the tiles), "norm" and "frames".
+    f0: True, or a dict of f0.track_gpu's keywords (fmin, fmax, W, hop, threshold, rms_gate): the call returns (stems, f0.Track) -- the
+    pitch track of the VOCAL stem (f0.py, csrc/f0.hip), from the mean of its channels at SAMPLE_RATE as the inverse transform leaves it
+    (scaled to `peak` where that rate is the one returned), after the Wiener or phase stages and before the resampling to sr_out: ONE
+    svs_f0_track launch, nothing waits for the host.  The stems are those of the call without it.  vocal_solo=False without
+    both_stems has no vocal stem to track: a ValueError before any device work."""
+    f0_options = None
+    if f0 is not None and f0 is not False:
+        from .f0 import check_options
+        f0_options = check_options(f0)
+        if not (vocal_solo or both_stems):
+            raise ValueError("f0= tracks the vocal stem, and vocal_solo=False without both_stems returns none")
     if tile_hop != INPUT_LEN:
         check_tile_hop(tile_hop, INPUT_LEN)
     phase_iters, wiener_iters = check_refinement(phase_iters, wiener_iters)       # before the waveform or the model is looked at
@@ -164,6 +176,10 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     else:
         outs = [istft_from_tiles(t, m, p, T, invert=invert, n_fft=n_fft, hop=hop, peak=peak_here) for t, m, p, invert in stems]
         out = outs[0] if len(outs) == 1 else torch.cat(outs)
+    track = None
+    if f0_options is not None:                                   # the vocal's rows come first
+        from .f0 import channel_mean, track_gpu
+        track = track_gpu(channel_mean(out[:C]), SAMPLE_RATE, **f0_options)
     if sr_out is not None:
         from .resample import resample_poly_gpu
         out = resample_poly_gpu(out, int(sr_out), SAMPLE_RATE)
@@ -171,8 +187,10 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
             _scale_rows(out, peak, ws=torch.empty(4096, dtype=torch.uint8, device=out.device))
     if both_stems:
         out = out.view(2, C, out.shape[1])
-        return out[:, 0] if squeeze else out
-    return out[0] if squeeze else out
+        out = out[:, 0] if squeeze else out
+    else:
+        out = out[0] if squeeze else out
+    return out if f0_options is None else (out, track)
 
 
 def _report_peaks(report, measured):
@@ -278,7 +296,7 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
                     subtype: str = "PCM_16", keep_length: bool = True, n_fft: int = WINDOW_SIZE, hop: int = HOP_SIZE,
                     dst_accomp_path: str | None = None, tile_hop: int = INPUT_LEN, phase_iters: int = 0, wiener_iters: int = 0,
                     loudness=None, ceiling: float = 0.9, report: dict | None = None, fullband: str | None = None, true_peak: bool = False,
-                    dither: str = "none", dither_seed: int = 0, limiter_ms: float | None = None):
+                    dither: str = "none", dither_seed: int = 0, limiter_ms: float | None = None, f0=None, f0_csv_path: str | None = None):
     """wav file -> separated wav file at the same rate and channel count, everything between the two files on the device:
     the PCM is copied as the file stores it (pcm.read_pcm_device), resample.resample_poly_gpu (no downmix) brings every channel to
     SAMPLE_RATE, separate_waveform(peak=None) separates them, and resample.resample_encode_gpu resamples back to the file's rate,
@@ -326,7 +344,20 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     loudness gain for the whole file: ONE gain curve for every channel of both files, against the true peaks with true_peak, then the
     rule above on the limited signal, so the bound on every written sample (or true peak) is unchanged.  L is measured before the
     limiter, so the written files read under the target by what the limiter removed; report then also receives "limiter":
-    {"reduction_db": the deepest gain reduction, "loudness": the integrated loudness of what was written}."""
+    {"reduction_db": the deepest gain reduction, "loudness": the integrated loudness of what was written}.
+
+    f0 / f0_csv_path (None: all of the above, byte for byte, and the written wav files are the same bytes with them): the pitch track of
+    the vocal stem (separate_waveform(f0=); f0: True or a dict of f0.track_gpu's keywords, True when only the path is given), written to
+    f0_csv_path as time,f0,voiced,aperiodicity,rms per frame (f0.write_csv) ahead of the way out; report receives "f0", the f0.Track of
+    device tensors.  vocal_solo=False without dst_accomp_path writes no vocal: a ValueError before any device work."""
+    if f0_csv_path is not None and (f0 is None or f0 is False):
+        f0 = True
+    tracking = f0 is not None and f0 is not False
+    if tracking:
+        from .f0 import check_options
+        f0 = check_options(f0)
+        if not vocal_solo and dst_accomp_path is None:
+            raise ValueError("f0= tracks the vocal stem, and vocal_solo=False without dst_accomp_path writes none")
     if limiter_ms is not None and loudness is None:
         raise ValueError("limiter_ms= belongs to loudness=: the peak rule never exceeds its peak, so there is nothing to limit")
     check_refinement(phase_iters, wiener_iters)
@@ -362,7 +393,14 @@ def separate_to_wav(model, src_path: str, dst_path: str, *, vocal_solo: bool = T
     aux = None if fullband is None else {}
     sep = separate_waveform(model, y, vocal_solo=vocal_solo, n_fft=n_fft, hop=hop, peak=None, precision=precision,
                             both_stems=dst_accomp_path is not None, tile_hop=tile_hop, phase_iters=phase_iters, wiener_iters=wiener_iters,
-                            aux=aux)
+                            aux=aux, f0=f0 if tracking else None)
+    if tracking:                                                   # the track is complete before the way out begins
+        sep, track = sep
+        if report is not None:
+            report["f0"] = track
+        if f0_csv_path is not None:
+            from .f0 import write_csv
+            write_csv(f0_csv_path, track)
     if fullband is not None:
         return _write_fullband(fullband, sep, aux, pcm, y, rate, channels, fr, hop, dst_path, dst_accomp_path, vocal_solo, subtype,
                                keep_length, loudness, ceiling, report, true_peak, dither, dither_seed, limiter_ms)
