@@ -958,6 +958,53 @@ int svs_f0_track(const float* x, int rows, int64_t n, int64_t ld_row, int W, int
                  int64_t n_frames, double threshold, float rms_gate, double sr, float* f0, float* ap, float* rms, int32_t* voiced,
                  hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Smoothing the pitch track (csrc/f0_smooth.hip; the definition is svs_unet_pytorch_amd/f0.py): K = 7 period
+ * candidates per frame from the difference function above, and an exact Viterbi decode over them and one unvoiced state.
+ * replaces: nothing in the reference.  All integer arithmetic is int64.
+ *   dip:        tau in [tau_min, tau_max] with (tau == tau_min || d'(tau) < d'(tau-1)) && (tau == tau_max || d'(tau) <= d'(tau+1))
+ *   candidates: the 7 dips with the smallest d' (equal d': the smaller tau) in ascending tau; count = min(7, dips) >= 1; per kept dip
+ *               ap = d'(tau), delta by the pick's parabolic rule, f0 = (float)(sr / (tau + delta)); slots >= count hold 0, 0.f, 0.f
+ *   cents:      int32 [tau_max + 1] on the device, built by the host: cents[0] = 0, cents[tau] = rint(1200 log2(sr / tau))
+ *   states:     0..6 the frame's candidates, 7 unvoiced; INF = 2^40
+ *   obs_t(k):   k < count and rms >= rms_gate: llrint((double)ap_k * 4096) + floor(octave_cost * (cents[tau_min] - cents[tau_k]) / 1200);
+ *               k = 7: unvoiced_cost; every other slot: INF
+ *   A_t(i, j):  i, j < 7: pitch_cost * |cents[tau_i] - cents[tau_j]| (the stored tau of either frame; an empty slot's 0 reads
+ *               cents[0] = 0); one of them 7: switch_cost; both 7: 0
+ *   recursion:  delta_0 = obs_0;  delta_t(j) = min_i(delta_{t-1}(i) + A_t(i, j)) + obs_t(j), psi_t(j) the smallest such i;
+ *               cost = min_j delta_{T-1}(j), the end state the smallest such j; state[t-1] = psi_t(state[t])
+ * svs_f0_dips: the candidate rule on `count` rows of d' in memory, one wave per row: seven rounds of a wave minimum over (d', tau).
+ *   Rules: 1 <= tau_min < tau_max <= 2048; sr positive and finite; count >= 0 (0 launches nothing); pointers non-null, 4-byte aligned.
+ * svs_f0_candidates: svs_f0_track's arguments and rules, plus cand_tau, cand_f0, cand_ap [rows][n_frames][7] and count [rows][n_frames].
+ *   One launch; d' never leaves LDS.  f0, ap, rms and voiced are bitwise svs_f0_track's (the same device functions, csrc/f0_frame.h);
+ *   the candidates are bitwise svs_f0_cmnd followed by svs_f0_dips; frames [a, b) with first_frame = a are those of the whole call.
+ * svs_f0_viterbi: the decode of every row over ALL n_frames of the call (pieces do not concatenate: the path is the call's best one).
+ *   A row is cut into chunks of `chunk` frames: (a) one wave per chunk forms the (min,+) product of its frames' 8x8 matrices
+ *   A_t(i,j) + obs_t(j), one entry per lane; (b) one wave per row carries delta across the chunk products; (c) one wave per chunk
+ *   reruns its frames from its entry vector and writes psi, 3 bits x 8 per frame; (d) the same launch composes them into an end-state ->
+ *   entry-state table; (e) one wave per row walks the tables backwards; (f) each chunk backtraces from its end state and writes
+ *   state.  Five launches.  Integer (min,+) products are associative without rounding, so state and cost are bit for bit those of the
+ *   sequential recursion for every chunk.  Plain adds and mins, no saturation: every path sum stays below 2^62.
+ *   Rules, each with its own message: 1 <= rows <= 64; 0 <= n_frames <= 2^20 (0 launches nothing); chunk in {16, 32, 64, 128};
+ *   1 <= tau_min < tau_max <= 2048; rms_gate finite, >= 0; each of the four costs in 0..2^20; pointers non-null, 4-byte aligned, cost
+ *   8-byte and the workspace (svs_f0_viterbi_workspace bytes; 0 for arguments it refuses) 16-byte aligned.  A cand_tau outside
+ *   0..tau_max is read as the nearer bound.
+ * svs_f0_smooth_select: per frame f < count, s = state[f]: s in 0..6: f0 = cand_f0[f][s], ap = cand_ap[f][s], voiced = 1; else the
+ *   raw pick's f0 and ap, voiced = 0.
+ * All: gfx950, 64-bit indices, no atomics, bitwise reproducible, nothing returns to the host. */
+int svs_f0_dips(const float* dprime, int64_t count /* rows*n_frames */, int tau_min, int tau_max, double sr, int32_t* cand_tau /* [count][7] */,
+                float* cand_f0 /* [count][7] */, float* cand_ap /* [count][7] */, int32_t* cand_count /* [count] */, hipStream_t stream);
+int svs_f0_candidates(const float* x, int rows, int64_t n, int64_t ld_row, int W, int tau_min, int tau_max, int hop, int64_t first_frame,
+                      int64_t n_frames, double threshold, float rms_gate, double sr, float* f0, float* ap, float* rms, int32_t* voiced,
+                      int32_t* cand_tau, float* cand_f0, float* cand_ap, int32_t* cand_count, hipStream_t stream);
+size_t svs_f0_viterbi_workspace(int rows, int64_t n_frames, int chunk);
+int svs_f0_viterbi(const int32_t* cand_tau, const float* cand_ap, const int32_t* cand_count, const float* rms, int rows, int64_t n_frames,
+                   const int32_t* cents /* [tau_max+1], device */, int tau_min, int tau_max, float rms_gate, int64_t pitch_cost,
+                   int64_t switch_cost, int64_t unvoiced_cost, int64_t octave_cost, int chunk, void* workspace,
+                   int32_t* state /* [rows][n_frames] */, int64_t* cost /* [rows] */, hipStream_t stream);
+int svs_f0_smooth_select(const int32_t* state, const float* cand_f0, const float* cand_ap, const float* raw_f0, const float* raw_ap,
+                         int64_t count /* rows*n_frames */, float* f0, float* ap, int32_t* voiced, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

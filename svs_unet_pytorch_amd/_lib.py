@@ -167,6 +167,11 @@ _SIGS = {
     "svs_f0_cmnd": (I, [P, I, L, L, I, I, I, L, L, P, P, P]),
     "svs_f0_pick": (I, [P, L, I, I, D, P, F, D, P, P, P, P]),
     "svs_f0_track": (I, [P, I, L, L, I, I, I, I, L, L, D, F, D, P, P, P, P, P]),
+    "svs_f0_dips": (I, [P, L, I, I, D, P, P, P, P, P]),
+    "svs_f0_candidates": (I, [P, I, L, L, I, I, I, I, L, L, D, F, D, P, P, P, P, P, P, P, P, P]),
+    "svs_f0_viterbi_workspace": (Z, [I, L, I]),
+    "svs_f0_viterbi": (I, [P, P, P, P, I, L, P, I, I, F, L, L, L, L, I, P, P, P, P]),
+    "svs_f0_smooth_select": (I, [P, P, P, P, P, L, P, P, P, P]),
 }
 
 

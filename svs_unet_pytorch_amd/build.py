@@ -46,9 +46,11 @@ def _stale(target, deps):
 # fp32 sources per lane and is built the same way too (it does not include fft_wave.h), and so is pitch.hip, which does the same
 # at four points per source.  f0.hip needs it as well: its arithmetic is fp64 but for ONE fp32 subtraction per term, and a lane forms
 # 2, 4 or 8 of those side by side from one broadcast sample and a register window that rotates -- adjacent independent fp32
-# subtractions whose operands sit in shuffled registers are exactly what the vectoriser packs with op_sel.
+# subtractions whose operands sit in shuffled registers are exactly what the vectoriser packs with op_sel.  f0_smooth.hip instantiates
+# the same device functions (csrc/f0_frame.h) in svs_f0_candidates, whose outputs must be f0.hip's bits: the same flag, the same reason.
 EXTRA_FLAGS = {"stft.hip": ["-fno-slp-vectorize"], "mrstft.hip": ["-fno-slp-vectorize"], "wiener.hip": ["-fno-slp-vectorize"],
-               "stretch.hip": ["-fno-slp-vectorize"], "pitch.hip": ["-fno-slp-vectorize"], "f0.hip": ["-fno-slp-vectorize"]}
+               "stretch.hip": ["-fno-slp-vectorize"], "pitch.hip": ["-fno-slp-vectorize"], "f0.hip": ["-fno-slp-vectorize"],
+               "f0_smooth.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src):

@@ -69,7 +69,9 @@ Melody (`--melody`): BSS-eval says how much accompaniment leaked into the vocal,
 tracks the reference and the estimated vocal (mono downmix, the file's rate) with the same YIN parameters (f0.py: f0.track_gpu under
 `--device gpu`, the float64 definition f0.yin_reference otherwise) and scores the estimate's track against the reference's with the
 five frame-level measures of the MIREX melody task (f0.melody_metrics): VR, VFA, RPA, RCA, OA, as fractions.  `--rms_gate_db` (-50 dB
-re full scale by default in this mode) makes the silent passages of the reference count as unvoiced.
+re full scale by default in this mode) makes the silent passages of the reference count as unvoiced.  `--f0_smooth` decodes both
+tracks with the same default costs (f0.py smooth=True; csrc/f0_smooth.hip on the device): RPA and OA then measure the stem, not the raw
+tracker's own octave flips.
 """
 from __future__ import annotations
 
@@ -1136,15 +1138,21 @@ def main(argv=None):
     parser.add_argument("--melody", action="store_true",
                         help="also score the melody: YIN pitch tracks of the estimated and the reference vocal, compared by voicing "
                              "recall / false alarm, raw pitch / chroma accuracy and overall accuracy (VR, VFA, RPA, RCA, OA)")
+    parser.add_argument("--f0_smooth", action="store_true",
+                        help="with --melody: Viterbi-decode both pitch tracks (7 candidates per frame, the same default costs)")
     parser.add_argument("--rms_gate_db", type=float, default=None, metavar="DB",
                         help="with --melody: frames whose rms lies below this level (dB re full scale) are unvoiced (default -50)")
     args = parser.parse_args(argv)
     if args.rms_gate_db is not None and not args.melody:
         parser.error("--rms_gate_db belongs to --melody")
+    if args.f0_smooth and not args.melody:
+        parser.error("--f0_smooth belongs to --melody")
     melody = ()
     if args.melody:
         from .f0 import MELODY as melody, MELODY_GATE_DB, gate_from_db
         melody_options = dict(rms_gate=gate_from_db(MELODY_GATE_DB if args.rms_gate_db is None else args.rms_gate_db))
+        if args.f0_smooth:
+            melody_options["smooth"] = True
     v4 = args.mode == "v4"
     if v4 and args.frame_window is None:
         args.frame_window = 1.0

@@ -3,7 +3,8 @@ definition (numpy), the device path on csrc/f0.hip (include/svs_hip.h, DESIGN.md
 MIREX melody task, and a command line.  The reference has no pitch estimator; pitch.py / csrc/pitch.hip SHIFT pitch for training.
 
     python -m svs_unet_pytorch_amd.f0 --src song.wav|folder --csv out.csv|folder [--fmin 65] [--fmax 1000] [--window W] [--hop H] \
-        [--threshold 0.15] [--rms_gate_db DB] [--device gpu|cpu]
+        [--threshold 0.15] [--rms_gate_db DB] [--device gpu|cpu] [--smooth [--pitch_cost 4] [--switch_cost 1024] [--unvoiced_cost 2048] \
+        [--octave_cost 82]]
 
 Geometry, from sr, fmin, fmax, W (the integration window in samples, default 2 tau_max), hop (default round(sr / 100), at least 1):
     tau_min = max(2, floor(sr / fmax)),  tau_max = ceil(sr / fmin),  span = W + tau_max,  frames = 1 + (n - span) // hop
@@ -20,7 +21,27 @@ Frame i of a row starts at sample t = i hop:
               tau + 1 <= tau_max and a - 2b + c > 0; else 0
     f0 = float32(sr / (tau + delta));  ap = b;  rms = float32(sqrt(mean of the frame's first W samples squared, in float64))
     voiced = found and rms >= rms_gate;  the frame's time is (t + span / 2) / sr
-There is no step 6 of the paper (the best local estimate), no smoothing over frames and no octave-error correction.
+There is no step 6 of the paper (the best local estimate); without `smooth` there is no smoothing over frames and no octave-error
+correction either.
+
+Smoothing (smooth=True or a dict of the four costs; csrc/f0_smooth.hip) keeps K = 7 period candidates per frame
+and lets an exact Viterbi decode pick the cheapest path through them and one unvoiced state.  All integer arithmetic is int64.
+    dip:        tau in [tau_min, tau_max] with (tau == tau_min or d'(tau) < d'(tau-1)) and (tau == tau_max or d'(tau) <= d'(tau+1));
+                a frame always has one
+    candidates: the 7 dips with the smallest d' (equal d': the smaller tau), stored in ascending tau; count = min(7, dips); per kept
+                dip ap = d'(tau), delta by the pick's parabolic rule, f0 = float32(sr / (tau + delta)); slots >= count hold 0, 0, 0
+    cents:      cents[0] = 0, cents[tau] = int32(rint(1200 log2(sr / tau))), built on the host (cents_table)
+    states:     0..6 the frame's candidates, 7 unvoiced; INF = 2^40
+    obs(k):     k < count and rms >= rms_gate: llrint(float64(ap_k) 4096) + (octave_cost (cents[tau_min] - cents[tau_k])) // 1200
+                (the product is exact, the rounding half to even); state 7: unvoiced_cost; every other slot INF
+    A(i, j):    voiced to voiced pitch_cost |cents[tau_i] - cents[tau_j]| (an empty slot's tau of 0 reads cents[0] = 0); voiced to
+                unvoiced or back switch_cost; unvoiced to unvoiced 0
+    recursion:  delta_0 = obs_0;  delta_t(j) = min_i(delta_{t-1}(i) + A_t(i, j)) + obs_t(j), psi_t(j) the smallest i that attains it;
+                the end state is the smallest j that attains min delta_{T-1} (= cost); backtrace through psi
+    track:      state < 7: f0 and ap of that candidate, voiced = 1; state 7: f0 and ap of the raw pick above, voiced = 0
+Defaults (starting points, not tuned): pitch_cost 4 per cent, switch_cost 1024, unvoiced_cost 2048, octave_cost 82 per octave of lag
+(it keeps the path off the sub-octave 2 T).  Limits: every cost in 0..2^20 and at most 2^20 frames, so every sum stays below 2^62.
+The decode is over the frames of ONE call: pieces given by first_frame concatenate for the candidates, NOT for the decoded path.
 """
 from __future__ import annotations
 
@@ -36,6 +57,9 @@ W_MAX, TAU_MAX, ROWS_MAX = 4096, 2048, 64                            # csrc/f0.h
 MELODY_GATE_DB = -50.0                                               # evaluate.py --melody: silent reference passages count as unvoiced
 CENTS = 50.0
 MELODY = ("VR", "VFA", "RPA", "RCA", "OA")
+K, UNVOICED, INF = 7, 7, 1 << 40                                     # csrc/f0_smooth.hip: F0_K, VIT_INF
+COSTS = {"pitch_cost": 4, "switch_cost": 1024, "unvoiced_cost": 2048, "octave_cost": 82}
+COST_MAX, FRAMES_MAX, CHUNKS, CHUNK = 1 << 20, 1 << 20, (16, 32, 64, 128), 64
 
 
 class Geometry(NamedTuple):
@@ -190,9 +214,12 @@ def pick_reference(dprime, sr, tau_min: int, tau_max: int, threshold=THRESHOLD, 
     return f0.reshape(lead), ap.reshape(lead), voiced.astype(np.int32).reshape(lead), taus.reshape(lead)
 
 
-def yin_reference(x, sr, fmin=FMIN, fmax=FMAX, W=None, hop=None, threshold=THRESHOLD, rms_gate=0.0, first_frame: int = 0, n_frames=None):
-    """The definition on x: (n,) or (rows, n).  Returns (Track, d') -- d' float32 (frames, tau_max + 1) or (rows, frames, tau_max + 1)."""
+def yin_reference(x, sr, fmin=FMIN, fmax=FMAX, W=None, hop=None, threshold=THRESHOLD, rms_gate=0.0, first_frame: int = 0, n_frames=None,
+                  smooth=None):
+    """The definition on x: (n,) or (rows, n).  Returns (Track, d') -- d' float32 (frames, tau_max + 1) or (rows, frames, tau_max + 1).
+    smooth (None: off; True or a dict of the four costs): the Track is the decoded one (smooth_reference over the call's frames)."""
     g = geometry(sr, fmin, fmax, W, hop, threshold, rms_gate)
+    costs = None if smooth is None or smooth is False else check_costs(smooth)
     x = np.asarray(x, dtype=np.float32)
     one = x.ndim == 1
     x = x[None] if one else x.reshape(-1, x.shape[-1])
@@ -200,10 +227,145 @@ def yin_reference(x, sr, fmin=FMIN, fmax=FMAX, W=None, hop=None, threshold=THRES
     first_frame, n_frames = frame_range(x.shape[1], g, first_frame, n_frames)
     dp, rms = cmnd_reference(x, g.W, g.tau_max, g.hop, first_frame, n_frames)
     f0, ap, voiced, _ = pick_reference(dp, g.sr, g.tau_min, g.tau_max, g.threshold, rms, g.rms_gate)
+    if costs is not None:
+        f0, ap, voiced, _, _ = smooth_reference(dp, rms, g.sr, g.tau_min, g.tau_max, g.threshold, g.rms_gate, costs)
     t = frame_times(g, n_frames, first_frame)
     if one:
         f0, ap, voiced, rms, dp = f0[0], ap[0], voiced[0], rms[0], dp[0]
     return Track(t, f0, voiced, ap, rms), dp
+
+
+# ------------------------------------------------------------------------------------------------
+# smoothing: candidates and the Viterbi decode (the definition; module docstring)
+# ------------------------------------------------------------------------------------------------
+def check_costs(smooth) -> dict:
+    """The four costs as ints: True (or an empty dict) gives COSTS; a dict may set any of them.  Each must be a whole number in
+    0..2^20 -- a ValueError with the cost's name otherwise, before any device work."""
+    given = {} if smooth is True else dict(smooth)
+    unknown = set(given) - set(COSTS)
+    if unknown:
+        raise ValueError(f"smooth= takes {', '.join(COSTS)}, not {sorted(unknown)}")
+    out = {}
+    for name, default in COSTS.items():
+        v = given.get(name, default)
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= COST_MAX:
+            raise ValueError(f"{name} must be a whole number in 0..2^20, got {v}")
+        out[name] = int(v)
+    return out
+
+
+def cents_table(sr, tau_max: int) -> np.ndarray:
+    """int32 (tau_max + 1,): cents[0] = 0, cents[tau] = rint(1200 log2(sr / tau)).  Built on the host; the device takes no logarithm."""
+    table = np.zeros(int(tau_max) + 1, np.int32)
+    table[1:] = np.rint(1200.0 * np.log2(float(sr) / np.arange(1, int(tau_max) + 1, dtype=np.float64))).astype(np.int32)
+    return table
+
+
+def candidates_reference(dprime, sr, tau_min: int, tau_max: int):
+    """The candidates of any float32 d' buffer (..., tau_max + 1): (tau int32 (..., 7), f0 float32 (..., 7), ap float32 (..., 7),
+    count int32 (...))."""
+    dp32 = np.asarray(dprime, dtype=np.float32)
+    if dp32.shape[-1] != tau_max + 1:
+        raise ValueError(f"d' must have tau_max + 1 = {tau_max + 1} values per frame, got {dp32.shape[-1]}")
+    lead = dp32.shape[:-1]
+    rows = dp32.reshape(-1, tau_max + 1)
+    tau = np.zeros((rows.shape[0], K), np.int32)
+    f0 = np.zeros((rows.shape[0], K), np.float32)
+    ap = np.zeros((rows.shape[0], K), np.float32)
+    count = np.zeros(rows.shape[0], np.int32)
+    for i, dp in enumerate(rows):
+        v = dp[tau_min:tau_max + 1]
+        left = np.concatenate([[True], v[1:] < v[:-1]])
+        right = np.concatenate([v[:-1] <= v[1:], [True]])
+        dips = tau_min + np.flatnonzero(left & right)
+        keep = np.sort(dips[np.lexsort((dips, dp[dips]))][:K])        # by (d', tau), then back in ascending tau
+        count[i] = keep.size
+        for k, t in enumerate(keep.tolist()):
+            b, delta = float(dp[t]), 0.0
+            if t - 1 >= 1 and t + 1 <= tau_max:
+                a, c = float(dp[t - 1]), float(dp[t + 1])
+                q = a - 2.0 * b + c
+                if q > 0.0:
+                    delta = min(1.0, max(-1.0, 0.5 * (a - c) / q))
+            tau[i, k], f0[i, k], ap[i, k] = t, float(sr) / (t + delta), dp[t]
+    return tau.reshape(lead + (K,)), f0.reshape(lead + (K,)), ap.reshape(lead + (K,)), count.reshape(lead)
+
+
+def viterbi_costs(cand_tau, cand_ap, count, rms, cents, tau_min: int, rms_gate=0.0, **costs):
+    """One row's (obs int64 (T, 8), A int64 (T, 8, 8)) -- A[t] leads from frame t - 1 to frame t, A[0] is unused (zero)."""
+    c = check_costs(costs)
+    cand_tau, count = np.asarray(cand_tau, dtype=np.int64), np.asarray(count, dtype=np.int64)
+    T = count.shape[0]
+    if cand_tau.shape != (T, K) or np.shape(cand_ap) != (T, K) or np.shape(rms) != (T,):
+        raise ValueError(f"one row takes cand_tau and cand_ap (T, {K}), count and rms (T,), got {cand_tau.shape}, {np.shape(cand_ap)}, "
+                         f"{count.shape}, {np.shape(rms)}")
+    cents = np.asarray(cents, dtype=np.int64)
+    if T and (cand_tau.min() < 0 or cand_tau.max() >= cents.shape[0]):
+        raise ValueError(f"a candidate's tau lies outside the cents table's 0..{cents.shape[0] - 1}")
+    cen = cents[cand_tau]                                             # (T, 7)
+    live = (np.arange(K)[None] < count[:, None]) & (np.asarray(rms, dtype=np.float32) >= np.float32(rms_gate))[:, None]
+    obs = np.full((T, K + 1), INF, np.int64)
+    voiced = np.rint(np.asarray(cand_ap, dtype=np.float32).astype(np.float64) * 4096.0).astype(np.int64) \
+        + (c["octave_cost"] * (cents[tau_min] - cen)) // 1200
+    obs[:, :K] = np.where(live, voiced, INF)
+    obs[:, K] = c["unvoiced_cost"]
+    A = np.full((T, K + 1, K + 1), c["switch_cost"], np.int64)
+    A[:, K, K] = 0
+    if T:
+        A[0] = 0
+        A[1:, :K, :K] = c["pitch_cost"] * np.abs(cen[:-1, :, None] - cen[1:, None, :])
+    return obs, A
+
+
+def viterbi_decode(obs, A):
+    """The textbook recursion on one row's int64 costs (viterbi_costs): (state int32 (T,), cost) with the smallest index on every tie."""
+    obs, A = np.asarray(obs, dtype=np.int64), np.asarray(A, dtype=np.int64)
+    T, S = obs.shape
+    if T == 0:
+        return np.zeros(0, np.int32), 0
+    psi = np.zeros((T, S), np.int64)
+    delta = obs[0].copy()
+    for t in range(1, T):
+        through = delta[:, None] + A[t]                               # (i, j)
+        psi[t] = np.argmin(through, axis=0)                           # the first i that attains the minimum
+        delta = through.min(axis=0) + obs[t]
+    state = np.zeros(T, np.int32)
+    state[-1] = int(np.argmin(delta))
+    for t in range(T - 1, 0, -1):
+        state[t - 1] = psi[t, state[t]]
+    return state, int(delta.min())
+
+
+def viterbi_reference(cand_tau, cand_ap, count, rms, cents, tau_min: int, rms_gate=0.0, **costs):
+    """The decode of candidate buffers (T, 7) / (T,) or (rows, T, 7) / (rows, T): (state int32, like count; cost int64, () or (rows,))."""
+    count = np.asarray(count)
+    if count.ndim == 1:
+        state, cost = viterbi_decode(*viterbi_costs(cand_tau, cand_ap, count, rms, cents, tau_min, rms_gate, **costs))
+        return state, np.int64(cost)
+    if count.shape[-1] > FRAMES_MAX:
+        raise ValueError(f"at most 2^20 frames are decoded at once, got {count.shape[-1]}")
+    out = [viterbi_reference(t, a, n, r, cents, tau_min, rms_gate, **costs) for t, a, n, r in zip(cand_tau, cand_ap, count, rms)]
+    return np.stack([s for s, _ in out]), np.array([c for _, c in out], np.int64)
+
+
+def select_reference(state, cand_f0, cand_ap, raw_f0, raw_ap):
+    """(f0, ap, voiced) of the decoded path: the candidate's where state < 7, the raw pick's and unvoiced where it is 7."""
+    state = np.asarray(state)
+    v = state < K
+    slot = np.minimum(state, K - 1)[..., None]
+    f0 = np.where(v, np.take_along_axis(np.asarray(cand_f0), slot, axis=-1)[..., 0], raw_f0).astype(np.float32)
+    ap = np.where(v, np.take_along_axis(np.asarray(cand_ap), slot, axis=-1)[..., 0], raw_ap).astype(np.float32)
+    return f0, ap, v.astype(np.int32)
+
+
+def smooth_reference(dprime, rms, sr, tau_min: int, tau_max: int, threshold=THRESHOLD, rms_gate=0.0, smooth=True):
+    """The smoothed (f0 float32, ap float32, voiced int32, state int32, cost int64) of a float32 d' buffer (frames, tau_max + 1) or
+    (rows, frames, tau_max + 1) and its rms: pick_reference, candidates_reference, viterbi_reference and select_reference in turn."""
+    costs = check_costs(smooth)
+    raw_f0, raw_ap, _, _ = pick_reference(dprime, sr, tau_min, tau_max, threshold, rms, rms_gate)
+    tau, f0, ap, count = candidates_reference(dprime, sr, tau_min, tau_max)
+    state, cost = viterbi_reference(tau, ap, count, np.asarray(rms, dtype=np.float32), cents_table(sr, tau_max), tau_min, rms_gate, **costs)
+    return select_reference(state, f0, ap, raw_f0, raw_ap) + (state, cost)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -296,13 +458,121 @@ def pick_gpu(dprime, sr, tau_min: int, threshold=THRESHOLD, rms=None, rms_gate=0
     return f0, ap, voiced
 
 
-def track_gpu(x, sr, fmin=FMIN, fmax=FMAX, W=None, hop=None, threshold=THRESHOLD, rms_gate=0.0, first_frame: int = 0, n_frames=None) -> Track:
-    """svs_f0_track, ONE launch: the Track of a float32 device signal (n,) or (rows, n) as device tensors (time: float64 (frames,)).
-    The geometry's rules and the frame range are checked before any device work; nothing waits for the host."""
+def dips_gpu(dprime, sr, tau_min: int):
+    """svs_f0_dips on a float32 device buffer (..., tau_max + 1): (tau int32 (..., 7), f0 float32 (..., 7), ap float32 (..., 7),
+    count int32 (...)), bitwise candidates_reference's on the same buffer."""
+    import torch
+    if not torch.is_tensor(dprime) or not dprime.is_cuda or dprime.dtype != torch.float32 or dprime.dim() < 1:
+        raise TypeError("d' must be a float32 device tensor (..., tau_max + 1)")
+    dprime = dprime.contiguous()
+    lead, tau_max = tuple(dprime.shape[:-1]), dprime.shape[-1] - 1
+    frames = int(np.prod(lead, dtype=np.int64))
+    tau = torch.empty(lead + (K,), dtype=torch.int32, device=dprime.device)
+    f0, ap = (torch.empty(lead + (K,), dtype=torch.float32, device=dprime.device) for _ in range(2))
+    count = torch.empty(lead, dtype=torch.int32, device=dprime.device)
+    with torch.cuda.device(dprime.device):
+        _lib.check(_lib.lib().svs_f0_dips(dprime.data_ptr(), frames, int(tau_min), tau_max, float(sr), tau.data_ptr(), f0.data_ptr(), ap.data_ptr(),
+                                          count.data_ptr(), _lib.stream_ptr(dprime.device)), "svs_f0_dips")
+    return tau, f0, ap, count
+
+
+def candidates_gpu(x, sr, fmin=FMIN, fmax=FMAX, W=None, hop=None, threshold=THRESHOLD, rms_gate=0.0, first_frame: int = 0, n_frames=None):
+    """svs_f0_candidates, ONE launch: (the raw Track of track_gpu, bit for bit; (tau int32, f0 float32, ap float32) (rows, frames, 7) and
+    count int32 (rows, frames) -- without the row axis for a 1-D signal)."""
     import torch
     g = geometry(sr, fmin, fmax, W, hop, threshold, rms_gate)
     x, rows, n, ld_row, one = _rows_gpu(x)
     first_frame, n_frames = frame_range(n, g, first_frame, n_frames)
+    f0, ap, rms, voiced, cand = _candidates(x, rows, n, ld_row, g, first_frame, n_frames)
+    t = torch.from_numpy(frame_times(g, n_frames, first_frame)).to(x.device)
+    if one:
+        return Track(t, f0[0], voiced[0], ap[0], rms[0]), tuple(c[0] for c in cand)
+    return Track(t, f0, voiced, ap, rms), cand
+
+
+def _candidates(x, rows, n, ld_row, g: Geometry, first_frame: int, n_frames: int):
+    import torch
+    f0, ap, rms = (torch.empty(rows, n_frames, dtype=torch.float32, device=x.device) for _ in range(3))
+    voiced, count = (torch.empty(rows, n_frames, dtype=torch.int32, device=x.device) for _ in range(2))
+    c_tau = torch.empty(rows, n_frames, K, dtype=torch.int32, device=x.device)
+    c_f0, c_ap = (torch.empty(rows, n_frames, K, dtype=torch.float32, device=x.device) for _ in range(2))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().svs_f0_candidates(x.data_ptr(), rows, n, ld_row, g.W, g.tau_min, g.tau_max, g.hop, first_frame, n_frames, g.threshold,
+                                                g.rms_gate, g.sr, f0.data_ptr(), ap.data_ptr(), rms.data_ptr(), voiced.data_ptr(), c_tau.data_ptr(),
+                                                c_f0.data_ptr(), c_ap.data_ptr(), count.data_ptr(), _lib.stream_ptr(x.device)), "svs_f0_candidates")
+    return f0, ap, rms, voiced, (c_tau, c_f0, c_ap, count)
+
+
+_CENTS = {}
+
+
+def cents_gpu(sr, tau_max: int, device):
+    """cents_table on the device, uploaded once per (sr, tau_max, device)."""
+    import torch
+    device = torch.device(device)
+    key = (float(sr), int(tau_max), device.type, torch.cuda.current_device() if device.index is None else device.index)
+    if key not in _CENTS:
+        _CENTS[key] = torch.from_numpy(cents_table(sr, tau_max)).to(device)
+    return _CENTS[key]
+
+
+def viterbi_gpu(cand_tau, cand_ap, count, rms, cents, tau_min: int, rms_gate=0.0, chunk: int = CHUNK, **costs):
+    """svs_f0_viterbi on device candidate buffers (rows, T, 7) / (rows, T) (or without the row axis): (state int32 like count, cost int64
+    (rows,) or ()), bitwise viterbi_reference's for every chunk in CHUNKS.  cents: the int32 device table (cents_gpu)."""
+    import torch
+    c = check_costs(costs)
+    if int(chunk) not in CHUNKS:
+        raise ValueError(f"chunk must be one of {CHUNKS}, got {chunk}")
+    one = count.dim() == 1
+    if one:
+        cand_tau, cand_ap, count, rms = cand_tau[None], cand_ap[None], count[None], rms[None]
+    rows, T = check_rows(count.shape[0]), count.shape[1]
+    if T > FRAMES_MAX:
+        raise ValueError(f"at most 2^20 frames are decoded at once, got {T}")
+    for name, t, dtype, shape in (("cand_tau", cand_tau, torch.int32, (rows, T, K)), ("cand_ap", cand_ap, torch.float32, (rows, T, K)),
+                                  ("count", count, torch.int32, (rows, T)), ("rms", rms, torch.float32, (rows, T)),
+                                  ("cents", cents, torch.int32, tuple(cents.shape[:1]))):
+        if not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be a {dtype} device tensor {shape}, got {t.dtype} {tuple(t.shape)}")
+    cand_tau, cand_ap, count, rms, cents = (t.contiguous() for t in (cand_tau, cand_ap, count, rms, cents))
+    tau_max = cents.shape[0] - 1
+    lib = _lib.lib()
+    ws = torch.empty(max(16, lib.svs_f0_viterbi_workspace(rows, T, int(chunk))), dtype=torch.uint8, device=count.device)
+    state = torch.empty(rows, T, dtype=torch.int32, device=count.device)
+    cost = torch.zeros(rows, dtype=torch.int64, device=count.device)
+    with torch.cuda.device(count.device):
+        _lib.check(lib.svs_f0_viterbi(cand_tau.data_ptr(), cand_ap.data_ptr(), count.data_ptr(), rms.data_ptr(), rows, T, cents.data_ptr(),
+                                      int(tau_min), tau_max, float(rms_gate), c["pitch_cost"], c["switch_cost"], c["unvoiced_cost"],
+                                      c["octave_cost"], int(chunk), ws.data_ptr(), state.data_ptr(), cost.data_ptr(),
+                                      _lib.stream_ptr(count.device)), "svs_f0_viterbi")
+    return (state[0], cost[0]) if one else (state, cost)
+
+
+def track_gpu(x, sr, fmin=FMIN, fmax=FMAX, W=None, hop=None, threshold=THRESHOLD, rms_gate=0.0, first_frame: int = 0, n_frames=None,
+              smooth=None) -> Track:
+    """svs_f0_track, ONE launch: the Track of a float32 device signal (n,) or (rows, n) as device tensors (time: float64 (frames,)).
+    The geometry's rules and the frame range are checked before any device work; nothing waits for the host.
+    smooth (None: the above, untouched; True or a dict of pitch_cost, switch_cost, unvoiced_cost, octave_cost): svs_f0_candidates,
+    svs_f0_viterbi over the call's frames and svs_f0_smooth_select instead -- f0, ap and voiced are the decoded path's, rms and time are
+    unchanged.  Pieces given by first_frame do NOT concatenate to the whole-signal decode: the path is the best one of the call."""
+    import torch
+    g = geometry(sr, fmin, fmax, W, hop, threshold, rms_gate)
+    costs = None if smooth is None or smooth is False else check_costs(smooth)
+    x, rows, n, ld_row, one = _rows_gpu(x)
+    first_frame, n_frames = frame_range(n, g, first_frame, n_frames)
+    if costs is not None:
+        if n_frames > FRAMES_MAX:
+            raise ValueError(f"at most 2^20 frames are decoded at once, got {n_frames}")
+        raw_f0, raw_ap, rms, _, (c_tau, c_f0, c_ap, count) = _candidates(x, rows, n, ld_row, g, first_frame, n_frames)
+        state, _ = viterbi_gpu(c_tau, c_ap, count, rms, cents_gpu(g.sr, g.tau_max, x.device), g.tau_min, g.rms_gate, **costs)
+        f0, ap = torch.empty_like(raw_f0), torch.empty_like(raw_ap)
+        voiced = torch.empty(rows, n_frames, dtype=torch.int32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().svs_f0_smooth_select(state.data_ptr(), c_f0.data_ptr(), c_ap.data_ptr(), raw_f0.data_ptr(), raw_ap.data_ptr(),
+                                                       rows * n_frames, f0.data_ptr(), ap.data_ptr(), voiced.data_ptr(),
+                                                       _lib.stream_ptr(x.device)), "svs_f0_smooth_select")
+        t = torch.from_numpy(frame_times(g, n_frames, first_frame)).to(x.device)
+        return Track(t, f0[0], voiced[0], ap[0], rms[0]) if one else Track(t, f0, voiced, ap, rms)
     f0, ap, rms = (torch.empty(rows, n_frames, dtype=torch.float32, device=x.device) for _ in range(3))
     voiced = torch.empty(rows, n_frames, dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
@@ -319,11 +589,14 @@ def channel_mean(x):
 
 
 def check_options(options) -> dict:
-    """The keywords of track_gpu that f0= of the separation calls takes (True or None-like: the defaults): a ValueError for anything else."""
+    """The keywords of track_gpu that f0= of the separation calls takes (True or None-like: the defaults; smooth among them): a ValueError
+    for anything else."""
     options = {} if options is True else dict(options)
-    unknown = set(options) - {"fmin", "fmax", "W", "hop", "threshold", "rms_gate"}
+    unknown = set(options) - {"fmin", "fmax", "W", "hop", "threshold", "rms_gate", "smooth"}
     if unknown:
         raise ValueError(f"f0= takes fmin, fmax, W, hop, threshold and rms_gate, not {sorted(unknown)}")
+    if options.get("smooth") is not None and options["smooth"] is not False:
+        check_costs(options["smooth"])                               # smooth: True or a dict of the four costs (track_gpu)
     return options
 
 
@@ -374,7 +647,18 @@ def main(argv=None):
     parser.add_argument("--threshold", type=float, default=THRESHOLD, help=f"absolute threshold on d' (default {THRESHOLD})")
     parser.add_argument("--rms_gate_db", type=float, default=None, help="frames whose rms lies below this level (dB re full scale) are unvoiced (default: off)")
     parser.add_argument("--device", default="gpu", choices=["gpu", "cpu"], help="gpu: csrc/f0.hip; cpu: the float64 definition")
+    parser.add_argument("--smooth", action="store_true",
+                        help="decode the track over 7 candidates per frame and an unvoiced state (Viterbi; csrc/f0_smooth.hip): fewer octave errors")
+    for name, default in COSTS.items():
+        parser.add_argument("--" + name, type=int, default=None, help=f"--smooth: whole number in 0..2^20, unit 1/4096 (default {default})")
     args = parser.parse_args(argv)
+    given = {name: getattr(args, name) for name in COSTS if getattr(args, name) is not None}
+    if given and not args.smooth:
+        parser.error(f"--{sorted(given)[0]} belongs to --smooth")
+    try:
+        smooth = check_costs(given) if args.smooth else None
+    except ValueError as e:
+        parser.error(str(e))
     device = None
     if args.device == "gpu":
         import torch
@@ -382,7 +666,8 @@ def main(argv=None):
             print("--device gpu needs a ROCm device (hand-written gfx950 kernels); --device cpu runs the float64 definition.")
             sys.exit(1)
         device = torch.device("cuda")
-    options = dict(fmin=args.fmin, fmax=args.fmax, W=args.window, hop=args.hop, threshold=args.threshold, rms_gate=gate_from_db(args.rms_gate_db))
+    options = dict(fmin=args.fmin, fmax=args.fmax, W=args.window, hop=args.hop, threshold=args.threshold, rms_gate=gate_from_db(args.rms_gate_db),
+                   smooth=smooth)
     if os.path.isdir(args.src):
         os.makedirs(args.csv, exist_ok=True)
         jobs = [(os.path.join(args.src, f), os.path.join(args.csv, f[:-4] + ".csv")) for f in sorted(os.listdir(args.src)) if f.endswith(".wav")]

@@ -10,7 +10,7 @@ evaluate.py accepts it beside the source's stems.
         [--no_keep_length] \
         [--win_size 512|1024|2048] [--hop_size N] [--tar_accomp accomp.wav | accomp_folder] [--tile_hop 128|64|32] [--phase_iters N]
         [--wiener_iters N] [--loudness LUFS|source] [--peak_ceiling 0.9] [--true_peak] [--fullband mask|accomp]
-        [--limiter [MS]] [--f0_csv track.csv | csv_folder]
+        [--limiter [MS]] [--f0_csv track.csv | csv_folder [--f0_smooth]]
 
 A folder as --src means every *.wav in it, written under the same name into the folder --tar.  --subtype PCM_16 (the
 default) is what the reference's data.py writes (data.py:166); PCM_24 writes 24-bit files, `source` the word length of each source
@@ -45,7 +45,9 @@ a stereo file keeps its channel balance.  Not beside --wiener_iters; a file at o
 (a folder when --src is one: one NAME.csv per source file) also writes the pitch track of the vocal stem (f0.py; csrc/f0.hip): a YIN
 tracker on the mean of the stem's channels at the network's 8,192 Hz, after the Wiener or phase stages and before the way out, one
 launch; time,f0,voiced,aperiodicity,rms per 10 ms frame.  The wav files are byte for byte those written without the flag; --vocal_solo 0
-writes no vocal stem, so it cannot be combined with it.  The reference has no such command: it goes through
+writes no vocal stem, so it cannot be combined with it.  --f0_smooth (only with --f0_csv) writes the decoded track instead: 7 period
+candidates per frame and an exact Viterbi decode over them and an unvoiced state (csrc/f0_smooth.hip), which removes most octave errors
+and voicing drop-outs of the raw tracker on a noisy stem; the csv columns are the same.  The reference has no such command: it goes through
 data.py to_spec, inference.py and data.py to_wave with .npy files in between.
 """
 from __future__ import annotations
@@ -109,6 +111,8 @@ def main(argv=None):
     parser.add_argument("--f0_csv", type=str, default=None, metavar="PATH",
                         help="also write the vocal stem's pitch track (YIN at the network rate): time,f0,voiced,aperiodicity,rms per frame; "
                              "a csv file, or a folder when --src is one")
+    parser.add_argument("--f0_smooth", action="store_true",
+                        help="with --f0_csv: write the Viterbi-decoded pitch track (7 candidates per frame, default costs) instead of the raw one")
     parser.add_argument("--ema", action="store_true", help="load the checkpoint's ema_state_dict (train.py --ema_decay) instead of its live weights")
     args = parser.parse_args(argv)
     if args.dither != "none" and args.subtype in ("PCM_32", "FLOAT"):
@@ -153,6 +157,8 @@ def main(argv=None):
                 parser.error(f"--limiter {args.limiter:g}: {path}: {e}")
     if args.f0_csv is not None and not args.vocal_solo:
         parser.error("--f0_csv tracks the vocal stem, and --vocal_solo 0 writes none: drop one of the two")
+    if args.f0_smooth and args.f0_csv is None:
+        parser.error("--f0_smooth belongs to --f0_csv: it chooses which pitch track that file holds")
     if args.tar_accomp is not None and not args.vocal_solo:
         parser.error("--tar_accomp writes the vocal to --tar and the accompaniment to --tar_accomp: it cannot be combined with --vocal_solo 0")
 
@@ -182,7 +188,7 @@ def main(argv=None):
                                            phase_iters=args.phase_iters, wiener_iters=args.wiener_iters, loudness=args.loudness,
                                            ceiling=args.peak_ceiling, report=report, fullband=args.fullband,
                                            true_peak=args.true_peak, dither=args.dither, dither_seed=args.dither_seed,
-                                           limiter_ms=args.limiter, f0_csv_path=f0_csv)
+                                           limiter_ms=args.limiter, f0={"smooth": True} if args.f0_smooth else None, f0_csv_path=f0_csv)
         print(f"{dst}: {frames} frames x {channels}" + ("" if dst_accomp is None else f"; {dst_accomp}: the same")
               + (f"; {describe(report['info'], report['gain'], args.true_peak)}" if "info" in report else "")
               + (f"; {describe_limiter(**report['limiter'])}" if "limiter" in report else "")

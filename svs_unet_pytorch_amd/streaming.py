@@ -123,7 +123,8 @@ def separate_waveform(model, y: torch.Tensor, vocal_solo: bool = True, n_fft: in
     check_refinement's rules are a ValueError before any device work.
     aux: a dict that receives what a post-filter at another rate needs (fullband.py): "y" (the (channels, n) signal at the network rate
     that was transformed), "tiles", "mask" (the one the stems were made from, in the layout of the tiles), "norm" and "frames".
-    f0: True, or a dict of f0.track_gpu's keywords (fmin, fmax, W, hop, threshold, rms_gate): the call returns (stems, f0.Track) -- the
+    f0: True, or a dict of f0.track_gpu's keywords (fmin, fmax, W, hop, threshold, rms_gate, smooth -- True or the four costs: the decoded
+    track of csrc/f0_smooth.hip, three entry points more): the call returns (stems, f0.Track) -- the
     pitch track of the VOCAL stem (f0.py, csrc/f0.hip), from the mean of its channels at SAMPLE_RATE as the inverse transform leaves it
     (scaled to `peak` where that rate is the one returned), after the Wiener or phase stages and before the resampling to sr_out: ONE
     svs_f0_track launch, nothing waits for the host.  The stems are those of the call without it.  vocal_solo=False without
